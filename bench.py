@@ -12,19 +12,26 @@ Contract (driver):  python bench.py --gpus N --steps K --warmup W   prints ONE J
   * N > 1: one process per GPU, independent replicas (the reference's only multi-GPU mode for
     off-policy agents, docker_batch.sh:2-8) -> "scaling": "weak", no data-path
     collective; a barrier + max-over-ranks brackets the timed region.
-  * roofline: the dominant kernel of the update, timed live with HIP events on the launch stream
+  * [full] roofline: the dominant kernel of the update, timed live with HIP events on the launch stream
     ("source": "hip_events"; the rocprofv3 summary of the same command is committed under profiles/).
-  * cpu_baseline: the CPU oracle (port of the reference path on torch-CPU fp32) on a bounded
+  * [full] cpu_baseline: the CPU oracle (port of the reference path on torch-CPU fp32) on a bounded
     sample, rank 0 / N=1 only: `value` with ONE thread (the reference's set_one_thread(), examples.py:623),
-    `multi_thread` = the best of an 8 / 16 / 32-thread sweep of the same learner, `all_cores_replicas` = 64 single-thread
-    learners side by side (how the CPU path scales on a host).
-  * parity_check: after the timed region, SIX more agent steps of the SAME pipelined configuration are replayed through
+    `multi_thread` = the best of an 8 / 16 / 32-thread sweep of the same learner, `all_cores_replicas` = one single-thread
+    learner per CPU this process may use (at most 15) side by side (how the CPU path scales on a host).
+  * [full] parity_check: after the timed region, SIX more agent steps of the SAME pipelined configuration are replayed through
     the CPU oracle, chained (the oracle carries its own parameters / optimizer state from step to step; the minibatch each
     update consumed comes from the learner): loss and every parameter at 1e-5 per step, the worst is reported.  Outside the
     timing.
+  * a plain run (`--gpus 1 --steps K --warmup W`) does only what the headline needs: set up, warm up, time the K steps, print
+    the line (metric, value, unit, ms_per_step, ...).  Everything marked [full] -- roofline, parity_check, long_run, host
+    / lane accounting, the eager profile, the replay gather line, the agent-API and other-config lines, cpu_baseline -- runs
+    only with `--full`.
+  * `--dump-outputs DIR`: after the timed steps, what the timed path computed in its last step (the online net's parameters
+    after the update, q, delta, loss, grad norm, minibatch indices, the actor's last action values) as DIR/<name>.npy,
+    float32 / float64.  Inputs are seeded: the same arguments give the same inputs from run to run.
   * `--gpus N` without a torchrun environment launches the N ranks itself (torch.distributed.run, 127.0.0.1).
   * a run of fewer than 500 timed steps (the driver's default is 20) is a few milliseconds: `value` is still exactly
-    those K steps (the contract), and `long_run` carries the same measurement over 2000 steps.  With a warm-up of fewer than
+    those K steps (the contract), and [full] `long_run` carries the same measurement over 2000 steps.  With a warm-up of fewer than
     100 steps, 300 untimed `setup_steps` run in front of it (graph capture on first use, first touch of the ring, clocks).
 """
 import argparse
@@ -52,6 +59,11 @@ def parse():
     ap.add_argument("--steps", type=int, default=2000)
     ap.add_argument("--warmup", type=int, default=200)
     ap.add_argument("--ring", type=int, default=1_000_000, help="replay capacity in frames")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline: roofline, parity check, long run, host / lane "
+                         "accounting, eager profile, replay gather, agent-API and other-config lines, CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-actor", action="store_true", help="skip actor inference (then env_steps is null)")
     ap.add_argument("--variant", type=int, default=-1, help="DRA_VAR_* kernel-variant mask (-1: library default)")
@@ -70,7 +82,12 @@ def parse():
                     help="dqn_pixel = BASELINE configs[1] (the headline); a2c_pixel / ppo_pixel = configs[4]: the on-policy agents, "
                          "environments sharded over the ranks, one gradient all-reduce per optimizer step (SURVEY.md 8e); "
                          "ppo_continuous = configs[2]: PPO on HalfCheetah shapes, 16 workers per GPU (replicas over the ranks)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.workload != "dqn_pixel":
+        ap.error("--dump-outputs covers the dqn_pixel workload (the headline)")
+    return args
 
 
 def spawn_ranks(args):
@@ -102,6 +119,17 @@ def gather_affinity(mine, world):
     out = [None] * world
     dist.all_gather_object(out, mine)
     return out
+
+
+def cpu_budget():
+    """CPUs this process may use: its affinity mask, or a smaller OMP_NUM_THREADS the launcher set (os.cpu_count() counts
+    the whole host, and a thread pool or a process fan-out sized by it only slows itself down)."""
+    n = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
+    try:
+        n = min(n, int(os.environ.get("OMP_NUM_THREADS", "")))
+    except ValueError:
+        pass
+    return max(1, n)
 
 
 def cpu_baseline(seconds=15.0, ring=20_000, worker=False):
@@ -159,7 +187,7 @@ def cpu_baseline(seconds=15.0, ring=20_000, worker=False):
     if worker:
         torch.set_num_threads(threads_before)
         return {"updates": n, "seconds": dt}
-    nproc = os.cpu_count() or 1
+    nproc = cpu_budget()
     # one learner on several threads: the best of a small sweep.  (torch.set_num_threads(nproc) on this host's 256 hardware
     # threads is an oversubscription artefact, not a baseline: 0.08 updates/s in round 2 -- a batch-32 NatureConv update has no
     # work for that many threads.)
@@ -202,10 +230,11 @@ def cpu_baseline(seconds=15.0, ring=20_000, worker=False):
             "all_cores_replicas": cpu_replicas(nproc)}
 
 
-def cpu_replicas(nproc, seconds=6.0, ring=5_000, limit=64):
+def cpu_replicas(nproc, seconds=6.0, ring=5_000, limit=15):
     """The CPU path as it scales on a host: R independent single-thread learners (own ring, own parameters: what the DQN
     family is on several GPUs too), one process each, all running for the same few seconds; the
-    aggregate updates/s.  R = min(cores, 64).  None when the workers cannot be run (never takes the bench line down)."""
+    aggregate updates/s.  R = min(cores, 15): the parent and its workers stay within 16 processes.  None when the workers
+    cannot be run (never takes the bench line down)."""
     import subprocess
     r = max(1, min(int(nproc), limit))
     env = dict(os.environ)
@@ -683,7 +712,7 @@ def ppo_continuous_main(args, d, zoo, rank, world):
                                     "chip a sequential 5.7 k-parameter update can use, not how well the kernel is scheduled; "
                                     "profiles/r05*_prof_ppo_mlp.json has cycles per phase"},
                "fused_update_launches": agent._mlp.launches}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = ppo_cpu_baseline()
         print(json.dumps(out), flush=True)
     agent.close()
@@ -782,6 +811,42 @@ def comm_check(args):
     return 0
 
 
+def headline(args, bench, world, dt, setup_steps):
+    """The result line's headline fields: the K timed steps of the dqn_pixel configuration (every run prints them)."""
+    ups = world * args.steps / dt
+    return {
+        "metric": "gradient-updates/sec", "value": ups, "unit": "updates/s", "n_gpus": world, "steps": args.steps,
+        "warmup": args.warmup, "setup_steps": setup_steps, "ms_per_step": 1e3 * dt / args.steps, "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+        "config": {"workload": "DQN Breakout 84x84x4 uint8, NatureConvBody, batch 32, %d-frame HBM replay ring, "
+                               "centered RMSprop, clip 5 (BASELINE configs[1])" % args.ring,
+                   "global_batch": B * world, "parallelism": "replicas x%d" % world,
+                   "actor_in_step": not args.no_actor, "async_actor": not args.sync_actor,
+                   "kernel_variant": bench.learner.variant},
+        "env_steps_per_sec": (4 * ups) if not args.no_actor else None,
+    }
+
+
+def dump_outputs(bench, path):
+    """`--dump-outputs DIR`: what the timed path computed in its last step -- the online net's parameters after that update
+    (state_dict names, module layout), the action values q and TD errors delta of its minibatch, the loss, the gradient's
+    global norm, the minibatch indices and the actor's last action values -- as DIR/<name>.npy (float32; the
+    indices as float64).  About 7 MB."""
+    lr = bench.learner
+    os.makedirs(path, exist_ok=True)
+    state = lr.export_state()          # synchronises (and completes a deferred optimizer segment) first
+    arrays = {"param." + k: v.numpy().astype(np.float32) for k, v in state["params"].items()}
+    arrays["q"] = lr.q.detach().cpu().numpy().astype(np.float32)
+    arrays["delta"] = lr.delta.detach().cpu().numpy().astype(np.float32)
+    arrays["loss"] = np.asarray([float(lr.loss.item())], dtype=np.float32)
+    arrays["grad_norm"] = lr.norm.detach().cpu().numpy().astype(np.float32)
+    arrays["minibatch_idx"] = lr.idx.detach().cpu().numpy().astype(np.float64)
+    arrays["actor_q"] = lr.actor_q.detach().cpu().numpy().astype(np.float32)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a))
+
+
 def main():
     args = parse()
     if args.cpu_replica_worker > 0:
@@ -847,8 +912,9 @@ def main():
     if distributed:
         dist.barrier()
         torch.cuda.synchronize()
-    bench.learner.host_stats(reset=True)
-    lane0 = bench.learner.lane_stats()
+    if args.full:
+        bench.learner.host_stats(reset=True)
+        lane0 = bench.learner.lane_stats()
     t0 = time.perf_counter()
     for _ in range(args.steps):
         bench.step()
@@ -858,21 +924,25 @@ def main():
         dist.barrier()
         torch.cuda.synchronize()
     dt = time.perf_counter() - t0
-    host = bench.learner.host_stats(reset=True)
-    host["python_loop_us_per_step"] = 1e6 * t_host / args.steps
-    lane1 = bench.learner.lane_stats()
-    n_lane = lane1["steps"] - lane0["steps"]
-    # DRA_VAR_FLAG_SYNC: how many of the timed steps ran in the event-free lane, and the C call's parts there (host microseconds)
-    host["lane"] = {"steps": n_lane, "hazard_bumps": lane1["hazard_bumps"] - lane0["hazard_bumps"],
-                    "host_waits": lane1["host_waits"] - lane0["host_waits"],
-                    "c_call_parts_us": {k: (lane1["host_us_per_step"][k] * lane1["steps"] - lane0["host_us_per_step"][k] * lane0["steps"])
-                                        / max(1, n_lane) for k in lane1["host_us_per_step"]}}
+    host = None
+    if args.full:
+        host = bench.learner.host_stats(reset=True)
+        host["python_loop_us_per_step"] = 1e6 * t_host / args.steps
+        lane1 = bench.learner.lane_stats()
+        n_lane = lane1["steps"] - lane0["steps"]
+        # DRA_VAR_FLAG_SYNC: how many of the timed steps ran in the event-free lane, and the C call's parts there (host microseconds)
+        host["lane"] = {"steps": n_lane, "hazard_bumps": lane1["hazard_bumps"] - lane0["hazard_bumps"],
+                        "host_waits": lane1["host_waits"] - lane0["host_waits"],
+                        "c_call_parts_us": {k: (lane1["host_us_per_step"][k] * lane1["steps"] - lane0["host_us_per_step"][k] * lane0["steps"])
+                                            / max(1, n_lane) for k in lane1["host_us_per_step"]}}
     if distributed:
         t = torch.tensor([dt], dtype=torch.float64, device="cuda" if dist.get_backend() == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(bench, args.dump_outputs)
     long_run = None
-    if args.steps < 500 and not args.no_long_run:
+    if args.full and args.steps < 500 and not args.no_long_run:
         # the contract's K steps are a few milliseconds; the same measurement over 2000 steps next to it (every rank runs
         # it so that the replicas keep loading the node the same way; not part of `value`)
         torch.cuda.synchronize()
@@ -890,7 +960,9 @@ def main():
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             dt_long = float(t.item())
         long_run = {"steps": 2000, "value": world * 2000 / dt_long, "ms_per_step": 1e3 * dt_long / 2000}
-    if rank == 0:
+    if rank == 0 and not args.full:
+        print(json.dumps(headline(args, bench, world, dt, setup_steps)), flush=True)
+    elif rank == 0:
         parity = None
         if not args.no_parity_check and not args.no_actor:   # first: the learner is still in exactly the timed state
             try:
@@ -1000,20 +1072,8 @@ def main():
             extra["replay_gather"] = {"error": repr(e)}
         if not args.no_actor:
             extra["host_us_per_step"] = bench.host_profile(100)
-        ups = world * args.steps / dt
-        out = {
-            "metric": "gradient-updates/sec", "value": ups, "unit": "updates/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "setup_steps": setup_steps, "ms_per_step": 1e3 * dt / args.steps, "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-            "config": {"workload": "DQN Breakout 84x84x4 uint8, NatureConvBody, batch 32, %d-frame HBM replay ring, "
-                                   "centered RMSprop, clip 5 (BASELINE configs[1])" % args.ring,
-                       "global_batch": B * world, "parallelism": "replicas x%d" % world,
-                       "actor_in_step": not args.no_actor, "async_actor": not args.sync_actor,
-                       "kernel_variant": bench.learner.variant},
-            "env_steps_per_sec": (4 * ups) if not args.no_actor else None,
-            "roofline": roof,
-        }
+        out = headline(args, bench, world, dt, setup_steps)
+        out["roofline"] = roof
         out.update(extra)
         out["host"] = host      # per step: time in the enqueueing C call, of which blocked on the GPU; whole python loop
         out["per_rank_cpu_affinity"] = affinity

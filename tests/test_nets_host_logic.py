@@ -111,12 +111,15 @@ def test_shared_body_with_two_optimisers_cannot_run_in_the_reference_either():
         value_loss.backward()
 
 
-def test_rollout_slots_hand_out_the_announced_rows_then_fall_back():
+def test_rollout_slots_hand_out_the_announced_rows_then_fall_back(monkeypatch):
     """nets.RolloutSlots: begin(rows, n) draws ONE [rows, n] block from torch's generator; forward i of the rollout gets row i
     and the rows to write into; any other batch size, a forward beyond the announced ones, or one after end() gets (None, None)
-    -- the caller draws torch.rand(B) itself; pin(u) overrides with a static row (a forward captured in its own graph)."""
+    -- the caller draws torch.rand(B) itself; pin(u) overrides with a static row (a forward captured in its own graph).
+    On the CPU device whatever device an earlier test of the session selected."""
     import torch
     from deeprl_amd.nets import RolloutSlots
+    from deeprl_amd.support import Config
+    monkeypatch.setattr(Config, "DEVICE", torch.device("cpu"))
     s = RolloutSlots()
     assert s.take(4) == (None, None) and s.next_uniform() is None
     torch.manual_seed(3)

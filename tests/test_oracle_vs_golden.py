@@ -435,81 +435,70 @@ def test_product_normalizers_equal_oracle():
     assert np.array_equal(SignNormalizer()(r), np.sign(r))
 
 
-@pytest.mark.skipif(not os.path.isdir(os.environ.get("DEEPRL_REFERENCE_ROOT", "/root/reference")),
-                    reason="the reference tree is only present in the authoring container")
-def test_committed_fixtures_are_the_reference_outputs(tmp_path):
-    """Pins tests/golden/*.npz to the reference LIVE: re-runs tests/golden/make_golden.py (which drives the
-    untouched /root/reference code through tests/ref_shim.py) into a scratch directory and compares every array
-    with the committed fixture bit for bit.  Skipped on the GPU box, where /root/reference does not exist."""
+def test_committed_fixtures_are_the_reference_outputs():
+    """Pins tests/golden/*.npz to the reference's outputs: tests/golden/fixture_digests.json holds one digest per file (every
+    key, and every array's dtype, shape and bytes) of what tests/golden/make_golden.py writes when it drives the untouched
+    reference code through tests/ref_shim.py (recorded by tests/golden/make_golden_crosscheck.py into a scratch directory);
+    every committed fixture must match it bit for bit."""
     import glob
-    import subprocess
-    import sys
+    import json
+    from golden import crosscheck_cases as C
     here = os.path.dirname(os.path.abspath(__file__))
-    env = dict(os.environ, GOLDEN_OUT=str(tmp_path))
-    subprocess.check_call([sys.executable, os.path.join(here, "golden", "make_golden.py")], env=env,
-                          stdout=subprocess.DEVNULL, stderr=subprocess.STDOUT)
+    with open(C.FIXTURE_DIGESTS_JSON) as f:
+        want = json.load(f)
     committed = sorted(glob.glob(os.path.join(here, "golden", "*.npz")))
+    committed = [f for f in committed if os.path.basename(f) not in (os.path.basename(C.REPLAY_STREAMS_NPZ),
+                                                                      os.path.basename(C.MODULES_NPZ))]
     assert len(committed) >= 12
+    assert sorted(os.path.basename(f) for f in committed) == sorted(want)
     for f in committed:
-        a = np.load(f, allow_pickle=True)
-        b = np.load(os.path.join(str(tmp_path), os.path.basename(f)), allow_pickle=True)
-        assert sorted(a.files) == sorted(b.files), f
-        for k in a.files:
-            if a[k].dtype == object:
-                assert str(a[k]) == str(b[k]), (f, k)
-            else:
-                assert a[k].dtype == b[k].dtype and np.array_equal(a[k], b[k], equal_nan=a[k].dtype.kind == "f"), (f, k)
+        assert C.fixture_file_digest(np.load(f, allow_pickle=True)) == want[os.path.basename(f)], f
 
 
-@pytest.mark.skipif(not os.path.isdir(os.environ.get("DEEPRL_REFERENCE_ROOT", "/root/reference")),
-                    reason="the reference tree is only present in the authoring container")
 @pytest.mark.parametrize("seed", [0, 1, 2, 3])
 def test_replay_oracle_equals_live_reference_on_random_streams(seed):
-    """Beyond the fixed fixtures: random feed / sample / update_priorities interleavings (random capacity,
-    history, n-step, discount; wrap-around; terminals) through the reference's own UniformReplay /
-    PrioritizedReplay (tests/ref_shim.py) and through the oracle -- identical samples, index streams, sampling
-    probabilities, tree contents and RNG positions."""
-    import ref_shim
-    ref = ref_shim.load()
-    rs = np.random.RandomState(100 + seed)
-    cap = int(rs.randint(40, 200))
-    h, n = int(rs.randint(1, 5)), int(rs.randint(1, 4))
-    gamma = float(rs.choice([1.0, 0.99, 0.5]))
-    b = 8
-    for cls_ref, cls_orc, per in ((ref.UniformReplay, UniformReplayOracle, False), (ref.PrioritizedReplay, PrioritizedReplayOracle, True)):
-        r = cls_ref(memory_size=cap, batch_size=b, n_step=n, discount=gamma, history_length=h)
-        o = cls_orc(cap, b, n, gamma, h)
+    """Beyond the fixed fixtures: random feed / sample / update_priorities interleavings (random capacity, history, n-step,
+    discount; wrap-around; terminals; tests/golden/crosscheck_cases.py) through the oracle, against what the reference's own
+    UniformReplay / PrioritizedReplay returned on the same streams (tests/golden/replay_streams.npz, written by
+    tests/golden/make_golden_crosscheck.py) -- identical samples, index streams, sampling probabilities, tree contents and
+    RNG positions."""
+    from golden import crosscheck_cases as C
+    z = np.load(C.REPLAY_STREAMS_NPZ, allow_pickle=False)
+    rs, p = C.replay_params(seed)
+    for kind, cls_orc in zip(C.REPLAY_KINDS, (UniformReplayOracle, PrioritizedReplayOracle)):
+        w = lambda k: z["s%d_%s_%s" % (seed, kind, k)]
+        o = cls_orc(p["cap"], p["b"], p["n"], p["gamma"], p["h"])
         np.random.seed(seed)
         random.seed(seed)
         st_np, st_py = np.random.get_state(), random.getstate()
-        fed = 0
-        for step in range(3 * cap):
-            frame = rs.randint(0, 256, size=(3, 3)).astype(np.uint8)
-            act, rew, msk = int(rs.randint(0, 4)), float(rs.randint(-1, 2)), int(rs.rand() > 0.2)
-            r.feed(dict(state=[frame], action=[act], reward=[rew], mask=[msk]))
-            o.feed_one(frame, np.int64(act), rew, msk)
-            fed += 1
-            if fed > h + n + 4 and step % 7 == 0:
-                # same RNG state into both samplers
-                np.random.set_state(st_np); random.setstate(st_py)
-                got = r.sample()
-                a_np, a_py = np.random.get_state(), random.getstate()
-                np.random.set_state(st_np); random.setstate(st_py)
+        n_sample = n_update = 0
+        want = None
+        for ev, data in C.replay_events(rs, p, kind):
+            if ev == "feed":
+                frame, act, rew, msk = data
+                o.feed_one(frame, np.int64(act), rew, msk)
+            elif ev == "sample":
+                # the same RNG state the reference sampled from
+                np.random.set_state(st_np)
+                random.setstate(st_py)
                 want = o.sample()
-                b_np, b_py = np.random.get_state(), random.getstate()
-                assert a_py == b_py and all(np.array_equal(x, y) for x, y in zip(a_np[1:3], b_np[1:3]))
-                st_np, st_py = a_np, a_py
-                assert np.array_equal(np.asarray(got.state), want[0]) and np.array_equal(np.asarray(got.next_state), want[3])
-                assert np.array_equal(np.asarray(got.action).reshape(-1), np.asarray(want[1]).reshape(-1))
-                assert np.array_equal(np.asarray(got.reward, dtype=np.float64), want[2])
-                assert np.array_equal(np.asarray(got.mask), want[4])
-                if per:
-                    assert np.array_equal(np.asarray(got.sampling_prob), want[5]) and np.array_equal(np.asarray(got.idx), want[6])
-                    prio = (rs.rand(b).astype(np.float32) * 2 + 0.1)
-                    info = list(zip(np.asarray(got.idx).tolist(), prio.tolist()))
-                    r.update_priorities(info)
-                    o.update_priorities(info)
-                    assert np.array_equal(r.tree.tree, o.tree.tree) and r.max_priority == o.max_priority
+                st_np, st_py = np.random.get_state(), random.getstate()
+                i = n_sample
+                n_sample += 1
+                assert C.np_rng_digest(st_np) == w("np_rng")[i] and C.py_rng_digest(st_py) == w("py_rng")[i]
+                assert np.array_equal(w("state")[i], want[0]) and np.array_equal(w("next_state")[i], want[3])
+                assert np.array_equal(w("action")[i], np.asarray(want[1]).reshape(-1))
+                assert np.array_equal(w("reward")[i], want[2])
+                assert np.array_equal(w("mask")[i], want[4])
+                if kind == "prioritized":
+                    assert np.array_equal(w("sampling_prob")[i], want[5]) and np.array_equal(w("idx")[i], want[6])
+            else:
+                info = list(zip(np.asarray(want[6]).tolist(), data.tolist()))
+                o.update_priorities(info)
+                assert np.array_equal(w("tree")[n_update], o.tree.tree) and w("max_priority")[n_update] == o.max_priority
+                n_update += 1
+        assert n_sample == len(w("state")) and n_sample > 0
+        assert n_update == (n_sample if kind == "prioritized" else 0)
 
 
 def test_atari_preprocess_oracle_vs_float64_area_average():

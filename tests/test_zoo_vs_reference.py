@@ -1,82 +1,29 @@
-"""deeprl_amd/zoo.py (the example configurations as data) against the reference's own examples.py (CPU, no GPU work):
-each reference entry point is executed through deeprl_amd.launch's loader with the agent constructor and run_steps
-replaced by a capture, and the Config it built is compared field by field with zoo.config(name).  Also: the launcher's
-loader / run_entry on the package's own zoo file.  Skipped where /root/reference is absent (the GPU box)."""
-import os
+"""deeprl_amd/zoo.py (the example configurations as data) against the reference's own examples.py (CPU, no GPU work): each
+reference entry point was executed through deeprl_amd.launch's loader with the agent constructor and run_steps replaced by a
+capture, and the Config it built was recorded field by field (tests/golden/crosscheck.json, written by
+tests/golden/make_golden_crosscheck.py); zoo.config(name) must describe the same.  Also: the launcher's loader / run_entry on
+the package's own zoo file."""
+import json
 
 import numpy as np
 import pytest
-import torch
 
-REF = os.environ.get("DEEPRL_REFERENCE_ROOT", "/root/reference")
-GAMES = {"dqn_feature": "CartPole-v0", "dqn_pixel": "BreakoutNoFrameskip-v4",
-         "quantile_regression_dqn_pixel": "BreakoutNoFrameskip-v4", "categorical_dqn_pixel": "BreakoutNoFrameskip-v4",
-         "a2c_pixel": "BreakoutNoFrameskip-v4", "ppo_pixel": "BreakoutNoFrameskip-v4", "ppo_continuous": "HalfCheetah-v2"}
-AGENTS = ["DQNAgent", "CategoricalDQNAgent", "QuantileRegressionDQNAgent", "A2CAgent", "PPOAgent", "NStepDQNAgent",
-          "OptionCriticAgent", "DDPGAgent", "TD3Agent"]
-PLAIN = (int, float, bool, str, type(None))
+from golden import crosscheck_cases as C
 
 
-def _schedule(s):
-    return None if s is None else (type(s).__name__, getattr(s, "inc", None), getattr(s, "current", None), getattr(s, "end", None),
-                                   getattr(s, "val", None))
-
-
-def _describe(cfg):
-    """Everything comparable about a Config without a GPU."""
-    out = {k: v for k, v in vars(cfg).items() if isinstance(v, PLAIN) and not k.startswith("_")}
-    out.pop("tag", None)
-    out["eps_schedule"] = _schedule(cfg.random_action_prob)
-    out["beta_schedule"] = _schedule(getattr(cfg, "replay_beta", None))
-    out["normalizers"] = (type(cfg.state_normalizer).__name__, getattr(cfg.state_normalizer, "coef", None),
-                          type(cfg.reward_normalizer).__name__)
-    out["replay_cls"] = getattr(getattr(cfg, "replay_cls", None), "__name__", None)
-    dummy = [torch.nn.Parameter(torch.zeros(3))]
-    for name in ("optimizer_fn", "actor_opt_fn", "critic_opt_fn"):
-        fn = getattr(cfg, name, None)
-        if fn is not None:
-            opt = fn(dummy)
-            out[name] = (type(opt).__name__, {k: v for k, v in opt.defaults.items() if isinstance(v, (int, float, bool, tuple))})
-    if cfg.replay_fn is not None:
-        rw = cfg.replay_fn()
-        out["replay"] = (rw.replay_cls.__name__, dict(rw.replay_kwargs), bool(rw.async_))
-    net = cfg.network_fn()
-    out["network"] = (type(net).__name__, [(k, tuple(v.shape)) for k, v in net.state_dict().items()])
-    task = cfg.task_fn()
-    out["task"] = (task.name, task.state_dim, task.action_dim, getattr(getattr(task, "env", None), "num_envs", None))
-    out["eval_env"] = (cfg.eval_env.name, getattr(getattr(cfg.eval_env, "env", None), "num_envs", None))
-    return out
-
-
-@pytest.mark.skipif(not os.path.isfile(os.path.join(REF, "examples.py")), reason="reference tree not present")
-@pytest.mark.parametrize("name", sorted(GAMES))
+@pytest.mark.parametrize("name", sorted(C.ZOO_GAMES))
 def test_zoo_entry_equals_reference_example(name):
-    import sys
     import deeprl_amd as d
-    from deeprl_amd import launch, zoo
-    saved = {k: v for k, v in sys.modules.items() if k == "deep_rl" or k.startswith("deep_rl.")}
+    from deeprl_amd import zoo
+    with open(C.CROSSCHECK_JSON) as f:
+        rec = json.load(f)["zoo"][name]
     d.select_device(-1)
-    try:
-        mod = launch.load_examples(os.path.join(REF, "examples.py"), "ref_examples_zoo")
-        got = {}
-        for a in AGENTS:
-            setattr(mod, a, lambda cfg, _a=a: (_a, cfg))
-        mod.run_steps = lambda pair: got.update(agent=pair[0], cfg=pair[1])
-        np.random.seed(0)
-        getattr(mod, name)(game=GAMES[name])
-        assert got["agent"] == zoo.ZOO[name]["agent"]
-        np.random.seed(0)
-        mine = zoo.config(name, game=GAMES[name])
-        want, have = _describe(got["cfg"]), _describe(mine)
-        have.pop("replay_kwargs", None)
-        want.pop("replay_kwargs", None)
-        assert set(want) == set(have), (sorted(set(want) ^ set(have)))
-        for k in sorted(want):
-            assert want[k] == have[k], "%s.%s: reference %r, zoo %r" % (name, k, want[k], have[k])
-    finally:
-        for k in [k for k in sys.modules if k == "deep_rl" or k.startswith("deep_rl.")]:
-            del sys.modules[k]
-        sys.modules.update(saved)
+    assert rec["agent"] == zoo.ZOO[name]["agent"]
+    np.random.seed(0)
+    want, have = rec["config"], C.describe_config(zoo.config(name, game=C.ZOO_GAMES[name]))
+    assert set(want) == set(have), (sorted(set(want) ^ set(have)))
+    for k in sorted(want):
+        assert want[k] == have[k], "%s.%s: reference %s, zoo %s" % (name, k, want[k], have[k])
 
 
 def test_launcher_runs_an_entry_with_capped_steps(tmp_path):

@@ -3,7 +3,7 @@
 TAG=$1; shift; OUT=gpurun_out/$TAG; mkdir -p $OUT; export TMPDIR=/tmp
 for rep in 1 2; do
 for kv in "$@"; do
-  env $kv python bench.py --no-cpu-baseline --no-long-run > $OUT/bench_${kv}_$rep.json 2> $OUT/bench_${kv}_$rep.err
+  env $kv python bench.py --full --no-cpu-baseline --no-long-run > $OUT/bench_${kv}_$rep.json 2> $OUT/bench_${kv}_$rep.err
   python - <<PY
 import json
 try:

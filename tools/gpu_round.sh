@@ -14,9 +14,9 @@ nproc > $OUT/nproc.txt
 rm -f gpurun_out/parity_errors.jsonl
 echo "== GPU tests"; timeout 1200 python -m pytest tests -q -m gpu -p no:cacheprovider > $OUT/pytest_gpu.log 2>&1; grep -E "^FAILED|^ERROR" $OUT/pytest_gpu.log | head -40; grep -E "passed|failed" $OUT/pytest_gpu.log | tail -2; tail -5 $OUT/pytest_gpu.log > $OUT/pytest_gpu_tail.txt
 python tools/parity_summary.py gpurun_out/parity_errors.jsonl > $OUT/parity_errors.json 2>/dev/null; head -c 600 $OUT/parity_errors.json; echo
-echo "== bench" ; timeout 500 python bench.py > $OUT/bench.json 2> $OUT/bench.err; head -c 400 $OUT/bench.json; echo
-echo "== bench (driver command)" ; timeout 500 python bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline > $OUT/bench_driver_cmd.json 2> $OUT/bench_driver_cmd.err; head -c 300 $OUT/bench_driver_cmd.json; echo
-echo "== rocprofv3 kernel trace" ; (cd /tmp && timeout 300 rocprofv3 --kernel-trace --stats -d $R/$OUT/prof -- python $R/bench.py --steps 600 --warmup 100 --no-cpu-baseline --no-parity-check > $R/$OUT/prof_bench.json 2> $R/$OUT/prof_bench.err)
+echo "== bench" ; timeout 500 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err; head -c 400 $OUT/bench.json; echo
+echo "== bench (driver command)" ; timeout 500 python bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline > $OUT/bench_driver_cmd.json 2> $OUT/bench_driver_cmd.err; head -c 300 $OUT/bench_driver_cmd.json; echo
+echo "== rocprofv3 kernel trace" ; (cd /tmp && timeout 300 rocprofv3 --kernel-trace --stats -d $R/$OUT/prof -- python $R/bench.py --full --steps 600 --warmup 100 --no-cpu-baseline --no-parity-check > $R/$OUT/prof_bench.json 2> $R/$OUT/prof_bench.err)
 python tools/prof_summary.py $OUT/prof > $OUT/rocprofv3_kernel_stats.txt 2>&1; head -32 $OUT/rocprofv3_kernel_stats.txt
 python tools/prof_timeline.py $OUT/prof 200 2 > $OUT/timeline.txt 2>&1
 find $OUT/prof -name "*.db" -size +20M -delete
@@ -41,5 +41,5 @@ echo "== NatureConv forward + backward at batch 256 / 512 / 1024, gather microbe
 python tools/bench_kernels.py > $OUT/bench_kernels.json 2> $OUT/bench_kernels.err
 echo "== prioritized agent step: kernel timeline"; (cd /tmp && timeout 200 rocprofv3 --kernel-trace -d $R/$OUT/prof_per -- python $R/tools/bench_agents.py --seconds 2 --cases dqn_pixel_per_device > $R/$OUT/prof_per.log 2>&1); python tools/prof_timeline.py $OUT/prof_per 3000 1 > $OUT/timeline_per.txt 2>&1; rm -rf $OUT/prof_per; grep -c . $OUT/timeline_per.txt
 echo "== agents bench"; timeout 400 python tools/bench_agents.py > $OUT/bench_agents.jsonl 2> $OUT/bench_agents.err; cat $OUT/bench_agents.jsonl | cut -c1-300
-echo "== launch contract: 2 ranks on this box (gloo barrier, replicas share the GPU)"; timeout 300 python bench.py --gpus 2 --steps 200 --warmup 20 --no-cpu-baseline --no-parity-check > $OUT/bench_2rank_one_box.json 2> $OUT/bench_2rank_one_box.err; head -c 300 $OUT/bench_2rank_one_box.json; echo
+echo "== launch contract: 2 ranks on this box (gloo barrier, replicas share the GPU)"; timeout 300 python bench.py --full --gpus 2 --steps 200 --warmup 20 --no-cpu-baseline --no-parity-check > $OUT/bench_2rank_one_box.json 2> $OUT/bench_2rank_one_box.err; head -c 300 $OUT/bench_2rank_one_box.json; echo
 echo "== done"
