@@ -1399,6 +1399,129 @@ class A2CAgent(BaseAgent):
         self.last_loss = self._learn(seen, actions, values, rewards_l, masks_l)
 
 
+class _QRollout:
+    """NStepDQNAgent's device path over VanillaNet(NatureConvBody) and device-resident synthetic Atari environments.  Per rollout
+    step the four launches of _PixelRollout with the Q head in conv1's launch (dra_rollout_conv1_qheads: [conv1 of step t | fc4's
+    fold + Q head + epsilon-greedy selection of step t - 1], conv2, conv3, fc4's 28 K-slice partial sums); step T is the TARGET
+    network's forward of the last observation (its conv1 launch carries the online head of step T - 1), then its max head
+    (dra_q_heads_fold28, NStepDQN_agent.py:56-57).  The update: returns, loss and the Q head's backward in one launch
+    (dra_nstep_q_loss_bwd), fc4 and the convolutions backpropagate through the activations the rollout stored (the reference keeps
+    the rollout's own forward graph, NStepDQN_agent.py:33-67), then the fused clip + optimizer step."""
+
+    def __init__(self, agent):
+        self.agent = agent
+        self.bufs = None
+        self.stage, self.events, self.k = None, None, 0
+
+    def eligible(self):
+        from .device_env import DeviceAtariVec
+        from .nets import Conv2d, Linear, NatureConvBody, VanillaNet
+        a = self.agent
+        net, cfg = a.network, a.config
+        if getattr(cfg, 'fused_rollout', True) is False or not DeviceAtariVec.eligible(a.task, cfg):
+            return False
+        if torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1:
+            return False        # data-parallel n-step DQN keeps the host path
+        if type(net) is not VanillaNet or type(net.body) is not NatureConvBody or getattr(net.body, 'noisy_linear', False):
+            return False
+        body = net.body
+        convs = [body.conv1, body.conv2, body.conv3]
+        if not all(type(c) is Conv2d and c.bias is not None and c.weight.permute(1, 2, 3, 0).is_contiguous() for c in convs):
+            return False
+        heads = [body.fc4, net.fc_head]
+        if not all(type(m) is Linear and m.bias is not None and m.weight.is_contiguous() for m in heads):
+            return False
+        envs = a.task.env.envs
+        n = len(envs)
+        return (body.fc4.fused_act == "relu" and tuple(body.fc4.weight.shape) == (512, 3136) and net.fc_head.fused_act is None
+                and 1 <= net.fc_head.weight.shape[0] <= 64 and envs[0].history == 4 and n <= 32
+                and int(cfg.rollout_length) * n <= 2048 and int(cfg.num_workers) == n)
+
+    def upload_exploration(self, t_len):
+        """Draws the rollout's exploration (support.plan_epsilon_greedy) and stages it into the persistent device buffers the
+        Q-head launches read (fixed addresses: graph replays see the new values)."""
+        from .support import plan_epsilon_greedy
+        a = self.agent
+        n, n_act = a.task.num_envs, int(a.network.fc_head.weight.shape[0])
+        explore, rand = plan_epsilon_greedy(a.config.random_action_prob, t_len, n, n_act, a.config.num_workers)
+        if self.stage is None or self.stage[0][0].shape[0] != t_len:
+            dev = Config.DEVICE
+            self.explore = torch.zeros((t_len, n), dtype=torch.uint8, device=dev)
+            self.random_action = torch.zeros((t_len, n), dtype=torch.int64, device=dev)
+            self.stage = [(torch.zeros((t_len, n), dtype=torch.uint8).pin_memory(), torch.zeros((t_len, n), dtype=torch.int64).pin_memory())
+                          for _ in range(4)]
+            self.events = [None] * 4
+        k = self.k
+        self.k = (k + 1) % len(self.stage)
+        if self.events[k] is not None:
+            self.events[k].synchronize()
+        e_h, r_h = self.stage[k]
+        e_h.numpy()[...] = explore
+        r_h.numpy()[...] = rand
+        self.explore.copy_(e_h, non_blocking=True)
+        self.random_action.copy_(r_h, non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record()
+        self.events[k] = ev
+
+    def _buffers(self, t_len, n, n_act):
+        if self.bufs is None or self.bufs['key'] != (t_len, n, n_act):
+            dev = Config.DEVICE
+            f = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+            self.bufs = dict(key=(t_len, n, n_act), y1=f(t_len + 1, n, 32, 20, 20), y2=f(t_len + 1, n, 64, 9, 9),
+                             y3=f(t_len + 1, n, 64, 7, 7), slabs=f(28, n, 512), phi=f(t_len, n, 512), q=f(t_len, n, n_act),
+                             action=torch.empty((t_len, n), dtype=torch.int64, device=dev), bootstrap=f(n))
+        return self.bufs
+
+    def compute(self, plan):
+        import ctypes
+        from ._lib import lib, stream_ptr
+        from .nets import _claim_direct, direct_param_grads, fc4_from_rollout
+        a = self.agent
+        cfg = a.config
+        net, tgt = a.network, a.target_network
+        t_len, n = plan.t_len, a.task.num_envs
+        head = net.fc_head
+        n_act = int(head.weight.shape[0])
+        b = self._buffers(t_len, n, n_act)
+        frames = a.task.states_all(plan)           # every observation of the planned rollout, one launch
+        coef = float(net.body.conv1.u8_coef)
+        arr = lambda t: (ctypes.c_void_p * 1)(t.data_ptr())
+        st = stream_ptr()
+        relu = ops.ACT["relu"]
+        online, target = net.body, tgt.body
+        for t in range(t_len + 1):
+            body = target if t == t_len else online
+            prev = t > 0
+            ops.rollout_conv1_qheads(frames[t], body.conv1.weight, body.conv1.bias, b['y1'][t], coef,
+                                     *((b['slabs'], online.fc4.bias, head.weight, head.bias, self.explore[t - 1],
+                                        self.random_action[t - 1], b['q'][t - 1], b['action'][t - 1], b['phi'][t - 1]) if prev else ()))
+            lib.dra_conv_fwd_koc(2, 1, arr(b['y1'][t]), arr(body.conv2.weight), arr(body.conv2.bias), arr(b['y2'][t]), n, 0, 1.0, relu, st)
+            lib.dra_conv_fwd_koc(3, 1, arr(b['y2'][t]), arr(body.conv3.weight), arr(body.conv3.bias), arr(b['y3'][t]), n, 0, 1.0, relu, st)
+            lib.dra_linear_fwd_slabs_one(1, arr(b['y3'][t]), arr(body.fc4.weight), n, 3136, 512, 28, ctypes.c_void_p(b['slabs'].data_ptr()), st)
+        ops.q_heads_fold28(b['slabs'], target.fc4.bias, tgt.fc_head.weight, tgt.fc_head.bias, out_max=b['bootstrap'])
+        a._rollout_step += t_len
+        # ---- the update over the rollout's own activations (the conv layers' _y_pre, fc4's stored output)
+        rows = t_len * n
+        for conv, key in ((online.conv1, 'y1'), (online.conv2, 'y2'), (online.conv3, 'y3')):
+            y = b[key][:t_len]
+            conv._y_pre = y.reshape((rows,) + tuple(y.shape[2:]))
+        y3 = online.conv3(online.conv2(online.conv1(frames[:t_len].reshape((rows,) + tuple(frames.shape[2:])))))
+        phi = fc4_from_rollout(online, y3.view(rows, -1), b['phi'].view(rows, 512))
+        a._fused.zero_grad(direct=True)
+        defer = a._fused if getattr(cfg, 'defer_conv_folds', True) else None
+        with direct_param_grads(True, defer_folds_to=defer, covers=[a._fused]):
+            _claim_direct((head.weight, head.bias))       # the loss launch writes the Q head's gradient in place
+            out = ops.nstep_q_loss_bwd(b['q'], b['action'], plan.reward, plan.mask, b['bootstrap'], cfg.discount, b['phi'].view(rows, 512),
+                                       head.weight, out=dict(ret=torch.empty((t_len, n), dtype=torch.float32, device=frames.device),
+                                                             loss=torch.empty(1, dtype=torch.float32, device=frames.device),
+                                                             dw=head.weight.grad, db=head.bias.grad,
+                                                             dphi=torch.empty((rows, 512), dtype=torch.float32, device=frames.device)))
+            torch.autograd.backward([phi], [out['dphi']])
+        a._fused.step(cfg.gradient_clip)
+        return dict(loss=out['loss'], ret=out['ret'], q=b['q'], action=b['action'], bootstrap=b['bootstrap'])
+
+
 class NStepDQNAgent(BaseAgent):
     """NStepDQN_agent.py:12-67: on-policy n-step Q-learning; returns via the scan kernel (use_gae off)."""
 
@@ -1414,9 +1537,42 @@ class NStepDQNAgent(BaseAgent):
                                        koc=nature_conv_weights(list(self.target_network.parameters())))
         ops.copy_f32(self._target_flat.flat, self._fused.flat.flat)
         self.total_steps = 0
+        self.grad_hook = None
+        self._rollout_step = 0
+        self._q_rollout = _QRollout(self)
+        if self._q_rollout.eligible():      # synthetic Atari emulators + VanillaNet(NatureConvBody): the rollout lives on the device
+            from .device_env import DeviceAtariVec
+            self.task = DeviceAtariVec(self.task)
+            self.network.body.conv1.u8_coef = float(config.state_normalizer.coef)
+        self._dev_graph = _OnPolicyGraph(self)
+        self.last_rollout = None
         self.states = self.task.reset()
 
+    def _step_device(self):
+        """step() over device-resident environments: the host lays the rollout out (DeviceAtariVec.plan) and draws its exploration
+        in the reference's order (support.plan_epsilon_greedy); the T Q-head forwards, the target network's bootstrap, the loss, the
+        backward over the rollout's own activations, clip and optimizer step are enqueued without a host round trip and, after two
+        eager rollouts, replayed as ONE captured graph (_QRollout.compute).  The target copy of NStepDQN_agent.py:48-50 runs
+        before the rollout: the parameters do not change inside one, so copying then gives the bootstrap copying at step t gives."""
+        config = self.config
+        t_len = config.rollout_length
+        plan = self.task.plan(t_len, config.reward_normalizer)
+        self._q_rollout.upload_exploration(t_len)
+        sync = False
+        for t in range(t_len):
+            self.record_online_return(plan.infos[t])
+            self.total_steps += config.num_workers
+            if self.total_steps // config.num_workers % config.target_network_update_freq == 0:
+                sync = True
+        if sync:
+            ops.copy_f32(self._target_flat.flat, self._fused.flat.flat)
+        out = self._dev_graph.run(plan, self._q_rollout.compute)
+        self.last_loss = out['loss']
+        self.last_rollout = out
+
     def step(self):
+        if getattr(self.task, 'on_device', False):
+            return self._step_device()
         config = self.config
         storage = Storage(config.rollout_length)
         states = self.states

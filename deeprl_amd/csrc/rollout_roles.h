@@ -118,15 +118,18 @@ __device__ __forceinline__ void policy_head_row(const PolicyHeadArgs& h, int b, 
 // 13.2 us, tools/fc4_small_probe.py -- its finish happens here, and in a rollout this head rides in the NEXT step's conv1 launch,
 // where the fold's loads cost nothing on the chain): thread t folds features t and t + 256 (2 KS loads in flight, slab 0 first, +
 // bias, ReLU: linear_finish_kernel's sum) into LDS, then wave 0 runs the head on them.  s_phi: 512 floats, so: >= A + 1 floats.
+// The fold itself (thread t < 256 of the row's workgroup: features t and t + 256 into s_phi, and out_x[b] when given) -- shared by
+// the policy head below and the Q head of an n-step DQN rollout (q_head_row_fold_wg): the same features, bit for bit.  K = 512.
 template <int KS>
-__device__ __forceinline__ void policy_head_row_fold_wg(const PolicyHeadArgs& h, int b, float* s_phi, float* so) {
+__device__ __forceinline__ void fold_row_slabs_wg(const float* __restrict__ slabs, const float* __restrict__ fold_bias, int B, int K,
+                                                  int b, float* s_phi, float* out_x) {
   const int t = threadIdx.x;
   float part[2][KS];
 #pragma unroll
   for (int j = 0; j < 2; ++j) {
-    const float* sl = h.slabs + (int64_t)b * h.K + t + 256 * j;
+    const float* sl = slabs + (int64_t)b * K + t + 256 * j;
 #pragma unroll
-    for (int s = 0; s < KS; ++s) part[j][s] = sl[(int64_t)s * h.B * h.K];
+    for (int s = 0; s < KS; ++s) part[j][s] = sl[(int64_t)s * B * K];
   }
 #pragma unroll
   for (int j = 0; j < 2; ++j) {
@@ -134,10 +137,16 @@ __device__ __forceinline__ void policy_head_row_fold_wg(const PolicyHeadArgs& h,
     float v = part[j][0];
 #pragma unroll
     for (int s = 1; s < KS; ++s) v += part[j][s];
-    v = rr_act(v + h.fold_bias[k], DRA_ACT_RELU);
+    v = rr_act(v + fold_bias[k], DRA_ACT_RELU);
     s_phi[k] = v;
-    if (h.out_x) h.out_x[(int64_t)b * h.K + k] = v;
+    if (out_x) out_x[(int64_t)b * K + k] = v;
   }
+}
+
+template <int KS>
+__device__ __forceinline__ void policy_head_row_fold_wg(const PolicyHeadArgs& h, int b, float* s_phi, float* so) {
+  const int t = threadIdx.x;
+  fold_row_slabs_wg<KS>(h.slabs, h.fold_bias, h.B, h.K, b, s_phi, h.out_x);
   __syncthreads();
   if (t >= 64) return;
   const int lane = t;
@@ -154,6 +163,45 @@ __device__ __forceinline__ void policy_head_row_fold_wg(const PolicyHeadArgs& h,
     h.out_v[b] = so[h.A];
     if (h.out_logits)
       for (int a = 0; a < h.A; ++a) h.out_logits[(int64_t)b * h.A + a] = so[a];
+  }
+}
+
+// The Q head of an n-step DQN rollout step (NStepDQN_agent.py:33-36: q = network(states)['q'], epsilon_greedy(epsilon, q)) for ONE
+// row per workgroup of four waves, its features folded from fc4's KS K-slice partial sums first (fold_row_slabs_wg: the A2C head's
+// fold, bit for bit): q = phi W^T + b [A <= 64] (heads_row_outputs_from), the first index of the row's maximum (np.argmax: exact
+// ties go to the lower index, a NaN wins), and the behaviour action explore[b] ? random_action[b] : argmax -- both planned on the
+// host in the reference's draw order, so no random draw and no compare against epsilon happens here.  Every output is optional:
+// out_phi [B][512], out_q [B][A], out_action [B] (needs explore / random_action), out_max [B] = max_a q (the bootstrap of the
+// target network, NStepDQN_agent.py:56-57).  s_phi: 512 floats, so: >= A floats.
+struct QHeadArgs {
+  const float *slabs, *fold_bias, *w, *b;
+  const uint8_t* explore;
+  const int64_t* random_action;
+  float *out_phi, *out_q, *out_max;
+  int64_t* out_action;
+  int B, A;
+};
+template <int KS>
+__device__ __forceinline__ void q_head_row_fold_wg(const QHeadArgs& h, int b, float* s_phi, float* so) {
+  const int t = threadIdx.x;
+  fold_row_slabs_wg<KS>(h.slabs, h.fold_bias, h.B, 512, b, s_phi, h.out_phi);
+  __syncthreads();
+  if (t >= 64) return;
+  const int lane = t;
+  heads_row_outputs_from([&](int k) { return s_phi[k]; }, h.w, h.b, h.A, nullptr, nullptr, 0, 512, /*act=*/0, lane,
+                         [&](int o, float v) { so[o] = v; });
+  if (lane == 0) {      // (the same lane wrote so[]: program order, no barrier)
+    float best = so[0];
+    int arg = 0;
+    for (int a = 1; a < h.A; ++a) {
+      if (best != best) break;                        // NaN: np.argmax stops at the first one
+      const float v = so[a];
+      if (v > best || v != v) { best = v; arg = a; }
+    }
+    if (h.out_q)
+      for (int a = 0; a < h.A; ++a) h.out_q[(int64_t)b * h.A + a] = so[a];
+    if (h.out_max) h.out_max[b] = best;
+    if (h.out_action) h.out_action[b] = h.explore[b] ? h.random_action[b] : (int64_t)arg;
   }
 }
 

@@ -274,6 +274,36 @@ class _Fc4PolicyHeadFn(torch.autograd.Function):
         return (dy3,) + ((None, None) if direct_4 else (dw4, db4)) + ((None,) * 4 if direct_h else (dw0, db0, dw1, db1)) + (None, None)
 
 
+class _Fc4FromRolloutFn(torch.autograd.Function):
+    """NatureConvBody's fc4 (+ ReLU) for a batch whose output the rollout already computed (phi_pre: an n-step DQN rollout's folded
+    features, kept by its Q-head launches): no launch forward; backward = fc4's one launch (input and weight gradients) from the
+    gradient of the PRE-activation (the caller's dphi carries the ReLU mask already: ops.nstep_q_loss_bwd)."""
+
+    @staticmethod
+    def forward(ctx, y3, w4, b4, phi_pre):
+        ctx.save_for_backward(y3, w4)
+        ctx.params = (w4, b4)
+        return phi_pre.view_as(phi_pre)
+
+    @staticmethod
+    def backward(ctx, dpre):
+        y3, w4 = ctx.saved_tensors
+        direct = _claim_direct(ctx.params)
+        g4 = [_grad_slot(p) if direct else None for p in ctx.params]
+        direct = all(g is not None and g.is_contiguous() for g in g4)
+        _SHARED[0] = _SHARED[0] or not direct
+        dy3, dw4, db4 = ops.linear_bwd_xw_512(dpre.contiguous(), y3, w4, True, *((g4[0], g4[1]) if direct else ()))
+        _mark_masked(dy3)
+        if not ctx.needs_input_grad[0]:
+            dy3 = None
+        return (dy3,) + ((None, None) if direct else (dw4, db4)) + (None,)
+
+
+def fc4_from_rollout(body, y3, phi_pre):
+    """body.fc4 applied to y3 [B, 3136] inside an autograd graph, its output being phi_pre [B, 512] (see _Fc4FromRolloutFn)."""
+    return _Fc4FromRolloutFn.apply(y3, body.fc4.weight, body.fc4.bias, phi_pre)
+
+
 class _CategoricalFn(torch.autograd.Function):
     """Categorical(logits) -> (log_pi_a, entropy) for given actions as one kernel each way (losses.hip K12)."""
 

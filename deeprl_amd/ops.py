@@ -721,6 +721,69 @@ def fc4_policy_heads_sample(y3, w4, b4, w0, b0, w1, b1, uniform, out=None):
     return a, lp, ent, v
 
 
+def _check_rows(name, batch, **tensors):
+    for k, (t, dt, n) in tensors.items():
+        if t is not None and (t.dtype != dt or t.numel() != n or not t.is_contiguous() or not t.is_cuda):
+            raise ValueError("%s: %s must be a contiguous device %s tensor of %d elements" % (name, k, dt, n))
+
+
+def q_heads_fold28(slabs, fold_bias, w, b, explore=None, random_action=None, out_q=None, out_action=None, out_phi=None,
+                   out_max=None):
+    """The Q head of an n-step DQN rollout step on fc4's 28 K-slice partial sums slabs [28, B, 512] in one launch (one workgroup
+    per row): phi = relu(sum of slices + fold_bias) -> out_phi, q = phi W^T + b -> out_q [B, A], action = explore ? random_action :
+    argmax q (first index of the maximum) -> out_action i64 [B], max_a q -> out_max [B].  Outputs are written in place."""
+    slabs, fold_bias, w = _c(slabs, _f32), _c(fold_bias, _f32), _c(w, _f32)
+    b = None if b is None else _c(b, _f32)
+    batch, a = int(slabs.shape[1]), int(w.shape[0])
+    if tuple(slabs.shape) != (28, batch, 512) or tuple(w.shape) != (a, 512):
+        raise ValueError("q_heads_fold28: slabs [28, B, 512], w [A, 512]")
+    _check_rows("q_heads_fold28", batch, explore=(explore, torch.uint8, batch), random_action=(random_action, torch.int64, batch),
+                out_q=(out_q, _f32, batch * a), out_action=(out_action, torch.int64, batch), out_phi=(out_phi, _f32, batch * 512),
+                out_max=(out_max, _f32, batch))
+    lib.dra_q_heads_fold28(ptr(slabs), ptr(fold_bias), ptr(w), ptr(b), ptr(explore), ptr(random_action), batch, a, ptr(out_q),
+                           ptr(out_action), ptr(out_phi), ptr(out_max), stream_ptr())
+
+
+def rollout_conv1_qheads(frames_u8, w1_koc, b1, y1, u8_coef, slabs_prev=None, fold_bias=None, w=None, b=None, explore=None,
+                         random_action=None, out_q=None, out_action=None, out_phi=None):
+    """conv1 (+ ReLU) of uint8 frames [B, 4, 84, 84] into y1 [B, 32, 20, 20] and -- slabs_prev given -- the previous step's Q head
+    (q_heads_fold28's q / action / phi outputs) in the same launch."""
+    batch = int(frames_u8.shape[0])
+    a = 0 if w is None else int(w.shape[0])
+    if frames_u8.dtype != torch.uint8 or not frames_u8.is_contiguous() or not y1.is_contiguous():
+        raise ValueError("rollout_conv1_qheads: contiguous uint8 frames and f32 output")
+    if slabs_prev is not None:
+        _check_rows("rollout_conv1_qheads", batch, slabs_prev=(slabs_prev, _f32, 28 * batch * 512), fold_bias=(fold_bias, _f32, 512),
+                    w=(w, _f32, a * 512), explore=(explore, torch.uint8, batch), random_action=(random_action, torch.int64, batch),
+                    out_q=(out_q, _f32, batch * a), out_action=(out_action, torch.int64, batch), out_phi=(out_phi, _f32, batch * 512))
+    lib.dra_rollout_conv1_qheads(ptr(frames_u8), ptr(w1_koc), ptr(b1), ptr(y1), batch, float(u8_coef), ptr(slabs_prev), ptr(fold_bias),
+                                 ptr(w), ptr(b), ptr(explore), ptr(random_action), a, ptr(out_q), ptr(out_action), ptr(out_phi),
+                                 stream_ptr())
+
+
+def nstep_q_loss_bwd(q, action, reward, mask, bootstrap, gamma, phi, w, out=None):
+    """NStepDQN_agent.py:56-67's returns, loss and the Q head's backward in ONE launch: q [T, N, A], action i64 [T, N], reward /
+    mask [T, N] (any trailing 1), bootstrap [N], phi [T * N, 512], w [A, 512] -> dict(ret [T, N], loss [1], dw [A, 512], db [A],
+    dphi [T * N, 512] (times fc4's ReLU mask)).  out: the same dict of preallocated tensors (dw / db may be gradient slots)."""
+    q, action, phi, w = _c(q, _f32), _c(action, torch.int64), _c(phi, _f32), _c(w, _f32)
+    reward, mask, bootstrap = _c(reward, _f32), _c(mask, _f32), _c(bootstrap, _f32)
+    t_len, n, a = int(q.shape[0]), int(q.shape[1]), int(q.shape[2])
+    rows = t_len * n
+    if (action.numel() != rows or reward.numel() != rows or mask.numel() != rows or bootstrap.numel() != n
+            or tuple(phi.shape) != (rows, 512) or tuple(w.shape) != (a, 512)):
+        raise ValueError("nstep_q_loss_bwd: inconsistent shapes")
+    dev = q.device
+    if out is None:
+        out = dict(ret=torch.empty((t_len, n), dtype=_f32, device=dev), loss=torch.empty(1, dtype=_f32, device=dev),
+                   dw=torch.empty((a, 512), dtype=_f32, device=dev), db=torch.empty(a, dtype=_f32, device=dev),
+                   dphi=torch.empty((rows, 512), dtype=_f32, device=dev))
+    _check_rows("nstep_q_loss_bwd", rows, ret=(out['ret'], _f32, rows), loss=(out['loss'], _f32, 1), dw=(out['dw'], _f32, a * 512),
+                db=(out['db'], _f32, a), dphi=(out['dphi'], _f32, rows * 512))
+    lib.dra_nstep_q_loss_bwd(ptr(q), ptr(action), ptr(reward), ptr(mask), ptr(bootstrap), float(gamma), ptr(phi), ptr(w), t_len, n, a,
+                             ptr(out['ret']), ptr(out['loss']), ptr(out['dw']), ptr(out['db']), ptr(out['dphi']), stream_ptr())
+    return out
+
+
 HEADS_BWD_MAX_BATCH = 8192
 
 

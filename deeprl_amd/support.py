@@ -126,6 +126,21 @@ def epsilon_greedy(epsilon, x):
         return np.where(dice < epsilon, random_actions, greedy_actions)
 
 
+def plan_epsilon_greedy(schedule, t_len, n_rows, n_actions, schedule_steps=1):
+    """The exploration of t_len consecutive 2-D epsilon_greedy calls drawn up front: per step, schedule(schedule_steps) (what
+    NStepDQN_agent.py:35 calls before each epsilon_greedy), then randint(n_actions, size=n_rows), then rand(n_rows) -- the
+    reference's draw order, neither draw depending on q -- so the generator ends where the step-by-step calls leave it.
+    -> (explore bool [t_len, n_rows] = dice < epsilon in float64, random_action int64 [t_len, n_rows]); the action of row b at
+    step t is random_action[t, b] where explore[t, b], else np.argmax(q_t[b])."""
+    explore = np.empty((t_len, n_rows), dtype=np.bool_)
+    random_action = np.empty((t_len, n_rows), dtype=np.int64)
+    for t in range(t_len):
+        epsilon = schedule(schedule_steps)
+        random_action[t] = np.random.randint(n_actions, size=n_rows)
+        explore[t] = np.random.rand(n_rows) < epsilon
+    return explore, random_action
+
+
 # ----------------------------------------------------------------------------------------------------
 # schedules (deep_rl/utils/schedule.py:7-31)
 class ConstantSchedule:

@@ -79,6 +79,14 @@ ZOO = {
         fields=dict(discount=0.99, use_gae=True, gae_tau=1.0, entropy_weight=0.01, rollout_length=5, gradient_clip=5,
                     max_steps=int(2e7)),
         normalizers=(ImageNormalizer, SignNormalizer)),
+    # examples.py:427-447
+    "n_step_dqn_pixel": dict(
+        agent="NStepDQNAgent", kw=dict(log_level=0), pre_fields=dict(num_workers=16),
+        task=lambda c: Task(c.game, num_envs=c.num_workers), eval_task=lambda c: Task(c.game),
+        optimizer=_rmsprop(lr=1e-4, alpha=0.99, eps=1e-5),
+        network=lambda c: N.VanillaNet(c.action_dim, N.NatureConvBody()),
+        fields=dict(discount=0.99, target_network_update_freq=10000, rollout_length=5, gradient_clip=5, max_steps=int(2e7)),
+        eps=(1.0, 0.05, 1e6), normalizers=(ImageNormalizer, SignNormalizer)),
     # examples.py:525-550
     "ppo_pixel": dict(
         agent="PPOAgent", kw=dict(skip=False), pre_fields=dict(num_workers=8),

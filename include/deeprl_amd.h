@@ -471,6 +471,33 @@ int dra_rollout_conv1_heads_phi(const void* frames_u8, const float* wt1, const f
                                 const float* b_v, const float* uniform, int n_actions, int64_t* out_action, float* out_log_pi_a,
                                 float* out_entropy, float* out_v, float* out_phi, void* stream);
 
+/* ---- n-step DQN on pixels over a device-resident rollout (NStepDQN_agent.py:12-67; agents.NStepDQNAgent): each rollout step is
+ * the four launches above with a Q head in place of the policy head, exploration planned on the host in the reference's draw
+ * order (epsilon_greedy, torch_utils.py:51-59: randint(A, size=N), then rand(N); explore = dice < epsilon), then the target
+ * network's forward of the last observation, its max head, and the update's loss + Q-head backward in one launch. */
+/* conv1 (+ ReLU) of uint8 frames [batch][4][84][84] -> y1, and, when slabs_prev != NULL, the Q head of the previous step in the
+ * same launch (NStepDQN_agent.py:33-36): phi = relu(fold_bias + sum of fc4's 28 K-slice partial sums slabs_prev [28][batch][512],
+ * slab 0 first -- the A2C head's fold, bit for bit) -> out_phi [batch][512] (optional), q = phi W^T + b [batch][n_actions <= 64]
+ * -> out_q (optional), action = explore[b] ? random_action[b] : the first index of the row's maximum (np.argmax) -> out_action */
+int dra_rollout_conv1_qheads(const void* frames_u8, const float* wt1, const float* b1, float* y1, int batch, double u8_coef,
+                             const float* slabs_prev, const float* fold_bias, const float* w_q, const float* b_q,
+                             const uint8_t* explore, const int64_t* random_action, int n_actions, float* out_q,
+                             int64_t* out_action, float* out_phi, void* stream);
+/* the same Q head on its own (the last step of a rollout), one workgroup per row; every output optional: out_q, out_action (needs
+ * explore / random_action), out_phi, and out_max [batch] = max_a q -- the "max" mode that bootstraps from the target network
+ * (NStepDQN_agent.py:56-57) */
+int dra_q_heads_fold28(const float* slabs, const float* fold_bias, const float* w_q, const float* b_q, const uint8_t* explore,
+                       const int64_t* random_action, int batch, int n_actions, float* out_q, int64_t* out_action, float* out_phi,
+                       float* out_max, void* stream);
+/* the update of one rollout (NStepDQN_agent.py:56-67) in one launch over R = t_len x n_env <= 2048 rows (t-major): ret [t_len][n_env]
+ * by the reference's recurrence ret = r + gamma m ret backwards from bootstrap [n_env]; out_loss [1] = 0.5 mean (q[r][a_r] - ret_r)^2
+ * (q [R][n_actions], action i64 [R]); the gradient of that loss through the Q head on the rollout's features phi [R][512]:
+ * dw_q [n_actions][512], db_q [n_actions] (fixed-order sums over the rows, no atomics) and dphi [R][512] times [phi > 0] (fc4's
+ * ReLU) for fc4's backward */
+int dra_nstep_q_loss_bwd(const float* q, const int64_t* action, const float* reward, const float* mask, const float* bootstrap,
+                         double gamma, const float* phi, const float* w_q, int t_len, int n_env, int n_actions, float* out_ret,
+                         float* out_loss, float* dw_q, float* db_q, float* dphi, void* stream);
+
 /* ---- fused DQN learner + device-resident actor: DQN_agent.py:24-45 (actor step), :114-138 (update) for
  * VanillaNet(NatureConvBody).  All five flat buffers are caller-owned f32[n_params] with the tensor order
  * conv1.w, conv1.b, conv2.w, conv2.b, conv3.w, conv3.b, fc4.w, fc4.b, head.w, head.b at `offset[]` (16-byte
