@@ -2337,6 +2337,158 @@ class TD3Agent(_DeterministicPolicyAgent):
 
 
 # ==================================================================================================== option-critic
+class _OCRollout:
+    """OptionCriticAgent's device path over OptionCriticNet(NatureConvBody) and device-resident synthetic Atari environments.  Per
+    rollout step the four launches of _PixelRollout with the option-critic head in conv1's launch (dra_rollout_conv1_ocheads:
+    [conv1 of step t | fc4's fold + q / beta / intra-option logits + option and action choice of step t - 1], conv2, conv3, fc4's
+    28 K-slice partial sums); step T is the TARGET network's forward of the last observation (its conv1 launch carries the online
+    head of step T - 1), then its bootstrap head (dra_oc_heads_fold28, OptionCritic_agent.py:87-93).  The update: returns,
+    advantages, the three losses and the heads' backward in one launch (dra_oc_loss_bwd), fc4 and the convolutions backpropagate
+    through the activations the rollout stored, then the fused clip + optimizer step.  The carried option state (prev_option,
+    is_initial) lives in persistent device buffers the head launches read and replace.  Random draws: one uniform_() [T, N, 3] per
+    rollout on torch's device generator (draw_uniforms, before the captured region), turned into options and actions by inverse
+    CDF -- the documented deviation of A2C's RolloutSlots: Categorical.sample()'s own stream is not reproduced."""
+
+    def __init__(self, agent):
+        self.agent = agent
+        self.bufs = None
+        self.stage, self.events, self.k = None, None, 0
+        self.uniform = None
+        self.eps = None
+
+    def eligible(self):
+        from .device_env import DeviceAtariVec
+        from .nets import Conv2d, Linear, NatureConvBody, OptionCriticNet
+        a = self.agent
+        net, cfg = a.network, a.config
+        if getattr(cfg, 'fused_rollout', True) is False or not DeviceAtariVec.eligible(a.task, cfg):
+            return False
+        if torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1:
+            return False        # data-parallel option-critic keeps the host path
+        if type(net) is not OptionCriticNet or type(net.body) is not NatureConvBody or getattr(net.body, 'noisy_linear', False):
+            return False
+        body = net.body
+        convs = [body.conv1, body.conv2, body.conv3]
+        if not all(type(c) is Conv2d and c.bias is not None and c.weight.permute(1, 2, 3, 0).is_contiguous() for c in convs):
+            return False
+        heads = [net.fc_q, net.fc_pi, net.fc_beta]
+        if not all(type(m) is Linear and m.bias is not None and m.weight.is_contiguous() and m.fused_act is None for m in heads):
+            return False
+        if not (type(body.fc4) is Linear and body.fc4.bias is not None and body.fc4.weight.is_contiguous()):
+            return False
+        n_opt, n_act = int(net.num_options), int(net.action_dim)
+        envs = a.task.env.envs
+        n = len(envs)
+        return (body.fc4.fused_act == "relu" and tuple(body.fc4.weight.shape) == (512, 3136) and 1 <= n_opt <= 8
+                and 1 <= n_act <= 18 and tuple(net.fc_q.weight.shape) == (n_opt, 512)
+                and tuple(net.fc_beta.weight.shape) == (n_opt, 512) and tuple(net.fc_pi.weight.shape) == (n_opt * n_act, 512)
+                and envs[0].history == 4 and n <= 32 and int(cfg.rollout_length) * n <= 2048 and int(cfg.num_workers) == n)
+
+    def state(self, n):
+        """The carried option state (OptionCritic_agent.py:26-27: ones at the start): persistent device buffers."""
+        dev = Config.DEVICE
+        self.prev_option = torch.ones(n, dtype=torch.int64, device=dev)
+        self.is_initial = torch.ones(n, dtype=torch.bool, device=dev)
+        return self.prev_option, self.is_initial
+
+    def upload_exploration(self, t_len):
+        """config.random_option_prob(num_workers) once per rollout step -- the reference's calls in its order -- staged into the
+        persistent [T] buffer the head launches read (a fixed address: graph replays see the new values).  -> the host values."""
+        a = self.agent
+        eps = np.asarray([a.config.random_option_prob(a.config.num_workers) for _ in range(t_len)], dtype=np.float64)
+        if self.stage is None or self.stage[0].shape[0] != t_len:
+            self.eps = torch.zeros(t_len, dtype=torch.float32, device=Config.DEVICE)
+            self.stage = [torch.zeros(t_len, dtype=torch.float32).pin_memory() for _ in range(4)]
+            self.events = [None] * 4
+        k = self.k
+        self.k = (k + 1) % len(self.stage)
+        if self.events[k] is not None:
+            self.events[k].synchronize()
+        self.stage[k].numpy()[...] = eps
+        self.eps.copy_(self.stage[k], non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record()
+        self.events[k] = ev
+        return eps
+
+    def draw_uniforms(self, t_len):
+        """One uniform_() [T, N, 3] on torch's device generator into a persistent buffer (columns: fresh option, continued option,
+        action).  Runs before the captured region, so replays read the new draw at the same address."""
+        n = self.agent.task.num_envs
+        if self.uniform is None or self.uniform.shape[0] != t_len:
+            self.uniform = torch.empty((t_len, n, 3), dtype=torch.float32, device=Config.DEVICE)
+        self.uniform.uniform_()
+
+    def _buffers(self, t_len, n, n_opt, n_act):
+        if self.bufs is None or self.bufs['key'] != (t_len, n, n_opt, n_act):
+            dev = Config.DEVICE
+            f = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+            i = lambda *shape: torch.empty(shape, dtype=torch.int64, device=dev)
+            self.bufs = dict(key=(t_len, n, n_opt, n_act), y1=f(t_len + 1, n, 32, 20, 20), y2=f(t_len + 1, n, 64, 9, 9),
+                             y3=f(t_len + 1, n, 64, 7, 7), slabs=f(28, n, 512), phi=f(t_len, n, 512), q=f(t_len, n, n_opt),
+                             beta=f(t_len, n, n_opt), logits=f(t_len, n, n_act), option=i(t_len, n), action=i(t_len, n),
+                             log_pi_a=f(t_len, n), entropy=f(t_len, n), prev_option=i(t_len, n), init=f(t_len, n), boot=f(n))
+        return self.bufs
+
+    def compute(self, plan):
+        import ctypes
+        from ._lib import lib, stream_ptr
+        from .nets import _claim_direct, direct_param_grads, fc4_from_rollout
+        a = self.agent
+        cfg = a.config
+        net, tgt = a.network, a.target_network
+        t_len, n = plan.t_len, a.task.num_envs
+        n_opt, n_act = int(net.num_options), int(net.action_dim)
+        b = self._buffers(t_len, n, n_opt, n_act)
+        frames = a.task.states_all(plan)           # every observation of the planned rollout, one launch
+        coef = float(net.body.conv1.u8_coef)
+        arr = lambda t: (ctypes.c_void_p * 1)(t.data_ptr())
+        st = stream_ptr()
+        relu = ops.ACT["relu"]
+        online, target = net.body, tgt.body
+        heads = (net.fc_q.weight, net.fc_q.bias, net.fc_beta.weight, net.fc_beta.bias, net.fc_pi.weight, net.fc_pi.bias)
+        keys = ("q", "beta", "logits", "option", "action", "log_pi_a", "entropy", "prev_option", "init", "phi")
+        for t in range(t_len + 1):
+            body = target if t == t_len else online
+            if t > 0:
+                s = t - 1
+                ops.rollout_conv1_ocheads(frames[t], body.conv1.weight, body.conv1.bias, b['y1'][t], coef, b['slabs'], online.fc4.bias,
+                                          heads, self.uniform[s], self.eps[s:s + 1], plan.mask[s], self.prev_option, self.is_initial,
+                                          out={k: b[k][s] for k in keys})
+            else:
+                ops.rollout_conv1_ocheads(frames[t], body.conv1.weight, body.conv1.bias, b['y1'][t], coef)
+            lib.dra_conv_fwd_koc(2, 1, arr(b['y1'][t]), arr(body.conv2.weight), arr(body.conv2.bias), arr(b['y2'][t]), n, 0, 1.0, relu, st)
+            lib.dra_conv_fwd_koc(3, 1, arr(b['y2'][t]), arr(body.conv3.weight), arr(body.conv3.bias), arr(b['y3'][t]), n, 0, 1.0, relu, st)
+            lib.dra_linear_fwd_slabs_one(1, arr(b['y3'][t]), arr(body.fc4.weight), n, 3136, 512, 28, ctypes.c_void_p(b['slabs'].data_ptr()), st)
+        ops.oc_heads_fold28(b['slabs'], target.fc4.bias, tgt.fc_q.weight, tgt.fc_q.bias, tgt.fc_beta.weight, tgt.fc_beta.bias,
+                            prev_option=self.prev_option, boot=b['boot'])
+        a._rollout_step += t_len
+        # ---- the update over the rollout's own activations (the conv layers' _y_pre, fc4's stored output)
+        rows = t_len * n
+        for conv, key in ((online.conv1, 'y1'), (online.conv2, 'y2'), (online.conv3, 'y3')):
+            y = b[key][:t_len]
+            conv._y_pre = y.reshape((rows,) + tuple(y.shape[2:]))
+        y3 = online.conv3(online.conv2(online.conv1(frames[:t_len].reshape((rows,) + tuple(frames.shape[2:])))))
+        phi = fc4_from_rollout(online, y3.view(rows, -1), b['phi'].view(rows, 512))
+        a._fused.zero_grad(direct=True)
+        defer = a._fused if getattr(cfg, 'defer_conv_folds', True) else None
+        dev = frames.device
+        f = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+        with direct_param_grads(True, defer_folds_to=defer, covers=[a._fused]):
+            _claim_direct(heads)       # the loss launch writes the three heads' gradients in place
+            out = ops.oc_loss_bwd(b, plan.reward, plan.mask, b['boot'], self.eps, cfg.discount, cfg.termination_regularizer,
+                                  cfg.entropy_weight, b['phi'].view(rows, 512), net.fc_q.weight, net.fc_pi.weight, net.fc_beta.weight,
+                                  out=dict(ret=f(t_len, n), adv=f(t_len, n), beta_adv=f(t_len, n), loss=f(4),
+                                           dw_q=net.fc_q.weight.grad, db_q=net.fc_q.bias.grad, dw_pi=net.fc_pi.weight.grad,
+                                           db_pi=net.fc_pi.bias.grad, dw_beta=net.fc_beta.weight.grad,
+                                           db_beta=net.fc_beta.bias.grad, dphi=f(rows, 512)))
+            torch.autograd.backward([phi], [out['dphi']])
+        a._fused.step(cfg.gradient_clip)
+        return dict(q=b['q'], beta=b['beta'], logits=b['logits'], option=b['option'], prev_option=b['prev_option'], init=b['init'],
+                    action=b['action'], log_pi_a=b['log_pi_a'], entropy=b['entropy'], boot=b['boot'], ret=out['ret'],
+                    advantage=out['adv'], beta_advantage=out['beta_adv'], loss=out['loss'][:1], losses=out['loss'])
+
+
 class OptionCriticAgent(BaseAgent):
     """OptionCritic_agent.py:11-119: n-step option-critic over `num_workers` environments.  Per rollout step: one forward
     (q over options, termination beta, intra-option policies), an epsilon-soft option choice that keeps the previous
@@ -2357,12 +2509,48 @@ class OptionCriticAgent(BaseAgent):
         self._sync_target()
         self.total_steps = 0
         self.worker_index = range_tensor(config.num_workers)
+        self.grad_hook = None
+        self._rollout_step = 0
+        self.last_rollout = None
+        self._oc_rollout = _OCRollout(self)
+        if self._oc_rollout.eligible():     # synthetic Atari emulators + OptionCriticNet(NatureConvBody): the rollout lives on the device
+            from .device_env import DeviceAtariVec
+            self.task = DeviceAtariVec(self.task)
+            self.network.body.conv1.u8_coef = float(config.state_normalizer.coef)
+            self._dev_graph = _OnPolicyGraph(self)
+            self.states = self.task.reset()
+            self.prev_options, self.is_initial_states = self._oc_rollout.state(config.num_workers)
+            return
         self.states = config.state_normalizer(self.task.reset())
         self.is_initial_states = torch.ones(config.num_workers, dtype=torch.bool, device=Config.DEVICE)
         self.prev_options = torch.ones(config.num_workers, dtype=torch.int64, device=Config.DEVICE)
 
     def _sync_target(self):
         ops.copy_f32(self._target_flat.flat, self._fused.flat.flat)
+
+    def _step_device(self):
+        """step() over device-resident environments: the host lays the rollout out (DeviceAtariVec.plan), calls the option
+        epsilon schedule once per rollout step in the reference's order and draws the rollout's uniforms (_OCRollout.draw_uniforms);
+        the T head forwards with their option / action choices, the target network's bootstrap, the loss, the backward over the
+        rollout's own activations, clip and optimizer step are enqueued without a host round trip and, after two eager rollouts,
+        replayed as ONE captured graph (_OCRollout.compute).  The target copy of OptionCritic_agent.py:83-85 runs before the
+        rollout: the parameters do not change inside one, so copying then gives the bootstrap copying at step t gives."""
+        config = self.config
+        t_len = config.rollout_length
+        plan = self.task.plan(t_len, config.reward_normalizer)
+        self._oc_rollout.upload_exploration(t_len)
+        self._oc_rollout.draw_uniforms(t_len)
+        sync = False
+        for t in range(t_len):
+            self.record_online_return(plan.infos[t])
+            self.total_steps += config.num_workers
+            if self.total_steps // config.num_workers % config.target_network_update_freq == 0:
+                sync = True
+        if sync:
+            self._sync_target()
+        out = self._dev_graph.run(plan, self._oc_rollout.compute)
+        self.last_loss = out['loss']
+        self.last_rollout = out
 
     def sample_option(self, prediction, epsilon, prev_option, is_initial):
         with torch.no_grad():
@@ -2379,6 +2567,8 @@ class OptionCriticAgent(BaseAgent):
             return torch.where(is_initial, fresh, continued)
 
     def step(self):
+        if getattr(self.task, 'on_device', False):
+            return self._step_device()
         config = self.config
         n, w = config.rollout_length, self.worker_index
         storage = Storage(n, ['beta', 'option', 'beta_advantage', 'prev_option', 'init_state', 'eps'])

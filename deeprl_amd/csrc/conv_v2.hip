@@ -1882,6 +1882,63 @@ DRA_API int dra_rollout_conv1_qheads(const void* frames_u8, const float* wt1, co
   return DRA_OK;
 }
 
+// An option-critic rollout step over NatureConvBody (agents.OptionCriticAgent's device path, OptionCritic_agent.py:55-63): the same
+// four launches, the head that rides in conv1's launch being the option-critic head with its option / action decisions
+// (rollout_roles.h oc_head_row_fold_wg) -- one workgroup per row of step t - 1, features folded from fc4's 28 K-slice partials.
+template <int NW>
+__global__ void __launch_bounds__(64 * NW)
+rollout_conv1_ocheads_kernel(const ConvV2Args a, const OCHeadArgs h, const int head_wgs) {
+  __shared__ float s_out[2 * 8 + 8 * 18];
+  __shared__ float s_phi[512];
+  if ((int)blockIdx.x < head_wgs) {
+    if (threadIdx.x >= 256) return;      // the head's workgroups are four waves (an exited wave does not hold a barrier up)
+    oc_head_row_fold_wg<28>(h, (int)blockIdx.x, s_phi, s_out);
+    return;
+  }
+  ActorFuse none;
+  none.mode = 0;
+  conv_fwd_v2_body<VG1, true, 1, NW, false>(a, none, (int)blockIdx.x - head_wgs, 0, 0, false);
+}
+
+DRA_API int dra_rollout_conv1_ocheads(const void* frames_u8, const float* wt1, const float* b1, float* y1, int batch, double u8_coef,
+                                      const float* slabs_prev, const float* fold_bias, const float* w_q, const float* b_q,
+                                      const float* w_beta, const float* b_beta, const float* w_pi, const float* b_pi,
+                                      const float* uniform, const float* eps, const float* mask, int64_t* prev_option,
+                                      uint8_t* is_initial, int n_options, int n_actions, float* out_q, float* out_beta,
+                                      float* out_logits, int64_t* out_option, int64_t* out_action, float* out_log_pi_a,
+                                      float* out_entropy, int64_t* out_prev_option, float* out_init, float* out_phi, void* stream) {
+  if (!frames_u8 || !wt1 || !b1 || !y1 || batch < 1 || batch > 4096) return DRA_EINVAL;
+  if (slabs_prev && (!fold_bias || !w_q || !w_beta || !w_pi || !uniform || !eps || !mask || !prev_option || !is_initial ||
+                     n_options < 1 || n_options > 8 || n_actions < 1 || n_actions > 18))
+    return DRA_EINVAL;
+  using T = V2Tile<VG1, 1>;
+  ConvV2Args a;
+  a.x[0] = frames_u8; a.wt[0] = wt1; a.bias[0] = b1; a.y[0] = y1;
+  a.batch = batch; a.act = DRA_ACT_RELU; a.coef = u8_coef; a.ring_slot = nullptr; a.ring_cap = 0; a.stack_age = nullptr;
+  a.slot_seq = nullptr; a.slot_entries = 0; a.slot_stride = 0; a.newest_frame = nullptr;
+  OCHeadArgs h;
+  memset(&h, 0, sizeof(h));
+  int head_wgs = 0;
+  if (slabs_prev) {
+    h.slabs = slabs_prev; h.fold_bias = fold_bias; h.wq = w_q; h.bq = b_q; h.wb = w_beta; h.bb = b_beta; h.wp = w_pi; h.bp = b_pi;
+    h.uniform = uniform; h.eps = eps; h.mask = mask; h.prev_option = prev_option; h.init = is_initial;
+    h.out_phi = out_phi; h.out_q = out_q; h.out_beta = out_beta; h.out_logits = out_logits; h.out_lp = out_log_pi_a;
+    h.out_ent = out_entropy; h.out_init = out_init; h.out_boot = nullptr; h.out_option = out_option; h.out_action = out_action;
+    h.out_prev = out_prev_option; h.B = batch; h.O = n_options; h.A = n_actions;
+    head_wgs = batch;
+  }
+  constexpr size_t img = (size_t)VG1::C * T::CS * sizeof(float);
+  constexpr size_t red8 = (size_t)8 * 16 * 64 * sizeof(float), red4 = (size_t)4 * 16 * 64 * sizeof(float);
+  constexpr size_t bytes8 = img > red8 ? img : red8, bytes4 = img > red4 ? img : red4;
+  // the same wave count dra_conv_fwd_koc picks for this batch (launch_conv_v2): bit-identical with the plain launch
+  if (batch <= kConvNw8MaxBatch && conv_b1_waves() == 8)
+    hipLaunchKernelGGL(rollout_conv1_ocheads_kernel<8>, dim3(head_wgs + T::TPG * batch), dim3(512), bytes8, dra_stream(stream), a, h, head_wgs);
+  else
+    hipLaunchKernelGGL(rollout_conv1_ocheads_kernel<4>, dim3(head_wgs + T::TPG * batch), dim3(256), bytes4, dra_stream(stream), a, h, head_wgs);
+  DRA_LAUNCH_CHECK();
+  return DRA_OK;
+}
+
 // Layout conversion [OC][K] <-> [K][OC] for one layer's weight tensor (tests, generic path, and
 // checkpoint interchange; the fused learner keeps KOC as its master layout and never converts).
 __global__ void __launch_bounds__(256)

@@ -205,6 +205,154 @@ __device__ __forceinline__ void q_head_row_fold_wg(const QHeadArgs& h, int b, fl
   }
 }
 
+// Three linear heads on the same features, their outputs spread over the NWAVES waves of a workgroup: wave `wave` runs the chunks
+// of eight outputs oc = 8 wave, 8 (wave + NWAVES), ... of [0, O0 + O1 + O2) -- the sibling of heads_row_outputs_from for a head
+// too wide for one wave (option-critic: 2 O + O A outputs), with that function's per-output arithmetic (lane-strided partial sums
+// in i order, then the butterfly, + bias).  K = 512.  sink(o, value) runs on lane 0 of the wave that owns output o.
+template <int NWAVES, class Sink>
+__device__ __forceinline__ void heads3_row_outputs_lds(const float* __restrict__ x, const float* __restrict__ w0,
+                                                       const float* __restrict__ b0, int O0, const float* __restrict__ w1,
+                                                       const float* __restrict__ b1, int O1, const float* __restrict__ w2,
+                                                       const float* __restrict__ b2, int O2, int wave, int lane, Sink sink) {
+  constexpr int K = 512;
+  float xv[8];
+#pragma unroll
+  for (int i = 0; i < 8; ++i) xv[i] = x[lane + 64 * i];
+  const int OT = O0 + O1 + O2;
+  for (int oc = 8 * wave; oc < OT; oc += 8 * NWAVES) {
+    float wv[8][8], bias[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      const int o = min(oc + u, OT - 1);
+      const float* __restrict__ row;
+      const float* __restrict__ bp;
+      int j;
+      if (o < O0) { row = w0; bp = b0; j = o; }
+      else if (o < O0 + O1) { row = w1; bp = b1; j = o - O0; }
+      else { row = w2; bp = b2; j = o - O0 - O1; }
+      row += (int64_t)j * K;
+#pragma unroll
+      for (int i = 0; i < 8; ++i) wv[u][i] = row[lane + 64 * i];
+      bias[u] = bp ? bp[j] : 0.f;
+    }
+    float part[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      float p = 0.f;
+#pragma unroll
+      for (int i = 0; i < 8; ++i) p += xv[i] * wv[u][i];
+      part[u] = p;
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+#pragma unroll
+      for (int u = 0; u < 8; ++u) part[u] += __shfl_xor(part[u], off, 64);
+    }
+    if (lane == 0) {
+#pragma unroll
+      for (int u = 0; u < 8; ++u) {
+        const int o = oc + u;
+        if (o < OT) sink(o, part[u] + bias[u]);
+      }
+    }
+  }
+}
+
+// Inverse CDF of a row of unnormalised weights p[0, n) at u, as Categorical(probs=p) sees it: the row is divided by its fp32 sum
+// (index order) in place, then the first k whose running fp32 sum exceeds u wins, the last index when none does --
+// categorical_row's rule (common.h).  (pi_hat of sample_option does not sum to one: beta is a vector over options.)
+__device__ __forceinline__ int inv_cdf_row(float* p, int n, float u) {
+  float s = 0.f;
+  for (int k = 0; k < n; ++k) s += p[k];
+  for (int k = 0; k < n; ++k) p[k] = p[k] / s;
+  float cum = 0.f;
+  for (int k = 0; k < n; ++k) {
+    cum += p[k];
+    if (cum > u) return k;
+  }
+  return n - 1;
+}
+
+// The option-critic head of a rollout step (OptionCritic_agent.py:55-63, network_heads.py:118-127) for ONE row per workgroup of
+// four waves, its features folded from fc4's KS K-slice partial sums first (fold_row_slabs_wg: the A2C / n-step fold, bit for bit):
+// q = phi Wq^T + bq [O], z_beta = phi Wb^T + bb [O] and the O A intra-option logits phi Wp^T + bp (row o A + a: action a of option
+// o) over all four waves (heads3_row_outputs_lds), then on one lane the decisions of sample_option (OptionCritic_agent.py:29-49):
+// beta = sigmoid(z_beta), g = the first index of q's maximum, pi_opt = eps / O with 1 - eps + eps / O at g, pi_hat = (1 - beta)
+// 1[o == prev] + beta pi_opt, option = init ? invCDF(pi_opt, u0) : invCDF(pi_hat, u1) (each row normalised by its sum first, as
+// Categorical(probs=) does: inv_cdf_row), then categorical_row on the chosen option's
+// A logits with u2: action, log pi(a), entropy.  The carried state is read and replaced in place: prev_option[b] <- option,
+// init[b] <- (mask[b] == 0) (the next step's is_initial_states = terminals); out_prev / out_init record what this step read.
+// Bootstrap mode (out_boot != nullptr; OptionCritic_agent.py:87-93, the target network over observation T): only q and z_beta,
+// out_boot[b] = (1 - beta[prev]) q[prev] + beta[prev] max q with prev = prev_option[b], the carried state untouched.
+// Every per-row output is optional.  uniform [B][3] (fresh option, continued option, action); eps [1]: this step's option epsilon.
+// s_phi: 512 floats; so: >= 2 O + O A floats.  O <= 8, A <= 18 (the launchers check).
+struct OCHeadArgs {
+  const float *slabs, *fold_bias, *wq, *bq, *wb, *bb, *wp, *bp;
+  const float *uniform, *eps, *mask;
+  int64_t* prev_option;
+  uint8_t* init;
+  float *out_phi, *out_q, *out_beta, *out_logits, *out_lp, *out_ent, *out_init, *out_boot;
+  int64_t *out_option, *out_action, *out_prev;
+  int B, O, A;
+};
+template <int KS>
+__device__ __forceinline__ void oc_head_row_fold_wg(const OCHeadArgs& h, int b, float* s_phi, float* so) {
+  const int t = threadIdx.x;
+  fold_row_slabs_wg<KS>(h.slabs, h.fold_bias, h.B, 512, b, s_phi, h.out_phi);
+  __syncthreads();
+  const int O = h.O, A = h.A;
+  const bool boot = h.out_boot != nullptr;
+  heads3_row_outputs_lds<4>(s_phi, h.wq, h.bq, O, h.wb, h.bb, O, h.wp, h.bp, boot ? 0 : O * A, t >> 6, t & 63,
+                            [&](int o, float v) { so[o] = v; });
+  __syncthreads();
+  if (t != 0) return;
+  const float* q = so;
+  const float* zb = so + O;
+  float beta[8];
+  for (int o = 0; o < O; ++o) beta[o] = 1.f / (1.f + expf(-zb[o]));
+  float qmax = q[0];
+  int g = 0;
+  for (int o = 1; o < O; ++o) {
+    if (qmax != qmax) break;                          // NaN: argmax stops at the first one
+    if (q[o] > qmax || q[o] != q[o]) { qmax = q[o]; g = o; }
+  }
+  const int64_t prev_in = h.prev_option[b];
+  const int prev = prev_in < 0 ? 0 : (prev_in >= O ? O - 1 : (int)prev_in);
+  if (h.out_q)
+    for (int o = 0; o < O; ++o) h.out_q[(int64_t)b * O + o] = q[o];
+  if (h.out_beta)
+    for (int o = 0; o < O; ++o) h.out_beta[(int64_t)b * O + o] = beta[o];
+  if (boot) {
+    h.out_boot[b] = (1.f - beta[prev]) * q[prev] + beta[prev] * qmax;
+    return;
+  }
+  const float eps = h.eps[0];
+  const float base = eps / (float)O, top = 1.f - eps + eps / (float)O;
+  float pi_opt[8], pi_hat[8];
+  for (int o = 0; o < O; ++o) {
+    pi_opt[o] = o == g ? top : base;
+    pi_hat[o] = (1.f - beta[o]) * (o == prev ? 1.f : 0.f) + beta[o] * pi_opt[o];
+  }
+  const float* u = h.uniform + (int64_t)b * 3;
+  const bool init = h.init[b] != 0;
+  const int fresh = inv_cdf_row(pi_opt, O, u[0]), continued = inv_cdf_row(pi_hat, O, u[1]);
+  const int option = init ? fresh : continued;
+  const float* logits = so + 2 * O + option * A;
+  int64_t act;
+  float lp, ent;
+  categorical_row(logits, A, false, 0, u[2], &act, &lp, &ent);
+  if (h.out_logits)
+    for (int a = 0; a < A; ++a) h.out_logits[(int64_t)b * A + a] = logits[a];
+  if (h.out_option) h.out_option[b] = option;
+  if (h.out_action) h.out_action[b] = act;
+  if (h.out_lp) h.out_lp[b] = lp;
+  if (h.out_ent) h.out_ent[b] = ent;
+  if (h.out_prev) h.out_prev[b] = prev_in;
+  if (h.out_init) h.out_init[b] = init ? 1.f : 0.f;
+  h.prev_option[b] = option;
+  h.init[b] = h.mask[b] == 0.f ? 1 : 0;
+}
+
 // A wide linear layer at rollout batch sizes (fc4 of NatureConvBody, 3136 -> 512, for the 8 / 16 environments of one rollout
 // step): a workgroup of EIGHT waves owns 8 / WPR output rows (o2 = index of the group), each row's reduction split over WPR waves
 // (K parts); a lane keeps its R float4 of the weight row in registers and, per round, the matching float4 of up to RB input

@@ -784,6 +784,120 @@ def nstep_q_loss_bwd(q, action, reward, mask, bootstrap, gamma, phi, w, out=None
     return out
 
 
+def _oc_head_checks(name, batch, n_opt, n_act, heads, uniform, eps, mask, prev_option, is_initial, out):
+    if not (1 <= n_opt <= 8 and 1 <= n_act <= 18):
+        raise ValueError("%s: at most 8 options and 18 actions" % name)
+    wq, bq, wb, bb, wp, bp = heads
+    i64, u8 = torch.int64, torch.uint8
+    _check_rows(name, batch, w_q=(wq, _f32, n_opt * 512), b_q=(bq, _f32, n_opt), w_beta=(wb, _f32, n_opt * 512),
+                b_beta=(bb, _f32, n_opt), w_pi=(wp, _f32, n_opt * n_act * 512), b_pi=(bp, _f32, n_opt * n_act),
+                uniform=(uniform, _f32, batch * 3), eps=(eps, _f32, 1), mask=(mask, _f32, batch),
+                prev_option=(prev_option, i64, batch), is_initial=(is_initial, is_initial.dtype if is_initial is not None else u8, batch))
+    if is_initial is not None and is_initial.dtype not in (u8, torch.bool):
+        raise ValueError("%s: is_initial must be uint8 or bool" % name)
+    shapes = dict(q=(_f32, batch * n_opt), beta=(_f32, batch * n_opt), logits=(_f32, batch * n_act), option=(i64, batch),
+                  action=(i64, batch), log_pi_a=(_f32, batch), entropy=(_f32, batch), prev_option=(i64, batch), init=(_f32, batch),
+                  phi=(_f32, batch * 512), boot=(_f32, batch))
+    unknown = set(out) - set(shapes)
+    if unknown:
+        raise ValueError("%s: unknown outputs %s" % (name, sorted(unknown)))
+    _check_rows(name, batch, **{k: (v, shapes[k][0], shapes[k][1]) for k, v in out.items()})
+
+
+def oc_heads_fold28(slabs, fold_bias, w_q, b_q, w_beta, b_beta, w_pi=None, b_pi=None, uniform=None, eps=None, mask=None,
+                    prev_option=None, is_initial=None, out=None, boot=None):
+    """The option-critic head of a rollout step on fc4's 28 K-slice partial sums slabs [28, B, 512] in one launch (one workgroup
+    per row; rollout_roles.h oc_head_row_fold_wg): q [B, O], beta [B, O], the option (sample_option with this step's eps [1] and
+    uniform [B, 3] columns fresh / continued), the action from the chosen option's policy, its logits [B, A], log pi(a), entropy
+    and phi [B, 512].  prev_option i64 [B] and is_initial u8 / bool [B] are the carried state, replaced in place (prev <- option,
+    init <- mask == 0); out: dict of preallocated outputs (any of q, beta, logits, option, action, log_pi_a, entropy, prev_option
+    (what the step read), init (likewise, f32), phi), written in place.  boot [B] given: the bootstrap mode
+    (OptionCritic_agent.py:87-93) -- q / beta of the target network and boot = (1 - beta[prev]) q[prev] + beta[prev] max q."""
+    slabs, fold_bias = _c(slabs, _f32), _c(fold_bias, _f32)
+    batch, n_opt = int(slabs.shape[1]), int(w_q.shape[0])
+    n_act = int(w_pi.shape[0]) // n_opt if w_pi is not None else 1
+    if tuple(slabs.shape) != (28, batch, 512):
+        raise ValueError("oc_heads_fold28: slabs [28, B, 512]")
+    if prev_option is None or (boot is None and (w_pi is None or uniform is None or eps is None or mask is None or is_initial is None)):
+        raise ValueError("oc_heads_fold28: prev_option always; w_pi, uniform, eps, mask, is_initial outside the bootstrap mode")
+    out = dict(out or {})
+    if boot is not None:
+        out['boot'] = boot
+    _oc_head_checks("oc_heads_fold28", batch, n_opt, n_act, (w_q, b_q, w_beta, b_beta, w_pi, b_pi), uniform, eps, mask, prev_option,
+                    is_initial, out)
+    g = out.get
+    lib.dra_oc_heads_fold28(ptr(slabs), ptr(fold_bias), ptr(w_q), ptr(b_q), ptr(w_beta), ptr(b_beta), ptr(w_pi), ptr(b_pi),
+                            ptr(uniform), ptr(eps), ptr(mask), ptr(prev_option), ptr(is_initial), batch, n_opt, n_act, ptr(g('q')),
+                            ptr(g('beta')), ptr(g('logits')), ptr(g('option')), ptr(g('action')), ptr(g('log_pi_a')),
+                            ptr(g('entropy')), ptr(g('prev_option')), ptr(g('init')), ptr(g('phi')), ptr(g('boot')), stream_ptr())
+    return out
+
+
+def rollout_conv1_ocheads(frames_u8, w1_koc, b1, y1, u8_coef, slabs_prev=None, fold_bias=None, heads=None, uniform=None, eps=None,
+                          mask=None, prev_option=None, is_initial=None, out=None):
+    """conv1 (+ ReLU) of uint8 frames [B, 4, 84, 84] into y1 [B, 32, 20, 20] and -- slabs_prev given -- the previous step's
+    option-critic head (oc_heads_fold28's decision mode; heads = (w_q, b_q, w_beta, b_beta, w_pi, b_pi)) in the same launch."""
+    batch = int(frames_u8.shape[0])
+    if frames_u8.dtype != torch.uint8 or not frames_u8.is_contiguous() or not y1.is_contiguous():
+        raise ValueError("rollout_conv1_ocheads: contiguous uint8 frames and f32 output")
+    out = dict(out or {})
+    n_opt = n_act = 0
+    heads = tuple(heads) if heads is not None else (None,) * 6
+    if slabs_prev is not None:
+        if any(x is None for x in (fold_bias, heads[0], heads[2], heads[4], uniform, eps, mask, prev_option, is_initial)):
+            raise ValueError("rollout_conv1_ocheads: the head needs fold_bias, heads, uniform, eps, mask and the carried state")
+        n_opt = int(heads[0].shape[0])
+        n_act = int(heads[4].shape[0]) // n_opt
+        _check_rows("rollout_conv1_ocheads", batch, slabs_prev=(slabs_prev, _f32, 28 * batch * 512), fold_bias=(fold_bias, _f32, 512))
+        _oc_head_checks("rollout_conv1_ocheads", batch, n_opt, n_act, heads, uniform, eps, mask, prev_option, is_initial, out)
+    g = out.get
+    lib.dra_rollout_conv1_ocheads(ptr(frames_u8), ptr(w1_koc), ptr(b1), ptr(y1), batch, float(u8_coef), ptr(slabs_prev), ptr(fold_bias),
+                                  *[ptr(x) for x in heads], ptr(uniform), ptr(eps), ptr(mask), ptr(prev_option), ptr(is_initial),
+                                  n_opt, n_act, ptr(g('q')), ptr(g('beta')), ptr(g('logits')), ptr(g('option')), ptr(g('action')),
+                                  ptr(g('log_pi_a')), ptr(g('entropy')), ptr(g('prev_option')), ptr(g('init')), ptr(g('phi')),
+                                  stream_ptr())
+    return out
+
+
+_OC_LOSS_OUTS = ("ret", "adv", "beta_adv", "loss", "dw_q", "db_q", "dw_pi", "db_pi", "dw_beta", "db_beta", "dphi")
+
+
+def oc_loss_bwd(rollout, reward, mask, ret_boot, eps, gamma, termination_regularizer, entropy_weight, phi, w_q, w_pi, w_beta,
+                out=None):
+    """OptionCritic_agent.py:95-117's returns, advantages, termination advantages, the three losses and the heads' backward in ONE
+    launch.  rollout: dict of the head's outputs over T steps x N environments (q / beta [T, N, O], logits [T, N, A], option /
+    action / prev_option i64 [T, N], init / log_pi_a / entropy [T, N]); reward / mask [T, N] (any trailing 1), ret_boot [N], eps
+    [T]; phi [T * N, 512]; w_q / w_beta [O, 512], w_pi [O * A, 512] -> dict(ret, adv, beta_adv [T, N], loss [4] = (total, q, pi,
+    beta), dw_q, db_q, dw_pi, db_pi, dw_beta, db_beta, dphi [T * N, 512] (times fc4's ReLU mask)).  out: the same dict of
+    preallocated tensors (the weight gradients may be gradient slots)."""
+    r = {k: _c(rollout[k], torch.int64 if k in ("option", "action", "prev_option") else _f32)
+         for k in ("q", "beta", "logits", "option", "action", "prev_option", "init", "log_pi_a", "entropy")}
+    reward, mask, ret_boot, eps, phi = _c(reward, _f32), _c(mask, _f32), _c(ret_boot, _f32), _c(eps, _f32), _c(phi, _f32)
+    w_q, w_pi, w_beta = _c(w_q, _f32), _c(w_pi, _f32), _c(w_beta, _f32)
+    t_len, n, n_opt = int(r['q'].shape[0]), int(r['q'].shape[1]), int(r['q'].shape[2])
+    n_act = int(r['logits'].shape[-1])
+    rows = t_len * n
+    if not (1 <= n_opt <= 8 and 1 <= n_act <= 18) or rows > 2048:
+        raise ValueError("oc_loss_bwd: at most 8 options, 18 actions and 2048 rows")
+    if (r['beta'].numel() != rows * n_opt or r['logits'].numel() != rows * n_act
+            or any(r[k].numel() != rows for k in ("option", "action", "prev_option", "init", "log_pi_a", "entropy"))
+            or reward.numel() != rows or mask.numel() != rows or ret_boot.numel() != n or eps.numel() != t_len
+            or tuple(phi.shape) != (rows, 512) or tuple(w_q.shape) != (n_opt, 512) or tuple(w_beta.shape) != (n_opt, 512)
+            or tuple(w_pi.shape) != (n_opt * n_act, 512)):
+        raise ValueError("oc_loss_bwd: inconsistent shapes")
+    dev = phi.device
+    shapes = dict(ret=(t_len, n), adv=(t_len, n), beta_adv=(t_len, n), loss=(4,), dw_q=(n_opt, 512), db_q=(n_opt,),
+                  dw_pi=(n_opt * n_act, 512), db_pi=(n_opt * n_act,), dw_beta=(n_opt, 512), db_beta=(n_opt,), dphi=(rows, 512))
+    if out is None:
+        out = {k: torch.empty(s, dtype=_f32, device=dev) for k, s in shapes.items()}
+    _check_rows("oc_loss_bwd", rows, **{k: (out[k], _f32, int(np.prod(s))) for k, s in shapes.items()})
+    lib.dra_oc_loss_bwd(ptr(r['q']), ptr(r['beta']), ptr(r['logits']), ptr(r['option']), ptr(r['action']), ptr(r['prev_option']),
+                        ptr(r['init']), ptr(r['log_pi_a']), ptr(r['entropy']), ptr(reward), ptr(mask), ptr(ret_boot), ptr(eps),
+                        float(gamma), float(termination_regularizer), float(entropy_weight), ptr(phi), ptr(w_q), ptr(w_pi),
+                        ptr(w_beta), t_len, n, n_opt, n_act, *[ptr(out[k]) for k in _OC_LOSS_OUTS], stream_ptr())
+    return out
+
+
 HEADS_BWD_MAX_BATCH = 8192
 
 

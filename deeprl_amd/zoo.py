@@ -87,6 +87,15 @@ ZOO = {
         network=lambda c: N.VanillaNet(c.action_dim, N.NatureConvBody()),
         fields=dict(discount=0.99, target_network_update_freq=10000, rollout_length=5, gradient_clip=5, max_steps=int(2e7)),
         eps=(1.0, 0.05, 1e6), normalizers=(ImageNormalizer, SignNormalizer)),
+    # examples.py:471-492
+    "option_critic_pixel": dict(
+        agent="OptionCriticAgent", kw=dict(log_level=0), pre_fields=dict(num_workers=16),
+        task=lambda c: Task(c.game, num_envs=c.num_workers), eval_task=lambda c: Task(c.game),
+        optimizer=_rmsprop(lr=1e-4, alpha=0.99, eps=1e-5),
+        network=lambda c: N.OptionCriticNet(N.NatureConvBody(), c.action_dim, num_options=4),
+        fields=dict(discount=0.99, target_network_update_freq=10000, rollout_length=5, gradient_clip=5, max_steps=int(2e7),
+                    entropy_weight=0.01, termination_regularizer=0.01),
+        option_eps=(0.1,), normalizers=(ImageNormalizer, SignNormalizer)),
     # examples.py:525-550
     "ppo_pixel": dict(
         agent="PPOAgent", kw=dict(skip=False), pre_fields=dict(num_workers=8),
@@ -135,6 +144,8 @@ def config(name, **kwargs):
             setattr(c, k, v)
     if "eps" in spec:
         c.random_action_prob = LinearSchedule(*spec["eps"])
+    if "option_eps" in spec:        # option-critic's epsilon over options (OptionCritic_agent.py:55)
+        c.random_option_prob = LinearSchedule(*spec["option_eps"])
     if "beta" in spec:
         c.replay_beta = LinearSchedule(spec["beta"][0], spec["beta"][1], c.max_steps)
     norm = spec.get("normalizers")

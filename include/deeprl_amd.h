@@ -498,6 +498,50 @@ int dra_nstep_q_loss_bwd(const float* q, const int64_t* action, const float* rew
                          double gamma, const float* phi, const float* w_q, int t_len, int n_env, int n_actions, float* out_ret,
                          float* out_loss, float* dw_q, float* db_q, float* dphi, void* stream);
 
+/* ---- option-critic on pixels over a device-resident rollout (OptionCritic_agent.py:29-119, network_heads.py:105-127;
+ * agents.OptionCriticAgent): each rollout step is the four launches above with the option-critic head in place of the policy head
+ * (q [O], beta = sigmoid(z_beta) [O], the O x A intra-option logits, fc_pi row o*A + a = action a of option o), the option and
+ * action chosen on the device by inverse CDF from given uniforms [batch][3] (fresh option, continued option, action: the reference
+ * draws them with Categorical(...).sample()), then the target network's forward of the last observation, its bootstrap head, and
+ * the update's three losses + the heads' backward in one launch.  O <= 8 options, A <= 18 actions. */
+/* conv1 (+ ReLU) of uint8 frames [batch][4][84][84] -> y1, and, when slabs_prev != NULL, the option-critic head of the previous
+ * step in the same launch (OptionCritic_agent.py:29-63): phi = relu(fold_bias + sum of fc4's 28 K-slice partial sums slabs_prev
+ * [28][batch][512], slab 0 first: the A2C head's fold, bit for bit) -> out_phi; q -> out_q [batch][O], beta -> out_beta [batch][O];
+ * sample_option (:29-49) with eps [1] (this step's option epsilon): option = is_initial ? invCDF(pi_opt, u0) : invCDF(pi_hat, u1),
+ * each row divided by its sum first as Categorical(probs=) does -> out_option; Categorical of the chosen option's logits (-> out_logits [batch][A]) with u2 -> out_action, out_log_pi_a,
+ * out_entropy.  The carried state is read and replaced in place: prev_option [batch] <- option, is_initial [batch] (u8) <-
+ * (mask [batch] == 0); out_prev_option / out_init record what this step read.  The per-row outputs are optional. */
+int dra_rollout_conv1_ocheads(const void* frames_u8, const float* wt1, const float* b1, float* y1, int batch, double u8_coef,
+                              const float* slabs_prev, const float* fold_bias, const float* w_q, const float* b_q,
+                              const float* w_beta, const float* b_beta, const float* w_pi, const float* b_pi,
+                              const float* uniform, const float* eps, const float* mask, int64_t* prev_option,
+                              uint8_t* is_initial, int n_options, int n_actions, float* out_q, float* out_beta,
+                              float* out_logits, int64_t* out_option, int64_t* out_action, float* out_log_pi_a,
+                              float* out_entropy, int64_t* out_prev_option, float* out_init, float* out_phi, void* stream);
+/* the same head on its own (the last step of a rollout), one workgroup per row.  out_boot != NULL selects the bootstrap mode of the
+ * target network over observation T (OptionCritic_agent.py:87-93): out_boot [batch] = (1 - beta[prev]) q[prev] + beta[prev] max q,
+ * prev = prev_option[b] (left as it is); only w_q / w_beta are read then (w_pi, uniform, eps, mask, is_initial may be NULL) */
+int dra_oc_heads_fold28(const float* slabs, const float* fold_bias, const float* w_q, const float* b_q, const float* w_beta,
+                        const float* b_beta, const float* w_pi, const float* b_pi, const float* uniform, const float* eps,
+                        const float* mask, int64_t* prev_option, uint8_t* is_initial, int batch, int n_options, int n_actions,
+                        float* out_q, float* out_beta, float* out_logits, int64_t* out_option, int64_t* out_action,
+                        float* out_log_pi_a, float* out_entropy, int64_t* out_prev_option, float* out_init, float* out_phi,
+                        float* out_boot, void* stream);
+/* the update of one rollout (OptionCritic_agent.py:95-117) in one launch over R = t_len x n_env <= 2048 rows (t-major): ret by
+ * ret = r + gamma m ret backwards from ret_boot [n_env], adv = ret - q[option], beta_adv = q[prev] - (max q (1 - eps_t) + mean q
+ * eps_t) + termination_regularizer (eps [t_len]); out_loss [4] = (pi_loss + q_loss + beta_loss, q_loss, pi_loss, beta_loss); the
+ * gradient of that sum through the three heads on the rollout's features phi [R][512]: dw_q / db_q [O][512] / [O], dw_pi / db_pi
+ * [O*A][512] / [O*A], dw_beta / db_beta (fixed-order sums over the rows, no atomics) and dphi [R][512] times [phi > 0] (fc4's
+ * ReLU) for fc4's backward.  q / beta [R][O], logits [R][A] (the chosen option's), option / action / prev_option i64 [R], init /
+ * log_pi_a / entropy / reward / mask f32 [R] */
+int dra_oc_loss_bwd(const float* q, const float* beta, const float* logits, const int64_t* option, const int64_t* action,
+                    const int64_t* prev_option, const float* init, const float* log_pi_a, const float* entropy, const float* reward,
+                    const float* mask, const float* ret_boot, const float* eps, double gamma, double termination_regularizer,
+                    double entropy_weight, const float* phi, const float* w_q, const float* w_pi, const float* w_beta, int t_len,
+                    int n_env, int n_options, int n_actions, float* out_ret, float* out_adv, float* out_beta_adv, float* out_loss,
+                    float* dw_q, float* db_q, float* dw_pi, float* db_pi, float* dw_beta, float* db_beta, float* dphi,
+                    void* stream);
+
 /* ---- fused DQN learner + device-resident actor: DQN_agent.py:24-45 (actor step), :114-138 (update) for
  * VanillaNet(NatureConvBody).  All five flat buffers are caller-owned f32[n_params] with the tensor order
  * conv1.w, conv1.b, conv2.w, conv2.b, conv3.w, conv3.b, fc4.w, fc4.b, head.w, head.b at `offset[]` (16-byte

@@ -10,7 +10,7 @@ after a warm-up.  Prints one JSON object per line: agent steps/s, env steps/s, g
   config 4  dqn_pixel + PrioritizedReplay (examples.py:55-97 with replay_cls=PrioritizedReplay),
             categorical_dqn_pixel examples.py:195-226, quantile_regression_dqn_pixel examples.py:129-160
   config 5  a2c_pixel examples.py:361-381 (16 workers), ppo_pixel examples.py:525-550 (8 workers)
-            n_step_dqn_pixel examples.py:427-447 (16 workers)
+            n_step_dqn_pixel examples.py:427-447 (16 workers), option_critic_pixel examples.py:471-492 (16 workers)
 """
 import argparse
 import json
@@ -110,6 +110,23 @@ def n_step_dqn_pixel(workers=16, device=True, **switches):
     return d.NStepDQNAgent(c), dict(env_per_step=5 * workers, updates_per_step=1)
 
 
+def option_critic_pixel(workers=16, device=True, **switches):
+    c = d.Config()
+    c.merge(dict(game="BreakoutNoFrameskip-v4", log_level=0, tag="bench", device_env=device, **switches))
+    c.num_workers = workers
+    c.task_fn = lambda: d.Task(c.game, num_envs=c.num_workers, seed=1)
+    c.eval_env = d.Task(c.game, seed=2)
+    c.optimizer_fn = lambda p: torch.optim.RMSprop(p, lr=1e-4, alpha=0.99, eps=1e-5)
+    c.network_fn = lambda: d.OptionCriticNet(d.NatureConvBody(), c.action_dim, num_options=4)
+    c.random_option_prob = d.LinearSchedule(0.1)
+    c.state_normalizer = d.ImageNormalizer()
+    c.reward_normalizer = d.SignNormalizer()
+    c.discount, c.target_network_update_freq, c.rollout_length, c.gradient_clip = 0.99, 10000, 5, 5
+    c.entropy_weight, c.termination_regularizer = 0.01, 0.01
+    c.max_steps = int(2e7)
+    return d.OptionCriticAgent(c), dict(env_per_step=5 * workers, updates_per_step=1)
+
+
 def ppo_continuous(workers=1, device=True, fused=True):
     c = d.Config()
     c.merge(dict(game="synthetic-continuous-HalfCheetah", log_level=0, tag="bench", device_env=device, fused_ppo_mlp=fused))
@@ -166,6 +183,8 @@ CASES = {
     "ppo_pixel_8": lambda: ppo_pixel(8),
     "n_step_dqn_pixel_16": lambda: n_step_dqn_pixel(16),                      # device-resident rollout + one captured graph
     "n_step_dqn_pixel_16_host": lambda: n_step_dqn_pixel(16, device=False),   # host emulators (the reference's loop)
+    "option_critic_pixel_16": lambda: option_critic_pixel(16),                      # device-resident rollout + one captured graph
+    "option_critic_pixel_16_host": lambda: option_critic_pixel(16, device=False),   # host emulators (the reference's loop)
     "a2c_pixel_16_nofc4head": lambda: a2c_pixel(16, fuse_fc4_head=False),      # fc4 finish / policy head as separate autograd nodes
     "ppo_pixel_8_nofc4head": lambda: ppo_pixel(8, fuse_fc4_head=False),
     "a2c_pixel_16_gemv": lambda: a2c_pixel(16, rollout_fc4_slices=False),       # rollout fc4 as the eight-wave GEMV (module path)
