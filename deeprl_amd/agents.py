@@ -236,6 +236,13 @@ class DQNActor(BaseActor):
         return entry
 
 
+def _fused_noisy(config, net):
+    """Noisy layers on csrc/noisy.hip: config.fused_noisy (default on) over a network that stages its noise in one block
+    (nets.RainbowNet), on the device.  Only then may the actor forward / the update of a noisy agent be captured."""
+    return (getattr(config, 'fused_noisy', True) is not False and Config.DEVICE.type == 'cuda' and net is not None
+            and hasattr(net, 'noise_block') and getattr(net, 'fused_noisy', False))
+
+
 def _capture_failed(config, what, error):
     """A hipGraph capture failed.  Falling back to the eager kernels silently would turn a broken capture into nothing but a
     slower number, so it is an error unless the configuration opts into the fallback (config.allow_eager_fallback = True:
@@ -268,8 +275,10 @@ class _GraphedQ:
     def usable(self, state):
         from .normalizers import RescaleNormalizer
         cfg = self.actor.config
-        if self.failed or cfg.noisy_linear or getattr(cfg, 'graph_update', True) is False:
+        if self.failed or getattr(cfg, 'graph_update', True) is False:
             return False
+        if cfg.noisy_linear and not _fused_noisy(cfg, self.actor._network):
+            return False        # the module path materialises the mixed weights with ATen kernels: eager
         if not isinstance(cfg.state_normalizer, RescaleNormalizer):
             return False
         first = state[0] if isinstance(state, (list, tuple)) else state
@@ -318,8 +327,13 @@ class _GraphedUpdate:
     """One DQN-family update (DQN_agent.py:114-134: normalise, target / online forwards, fused loss kernel,
     backward, clip, optimizer) as ONE hipGraph replay over static minibatch buffers that the ring gather refills
     in place.  Captured with torch.cuda.graphs after two eager updates (which also run every lazy one-time
-    initialisation); same kernels and arguments as the eager path -> bit-identical parameters.  Uniform replay
-    only: the PER importance exponent changes every update and is a kernel argument."""
+    initialisation); same kernels and arguments as the eager path -> bit-identical parameters.
+
+    Agents without noisy layers: uniform replay only.  Noisy layers on csrc/noisy.hip (_fused_noisy): uniform replay and the
+    PER form -- rp.draw() -> gather into the static buffers -> sampling probabilities and the importance exponent in one
+    small upload (the captured launches read beta from a device word) -> replay -> rp.commit_device(tree_idx, prio): the
+    priorities never visit the host.  reset_noise() (target, then online: DQN_agent.py:116-118) runs outside the captured
+    region; the graph reads the noise through static addresses."""
     WARMUP = 2
 
     def __init__(self, agent):
@@ -330,11 +344,28 @@ class _GraphedUpdate:
         self.out = None
         self.signature = None
         self.failed = False
+        self.per_words = None       # [batch sampling probabilities | beta] f32, device
+        self._per_up = None
 
     def usable(self, rp):
         cfg = self.agent.config
-        return not (self.failed or cfg.noisy_linear or getattr(cfg, 'graph_update', True) is False or hasattr(rp, 'draw')
-                    or self.agent._fused is None)
+        if self.failed or getattr(cfg, 'graph_update', True) is False or self.agent._fused is None:
+            return False
+        if cfg.noisy_linear:
+            return _fused_noisy(cfg, self.agent.network) and _fused_noisy(cfg, self.agent.target_network)
+        return not hasattr(rp, 'draw')
+
+    def _upload_per(self, prob, beta):
+        from .replay import _PinnedUploader
+        b = len(prob)
+        if self.per_words is None:
+            dev = next(self.agent.network.parameters()).device
+            self.per_words = torch.zeros(b + 1, dtype=torch.float32, device=dev)
+            self._per_up = _PinnedUploader(torch.float32, b + 1, dev)
+        words = np.empty(b + 1, dtype=np.float32)
+        words[:b] = prob            # (f64 -> f32: the rounding the eager path's .float() applies)
+        words[b] = beta
+        self._per_up.upload_into(self.per_words, words)
 
     def run(self, rp):
         """Returns the loss-kernel outputs of the update it performed, or None (caller runs the eager update)."""
@@ -346,19 +377,36 @@ class _GraphedUpdate:
         opt = agent._fused
         if self.graph is not None and self.signature != opt.hyper_signature():
             self.graph = None       # a hyper-parameter baked into the graph changed (lr schedule): re-capture
-        idx = rp.draw_indices()
+        per = hasattr(rp, 'draw')
+        tree_idx = None
+        if per:
+            tree_idx, prob, idx = rp.draw()
+            self._upload_per(prob, cfg.replay_beta())
+        else:
+            idx = rp.draw_indices()
+        if cfg.noisy_linear:
+            agent.target_network.reset_noise()
+            agent.network.reset_noise()
         if self.graph is None:
             try:
                 self.static = rp.gather(idx)
-                tr = rp.TransitionCLS(state=self.static['state'], action=self.static['action'], reward=self.static['reward'],
-                                      next_state=self.static['next_state'], mask=self.static['mask'])
+                fields = dict(state=self.static['state'], action=self.static['action'], reward=self.static['reward'],
+                              next_state=self.static['next_state'], mask=self.static['mask'])
+                per_args = None
+                if per:
+                    b = len(idx)
+                    fields.update(sampling_prob=self.per_words[:b], idx=None)
+                    # beta < 0: dra_td_loss reads the exponent behind the probabilities; beta_dev: dra_per_weights_dev
+                    per_args = dict(sampling_prob=self.per_words[:b], beta=-1.0, beta_dev=self.per_words[b:b + 1],
+                                    replay_eps=cfg.replay_eps, replay_alpha=cfg.replay_alpha)
+                tr = rp.TransitionCLS(**fields)
                 opt.enable_graph_mode()
                 g = torch.cuda.CUDAGraph()
                 torch.cuda.synchronize()
                 with _capture(g):
-                    out, (net_out, grad) = agent._loss_grad(tr, None)
+                    out, (net_out, grad) = agent._loss_grad(tr, per_args)
                     opt.zero_grad()
-                    net_out.backward(grad)
+                    agent._backward(net_out, grad)
                     opt.step(cfg.gradient_clip)
                 self.out = out
                 self.graph = g
@@ -368,12 +416,19 @@ class _GraphedUpdate:
                 self.failed = True
                 self.graph = None
                 opt.graph_mode = False
-                return agent._learn(rp.TransitionCLS(**{k: v for k, v in rp.gather(idx).items()
-                                                        if k in rp.TransitionCLS._fields}))
+                g = rp.gather(idx)
+                if per:
+                    dev = g['state'].device
+                    g.update(sampling_prob=torch.from_numpy(prob).to(dev), idx=torch.from_numpy(tree_idx).to(dev))
+                    return agent._learn(rp.TransitionCLS(**{k: v for k, v in g.items() if k in rp.TransitionCLS._fields}),
+                                        beta=float(self.per_words[-1].item()))
+                return agent._learn(rp.TransitionCLS(**{k: v for k, v in g.items() if k in rp.TransitionCLS._fields}))
         else:
             rp.gather(idx, out=self.static)
         opt.prepare_step()
         self.graph.replay()
+        if per:
+            rp.commit_device(tree_idx, self.out['prio'])      # replay.py:193-196, the priorities stay on the device
         return self.out
 
 
@@ -390,6 +445,9 @@ class DQNAgent(BaseAgent):
         self.actor = self.ActorCLS(config)
         self.network = config.network_fn()
         self.target_network = config.network_fn()
+        for net in (self.network, self.target_network):
+            if hasattr(net, 'set_fused_noisy'):     # noisy layers on csrc/noisy.hip (default) or on the module path
+                net.set_fused_noisy(getattr(config, 'fused_noisy', True) is not False)
         self.target_network.load_state_dict(self.network.state_dict())
         self.optimizer = config.optimizer_fn(self.network.parameters())
         self._fused = FusedOptimizer.adopt(self.optimizer)           # re-homes network params in one flat buffer
@@ -723,12 +781,34 @@ class DQNAgent(BaseAgent):
             action = action.long()
         return action.contiguous(), reward.contiguous(), mask.contiguous()
 
-    def _per_args(self, transitions):
+    def _per_args(self, transitions, beta=None):
         config = self.config
         sp = transitions.sampling_prob
         sp = sp.float() if isinstance(sp, torch.Tensor) else tensor(sp)
-        return dict(sampling_prob=sp.contiguous(), beta=config.replay_beta(), replay_eps=config.replay_eps,
-                    replay_alpha=config.replay_alpha)
+        return dict(sampling_prob=sp.contiguous(), beta=config.replay_beta() if beta is None else beta,
+                    replay_eps=config.replay_eps, replay_alpha=config.replay_alpha)
+
+    def _noisy_on_kernels(self):
+        return bool(self.config.noisy_linear) and _fused_noisy(self.config, self.network)
+
+    def _backward(self, net_out, grad):
+        """The update's backward pass.  With noisy layers on csrc/noisy.hip every layer writes its parameter gradients straight
+        into .grad (nets.direct_param_grads: the online network is differentiated once per update, so 0 + g == g) -- autograd's
+        accumulation would re-read and re-write fc4's two 6.4 MB gradients with an element-wise kernel each."""
+        if self._noisy_on_kernels():
+            from .nets import direct_param_grads
+            with direct_param_grads(True):
+                net_out.backward(grad)
+        else:
+            net_out.backward(grad)
+
+    def _device_priorities(self):
+        """New priorities go to the tree without visiting the host (PrioritizedReplay.commit_device): the default for noisy
+        agents on csrc/noisy.hip; config.device_priorities overrides (False: the host round trip of update_priorities)."""
+        want = getattr(self.config, 'device_priorities', None)
+        if want is None:
+            want = self._noisy_on_kernels()
+        return bool(want) and hasattr(self._inner_replay(), 'commit_device')
 
     def _loss_grad(self, transitions, per):
         """Forward passes + the fused TD kernel.  Returns (kernel outputs, (net_output, grad))."""
@@ -740,20 +820,24 @@ class DQNAgent(BaseAgent):
             q_next_online = self.network(next_states)['q'] if config.double_q else None
         action, reward, mask = self._batch_scalars(transitions)
         q = self.network(states)['q']
+        per = {k: v for k, v in (per or {}).items() if k != 'beta_dev'}     # (td_loss reads a device beta behind the probabilities)
         out = ops.td_loss(q.detach(), q_next, action, reward, mask, config.discount ** config.n_step,
-                          q_next_online=q_next_online, **(per or {}))
+                          q_next_online=q_next_online, **per)
         return out, (q, out['dq'])
 
-    def _learn(self, transitions):
+    def _learn(self, transitions, beta=None):
         config = self.config
         is_per = isinstance(transitions, PrioritizedTransition)
-        out, (net_out, grad) = self._loss_grad(transitions, self._per_args(transitions) if is_per else None)
+        out, (net_out, grad) = self._loss_grad(transitions, self._per_args(transitions, beta) if is_per else None)
         if is_per:
             idxs = transitions.idx
             idxs = to_np(idxs.long()) if isinstance(idxs, torch.Tensor) else np.asarray(idxs, dtype=np.int64)
-            self.replay.update_priorities(zip(idxs, to_np(out['prio'])))
+            if self._device_priorities():
+                self._inner_replay().commit_device(idxs, out['prio'].contiguous())
+            else:
+                self.replay.update_priorities(zip(idxs, to_np(out['prio'])))
         self._fused.zero_grad()
-        net_out.backward(grad)
+        self._backward(net_out, grad)
         with config.lock:
             self._fused.step(config.gradient_clip)
         return out
@@ -849,6 +933,10 @@ class DQNAgent(BaseAgent):
         ops.copy_f32(self._target_flat.flat, self._fused.flat.flat)
         for tb, b in zip(self.target_network.buffers(), self.network.buffers()):
             tb.copy_(b)
+        # (a NoisyLinear forms weight_epsilon / bias_epsilon on demand: the copies are as current as the originals were)
+        for tm, m in zip(self.target_network.modules(), self.network.modules()):
+            if hasattr(m, '_eps_stale'):
+                tm._eps_stale = m._eps_stale
 
 
 class CategoricalDQNActor(DQNActor):
@@ -905,12 +993,19 @@ class CategoricalDQNAgent(DQNAgent):
         action, reward, mask = self._batch_scalars(transitions)
         logits = self.network(states)['logits']
         weights = prio_w = None
-        if per is not None:
+        dev_beta = per is not None and per.get('beta_dev') is not None      # (captured update: beta lives in a device word)
+        if dev_beta:
+            _, weights = ops.per_weights_dev(None, per['sampling_prob'], per['beta_dev'], per['replay_eps'], per['replay_alpha'])
+        elif per is not None:
             _, weights = ops.per_weights(None, per['sampling_prob'], per['beta'], per['replay_eps'], per['replay_alpha'])
         out = ops.c51_loss(logits.detach().contiguous(), logits_t.contiguous(), action, reward, mask,
                            config.discount ** config.n_step, self.atoms, config.categorical_v_min,
                            config.categorical_v_max, logits_next_online=logits_o, weights=weights)
-        if per is not None:
+        if dev_beta:
+            out['prio'], _ = ops.per_weights_dev(out['kl'], per['sampling_prob'], per['beta_dev'], per['replay_eps'],
+                                                 per['replay_alpha'])
+            out['weights'] = weights
+        elif per is not None:
             out['prio'], _ = ops.per_weights(out['kl'], per['sampling_prob'], per['beta'], per['replay_eps'],
                                              per['replay_alpha'])
             out['weights'] = weights

@@ -533,11 +533,101 @@ class Conv2d(nn.Conv2d):
 
 
 # ---------------------------------------------------------------------------------------------------- NoisyLinear
+class _NoisyLinearFn(torch.autograd.Function):
+    """A NoisyLinear layer in training mode on csrc/noisy.hip: forward and backward straight from the raw noise vectors; the
+    mixed weight W_mu + W_sigma * eps_W and eps_W itself are never written."""
+
+    @staticmethod
+    def forward(ctx, x, w_mu, w_sigma, b_mu, b_sigma, e_in, e_out, e_b, act, x_relu):
+        y = ops.noisy_linear_fwd(x, w_mu, w_sigma, b_mu, b_sigma, e_in, e_out, e_b, act=act)
+        ctx.save_for_backward(x, w_mu, w_sigma, y)
+        ctx.noise = (e_in, e_out, e_b)          # (buffers that reset_noise() rewrites in place: not autograd-tracked state)
+        ctx.act, ctx.x_relu = act, bool(x_relu)
+        ctx.params = (w_mu, w_sigma, b_mu, b_sigma)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, w_mu, w_sigma, y = ctx.saved_tensors
+        dy = dy.contiguous()
+        dpre = dy if (ctx.act == "relu" and _already_masked(dy)) else (ops.act_bwd(dy, y, ctx.act) if ctx.act else dy)
+        want_dx = bool(ctx.needs_input_grad[0])
+        slots = _noisy_slots(ctx.params)
+        dx, dwm, dws, dbm, dbs = ops.noisy_linear_bwd(dpre, x, w_mu, w_sigma, *ctx.noise, x_relu=ctx.x_relu, want_dx=want_dx,
+                                                      **slots)
+        if ctx.x_relu and dx is not None:
+            _mark_masked(dx)
+        if slots:
+            return dx, None, None, None, None, None, None, None, None, None
+        return dx, dwm, dws, dbm, dbs, None, None, None, None, None
+
+
+def _noisy_slots(params):
+    """Keyword arguments that send a noisy layer's four parameter gradients straight into the parameters' .grad (inside
+    direct_param_grads, first visit), or {} (autograd accumulates what the kernel returns)."""
+    slots = [_grad_slot(p) for p in params] if _claim_direct(params) else [None]
+    if all(g is not None and g.is_contiguous() for g in slots):
+        return dict(dw_mu=slots[0], dw_sigma=slots[1], db_mu=slots[2], db_sigma=slots[3])
+    _SHARED[0] = True
+    return {}
+
+
+class _DuelingAtomsFn(torch.autograd.Function):
+    """logits = value + (advantage - mean_a advantage) over atoms (network_heads.py:79-86), one launch each way."""
+
+    @staticmethod
+    def forward(ctx, value, advantage):
+        return ops.dueling_atoms_fwd(value, advantage)
+
+    @staticmethod
+    def backward(ctx, g):
+        return ops.dueling_atoms_bwd(g.contiguous())
+
+
+class _NoisyDuelingHeadsFn(torch.autograd.Function):
+    """RainbowNet's two noisy heads and the dueling combination on the shared features: forward = two noisy GEMMs + the dueling
+    launch; backward = its transpose, with the advantage head's input-gradient launch adding the value head's (no separate
+    accumulation) and applying the ReLU mask of the features (the body's fc4 ends in a fused ReLU)."""
+
+    @staticmethod
+    def forward(ctx, phi, vw_mu, vw_sigma, vb_mu, vb_sigma, ve_in, ve_out, ve_b, aw_mu, aw_sigma, ab_mu, ab_sigma, ae_in, ae_out,
+                ae_b, action_dim, num_atoms, x_relu):
+        value = ops.noisy_linear_fwd(phi, vw_mu, vw_sigma, vb_mu, vb_sigma, ve_in, ve_out, ve_b)
+        adv = ops.noisy_linear_fwd(phi, aw_mu, aw_sigma, ab_mu, ab_sigma, ae_in, ae_out, ae_b)
+        ctx.save_for_backward(phi, vw_mu, vw_sigma, aw_mu, aw_sigma)
+        ctx.noise = (ve_in, ve_out, ve_b, ae_in, ae_out, ae_b)
+        ctx.vparams, ctx.aparams = (vw_mu, vw_sigma, vb_mu, vb_sigma), (aw_mu, aw_sigma, ab_mu, ab_sigma)
+        ctx.x_relu = bool(x_relu)
+        return ops.dueling_atoms_fwd(value, adv.view(-1, action_dim, num_atoms))
+
+    @staticmethod
+    def backward(ctx, g):
+        phi, vw_mu, vw_sigma, aw_mu, aw_sigma = ctx.saved_tensors
+        dv, da = ops.dueling_atoms_bwd(g.contiguous())
+        want_dx = bool(ctx.needs_input_grad[0])
+        vslots, aslots = _noisy_slots(ctx.vparams), _noisy_slots(ctx.aparams)
+        rv = ops.noisy_linear_bwd(dv, phi, vw_mu, vw_sigma, *ctx.noise[:3], want_dx=want_dx, **vslots)
+        ra = ops.noisy_linear_bwd(da.view(da.shape[0], -1), phi, aw_mu, aw_sigma, *ctx.noise[3:], x_relu=ctx.x_relu, want_dx=want_dx,
+                                  dx_add=rv[0], **aslots)
+        if ctx.x_relu and ra[0] is not None:
+            _mark_masked(ra[0])
+        gv = (None,) * 4 if vslots else rv[1:]
+        ga = (None,) * 4 if aslots else ra[1:]
+        return (ra[0],) + tuple(gv) + (None,) * 3 + tuple(ga) + (None,) * 6
+
+
 class NoisyLinear(nn.Module):
     """Linear layer with factorised Gaussian parameter noise (Fortunato et al.; parameter / buffer names and initial
     values of network_utils.py:31-83 so that Rainbow checkpoints interchange):  y = x (W_mu + W_sigma * eps_W)^T +
     (b_mu + b_sigma * eps_b),  eps_W = f(e_out) f(e_in)^T,  eps_b = f(e_b),  f(e) = sign(e) sqrt|e|,  e ~ N(0, NOISY_LAYER_STD^2)
-    redrawn by reset_noise().  Evaluation mode uses the means only.  The mixed weight feeds the HIP GEMM."""
+    redrawn by reset_noise().  Evaluation mode uses the means only.
+
+    fused_noisy (default on; DQNAgent copies config.fused_noisy onto its networks): in training mode on the device the layer
+    runs on csrc/noisy.hip from the three raw noise vectors; weight_epsilon / bias_epsilon stay in state_dict() with the
+    reference's names and values but are formed only when somebody asks for them (state_dict(), ensure_epsilon()).  Off: the
+    mixed weight is materialised and feeds the plain HIP GEMM (the path every CPU tensor takes as well)."""
+    fused_noisy = True
+    masks_input_relu = False    # set by a body whose previous layer ends in a fused ReLU (see _MASKED); csrc/noisy.hip path only
 
     def __init__(self, in_features, out_features, std_init=0.4):
         super(NoisyLinear, self).__init__()
@@ -550,6 +640,7 @@ class NoisyLinear(nn.Module):
         for name, n in (('noise_in', in_features), ('noise_out_weight', out_features), ('noise_out_bias', out_features)):
             self.register_buffer(name, torch.zeros(n))
         self.fused_act = None
+        self._eps_stale = False
         self.reset_parameters()
         self.reset_noise()
 
@@ -564,26 +655,120 @@ class NoisyLinear(nn.Module):
     def transform_noise(x):
         return x.sign().mul(x.abs().sqrt())
 
+    NOISE_NAMES = ('noise_in', 'noise_out_weight', 'noise_out_bias')       # the reference's draw order within a layer
+
     def reset_noise(self):
         """network_utils.py:73-80.  The three normal vectors are drawn from torch's CPU generator, in the reference's
         order and with its tensor sizes (the reference's buffers live on Config.DEVICE = CPU there), and uploaded: like
         every other random stream of the hot path the noise is host-drawn, so a seeded run consumes the generator exactly
-        as the reference does.  The factorised products are formed on the device."""
+        as the reference does.  (A RainbowNet draws the same stream for all its layers into one staging block and uploads
+        it with one copy: _NoiseBlock.)"""
         for e in (self.noise_in, self.noise_out_weight, self.noise_out_bias):       # this draw order
             e.copy_(torch.empty(e.shape, dtype=e.dtype).normal_(std=Config.NOISY_LAYER_STD))
-        self.refresh_epsilon()
+        self.noise_changed()
+
+    def noise_changed(self):
+        """The noise vectors hold new values: the factorised products are stale.  The fused path never needs them; the module
+        path forms them now, as before."""
+        if self.fused_noisy:
+            self._eps_stale = True
+        else:
+            self.refresh_epsilon()
 
     def refresh_epsilon(self):
         """weight_epsilon = f(noise_out_weight) f(noise_in)^T, bias_epsilon = f(noise_out_bias) from the current noise vectors."""
         f = self.transform_noise
         self.weight_epsilon.copy_(torch.outer(f(self.noise_out_weight), f(self.noise_in)))
         self.bias_epsilon.copy_(f(self.noise_out_bias))
+        self._eps_stale = False
+
+    def ensure_epsilon(self):
+        if self._eps_stale:
+            with torch.no_grad():
+                self.refresh_epsilon()
+
+    # weight_epsilon / bias_epsilon are part of the reference's state dict: hand out current values, accept loaded ones
+    def _save_to_state_dict(self, destination, prefix, keep_vars):
+        self.ensure_epsilon()
+        super(NoisyLinear, self)._save_to_state_dict(destination, prefix, keep_vars)
+
+    def _load_from_state_dict(self, state_dict, prefix, *args, **kwargs):
+        super(NoisyLinear, self)._load_from_state_dict(state_dict, prefix, *args, **kwargs)
+        has_noise = any(prefix + n in state_dict for n in self.NOISE_NAMES)
+        has_eps = prefix + 'weight_epsilon' in state_dict and prefix + 'bias_epsilon' in state_dict
+        if has_noise and not has_eps:
+            self._eps_stale = True      # new noise vectors without their products
+        elif has_eps:
+            self._eps_stale = False     # the loaded products stand (the reference keeps them consistent with the vectors)
 
     def forward(self, x):
         if not self.training:
             return linear(x, self.weight_mu, self.bias_mu, self.fused_act)
+        if self.fused_noisy and x.is_cuda and x.dim() == 2 and x.shape[0] <= 1024 and x.dtype == torch.float32:
+            return _NoisyLinearFn.apply(x, self.weight_mu, self.weight_sigma, self.bias_mu, self.bias_sigma, self.noise_in,
+                                        self.noise_out_weight, self.noise_out_bias, self.fused_act, self.masks_input_relu)
+        self.ensure_epsilon()
         return linear(x, self.weight_mu + self.weight_sigma * self.weight_epsilon,
                       self.bias_mu + self.bias_sigma * self.bias_epsilon, self.fused_act)
+
+
+class _NoiseBlock:
+    """The noise vectors of several NoisyLinear layers as views of ONE flat device buffer, refilled by one asynchronous copy from a
+    rotating pinned staging block (an event per slot guards its reuse, as agents._GraphedQ stages observations).  The draws stay
+    on the host: one normal_ per vector from torch's CPU generator, in the reference's order -- a single draw of the concatenated
+    length would not give the same stream.  Static addresses: a captured graph reads whatever the last reset_noise() uploaded."""
+    SLOTS = 4
+
+    def __init__(self, layers):
+        self.layers = list(layers)                  # [(name, NoisyLinear)] in draw order
+        self.slices = {}                            # (layer name, buffer name) -> (offset, length), offsets 16-byte aligned
+        off = 0
+        for lname, m in self.layers:
+            for bname in NoisyLinear.NOISE_NAMES:
+                n = getattr(m, bname).numel()
+                self.slices[(lname, bname)] = (off, n)
+                off += (n + 3) // 4 * 4
+        self.numel = off
+        dev = self.layers[0][1].noise_in.device
+        self.device = dev
+        self.flat = torch.zeros(off, dtype=torch.float32, device=dev)
+        for lname, m in self.layers:
+            for bname in NoisyLinear.NOISE_NAMES:
+                o, n = self.slices[(lname, bname)]
+                self.flat[o:o + n].copy_(getattr(m, bname))
+                m._buffers[bname] = self.flat[o:o + n]
+        pin = dev.type == 'cuda'
+        self.stage = [torch.zeros(off, dtype=torch.float32).pin_memory() if pin else torch.zeros(off, dtype=torch.float32)
+                      for _ in range(self.SLOTS if pin else 1)]
+        self.events = [None] * len(self.stage)
+        self.k = 0
+        self.host = self.stage[0]                   # the staging block the last draw() filled
+
+    def intact(self):
+        """The modules' buffers are still the views (Module.to() / .cuda() replace them by fresh tensors)."""
+        base = self.flat.data_ptr()
+        return all(getattr(m, b).data_ptr() == base + 4 * self.slices[(ln, b)][0] for ln, m in self.layers
+                   for b in NoisyLinear.NOISE_NAMES)
+
+    def draw(self):
+        k = self.k
+        self.k = (k + 1) % len(self.stage)
+        if self.events[k] is not None:
+            self.events[k].synchronize()
+        host = self.stage[k]
+        std = Config.NOISY_LAYER_STD
+        for lname, _ in self.layers:
+            for bname in NoisyLinear.NOISE_NAMES:
+                o, n = self.slices[(lname, bname)]
+                host[o:o + n].normal_(std=std)
+        self.host = host
+        self.flat.copy_(host, non_blocking=True)
+        if self.device.type == 'cuda':
+            if self.events[k] is None:
+                self.events[k] = torch.cuda.Event()
+            self.events[k].record()
+        for _, m in self.layers:
+            m.noise_changed()
 
 
 # ---------------------------------------------------------------------------------------------------- bodies
@@ -605,7 +790,13 @@ class NatureConvBody(nn.Module):
         self.conv2.input_is_relu = self.conv3.input_is_relu = True
         if not noisy_linear:
             self.fc4.input_is_relu = True
+        else:
+            self.fc4.masks_input_relu = True    # (its csrc/noisy.hip backward only; the module path leaves the mask to conv3)
         self.noisy_linear = noisy_linear
+
+    def noisy_layers(self):
+        """[(name, layer)] of this body's NoisyLinear layers, in the order reset_noise() draws them."""
+        return [('fc4', self.fc4)] if self.noisy_linear else []
 
     def reset_noise(self):
         if self.noisy_linear:
@@ -646,6 +837,9 @@ class FCBody(nn.Module):
             layer.fused_act = self._fused
         self.feature_dim = dims[-1]
         self.noisy_linear = noisy_linear
+
+    def noisy_layers(self):
+        return [('layers.%d' % i, layer) for i, layer in enumerate(self.layers)] if self.noisy_linear else []
 
     def reset_noise(self):
         if self.noisy_linear:
@@ -724,24 +918,72 @@ class CategoricalNet(nn.Module, BaseNet):
 
 class RainbowNet(nn.Module, BaseNet):
     """Dueling heads over atoms: logits[a] = value + (advantage[a] - mean_a advantage), softmax over the atoms; the
-    heads (and the body's fc4) are NoisyLinear when noisy_linear (module names of network_heads.py:57-86)."""
+    heads (and the body's fc4) are NoisyLinear when noisy_linear (module names of network_heads.py:57-86).
+
+    fused_noisy (default on): on the device the noisy heads + dueling combination are one autograd node over csrc/noisy.hip,
+    and reset_noise() draws all layers' vectors into one pinned block that reaches the device as one copy (_NoiseBlock)."""
+    fused_noisy = True
 
     def __init__(self, action_dim, num_atoms, body, noisy_linear):
         super(RainbowNet, self).__init__()
         self.fc_value = _head(body.feature_dim, num_atoms, noisy=noisy_linear)
         self.fc_advantage = _head(body.feature_dim, action_dim * num_atoms, noisy=noisy_linear)
         self.action_dim, self.num_atoms, self.body, self.noisy_linear = action_dim, num_atoms, body, noisy_linear
+        self._noise_block = None
         self.to(Config.DEVICE)
 
+    def set_fused_noisy(self, on):
+        """Switches this network and its NoisyLinear layers between csrc/noisy.hip and the module path."""
+        on = bool(on)
+        self.fused_noisy = on
+        for m in self.modules():
+            if isinstance(m, NoisyLinear):
+                m.fused_noisy = on
+                if not on:
+                    m.ensure_epsilon()      # the module path keeps the products current
+
+    def noisy_layers(self):
+        """[(name, layer)] in the reference's draw order: fc_value, fc_advantage, then the body's (network_heads.py:73-77)."""
+        if not self.noisy_linear:
+            return []
+        body = [('body.' + n, m) for n, m in getattr(self.body, 'noisy_layers', lambda: [])()]
+        return [('fc_value', self.fc_value), ('fc_advantage', self.fc_advantage)] + body
+
+    def noise_block(self):
+        """The staging block of the fused reset_noise() (built on first use; rebuilt when the buffers were moved)."""
+        if self._noise_block is None or not self._noise_block.intact():
+            self._noise_block = _NoiseBlock(self.noisy_layers())
+        return self._noise_block
+
     def reset_noise(self):
-        if self.noisy_linear:
-            for m in (self.fc_value, self.fc_advantage, self.body):
-                m.reset_noise()
+        if not self.noisy_linear:
+            return
+        # (a body that redraws noise of its own without listing its layers keeps the per-module draw)
+        if self.fused_noisy and (hasattr(self.body, 'noisy_layers') or not hasattr(self.body, 'reset_noise')):
+            self.noise_block().draw()
+            return
+        for m in (self.fc_value, self.fc_advantage, self.body):
+            m.reset_noise()
+
+    def _heads(self, phi):
+        if (self.noisy_linear and self.fused_noisy and self.training and phi.is_cuda and phi.dim() == 2 and phi.shape[0] <= 1024
+                and self.fc_value.fused_noisy and self.fc_advantage.fused_noisy):
+            v, a = self.fc_value, self.fc_advantage
+            x_relu = bool(getattr(self.body, 'noisy_linear', False)) and getattr(getattr(self.body, 'fc4', None), 'fused_noisy', False) \
+                and getattr(self.body.fc4, 'fused_act', None) == 'relu' and torch.is_grad_enabled()
+            return _NoisyDuelingHeadsFn.apply(phi, v.weight_mu, v.weight_sigma, v.bias_mu, v.bias_sigma, v.noise_in,
+                                              v.noise_out_weight, v.noise_out_bias, a.weight_mu, a.weight_sigma, a.bias_mu,
+                                              a.bias_sigma, a.noise_in, a.noise_out_weight, a.noise_out_bias, self.action_dim,
+                                              self.num_atoms, x_relu)
+        adv = self.fc_advantage(phi).view(-1, self.action_dim, self.num_atoms)
+        value = self.fc_value(phi)
+        if self.fused_noisy and phi.is_cuda:
+            return _DuelingAtomsFn.apply(value.contiguous(), adv.contiguous())
+        return value.view(-1, 1, self.num_atoms) + adv - adv.mean(1, keepdim=True)
 
     def forward(self, x):
         phi = self.body(tensor(x))
-        adv = self.fc_advantage(phi).view(-1, self.action_dim, self.num_atoms)
-        logits = self.fc_value(phi).view(-1, 1, self.num_atoms) + adv - adv.mean(1, keepdim=True)
+        logits = self._heads(phi)
         return dict(prob=F.softmax(logits, dim=-1), log_prob=F.log_softmax(logits, dim=-1), logits=logits)
 
 

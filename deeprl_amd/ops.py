@@ -988,6 +988,98 @@ def linear_bwd_x(dy, w, xact=None, act=None, dx=None):
     return dx
 
 
+# ------------------------------------------------------------------------------------------ noisy layers (csrc/noisy.hip)
+_noisy_ws_need = {}
+
+
+def _noisy_workspace(device, rows, fin, fout, which):
+    need = _noisy_ws_need.get((rows, fin, fout))
+    if need is None:
+        f, b = ctypes.c_int64(0), ctypes.c_int64(0)
+        lib.dra_noisy_workspace_floats(rows, fin, fout, ctypes.byref(f), ctypes.byref(b))
+        need = _noisy_ws_need[(rows, fin, fout)] = (f.value, b.value)
+    return _workspace(device, need[which])
+
+
+def noisy_linear_fwd(x, w_mu, w_sigma, b_mu, b_sigma, noise_in, noise_out_weight, noise_out_bias, act=None):
+    """y = act(x W^T + b) of a NoisyLinear layer (network_utils.py:54-62) from the raw noise vectors; the mixed weight is never
+    formed.  x [rows <= 1024, in], w_* [out, in]."""
+    x, w_mu, w_sigma = _c(x, _f32), _c(w_mu, _f32), _c(w_sigma, _f32)
+    rows, fin = x.shape
+    fout = w_mu.shape[0]
+    if w_mu.shape != (fout, fin) or w_sigma.shape != (fout, fin) or noise_in.numel() != fin or noise_out_weight.numel() != fout \
+            or noise_out_bias.numel() != fout or b_mu.numel() != fout or b_sigma.numel() != fout:
+        raise DraError("noisy_linear_fwd: shapes do not agree")
+    y = torch.empty((rows, fout), dtype=_f32, device=x.device)
+    ws = _noisy_workspace(x.device, rows, fin, fout, 0)
+    lib.dra_noisy_linear_fwd(ptr(x), ptr(w_mu), ptr(w_sigma), ptr(_c(b_mu, _f32)), ptr(_c(b_sigma, _f32)), ptr(_c(noise_in, _f32)),
+                             ptr(_c(noise_out_weight, _f32)), ptr(_c(noise_out_bias, _f32)), ptr(y), rows, fin, fout, ACT[act],
+                             ptr(ws), ws.numel(), stream_ptr())
+    return y
+
+
+def noisy_linear_bwd(g, x, w_mu, w_sigma, noise_in, noise_out_weight, noise_out_bias, x_relu=False, want_dx=True, dw_mu=None,
+                     dw_sigma=None, db_mu=None, db_sigma=None, dx_add=None):
+    """Backward of noisy_linear_fwd from g = dL/d(pre-activation) -> (dx, dw_mu, dw_sigma, db_mu, db_sigma); the four parameter
+    gradients go into the given (contiguous) tensors when all four are passed.  dx_add [rows, in]: added to dx (the input gradient
+    of another head on the same features).  x_relu: x is a fused-ReLU output, dx comes back as the gradient of its
+    pre-activation."""
+    g, x, w_mu, w_sigma = _c(g, _f32), _c(x, _f32), _c(w_mu, _f32), _c(w_sigma, _f32)
+    rows, fin = x.shape
+    fout = w_mu.shape[0]
+    if g.shape != (rows, fout) or w_mu.shape != (fout, fin) or w_sigma.shape != (fout, fin):
+        raise DraError("noisy_linear_bwd: shapes do not agree")
+    dev = x.device
+    if dw_mu is None:
+        dw_mu, dw_sigma = torch.empty((fout, fin), dtype=_f32, device=dev), torch.empty((fout, fin), dtype=_f32, device=dev)
+        db_mu, db_sigma = torch.empty(fout, dtype=_f32, device=dev), torch.empty(fout, dtype=_f32, device=dev)
+    dx = torch.empty((rows, fin), dtype=_f32, device=dev) if want_dx else None
+    ws = _noisy_workspace(dev, rows, fin, fout, 1)
+    lib.dra_noisy_linear_bwd(ptr(g), ptr(x), ptr(w_mu), ptr(w_sigma), ptr(_c(noise_in, _f32)), ptr(_c(noise_out_weight, _f32)),
+                             ptr(_c(noise_out_bias, _f32)), ptr(x if (x_relu and want_dx) else None),
+                             ptr(None if (dx_add is None or not want_dx) else _c(dx_add, _f32)), ptr(dw_mu), ptr(dw_sigma),
+                             ptr(db_mu), ptr(db_sigma), ptr(dx), rows, fin, fout, ptr(ws), ws.numel(), stream_ptr())
+    return dx, dw_mu, dw_sigma, db_mu, db_sigma
+
+
+def dueling_atoms_fwd(value, advantage):
+    """logits[b, a, :] = value[b, :] + (advantage[b, a, :] - mean_a advantage[b, :, :]) (network_heads.py:79-86); value [B, Z],
+    advantage [B, A, Z]."""
+    value, advantage = _c(value, _f32), _c(advantage, _f32)
+    b, a, z = advantage.shape
+    if value.shape != (b, z):
+        raise DraError("dueling_atoms_fwd: value %s does not fit advantage %s" % (tuple(value.shape), tuple(advantage.shape)))
+    out = torch.empty_like(advantage)
+    lib.dra_dueling_atoms_fwd(ptr(value), ptr(advantage), b, a, z, ptr(out), stream_ptr())
+    return out
+
+
+def dueling_atoms_bwd(g_logits):
+    """(d_value [B, Z], d_advantage [B, A, Z]) of dueling_atoms_fwd."""
+    g = _c(g_logits, _f32)
+    b, a, z = g.shape
+    dv = torch.empty((b, z), dtype=_f32, device=g.device)
+    da = torch.empty_like(g)
+    lib.dra_dueling_atoms_bwd(ptr(g), b, a, z, ptr(dv), ptr(da), stream_ptr())
+    return dv, da
+
+
+def per_weights_dev(loss_vec, sampling_prob, beta_dev, replay_eps, replay_alpha, prio=None, w=None):
+    """per_weights with the importance exponent in a device word (beta_dev: f32 tensor of one element): no per-update launch
+    argument, so the launch can be captured."""
+    sp = _c(sampling_prob, _f32)
+    b = sp.numel()
+    if beta_dev.dtype != _f32 or beta_dev.numel() < 1:
+        raise DraError("per_weights_dev: beta_dev must hold one f32")
+    if prio is None and loss_vec is not None:
+        prio = torch.empty(b, dtype=_f32, device=sp.device)
+    if w is None:
+        w = torch.empty(b, dtype=_f32, device=sp.device)
+    lib.dra_per_weights_dev(ptr(None if loss_vec is None else _c(loss_vec, _f32)), ptr(sp), b, ptr(_dev(beta_dev)),
+                            float(replay_eps), float(replay_alpha), ptr(prio), ptr(w), stream_ptr())
+    return prio, w
+
+
 # ------------------------------------------------------------------------------------------ optimiser
 def norm_partials():
     return lib.dra_norm_partials.raw()

@@ -16,7 +16,7 @@ import torch.nn.functional as F
 from deeprl_amd import agents as A, nets as N
 from deeprl_amd.envs import Task
 from deeprl_amd.normalizers import ImageNormalizer, MeanStdNormalizer, SignNormalizer
-from deeprl_amd.replay import ReplayWrapper, UniformReplay
+from deeprl_amd.replay import PrioritizedReplay, ReplayWrapper, UniformReplay
 from deeprl_amd.support import Config, LinearSchedule, generate_tag, run_steps
 
 
@@ -70,6 +70,19 @@ ZOO = {
                     gradient_clip=0.5, max_steps=int(2e7)),
         normalizers=(ImageNormalizer, SignNormalizer),
         replay=dict(memory_size=int(1e6), history_length=4, fixed_cls=UniformReplay, fixed_async=True), eps=(1.0, 0.01, 1e6)),
+    # examples.py:283-336 (Config.NOISY_LAYER_STD is a CLASS attribute the entry point raises to 0.5 when it runs)
+    "rainbow_pixel": dict(
+        agent="CategoricalDQNAgent",
+        kw=dict(log_level=0, n_step=1, replay_cls=PrioritizedReplay, async_replay=True, noisy_linear=True),
+        task=lambda c: Task(c.game), eval_task="same", class_fields=dict(NOISY_LAYER_STD=0.5),
+        optimizer=_adam(lr=0.000625, eps=1.5e-4),
+        network=lambda c: N.RainbowNet(c.action_dim, c.categorical_n_atoms, N.NatureConvBody(noisy_linear=c.noisy_linear),
+                                       noisy_linear=c.noisy_linear),
+        fields=dict(max_steps=int(2e7), categorical_v_max=10, categorical_v_min=-10, categorical_n_atoms=51, batch_size=32,
+                    discount=0.99, history_length=4, replay_eps=0.01, replay_alpha=0.5, target_network_update_freq=2000,
+                    exploration_steps=20000, sgd_update_frequency=4, double_q=True, async_actor=True, gradient_clip=10),
+        normalizers=(ImageNormalizer, SignNormalizer),
+        replay=dict(memory_size=int(1e6), with_n_step=True), eps=(1, 0.01, 25e4), beta=(0.4, 1.0)),
     # examples.py:361-381
     "a2c_pixel": dict(
         agent="A2CAgent", kw=dict(log_level=0), pre_fields=dict(num_workers=16),
@@ -132,6 +145,8 @@ def config(name, **kwargs):
         setattr(c, k, v)
     c.task_fn = lambda: spec["task"](c)
     c.eval_env = c.task_fn() if spec.get("eval_task") == "same" else spec["eval_task"](c)
+    for k, v in spec.get("class_fields", {}).items():      # what the entry point sets on the Config CLASS
+        setattr(Config, k, v)
     if "optimizer" in spec:
         c.optimizer_fn = spec["optimizer"]
     if "actor_opt" in spec:

@@ -259,6 +259,35 @@ int dra_linear_bwd_w(const float* dy, const float* x, float* dw, float* db, int 
 int dra_linear_bwd_x(const float* dy, const float* w, const float* xact, float* dx, int batch, int in_features,
                      int out_features, int act, void* stream);
 
+/* ---- Rainbow's noisy layers (csrc/noisy.hip): deep_rl/network/network_utils.py:31-83 (NoisyLinear; :54-62 forward, :73-83
+ * reset_noise / transform_noise).  y = act(x W^T + b), W = w_mu + w_sigma * (f(noise_out_weight) f(noise_in)^T),
+ * b = b_mu + b_sigma * f(noise_out_bias), f(e) = sign(e) sqrt|e|, straight from the three RAW noise vectors: neither W nor
+ * weight_epsilon is written to memory, w_mu and w_sigma are read once per launch.  x [rows <= 1024][in], w_* [out][in], all f32;
+ * act in {DRA_ACT_NONE, DRA_ACT_RELU}.  Fixed summation order (no atomics): repeated calls give the same bits.
+ * workspace: dra_noisy_workspace_floats(rows, in, out) floats of scratch (split-K / split-N slabs), 16-byte aligned. */
+int dra_noisy_workspace_floats(int rows, int in_features, int out_features, int64_t* fwd_floats, int64_t* bwd_floats);
+int dra_noisy_linear_fwd(const float* x, const float* w_mu, const float* w_sigma, const float* b_mu, const float* b_sigma,
+                         const float* noise_in, const float* noise_out_weight, const float* noise_out_bias, float* y, int rows,
+                         int in_features, int out_features, int act, float* workspace, int64_t workspace_floats, void* stream);
+/* backward of the same from g = dL/d(pre-activation) [rows][out]: dw_mu = g^T x, dw_sigma = dw_mu * weight_epsilon (one contraction,
+ * two stores), db_mu = sum_rows g, db_sigma = db_mu * f(noise_out_bias), dx = g w_mu + ((g * f(noise_out_weight)) w_sigma) *
+ * f(noise_in), plus dx_add [rows][in] when given (the input gradient of another head on the same features), times [x_relu > 0]
+ * when x_relu (the layer's input, a fused-ReLU output) is given.  dw_* / db_* (pairwise) and dx may be NULL. */
+int dra_noisy_linear_bwd(const float* g, const float* x, const float* w_mu, const float* w_sigma, const float* noise_in,
+                         const float* noise_out_weight, const float* noise_out_bias, const float* x_relu, const float* dx_add,
+                         float* dw_mu, float* dw_sigma, float* db_mu, float* db_sigma, float* dx, int rows, int in_features,
+                         int out_features, float* workspace, int64_t workspace_floats, void* stream);
+/* network_heads.py:79-86 (RainbowNet.forward): logits[b][a][z] = value[b][z] + (advantage[b][a][z] - mean_a advantage[b][.][z]),
+ * and its transpose: d_value = sum_a g, d_advantage = g - d_value / n_actions. */
+int dra_dueling_atoms_fwd(const float* value, const float* advantage, int batch, int n_actions, int n_atoms, float* logits,
+                          void* stream);
+int dra_dueling_atoms_bwd(const float* g_logits, int batch, int n_actions, int n_atoms, float* d_value, float* d_advantage,
+                          void* stream);
+/* DQN_agent.py:121-127: dra_per_weights with the importance exponent read from *beta_dev (a device word), so that the launch
+ * has no per-update argument and replays from a captured graph.  Same arithmetic, same bits. */
+int dra_per_weights_dev(const float* loss_vec, const float* sampling_prob, int batch, const float* beta_dev, float replay_eps,
+                        float replay_alpha, float* out_prio, float* out_weights, void* stream);
+
 /* ---- Atari frame preprocessing (csrc/preproc.hip): deep_rl/component/envs.py:39-47 -> baselines' MaxAndSkipEnv (max of the
  * last two raw frames) + WarpFrame (cv2 RGB2GRAY, cv2.resize INTER_AREA to 84x84), restated from OpenCV's published
  * algorithms; parity unpinned by the reference (cv2 / baselines are not in the image).  dra_resize_area_tab builds one

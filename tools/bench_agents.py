@@ -9,6 +9,8 @@ after a warm-up.  Prints one JSON object per line: agent steps/s, env steps/s, g
             DQNAgent; `_generic` = config.fused_learner False, the autograd path the other agents use)
   config 4  dqn_pixel + PrioritizedReplay (examples.py:55-97 with replay_cls=PrioritizedReplay),
             categorical_dqn_pixel examples.py:195-226, quantile_regression_dqn_pixel examples.py:129-160
+            rainbow_pixel examples.py:283-336 (PER + double Q + noisy dueling C51; `_modules` = config.fused_noisy False and
+            config.graph_update False: materialised noisy weights through the plain GEMM, eager launches)
   config 5  a2c_pixel examples.py:361-381 (16 workers), ppo_pixel examples.py:525-550 (8 workers)
             n_step_dqn_pixel examples.py:427-447 (16 workers), option_critic_pixel examples.py:471-492 (16 workers)
 """
@@ -37,10 +39,10 @@ class _Quiet:
         pass
 
 
-def dqn_family(kind, replay_cls, ring=200_000, fused=True, device=False, async_actor=None):
+def dqn_family(kind, replay_cls, ring=200_000, fused=True, device=False, async_actor=None, **switches):
     c = d.Config()
     c.merge(dict(game="synthetic-atari", log_level=0, tag="bench", n_step=1, replay_cls=replay_cls, async_replay=False,
-                 fused_learner=fused, device_env=device))     # device=False: HOST emulator; True: device-resident environment
+                 fused_learner=fused, device_env=device, **switches))     # device=False: HOST emulator; True: device-resident environment
     c.task_fn = lambda: d.Task(c.game, seed=1)
     c.eval_env = c.task_fn()
     if kind == "dqn":
@@ -53,6 +55,15 @@ def dqn_family(kind, replay_cls, ring=200_000, fused=True, device=False, async_a
         c.categorical_v_max, c.categorical_v_min, c.categorical_n_atoms = 10, -10, 51
         c.network_fn = lambda: d.CategoricalNet(c.action_dim, c.categorical_n_atoms, d.NatureConvBody())
         c.gradient_clip = 0.5
+        agent_cls = d.CategoricalDQNAgent
+    elif kind == "rainbow":
+        d.Config.NOISY_LAYER_STD = 0.5
+        c.noisy_linear = True
+        c.optimizer_fn = lambda p: torch.optim.Adam(p, lr=0.000625, eps=1.5e-4)
+        c.categorical_v_max, c.categorical_v_min, c.categorical_n_atoms = 10, -10, 51
+        c.network_fn = lambda: d.RainbowNet(c.action_dim, c.categorical_n_atoms, d.NatureConvBody(noisy_linear=True),
+                                            noisy_linear=True)
+        c.gradient_clip = 10
         agent_cls = d.CategoricalDQNAgent
     else:
         c.optimizer_fn = lambda p: torch.optim.Adam(p, lr=0.00005, eps=0.01 / 32)
@@ -73,7 +84,7 @@ def dqn_family(kind, replay_cls, ring=200_000, fused=True, device=False, async_a
     c.target_network_update_freq = 10000
     c.exploration_steps = 300          # the update phase is what is timed
     c.sgd_update_frequency = 4
-    c.double_q = False
+    c.double_q = kind == "rainbow"
     c.async_actor = bool(device) if async_actor is None else bool(async_actor)   # the reference's default for the pixel DQN family
     c.max_steps = int(2e7)
     return agent_cls(c), dict(env_per_step=4, updates_per_step=1)
@@ -171,6 +182,8 @@ CASES = {
     "c51_pixel_uniform": lambda: dqn_family("c51", d.UniformReplay),
     "c51_pixel_per": lambda: dqn_family("c51", d.PrioritizedReplay),
     "qr_dqn_pixel_uniform": lambda: dqn_family("qr", d.UniformReplay),
+    "rainbow_pixel_per": lambda: dqn_family("rainbow", d.PrioritizedReplay),      # noisy layers on csrc/noisy.hip, captured actor forward + PER update
+    "rainbow_pixel_per_modules": lambda: dqn_family("rainbow", d.PrioritizedReplay, fused_noisy=False, graph_update=False),
     "dqn_pixel_per_device": lambda: dqn_family("dqn", d.PrioritizedReplay, device=True),
     "dqn_pixel_per_device_sync": lambda: dqn_family("dqn", d.PrioritizedReplay, device=True, async_actor=False),
     "dqn_pixel_uniform_device": lambda: dqn_family("dqn", d.UniformReplay, device=True),
@@ -210,7 +223,7 @@ def main():
     for name in a.cases.split(","):
         try:
             agent, meta = CASES[name]()
-            warm = 120 if "dqn" in name or "c51" in name else 4      # DQN family: past exploration_steps; on-policy: past graph capture
+            warm = 120 if "dqn" in name or "c51" in name or "rainbow" in name else 4      # DQN family: past exploration_steps; on-policy: past graph capture
             for _ in range(warm):
                 agent.step()
             torch.cuda.synchronize()
