@@ -234,7 +234,7 @@ __device__ __forceinline__ float huber1_grad(float d) { return fabsf(d) < 1.f ? 
 // actions, the online row of the stored action as soon as the action is known); tau_i = (2i+1)/(2N) is formed once per
 // thread (fp64, then f32 as the reference's tensor() does) and kept in LDS -- the first version divided in fp64 inside
 // the inner loop and loaded the rows one action at a time: 34 us at B=32, N=200 (profiles/r02zu_kernel_stats_qr_*).
-// Same arithmetic, same summation order.
+// Same terms, same order; the gradient pass sums them four at a time in fp32 and the fours in fp64.
 __global__ void __launch_bounds__(1024)
 qr_loss_kernel(const float* __restrict__ theta, const float* __restrict__ theta_t, const void* __restrict__ action,
                int action_i64, const float* __restrict__ reward, const float* __restrict__ mask, int B, int A, int N,
@@ -278,24 +278,33 @@ qr_loss_kernel(const float* __restrict__ theta, const float* __restrict__ theta_
     __syncthreads();
     if (on) {
       const float tau = s_tau[i];
-      float acc = 0.f;
+      // a quantile far below (above) every target adds the SAME term tau (1 - tau) N times; the roundings of a serial float
+      // sum then all point one way and grow linearly with N -- 1.4e-5 of the gradient's scale at N = 1023
+      // (a float32 emulation of this loop on the CPU, case b8a4n1023 of tests/loss_edge_cases.py).  So four terms at a time are added in fp32 (three roundings, whatever N is) and the
+      // fours are carried in fp64: one convert and one fp64 add per four terms.  The terms themselves stay fp32, as the
+      // reference forms them.
+      double acc = 0.0;
       const float4* s_t4 = reinterpret_cast<const float4*>(s_t);
       const int n4 = N >> 2;
 #pragma unroll 4
       for (int j4 = 0; j4 < n4; ++j4) {     // same terms in the same order, one ds_read_b128 per four of them
         const float4 v = s_t4[j4];
         const float tj[4] = {v.x, v.y, v.z, v.w};
+        float part = 0.f;
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
           const float d = tj[u] - th_i;
-          acc += huber1_grad(d) * fabsf(tau - (d < 0.f ? 1.f : 0.f));
+          part += huber1_grad(d) * fabsf(tau - (d < 0.f ? 1.f : 0.f));
         }
+        acc += (double)part;
       }
+      float part = 0.f;
       for (int j = n4 << 2; j < N; ++j) {
         const float d = s_t[j] - th_i;
-        acc += huber1_grad(d) * fabsf(tau - (d < 0.f ? 1.f : 0.f));
+        part += huber1_grad(d) * fabsf(tau - (d < 0.f ? 1.f : 0.f));
       }
-      g[a * N + i] = -acc / ((float)N * (float)B);  // loss = mean_j mean_b sum_i rho ; d(d)/d(theta) = -1
+      acc += (double)part;
+      g[a * N + i] = -(float)acc / ((float)N * (float)B);  // loss = mean_j mean_b sum_i rho ; d(d)/d(theta) = -1
     }
     return;
   }

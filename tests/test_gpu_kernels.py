@@ -932,8 +932,8 @@ def test_grad_sqnorm_segs_many_slabs(dev):
 @pytest.mark.parametrize("b,a", [(1, 2), (16, 4), (80, 18), (1024, 6), (300, 64)])
 def test_categorical_policy_kernels_vs_torch(dev, b, a):
     """K12 (network_heads.py:249-254): log_prob / entropy of Categorical(logits) and their gradient w.r.t. the logits against
-    torch.distributions on the CPU in fp32 (absolute 2e-6 on values of magnitude <= log(A)); sampled actions are the inverse
-    CDF of the given uniforms."""
+    torch.distributions on the CPU in fp32 (absolute 2e-6 on values of magnitude <= log(A)); sampled actions are exactly
+    the float64 inverse CDF of the given uniforms."""
     from deeprl_amd import nets, ops
     rs = np.random.RandomState(b * 131 + a)
     logits = (rs.standard_normal((b, a)) * 3).astype(np.float32)
@@ -953,12 +953,15 @@ def test_categorical_policy_kernels_vs_torch(dev, b, a):
     # sampling: action = first index whose cumulative probability exceeds u
     u = rs.rand(b).astype(np.float32)
     got, lp_s, _ = ops.categorical_fwd(torch.from_numpy(logits).to(dev), uniform=torch.from_numpy(u).to(dev))
+    # exactly the float64 inverse CDF; only a row whose uniform lies within 1e-6 of a step of the CDF may differ, and at
+    # most 1 % of the rows are such rows (tests/loss_edge_cases.py)
+    from loss_edge_cases import CUM_GAP, exempt_rows, inverse_cdf
     p = torch.softmax(torch.from_numpy(logits).double(), dim=-1).numpy()
-    cum = np.cumsum(p, axis=1)
+    want_a, margin = inverse_cdf(p, u)
+    near, n_near, cap = exempt_rows(margin, CUM_GAP, b, False)
+    assert n_near <= cap, (n_near, cap)
     got = got.cpu().numpy()
-    for i in range(b):
-        lo = cum[i, got[i] - 1] if got[i] > 0 else 0.0
-        assert lo - 1e-6 <= u[i] <= cum[i, got[i]] + 1e-6 or got[i] == a - 1, (i, got[i], u[i])
+    assert np.array_equal(got[~near], want_a[~near]), np.nonzero((got != want_a) & ~near)[0]
     np.testing.assert_allclose(lp_s.cpu().numpy(), np.log(p[np.arange(b), got]), rtol=1e-5, atol=3e-6)
 
 
