@@ -1356,10 +1356,70 @@ class A2CAgent(BaseAgent):
         self._pixel_rollout = _PixelRollout(self)
         self.network.fuse_fc4_head = bool(getattr(config, 'fuse_fc4_head', True))
         self.network.rollout_fc4_slices = bool(getattr(config, 'rollout_fc4_slices', True))
+        # action noise of the device rollout: the rank-invariant stream when one is configured, else a seed of its own
+        self._noise_seed = self.dp.noise_seed
+        self._mlp_rollout, self._mlp_sig = None, None
+        from .device_env import DeviceContinuousVec
+        if DeviceContinuousVec.eligible(self.task, config):
+            # synthetic continuous-control environments under GaussianActorCriticNet over two small MLPs (a2c_continuous,
+            # examples.py:384-404): observations, counters and the observation statistics move to the device; a rollout is one
+            # launch (csrc/a2c_mlp.hip) and the update's Gaussian head one kernel each way (_step_device_mlp)
+            from . import a2c_mlp
+            shape = a2c_mlp.eligible(self)
+            if shape is not None:
+                self.task = DeviceContinuousVec(self.task, self.states, config.state_normalizer)
+                self.states = None
+                self.network.fused_gauss_head = True
+                self._mlp_rollout = a2c_mlp.Rollout(self, shape)
 
     def close(self):
         close_obj(self.task)
         self.dp.close()
+
+    def save(self, filename):
+        """The reference's two files (BaseAgent.py:24-27); on the device rollout path also `<filename>.sampler`: seed and position
+        of the counter-hash action noise (as PPOAgent.save)."""
+        BaseAgent.save(self, filename)
+        if self._mlp_rollout is not None and self.dp.is_main:
+            with open(filename + '.sampler', 'wb') as f:
+                pickle.dump(self.dp.sampler_state(), f)
+
+    def load(self, filename):
+        BaseAgent.load(self, filename)
+        if self._mlp_rollout is not None and os.path.isfile(filename + '.sampler'):
+            with open(filename + '.sampler', 'rb') as f:
+                self.dp.load_sampler_state(pickle.load(f), Config.DEVICE)
+            self._noise_seed = self.dp.noise_seed
+
+    def _step_device_mlp(self):
+        """step() over device_env.DeviceContinuousVec: A2C_agent.py:22-41 is ONE launch (dra_a2c_mlp_rollout: per step the
+        normalised observation, both forwards, action = mean + softplus(std) * noise, environment step), then _learn_stacked on
+        the rollout's buffers -- after _OnPolicyGraph.WARMUP eager rollouts both are replayed from one captured graph (a single
+        stream, no parallel branches).  The host keeps a shadow of rewards / terminals for the episodic-return log lines."""
+        from collections import namedtuple
+        config, task, dp = self.config, self.task, self.dp
+        t_len = int(config.rollout_length)
+        events = task.shadow(t_len)
+        if dp.step_dev is None:
+            dp.step_dev = torch.zeros(1, dtype=torch.int64, device=Config.DEVICE)
+        for t, i, ret in events:        # BaseAgent.record_online_return at the step the episode ended
+            at = self.total_steps + t * dp.global_workers + i
+            self.logger.add_scalar('episodic_return_train', ret, at)
+            self.logger.info('steps %d, episodic_return_train %s' % (at, ret))
+        self.total_steps += t_len * dp.global_workers
+        # what the captured launch has baked in besides the optimizer's hyper-parameters (_OnPolicyGraph's own key): whether
+        # the normaliser's statistics are updated, and the seed of the noise stream
+        sig = (bool(getattr(config.state_normalizer, 'read_only', False)), int(self._noise_seed))
+        if sig != self._mlp_sig:
+            self._dev_graph.graph, self._mlp_sig = None, sig
+        plan = namedtuple('MlpPlan', ['counters', 't_len'])(task.env_counter, t_len)
+        self.last_loss = self._dev_graph.run(plan, self._mlp_compute)
+
+    def _mlp_compute(self, plan):
+        b = self._mlp_rollout.run(plan.t_len, self._mlp_sig[0])
+        self._rollout_step += plan.t_len
+        rows = plan.t_len * self.task.num_envs
+        return self._learn_stacked(b['state'].view(rows, -1), b['action'].view(rows, -1), b['v'], b['reward'], b['mask'])
 
     def _step_device(self):
         """step() over device-resident environments: the host lays the rollout out (counters, rewards, terminals of every
@@ -1466,6 +1526,8 @@ class A2CAgent(BaseAgent):
 
     def step(self):
         if getattr(self.task, 'on_device', False):
+            if self._mlp_rollout is not None:
+                return self._step_device_mlp()
             return self._step_device()
         config = self.config
         states = self.states

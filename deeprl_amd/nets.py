@@ -319,6 +319,34 @@ class _CategoricalFn(torch.autograd.Function):
         return ops.categorical_bwd(logits, action, g_lp, g_ent), None
 
 
+class _GaussHeadFn(torch.autograd.Function):
+    """tanh, softplus, Normal(mean, scale).log_prob(action).sum(-1), .entropy().sum(-1) of GaussianActorCriticNet for given actions
+    as one kernel each way (csrc/a2c_mlp.hip: dra_gauss_head_fwd / _bwd) instead of about a dozen element-wise launches each way.
+    `mean` is returned for the caller's dict and carries no gradient (nothing on the A2C / PPO update paths differentiates it)."""
+
+    @staticmethod
+    def forward(ctx, z, std, action):
+        mean, lp, ent = ops.gauss_head_fwd(z, std, action)
+        ctx.save_for_backward(z, std, action)
+        ctx.std_param = std             # (the Parameter object itself: its .grad is where a direct write goes)
+        ctx.mark_non_differentiable(mean)
+        return mean, lp, ent
+
+    @staticmethod
+    def backward(ctx, g_mean, g_lp, g_ent):
+        z, std, action = ctx.saved_tensors
+        zero = lambda: torch.zeros((z.shape[0], 1), dtype=z.dtype, device=z.device)
+        g_lp = zero() if g_lp is None else g_lp
+        g_ent = zero() if g_ent is None else g_ent
+        slot = _grad_slot(ctx.std_param) if _claim_direct((ctx.std_param,)) else None
+        if slot is not None and slot.is_contiguous():
+            dz, _ = ops.gauss_head_bwd(z, std, action, g_lp, g_ent, dstd=slot)
+            return dz, None, None
+        _SHARED[0] = True
+        dz, dstd = ops.gauss_head_bwd(z, std, action, g_lp, g_ent)
+        return dz, dstd.view(std.shape), None
+
+
 class RolloutSlots:
     """Where a categorical actor-critic's no-grad forwards of ONE rollout get their uniforms and put their results.  The
     reference draws inside every forward (network_heads.py:251 dist.sample()); here the agent announces a rollout of `rows`
@@ -1062,7 +1090,9 @@ class DeterministicActorCriticNet(nn.Module, BaseNet):
 
 
 class GaussianActorCriticNet(nn.Module, BaseNet):
-    """network_heads.py:173-214 (PPO / A2C continuous)."""
+    """network_heads.py:173-214 (PPO / A2C continuous).  `fused_gauss_head` (off unless an agent turns it on: A2CAgent's device
+    path): forward(obs, action) routes tanh / softplus / log-probability / entropy through _GaussHeadFn."""
+    fused_gauss_head = False
 
     def __init__(self, state_dim, action_dim, phi_body=None, actor_body=None, critic_body=None):
         super(GaussianActorCriticNet, self).__init__()
@@ -1081,6 +1111,13 @@ class GaussianActorCriticNet(nn.Module, BaseNet):
         phi = self.phi_body(obs)
         phi_a = self.actor_body(phi)
         phi_v = self.critic_body(phi)
+        if (action is not None and self.fused_gauss_head and obs.is_cuda and isinstance(action, torch.Tensor) and action.is_cuda
+                and action.dtype == torch.float32 and self.std.dtype == torch.float32):
+            # the update's forward over stored actions (A2C_agent.py:55-61 reads log_pi_a, entropy, v): the head as one kernel
+            z = self.fc_action(phi_a)
+            v = self.fc_critic(phi_v)
+            mean, log_prob, entropy = _GaussHeadFn.apply(z, self.std, action)
+            return {'action': action, 'log_pi_a': log_prob, 'entropy': entropy, 'mean': mean, 'v': v}
         mean = torch.tanh(self.fc_action(phi_a))
         v = self.fc_critic(phi_v)
         scale = F.softplus(self.std)

@@ -314,6 +314,43 @@ def a2c_loss(log_pi_a, entropy, v, adv, ret, entropy_weight, value_loss_weight):
     return out4, g
 
 
+def _gauss_head_args(z, std, action):
+    z, std, action = _c(z, _f32), _c(std, _f32), _c(action, _f32)
+    if z.dim() != 2 or tuple(action.shape) != tuple(z.shape) or std.numel() != z.shape[1] or z.shape[0] < 1:
+        raise DraError("gauss_head: z / action [n, A] and std [A] expected, got %s, %s, %s" %
+                       (tuple(z.shape), tuple(action.shape), tuple(std.shape)))
+    return z, std, action
+
+
+def gauss_head_fwd(z, std, action):
+    """network_heads.py:200-214 behind fc_action for given actions (csrc/a2c_mlp.hip): z [n, A] = fc_action's output, std [A],
+    action [n, A] -> (mean = tanh(z) [n, A], log_pi_a [n, 1], entropy [n, 1]) with scale = softplus(std)."""
+    z, std, action = _gauss_head_args(z, std, action)
+    n, a_dim = z.shape
+    mean = torch.empty_like(z)
+    lp = torch.empty((n, 1), dtype=_f32, device=z.device)
+    ent = torch.empty((n, 1), dtype=_f32, device=z.device)
+    lib.dra_gauss_head_fwd(ptr(z), ptr(std), ptr(action), n, a_dim, ptr(mean), ptr(lp), ptr(ent), stream_ptr())
+    return mean, lp, ent
+
+
+def gauss_head_bwd(z, std, action, g_log_pi_a, g_entropy, dstd=None):
+    """Gradient of gauss_head_fwd for g_log_pi_a, g_entropy [n, 1] -> (dz [n, A], dstd [A]); `dstd`: a contiguous f32 [A]
+    tensor to write into (a parameter's .grad slot).  The reduction over n has a fixed order: equal bits on every launch."""
+    z, std, action = _gauss_head_args(z, std, action)
+    n, a_dim = z.shape
+    g_lp, g_ent = _c(g_log_pi_a, _f32), _c(g_entropy, _f32)
+    if g_lp.numel() != n or g_ent.numel() != n:
+        raise DraError("gauss_head_bwd: one gradient per row expected")
+    dz = torch.empty_like(z)
+    if dstd is None:
+        dstd = torch.empty(a_dim, dtype=_f32, device=z.device)
+    elif not dstd.is_cuda or dstd.dtype != _f32 or not dstd.is_contiguous() or dstd.numel() != a_dim:
+        raise DraError("gauss_head_bwd: dstd must be a contiguous f32 device tensor of action_dim elements")
+    lib.dra_gauss_head_bwd(ptr(z), ptr(std), ptr(action), ptr(g_lp), ptr(g_ent), n, a_dim, ptr(dz), ptr(dstd), stream_ptr())
+    return dz, dstd
+
+
 # ------------------------------------------------------------------------------------------ scan
 def gae(reward, mask, value, gamma, tau, use_gae):
     """reward, mask: [T,N(,1)] f32; value: [T+1,N(,1)] f32 -> (adv, ret) shaped like reward."""

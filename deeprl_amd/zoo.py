@@ -92,6 +92,15 @@ ZOO = {
         fields=dict(discount=0.99, use_gae=True, gae_tau=1.0, entropy_weight=0.01, rollout_length=5, gradient_clip=5,
                     max_steps=int(2e7)),
         normalizers=(ImageNormalizer, SignNormalizer)),
+    # examples.py:384-404
+    "a2c_continuous": dict(
+        agent="A2CAgent", kw=dict(log_level=0), pre_fields=dict(num_workers=16),
+        task=lambda c: Task(c.game, num_envs=c.num_workers), eval_task=lambda c: Task(c.game),
+        optimizer=_rmsprop(lr=0.0007),
+        network=lambda c: N.GaussianActorCriticNet(c.state_dim, c.action_dim, actor_body=N.FCBody(c.state_dim),
+                                                   critic_body=N.FCBody(c.state_dim)),
+        fields=dict(discount=0.99, use_gae=True, gae_tau=1.0, entropy_weight=0.01, rollout_length=5, gradient_clip=5,
+                    max_steps=int(2e7))),
     # examples.py:427-447
     "n_step_dqn_pixel": dict(
         agent="NStepDQNAgent", kw=dict(log_level=0), pre_fields=dict(num_workers=16),

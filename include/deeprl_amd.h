@@ -858,6 +858,54 @@ int dra_ppo_mlp_rollout(const dra_ppo_mlp_cfg* cfg, const dra_ppo_mlp_net* actor
 int dra_ppo_mlp_rollout_profile(const dra_ppo_mlp_cfg* cfg, const dra_ppo_mlp_net* actor, const dra_ppo_mlp_net* critic,
                                 const dra_ppo_mlp_rollout_io* io, int64_t* cycles, void* stream);
 
+/* ---- a2c_mlp: a2c_continuous (examples.py:384-404) over device-resident synthetic environments.  GaussianActorCriticNet
+ * (network_heads.py:173-214) with an identity phi_body and two FCBody(state_dim, (H, H)) networks of one gate (relu or tanh),
+ * H in {32, 64}, state_dim <= 64, action_dim <= 16, n_env <= 64, all parameters in ONE flat buffer (one optimiser). */
+typedef struct dra_a2c_mlp_net {
+  const float* param;                /* the optimiser's flat parameter buffer (device); read only */
+  int32_t a_w1, a_b1, a_w2, a_b2, a_w3, a_b3;   /* actor_body.layers[0..1], fc_action: float offsets into param */
+  int32_t c_w1, c_b1, c_w2, c_b2, c_w3, c_b3;   /* critic_body.layers[0..1], fc_critic */
+  int32_t off_std;                   /* std [action_dim] */
+  int32_t gate;                      /* 1 relu, 2 tanh */
+  int32_t state_dim, action_dim, hidden, reserved;
+} dra_a2c_mlp_net;
+/* A2C_agent.py:22-41 in ONE launch of one workgroup: for t < t_len [normalise the current observation (normalizer.py:28-51:
+ * statistics folded first when rms_update != 0; the identity is mean 0, var 1, epsilon 0, clip inf), store it, forward both
+ * networks, action = tanh(fc_action(.)) + softplus(std) * noise(noise_seed, *sampler_step + t, n_global, env0 + env, dim),
+ * environment step (csrc/cont_env.h), reward * reward_coef, mask = 1 - done], then the bootstrap observation's normalisation
+ * and value.  The fields are those of dra_ppo_mlp_rollout_io without the log-probability; cur_state is an OUTPUT here. */
+typedef struct dra_a2c_mlp_rollout_io {
+  double* env_state;        /* [n_env][S] raw observations (in/out) */
+  int64_t* env_counter;     /* [n_env] (in/out) */
+  const int64_t* env_seed;  /* [n_env] */
+  double* rms;              /* mean [S], var [S], count [1] (in; out when rms_update != 0) */
+  float* cur_state;         /* [n_env][S] normalised observation the bootstrap value was computed from (out) */
+  int64_t* sampler_step;    /* device int64: position of the action-noise stream (advanced by t_len + 1: A2C_agent.py:41's
+                             * bootstrap forward samples an action too) */
+  float* out_state;         /* [t_len][n_env][S] */
+  float* out_action;        /* [t_len][n_env][A] */
+  float* out_v;             /* [t_len + 1][n_env] */
+  float* out_reward;        /* [t_len][n_env]  f32(reward * reward_coef) */
+  float* out_mask;          /* [t_len][n_env]  1 - done */
+  int64_t env0, n_global;   /* first GLOBAL environment index / global environment count (noise stream) */
+  uint64_t noise_seed;
+  int64_t horizon;
+  double reward_coef, rms_epsilon, rms_clip;
+  int32_t rms_update, t_len, n_env, reserved;
+} dra_a2c_mlp_rollout_io;
+int dra_a2c_mlp_supported(int state_dim, int action_dim, int hidden, int n_env, int gate);   /* 0 = yes */
+int dra_a2c_mlp_rollout(const dra_a2c_mlp_net* net, const dra_a2c_mlp_rollout_io* io, void* stream);
+/* network_heads.py:200-214 behind fc_action, for given actions: z [n][a_dim] = fc_action's output, std [a_dim], action
+ * [n][a_dim] -> mean = tanh(z) [n][a_dim]; scale = softplus(std) (linear above 20); log_pi_a [n] = sum_d (-(a - mean)^2 /
+ * (2 scale^2) - log scale - log sqrt(2 pi)); entropy [n] = sum_d (0.5 + 0.5 log(2 pi) + log scale).  a_dim <= 64; evaluated
+ * in fp64, rounded once. */
+int dra_gauss_head_fwd(const float* z, const float* std, const float* action, int n, int a_dim, float* mean, float* log_pi_a,
+                       float* entropy, void* stream);
+/* its gradient for g_log_pi_a, g_entropy [n] (A2C_agent.py:55-61's losses reach the head through these two): dz [n][a_dim]
+ * (through the tanh), dstd [a_dim] (through the softplus; rows summed in a fixed order -- the same bits on every launch). */
+int dra_gauss_head_bwd(const float* z, const float* std, const float* action, const float* g_log_pi_a, const float* g_entropy,
+                       int n, int a_dim, float* dz, float* dstd, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

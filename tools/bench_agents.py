@@ -12,6 +12,7 @@ after a warm-up.  Prints one JSON object per line: agent steps/s, env steps/s, g
             rainbow_pixel examples.py:283-336 (PER + double Q + noisy dueling C51; `_modules` = config.fused_noisy False and
             config.graph_update False: materialised noisy weights through the plain GEMM, eager launches)
   config 5  a2c_pixel examples.py:361-381 (16 workers), ppo_pixel examples.py:525-550 (8 workers)
+            a2c_continuous examples.py:384-404 (16 workers; `_host` = config.device_env False: python environments, module head)
             n_step_dqn_pixel examples.py:427-447 (16 workers), option_critic_pixel examples.py:471-492 (16 workers)
 """
 import argparse
@@ -100,6 +101,20 @@ def a2c_pixel(workers=16, device=True, **switches):
     c.network_fn = lambda: d.CategoricalActorCriticNet(c.state_dim, c.action_dim, d.NatureConvBody())
     c.state_normalizer = d.ImageNormalizer()
     c.reward_normalizer = d.SignNormalizer()
+    c.discount, c.use_gae, c.gae_tau, c.entropy_weight, c.rollout_length, c.gradient_clip = 0.99, True, 1.0, 0.01, 5, 5
+    c.max_steps = int(2e7)
+    return d.A2CAgent(c), dict(env_per_step=5 * workers, updates_per_step=1)
+
+
+def a2c_continuous(workers=16, device=True, **switches):
+    c = d.Config()
+    c.merge(dict(game="synthetic-continuous-HalfCheetah", log_level=0, tag="bench", device_env=device, **switches))
+    c.num_workers = workers
+    c.task_fn = lambda: d.Task(c.game, num_envs=c.num_workers, seed=1)
+    c.eval_env = d.Task(c.game, seed=2)
+    c.optimizer_fn = lambda p: torch.optim.RMSprop(p, lr=0.0007)
+    c.network_fn = lambda: d.GaussianActorCriticNet(c.state_dim, c.action_dim, actor_body=d.FCBody(c.state_dim),
+                                                    critic_body=d.FCBody(c.state_dim))
     c.discount, c.use_gae, c.gae_tau, c.entropy_weight, c.rollout_length, c.gradient_clip = 0.99, True, 1.0, 0.01, 5, 5
     c.max_steps = int(2e7)
     return d.A2CAgent(c), dict(env_per_step=5 * workers, updates_per_step=1)
@@ -205,6 +220,8 @@ CASES = {
     "a2c_pixel_16_modules": lambda: a2c_pixel(16, fused_rollout=False),         # rollout through network.forward (5 launches / step)
     "ppo_pixel_8_modules": lambda: ppo_pixel(8, fused_rollout=False),
     "ppo_pixel_8_host": lambda: ppo_pixel(8, device=False),
+    "a2c_continuous": lambda: a2c_continuous(16),                      # device-resident rollout (csrc/a2c_mlp.hip) + one captured graph
+    "a2c_continuous_host": lambda: a2c_continuous(16, device=False),   # 16 python environments stepped one by one, module head
     "ppo_continuous_1": lambda: ppo_continuous(1),
     "ppo_continuous_16": lambda: ppo_continuous(16),                                  # device environments + persistent kernels
     "ppo_continuous_16_host": lambda: ppo_continuous(16, device=False),               # host environments, persistent update kernel
