@@ -805,7 +805,8 @@ adam_step_ctr_kernel(float* __restrict__ p, const float* __restrict__ g, float* 
     s_hyper[0] = (float)((double)lr / bc1);
     s_hyper[1] = (float)(1.0 / sqrt(bc2));
   }
-  const float coef = clip_coef_from_partials(partials, n_partials, max_norm, out_norm);   // (synchronises the workgroup)
+  const float coef = clip_coef_from_partials(partials, n_partials, max_norm, out_norm);   // (synchronises the workgroup ...
+  if (!partials) __syncthreads();   // ... unless no clipping is requested: it returns at once, and waves 1-3 read s_hyper unwritten)
   const float step_size = s_hyper[0], inv_sqrt_bc2 = s_hyper[1];
   const float omb1 = 1.f - beta1, omb2 = 1.f - beta2;
   auto elem = [&](float& pp, float gg, float& mm, float& vv) {

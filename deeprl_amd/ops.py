@@ -1127,10 +1127,43 @@ def grad_sqnorm(grad, partials, slabs=None, n_slabs=0, slab_stride=0):
 
 
 def rmsprop_step(param, grad, square_avg, grad_avg, partials, n_partials, max_norm, lr, alpha, eps, centered,
-                 out_norm=None):
+                 out_norm=None, param_copy=None):
+    """param_copy (optional): the updated parameters are also written there (dra_rmsprop_step_copy)."""
+    if param_copy is not None:
+        lib.dra_rmsprop_step_copy(ptr(param), ptr(grad), ptr(square_avg), ptr(grad_avg), param.numel(), ptr(partials),
+                                  int(n_partials), float(max_norm if max_norm else 0.0), float(lr), float(alpha), float(eps),
+                                  int(bool(centered)), ptr(out_norm), ptr(param_copy), stream_ptr())
+        return
     lib.dra_rmsprop_step(ptr(param), ptr(grad), ptr(square_avg), ptr(grad_avg), param.numel(), ptr(partials),
                          int(n_partials), float(max_norm if max_norm else 0.0), float(lr), float(alpha), float(eps),
                          int(bool(centered)), ptr(out_norm), stream_ptr())
+
+
+OPT_RMSPROP, OPT_ADAM = 0, 1      # DRA_OPT_RMSPROP / DRA_OPT_ADAM (include/deeprl_amd.h)
+
+
+def clip_step_late_blocks(seg):
+    """seg: (begin, count, slabs_tensor, slab_stride, n_slabs).  Fold workgroups (= slots published) of clip_step_late:
+    pure host arithmetic."""
+    n = ctypes.c_int(0)
+    lib.dra_clip_step_late_blocks(_fold_seg_array([seg]), ctypes.byref(n))
+    return n.value
+
+
+def clip_step_late(param, grad, state1, state2, seg, partials, n_prior, timeout_flag, optimizer, max_norm, hyper, centered,
+                   step_dev=None, out_norm=None, param_copy=None):
+    """The late-fold optimizer launch (dra_clip_step_late): folds `seg` (the one segment still in slabs, from element 0),
+    publishes its sums of squares into partials[n_prior, n_prior + clip_step_late_blocks(seg)) -- which must hold -1.0 at
+    launch -- and steps.  optimizer: OPT_RMSPROP with hyper = (lr, alpha, eps) or OPT_ADAM with hyper = (lr, beta1, eps,
+    beta2) and the int64 device tensor `step_dev`; timeout_flag: a pinned host int32 tensor (non-zero afterwards: a
+    bounded device-side wait gave up, the results are invalid)."""
+    if timeout_flag.is_cuda or not timeout_flag.is_pinned() or timeout_flag.dtype != torch.int32:
+        raise DraError("clip_step_late: timeout_flag must be a pinned host int32 tensor")
+    hyper = tuple(float(h) for h in hyper)
+    hp = (ctypes.c_float * 4)(*(hyper + (0.0,) * (4 - len(hyper))))
+    lib.dra_clip_step_late(ptr(param), ptr(grad), ptr(state1), ptr(state2), param.numel(), _fold_seg_array([seg]),
+                           ptr(partials), int(n_prior), ptr(timeout_flag), int(optimizer), float(max_norm if max_norm else 0.0),
+                           hp, int(bool(centered)), ptr(step_dev), ptr(out_norm), ptr(param_copy), stream_ptr())
 
 
 def adam_step(param, grad, exp_avg, exp_avg_sq, partials, n_partials, max_norm, lr, beta1, beta2, eps, step,
