@@ -488,6 +488,11 @@ DRA_API int dra_noisy_linear_bwd(const float* g, const float* x, const float* w_
   if (db_mu && !dw_mu) return DRA_EINVAL;
   const int K = in_features, N = out_features;
   hipStream_t st = dra_stream(stream);
+  // (every check before the first launch: a refused call writes nothing)
+  const bool dx_vec = dx && K % 4 == 0 && aligned16(w_mu) && aligned16(w_sigma) && aligned16(dx) && aligned16(workspace) && workspace;
+  const BwdPlan p = bwd_plan(rows, K, N);
+  const int64_t total = (int64_t)rows * K;
+  if (dx_vec && workspace_floats < (int64_t)p.nb * total) return DRA_EINVAL;
   if (dw_mu) {
     const bool vec = K % 4 == 0 && aligned16(x) && aligned16(dw_mu) && aligned16(dw_sigma);
     const int units = vec ? K / 4 : K;       // threads along K
@@ -506,12 +511,8 @@ DRA_API int dra_noisy_linear_bwd(const float* g, const float* x, const float* w_
     DRA_LAUNCH_CHECK();
   }
   if (dx) {
-    const bool vec = K % 4 == 0 && aligned16(w_mu) && aligned16(w_sigma) && aligned16(dx) && aligned16(workspace);
-    const int64_t total = (int64_t)rows * K;
-    if (vec && workspace) {
-      const BwdPlan p = bwd_plan(rows, K, N);
+    if (dx_vec) {
       const int npw = p.npw, nb = p.nb;
-      if (workspace_floats < (int64_t)nb * total) return DRA_EINVAL;
       hipLaunchKernelGGL(noisy_bwd_x_mfma_kernel, dim3(p.col_blocks, nb, p.row_groups), dim3(256), 0, st, g, w_mu, w_sigma, noise_in,
                          noise_out_weight, rows, K, N, npw, workspace);
       DRA_LAUNCH_CHECK();

@@ -32,13 +32,15 @@ DRA_API int dra_q_heads_fold28(const float* slabs, const float* fold_bias, const
 //     same arithmetic as scan.hip's use_gae = 0 replay), loss = 0.5 mean_r (q[r][a_r] - ret_r)^2, and the gradient of that loss
 //     through the Q head: dq_r = (q[r][a_r] - ret_r) / R at the taken action only (d/dq of 0.5 mean(.)^2, what the
 //     autograd path hands the head), so
-//   workgroups [0, A): dW[a][k] = sum_r [a_r == a] dq_r phi[r][k], db[a] = sum_r [a_r == a] dq_r -- ascending r, one thread per
-//     (a, k): a fixed-order reduction, no atomics, eager runs and graph replays give the same bits
+//   workgroups [0, A): dW[a][k] = sum_r [a_r == a] dq_r phi[r][k], db[a] = sum_r [a_r == a] dq_r -- a fixed tree (8 rows, 16 of those
+//     sums, then the sums of 128 rows, each level in ascending r), one thread per (a, k): a fixed-order reduction, no atomics, eager runs and
+//     graph replays give the same bits
 //   workgroups [A, A + ceil(R / 4)): four rows each, dphi[r][k] = dq_r W[a_r][k] [phi[r][k] > 0] (fc4's fused ReLU)
 // Every workgroup forms the R returns / differences itself in LDS (R <= 2048: a few hundred loads); workgroup 0 writes ret and
 // the loss.  phi: fc4's output [R][512] of the rollout (rows t-major), w: [A][512].
 constexpr int kNstepMaxRows = 2048;
 constexpr int kNstepRowsPerWg = 4;
+constexpr int kNstepSumInner = 8, kNstepSumOuter = 128;
 __global__ void __launch_bounds__(256)
 nstep_q_loss_bwd_kernel(const float* __restrict__ q, const int64_t* __restrict__ action, const float* __restrict__ reward,
                         const float* __restrict__ mask, const float* __restrict__ bootstrap, float gamma,
@@ -69,14 +71,31 @@ nstep_q_loss_bwd_kernel(const float* __restrict__ q, const int64_t* __restrict__
       for (int r = 0; r < R; ++r) s = __fadd_rn(s, __fmul_rn(s_diff[r], s_diff[r]));
       out_loss[0] = __fmul_rn(0.5f, __fdiv_rn(s, rows_f));
     }
+    // a fixed tree of three levels: 8 rows in ascending order, 16 such sums in ascending order (128 rows), then the up to 16
+    // sums of 128 rows in ascending order -- at most 40 additions between a term and the sum of 2048 of them.  With all rows on
+    // one action db is a mean of differences of both signs, some 400 times smaller than the sum of their magnitudes.
     float acc0 = 0.f, acc1 = 0.f, accb = 0.f;
-    for (int r = 0; r < R; ++r) {
-      if (s_act[r] != a) continue;
-      const float g = __fdiv_rn(s_diff[r], rows_f);
-      const float* pr = phi + (int64_t)r * 512;
-      acc0 = __fadd_rn(acc0, __fmul_rn(g, pr[tid]));
-      acc1 = __fadd_rn(acc1, __fmul_rn(g, pr[tid + 256]));
-      accb = __fadd_rn(accb, g);
+    for (int ro = 0; ro < R; ro += kNstepSumOuter) {
+      float m0 = 0.f, m1 = 0.f, mb = 0.f;
+      const int rm_end = min(R, ro + kNstepSumOuter);
+      for (int rm = ro; rm < rm_end; rm += kNstepSumInner) {
+        float c0 = 0.f, c1 = 0.f, cb = 0.f;
+        const int re = min(R, rm + kNstepSumInner);
+        for (int r = rm; r < re; ++r) {
+          if (s_act[r] != a) continue;
+          const float g = __fdiv_rn(s_diff[r], rows_f);
+          const float* pr = phi + (int64_t)r * 512;
+          c0 = __fadd_rn(c0, __fmul_rn(g, pr[tid]));
+          c1 = __fadd_rn(c1, __fmul_rn(g, pr[tid + 256]));
+          cb = __fadd_rn(cb, g);
+        }
+        m0 = __fadd_rn(m0, c0);
+        m1 = __fadd_rn(m1, c1);
+        mb = __fadd_rn(mb, cb);
+      }
+      acc0 = __fadd_rn(acc0, m0);
+      acc1 = __fadd_rn(acc1, m1);
+      accb = __fadd_rn(accb, mb);
     }
     dw[(int64_t)a * 512 + tid] = acc0;
     dw[(int64_t)a * 512 + tid + 256] = acc1;
