@@ -207,11 +207,40 @@ template <bool COH> __device__ __forceinline__ void mega_st(float* p, float v) {
 }
 
 
-// 64- / 128-bit agent-scope loads for float4-shaped staging (two 8-byte relaxed atomic loads: the compiler tracks them)
+// ---- 16-byte hand-over accesses (round 6) -------------------------------------------------------------------------------------
+// A 4-byte write-through store is one fabric write of its own and an 8-byte agent-scope load runs at 0.54-0.70x the 16-byte
+// rate; a 16-byte write-through store costs what a plain one does.  mega_ld4<true> / mega_st4<true> are ONE
+// buffer_load_dwordx4 ... sc1 / buffer_store_dwordx4 ... sc1 (the raw-buffer builtins with the sc1 bit: the compiler counts
+// them in vmcnt like any other access).  `base` is WAVE-UNIFORM (it becomes the buffer resource, in scalar registers), the
+// per-lane part is a 32-bit index: every buffer handed over inside a launch is far below 4 GB.
+// DRA_EXP_WIDE_HANDOVER is the A/B switch of every site that uses them (`make exp EXPFLAGS=-DDRA_EXP_WIDE_HANDOVER=0` builds
+// the 4- / 8-byte forms): bit 0 = 16-byte loads (slab folds, dy staging), bit 1 = the forward chain's conv1 -> conv2 planes
+// (conv_v2.hip).  (The weight-gradient slab stores as 16-byte stores -- each MFMA register group transposed inside its quad of
+// lanes -- measured slower than the 4-byte ones and were removed: DESIGN_HISTORY.md round 6, row 29.)
+#ifndef DRA_EXP_WIDE_HANDOVER
+#define DRA_EXP_WIDE_HANDOVER 3
+#endif
+constexpr bool kWideLd4 = (DRA_EXP_WIDE_HANDOVER & 1) != 0;
+constexpr bool kWideFwdPlanes = (DRA_EXP_WIDE_HANDOVER & 2) != 0;
 typedef float dra_f4 __attribute__((ext_vector_type(4)));
-template <bool COH> __device__ __forceinline__ dra_f4 mega_ld4(const dra_f4* p) {
-  if constexpr (COH) {
-    const unsigned long long* q = reinterpret_cast<const unsigned long long*>(p);
+typedef unsigned dra_u4 __attribute__((ext_vector_type(4)));
+constexpr int kBufSc1 = 16;             // aux bit of the raw-buffer builtins that sets sc1 on gfx950
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t mega_rsrc(const void* base) {
+  // raw buffer (stride 0), no bound (the callers clamp their indices).  Word 3 = 0x00020000 (DATA_FORMAT 32) with the dst-sel /
+  // num-format fields left zero: only the untyped raw_buffer_load / store builtins use this resource, which ignore them
+  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, -1, 0x00020000);
+}
+// float4 number `idx4` behind the wave-uniform, 16-byte aligned `base`.  The 16-byte coherent form addresses with a 32-bit byte
+// offset: idx4 < 2^27 there (the launchers of the chained kernels check what is not a compile-time size); the other forms keep
+// 64-bit pointer arithmetic
+template <bool COH> __device__ __forceinline__ dra_f4 mega_ld4(const dra_f4* base, int64_t idx4) {
+  if constexpr (COH && kWideLd4) {
+    const dra_u4 u = __builtin_amdgcn_raw_buffer_load_b128(mega_rsrc(base), (int)idx4 * 16, 0, kBufSc1);
+    dra_f4 v;
+    v.x = __uint_as_float(u.x); v.y = __uint_as_float(u.y); v.z = __uint_as_float(u.z); v.w = __uint_as_float(u.w);
+    return v;
+  } else if constexpr (COH) {   // two 8-byte relaxed atomic loads
+    const unsigned long long* q = reinterpret_cast<const unsigned long long*>(base + idx4);
     const unsigned long long a = __hip_atomic_load(q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     const unsigned long long b = __hip_atomic_load(q + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     dra_f4 v;
@@ -219,7 +248,18 @@ template <bool COH> __device__ __forceinline__ dra_f4 mega_ld4(const dra_f4* p) 
     v.z = __uint_as_float((unsigned)b); v.w = __uint_as_float((unsigned)(b >> 32));
     return v;
   } else {
-    return *p;
+    return base[idx4];
+  }
+}
+// v to the four floats that start `off` floats (a multiple of 4, < 2^29) behind the wave-uniform, 16-byte aligned `base`.  (A
+// primitive: which sites store 16 bytes is decided by the caller's DRA_EXP_WIDE_HANDOVER bit, not here.)
+template <bool COH> __device__ __forceinline__ void mega_st4(float* base, int off, dra_f4 v) {
+  if constexpr (COH) {
+    dra_u4 u;
+    u.x = __float_as_uint(v.x); u.y = __float_as_uint(v.y); u.z = __float_as_uint(v.z); u.w = __float_as_uint(v.w);
+    __builtin_amdgcn_raw_buffer_store_b128(u, mega_rsrc(base), off * 4, 0, kBufSc1);
+  } else {
+    *reinterpret_cast<dra_f4*>(base + off) = v;
   }
 }
 

@@ -245,6 +245,10 @@ __device__ __forceinline__ void conv_fwd_v2_body(const ConvV2Args& a, const Acto
   const int z = bz;
   const int bi = bx / T::TPG, grp = bx - bi * T::TPG;
   const int oc0 = by * 32;
+  // 16-byte hand-over of the planes (common.h DRA_EXP_WIDE_HANDOVER): a producer whose planes are whole float4s per tile stores
+  // one float4 per lane (WIDE_OUT, the epilogue below); a consumer whose rows are whole float4s loads them as such (WIDE_IN)
+  constexpr bool WIDE_OUT = COH && kWideFwdPlanes && NW == 4 && PT == 1 && G::P % 4 == 0 && !FUSE;
+  constexpr bool WIDE_IN = CIN && kWideFwdPlanes && !U8 && G::H % 4 == 0 && G::H <= 32 && (T::NR * G::H) / 4 <= 64 && G::C % NW == 0;
   const int p0 = grp * PT * 32;
   const int np = min(32 * PT, G::P - p0);
   const int oh0 = p0 / G::OH, oh1 = (p0 + np - 1) / G::OH;
@@ -289,10 +293,14 @@ __device__ __forceinline__ void conv_fwd_v2_body(const ConvV2Args& a, const Acto
   };
   auto request_weights = [&]() {
     request_weights_range(std::integral_constant<int, 0>{}, std::integral_constant<int, NJ0>{});
+    if constexpr (WIDE_OUT) {   // the ONE output row this lane finalises (the epilogue's wide map)
+      bias_r[0] = a.bias[z][oc0 + 8 * wave + (lane >> 3)];
+    } else {
 #pragma unroll
-    for (int q = 0; q < RPW; ++q) {
-      const int r = wave * RPW + q;
-      bias_r[q] = a.bias[z][oc0 + (r & 3) + 8 * (r >> 2) + 4 * h];
+      for (int q = 0; q < RPW; ++q) {
+        const int r = wave * RPW + q;
+        bias_r[q] = a.bias[z][oc0 + (r & 3) + 8 * (r >> 2) + 4 * h];
+      }
     }
   };
   static_assert(!CIN || (!U8 && G::H <= 32), "chained input: the fp32 row-shaped staging");
@@ -439,6 +447,36 @@ __device__ __forceinline__ void conv_fwd_v2_body(const ConvV2Args& a, const Acto
         }
       }
     }
+  } else if constexpr (WIDE_IN) {
+    // rows of whole float4s (conv2: 80 bytes = 5 float4): the rows ir0 .. ir0 + nrows - 1 of a channel are ONE contiguous,
+    // 16-byte aligned run of nrows * V float4s, lane e of a wave loads float4 e of it (one 16-byte agent-scope load per lane and
+    // channel instead of LPT 4-byte ones) and scatters its four columns to the de-interleaved LDS columns
+    constexpr int V = G::H / 4;                                  // float4s per image row
+    constexpr int CPT = G::C / NW;
+    dra_f4 raw4[CPT];
+    const dra_f4* xf4 = reinterpret_cast<const dra_f4*>(a.x[z]);
+    const int nv = nrows * V;
+    const int e = min(lane, nv - 1);
+    const int row = e / V, c4 = e - row * V;
+#pragma unroll
+    for (int ci = 0; ci < CPT; ++ci) {
+      const int c = wave + NW * ci;
+      raw4[ci] = mega_ld4<true>(xf4, ((bi * G::C + c) * G::H + ir0) * V + e);
+    }
+#pragma unroll
+    for (int ci = 0; ci < CPT; ++ci) {
+      const int c = wave + NW * ci;
+      float* dst = lds + c * T::CS + row * G::RW;
+      dra_f4 v = raw4[ci];
+      asm volatile("" : "+v"(v));  // keep the loads batched in front of the LDS writes
+      if (lane < nv) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) dst[lds_col<G>(4 * c4 + k)] = v[k];
+      }
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    request_weights_range(std::integral_constant<int, NJ0>{}, std::integral_constant<int, KS::NJ>{});
+    __builtin_amdgcn_sched_barrier(0);
   } else {
     constexpr int LR = G::H > 16 ? 32 : 16;                     // lanes per image row
     constexpr int RP = 64 / LR;                                  // rows per pass
@@ -513,6 +551,20 @@ __device__ __forceinline__ void conv_fwd_v2_body(const ConvV2Args& a, const Acto
   // wave w finalises accumulator registers RPW*w .. RPW*w+RPW-1 (MFMA C/D rows (r&3) + 8*(r>>2) + 4*h); the NW partials are
   // added as a fixed balanced tree: run-to-run deterministic
   float* __restrict__ y = a.y[z];
+  if constexpr (WIDE_OUT) {
+    // wave w finalises the same 8 output rows 8w .. 8w + 7 x 32 positions as below, but lane = (row j = lane >> 3, positions
+    // 4 (lane & 7) .. + 3): row j is accumulator register 4w + (j & 3) of half-wave j >> 2, so the four positions are four
+    // NEIGHBOURING lanes' slots of one wave partial -- one ds_read_b128 per partial, the same (w0 + w1) + (w2 + w3) tree per
+    // element, and ONE 16-byte write-through store per lane (eight lanes write a row's 128 bytes in one instruction)
+    const int j = lane >> 3, c4 = lane & 7;
+    const float* rt = red + ((wave * RPW + (j & 3)) * 64 + (j >> 2) * 32 + 4 * c4);
+    const dra_f4 w0 = *reinterpret_cast<const dra_f4*>(rt + 0 * 16 * 64), w1 = *reinterpret_cast<const dra_f4*>(rt + 1 * 16 * 64);
+    const dra_f4 w2 = *reinterpret_cast<const dra_f4*>(rt + 2 * 16 * 64), w3 = *reinterpret_cast<const dra_f4*>(rt + 3 * 16 * 64);
+    dra_f4 v;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) v[k] = v2_act(((w0[k] + w1[k]) + (w2[k] + w3[k])) + bias_r[0], a.act);
+    if (4 * c4 < np) mega_st4<true>(y, (bi * G::OC + oc0 + 8 * wave + j) * G::P + p0 + 4 * c4, v);
+  } else {
 #pragma unroll
   for (int t = 0; t < PT; ++t) {
 #pragma unroll
@@ -528,6 +580,7 @@ __device__ __forceinline__ void conv_fwd_v2_body(const ConvV2Args& a, const Acto
       const float v = v2_act(s + bias_r[q], a.act);
       if (32 * t + li < np) mega_st<COH>(&y[((int64_t)(bi * G::OC + oc0 + row)) * G::P + p0 + 32 * t + li], v);
     }
+  }
   }
   DRA_STAMP(TRR, 5);   // reduction folded, stores issued
   if constexpr (COH) mega_publish(ms);
@@ -1532,6 +1585,9 @@ int dra_conv_fwd_chain(const void* frames, const int64_t* idx, int64_t* idx_copy
     return DRA_EINVAL;
   if ((idx_tagged != nullptr) != (update_seq != nullptr)) return DRA_EINVAL;
   if (g_rider_next.armed) { g_rider_next.armed = false; return DRA_EINVAL; }   // (the chain's riders come through `rider`)
+  if (kWideFwdPlanes)   // conv1's planes are handed over in 16-byte accesses
+    for (int z = 0; z < nz; ++z)
+      if (((uintptr_t)y1[z]) & 15) return DRA_EINVAL;
   FwdChainArgs a;
   a.announce = g_chain_announce;
   g_chain_announce = nullptr;

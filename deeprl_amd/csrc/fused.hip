@@ -456,6 +456,10 @@ int dra_conv_bwd_chain(const float* dy3, const float* y2, const float* wt3, floa
       batch > 32 || !n_partials3 || !n_partials2 || !fold_ok(fold3, grad, partials3) || !fold_ok(fold2, grad, partials2) || !counters ||
       !epoch || !timeout_flag)
     return DRA_EINVAL;
+  // the chained folds read their slabs in 16-byte accesses behind a 32-bit byte offset (common.h mega_ld4); the activation /
+  // gradient buffers of the other roles are at most 32 samples of a compile-time size
+  if (kWideLd4 && ((int64_t)fold3->n_slabs * fold3->slab_stride * 4 >= (1ll << 31) || (int64_t)fold2->n_slabs * fold2->slab_stride * 4 >= (1ll << 31)))
+    return DRA_EINVAL;
   BD3 d3 = make_dgrad_one<G3, 1>(dy3, wt3, y2, dy2, batch, act);
   WG3l w3 = make_wgrad_one<WG3l>(dy3, y2, dw3, db3, stride3, batch, 1.0);
   BD2 d2 = make_dgrad_one<G2, 2>(dy2, wt2, y1, dy1, batch, act);

@@ -227,13 +227,12 @@ struct FoldRole {
       for (int i = tid; i < n_reset; i += 256) __hip_atomic_store(reset_slots + i, -1.0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     const int64_t i = (int64_t)bid * EPB + el;
     const int64_t ic = i < count4 ? i : count4 - 1;
-    const float4* __restrict__ sl = reinterpret_cast<const float4*>(slabs) + ic;
     float4 t[SPT];
     if constexpr (CIN) mega_wait(hook.sync(0));
 #pragma unroll
     for (int u = 0; u < SPT; ++u) {
       const int s = g + NG * u;
-      const dra_f4 v4 = mega_ld4<CIN>(reinterpret_cast<const dra_f4*>(sl + (int64_t)(s < n_slabs ? s : 0) * stride4));
+      const dra_f4 v4 = mega_ld4<CIN>(reinterpret_cast<const dra_f4*>(slabs), ic + (int64_t)(s < n_slabs ? s : 0) * stride4);
       t[u] = make_float4(v4.x, v4.y, v4.z, v4.w);
     }
     __builtin_amdgcn_sched_barrier(0);
@@ -540,14 +539,15 @@ struct ConvWgradOne {
 #pragma unroll
       for (int q = 0; q < RD; ++q) {
         const int f = min(tid + 256 * q, NVD - 1);
-        const float* src;
+        int f4;                                              // float4 index behind dyb
         if constexpr (WHOLE) {
-          src = dyb + 4 * f;
+          f4 = f;
         } else {
+          static_assert(WHOLE || G::P % 4 == 0, "float4 dY staging");
           const int oc = f / (RUN / 4), v = f - oc * (RUN / 4);
-          src = dyb + oc * G::P + 4 * v;
+          f4 = oc * (G::P / 4) + v;
         }
-        const dra_f4 v4 = mega_ld4<decltype(coh)::value>(reinterpret_cast<const dra_f4*>(src));
+        const dra_f4 v4 = mega_ld4<decltype(coh)::value>(reinterpret_cast<const dra_f4*>(dyb), f4);
         draw[q] = make_float4(v4.x, v4.y, v4.z, v4.w);
       }
     };

@@ -125,7 +125,7 @@ struct ConvDgradLin {
     if constexpr (CIN) {
       mega_wait(ms);
 #pragma unroll
-      for (int q = 0; q < RV; ++q) rawv[q] = mega_ld4<true>(dyb4 + min(tid + 256 * q, NV - 1));
+      for (int q = 0; q < RV; ++q) rawv[q] = mega_ld4<true>(reinterpret_cast<const dra_f4*>(dyb4), min(tid + 256 * q, NV - 1));
     }
     lin_f4* lds4 = reinterpret_cast<lin_f4*>(lds);
     for (int i = tid; i < ZERO / 4; i += 256) lds4[NSRC / 4 + i] = lin_f4{0.f, 0.f, 0.f, 0.f};
@@ -246,7 +246,7 @@ struct ConvWgradLin {
     if constexpr (CIN) {      // (the input channels above are in flight while this workgroup waits for its sample's gradient)
       mega_wait(ms);
 #pragma unroll
-      for (int q = 0; q < RD; ++q) draw[q] = mega_ld4<true>(dyb4 + min(tid + 256 * q, NVD - 1));
+      for (int q = 0; q < RD; ++q) draw[q] = mega_ld4<true>(reinterpret_cast<const dra_f4*>(dyb4), min(tid + 256 * q, NVD - 1));
     }
     lin_f4* img4 = reinterpret_cast<lin_f4*>(img);
     lin_f4* dyl4 = reinterpret_cast<lin_f4*>(dyl);
