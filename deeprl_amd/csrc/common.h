@@ -43,6 +43,62 @@ __device__ __forceinline__ void rmsprop_elem(float& p, float g, float& s, float&
   p = p - lr * (gk / avg);
 }
 
+// ---- 16-byte hand-over accesses (round 6) -------------------------------------------------------------------------------------
+// A 4-byte write-through store is one fabric write of its own and an 8-byte agent-scope load runs at 0.54-0.70x the 16-byte
+// rate; a 16-byte write-through store costs what a plain one does.  mega_ld4<true> / mega_st4<true> are ONE
+// buffer_load_dwordx4 ... sc1 / buffer_store_dwordx4 ... sc1 (the raw-buffer builtins with the sc1 bit: the compiler counts
+// them in vmcnt like any other access).  `base` is WAVE-UNIFORM (it becomes the buffer resource, in scalar registers), the
+// per-lane part is a 32-bit index: every buffer handed over inside a launch is far below 4 GB.
+// DRA_EXP_WIDE_HANDOVER is the A/B switch of every site that uses them (`make exp EXPFLAGS=-DDRA_EXP_WIDE_HANDOVER=0` builds
+// the 4- / 8-byte forms): bit 0 = 16-byte loads (slab folds, dy staging), bit 1 = the forward chain's conv1 -> conv2 planes
+// (conv_v2.hip).  (The weight-gradient slab stores as 16-byte stores -- each MFMA register group transposed inside its quad of
+// lanes -- measured slower than the 4-byte ones and were removed: DESIGN_HISTORY.md round 6, row 29.)
+#ifndef DRA_EXP_WIDE_HANDOVER
+#define DRA_EXP_WIDE_HANDOVER 3
+#endif
+constexpr bool kWideLd4 = (DRA_EXP_WIDE_HANDOVER & 1) != 0;
+constexpr bool kWideFwdPlanes = (DRA_EXP_WIDE_HANDOVER & 2) != 0;
+typedef float dra_f4 __attribute__((ext_vector_type(4)));
+typedef unsigned dra_u4 __attribute__((ext_vector_type(4)));
+constexpr int kBufSc1 = 16;             // aux bit of the raw-buffer builtins that sets sc1 on gfx950
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t mega_rsrc(const void* base) {
+  // raw buffer (stride 0), no bound (the callers clamp their indices).  Word 3 = 0x00020000 (DATA_FORMAT 32) with the dst-sel /
+  // num-format fields left zero: only the untyped raw_buffer_load / store builtins use this resource, which ignore them
+  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, -1, 0x00020000);
+}
+// float4 number `idx4` behind the wave-uniform, 16-byte aligned `base`.  The 16-byte coherent form addresses with a 32-bit byte
+// offset: idx4 < 2^27 there (the launchers of the chained kernels check what is not a compile-time size); the other forms keep
+// 64-bit pointer arithmetic
+template <bool COH> __device__ __forceinline__ dra_f4 mega_ld4(const dra_f4* base, int64_t idx4) {
+  if constexpr (COH && kWideLd4) {
+    const dra_u4 u = __builtin_amdgcn_raw_buffer_load_b128(mega_rsrc(base), (int)idx4 * 16, 0, kBufSc1);
+    dra_f4 v;
+    v.x = __uint_as_float(u.x); v.y = __uint_as_float(u.y); v.z = __uint_as_float(u.z); v.w = __uint_as_float(u.w);
+    return v;
+  } else if constexpr (COH) {   // two 8-byte relaxed atomic loads
+    const unsigned long long* q = reinterpret_cast<const unsigned long long*>(base + idx4);
+    const unsigned long long a = __hip_atomic_load(q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const unsigned long long b = __hip_atomic_load(q + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    dra_f4 v;
+    v.x = __uint_as_float((unsigned)a); v.y = __uint_as_float((unsigned)(a >> 32));
+    v.z = __uint_as_float((unsigned)b); v.w = __uint_as_float((unsigned)(b >> 32));
+    return v;
+  } else {
+    return base[idx4];
+  }
+}
+// v to the four floats that start `off` floats (a multiple of 4, < 2^29) behind the wave-uniform, 16-byte aligned `base`.  (A
+// primitive: which sites store 16 bytes is decided by the caller's DRA_EXP_WIDE_HANDOVER bit, not here.)
+template <bool COH> __device__ __forceinline__ void mega_st4(float* base, int off, dra_f4 v) {
+  if constexpr (COH) {
+    dra_u4 u;
+    u.x = __float_as_uint(v.x); u.y = __float_as_uint(v.y); u.z = __float_as_uint(v.z); u.w = __float_as_uint(v.w);
+    __builtin_amdgcn_raw_buffer_store_b128(u, mega_rsrc(base), off * 4, 0, kBufSc1);
+  } else {
+    *reinterpret_cast<dra_f4*>(base + off) = v;
+  }
+}
+
 // ---- DRA_VAR_DEFER_FC4 (round 6): the fc4 segment of the DQN learner's optimizer step, deferred ------------------------------
 // fc4's weights are 95 % of the parameters: 51 of the 54 MB the optimizer launch moves, on the update's critical path for ~8 of
 // its ~15 us.  Nothing reads them before fc4's forward of the NEXT update (the fourth launch of its graph, ~31 us in) -- and
@@ -60,18 +116,39 @@ struct DraFc4Rider {
   float lr, alpha, eps;
   int centered;
 };
-// (DRA_EXP_RIDER_NT=1: gradient / optimizer-state / copy traffic of the riders as non-temporal accesses -- an A/B build)
-#ifndef DRA_EXP_RIDER_NT
-#define DRA_EXP_RIDER_NT 0
+// DRA_EXP_RIDER_WT: how the riders of the chained forward launch (fc4_rider_run<true>) store.  Their launch announces their
+// completion itself, so the actor copy has to be written through; as four 4-byte agent-scope stores per float4 that is one fabric
+// write per float (1.6 M per update), and what the riders store plainly (p, s1, s2: 19.3 MB) is still dirty in the L2 when the
+// launch ends, in front of fc4's forward.  Levels (`make exp EXPFLAGS=-DDRA_EXP_RIDER_WT=n` builds the others for an A/B):
+//   0  the copy as four 4-byte write-through stores, p / s1 / s2 as plain float4 stores
+//   1  the copy as ONE mega_st4<true> (buffer_store_dwordx4 ... sc1) per float4
+//   2  level 1 + s1 and (centered) s2 as mega_st4<true>
+//   3  level 2 + p
+// The arithmetic, the grid and the completion protocol (vmcnt(0), barrier, count) are the same at every level: same bits.  The
+// plain form (fc4_rider_run<false>: the flush kernel, the per-layer launches' riders) does not change with the switch.
+// Measured (profiles/rider_wt_ab.jsonl, six interleaved alternations of bench.py --steps 2000 on one box): level 0 11 010-11 062
+// updates/s, level 1 11 248-11 344, level 2 11 284-11 406, level 3 11 256-11 394 -- the copy's width is the gain (+2.5 %), levels
+// 2 and 3 are inside each other's spread; 3 is the default.  (DRA_EXP_RIDER_NT, the riders' gradient / state / copy traffic as
+// non-temporal accesses, measured 11 094-11 229 in the same session and was removed: below every level here, and a non-temporal
+// store of the copy is not written through.)
+#ifndef DRA_EXP_RIDER_WT
+#define DRA_EXP_RIDER_WT 3
 #endif
 constexpr int kRiderNV = 3;           // float4 per thread of a rider workgroup (256 threads)
 __host__ __device__ inline int fc4_rider_blocks(int64_t count4) { return (int)((count4 + 256 * kRiderNV - 1) / (256 * kRiderNV)); }
+// what a launcher of fc4_rider_run<true> checks: mega_st4 addresses with a 32-bit float offset below 2^29 behind 16-byte aligned bases
+static inline bool fc4_rider_wt_ok(const DraFc4Rider& r) {
+  if (r.begin4 < 0 || r.count4 < 1 || r.begin4 >= ((int64_t)1 << 27) || r.count4 >= ((int64_t)1 << 27)) return false;
+  if (4 * (r.begin4 + r.count4) >= ((int64_t)1 << 29)) return false;
+  return (((uintptr_t)r.p | (uintptr_t)r.g | (uintptr_t)r.s1 | (uintptr_t)r.s2 | (uintptr_t)r.p_copy) & 15) == 0;
+}
 
 // rider workgroup `rb` of `nrb` (nrb * 256 * kRiderNV >= count4).  COPY_WT: the actor copy is written THROUGH (agent-scope stores) --
 // for riders whose completion is announced from inside their own launch (the forward chain: no launch boundary writes the L2 back
 // before the actor, on another XCD, is told that the copy is complete)
 template <bool COPY_WT = false>
 __device__ __forceinline__ void fc4_rider_run(const DraFc4Rider& r, int rb) {
+  constexpr int WT = COPY_WT ? DRA_EXP_RIDER_WT : 0;
   if (*r.pending == 0) return;
   const int64_t i0 = (int64_t)rb * (256 * kRiderNV) + threadIdx.x;
   float4 P[kRiderNV], G[kRiderNV], S[kRiderNV], A[kRiderNV];
@@ -82,16 +159,7 @@ __device__ __forceinline__ void fc4_rider_run(const DraFc4Rider& r, int rb) {
 #pragma unroll
   for (int v = 0; v < kRiderNV; ++v) {
     const int64_t i = i0 + 256 * v, ic = i < r.count4 ? i : r.count4 - 1;
-#if DRA_EXP_RIDER_NT
-    P[v] = p4[ic];
-    typedef float nt_f4 __attribute__((ext_vector_type(4)));
-    const nt_f4 gq = __builtin_nontemporal_load(reinterpret_cast<const nt_f4*>(g4 + ic));
-    const nt_f4 sq = __builtin_nontemporal_load(reinterpret_cast<const nt_f4*>(s4 + ic));
-    const nt_f4 aq = __builtin_nontemporal_load(reinterpret_cast<const nt_f4*>(a4 + ic));
-    G[v] = make_float4(gq.x, gq.y, gq.z, gq.w); S[v] = make_float4(sq.x, sq.y, sq.z, sq.w); A[v] = make_float4(aq.x, aq.y, aq.z, aq.w);
-#else
     P[v] = p4[ic]; G[v] = g4[ic]; S[v] = s4[ic]; A[v] = a4[ic];
-#endif
   }
   const float coef = *r.coef, oma = 1.f - r.alpha;
 #pragma unroll
@@ -101,16 +169,15 @@ __device__ __forceinline__ void fc4_rider_run(const DraFc4Rider& r, int rb) {
       float* pp = &P[v].x; const float* gg = &G[v].x; float* ss = &S[v].x; float* aa = &A[v].x;
 #pragma unroll
       for (int k = 0; k < 4; ++k) rmsprop_elem(pp[k], gg[k], ss[k], aa[k], coef, r.alpha, oma, r.lr, r.eps, r.centered);
-      reinterpret_cast<float4*>(r.p)[r.begin4 + i] = P[v];
-#if DRA_EXP_RIDER_NT
-      typedef float nt_f4 __attribute__((ext_vector_type(4)));
-      const nt_f4 pq = {P[v].x, P[v].y, P[v].z, P[v].w}, sq = {S[v].x, S[v].y, S[v].z, S[v].w}, aq = {A[v].x, A[v].y, A[v].z, A[v].w};
-      if (r.p_copy) __builtin_nontemporal_store(pq, reinterpret_cast<nt_f4*>(r.p_copy) + r.begin4 + i);
-      __builtin_nontemporal_store(sq, reinterpret_cast<nt_f4*>(r.s1) + r.begin4 + i);
-      if (r.centered) __builtin_nontemporal_store(aq, reinterpret_cast<nt_f4*>(r.s2) + r.begin4 + i);
-#else
+      // (the bases are kernel arguments, hence wave-uniform; the launcher checked fc4_rider_wt_ok: off + 3 < 2^29)
+      const int off = 4 * (int)(r.begin4 + i);
+      const dra_f4 pv = {P[v].x, P[v].y, P[v].z, P[v].w}, sv = {S[v].x, S[v].y, S[v].z, S[v].w}, av = {A[v].x, A[v].y, A[v].z, A[v].w};
+      if constexpr (WT >= 3) mega_st4<true>(r.p, off, pv);
+      else reinterpret_cast<float4*>(r.p)[r.begin4 + i] = P[v];
       if (r.p_copy) {
-        if constexpr (COPY_WT) {
+        if constexpr (WT >= 1) {
+          mega_st4<true>(r.p_copy, off, pv);
+        } else if constexpr (COPY_WT) {
           float* pc = r.p_copy + 4 * (r.begin4 + i);
 #pragma unroll
           for (int k = 0; k < 4; ++k) __hip_atomic_store(pc + k, pp[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -118,9 +185,13 @@ __device__ __forceinline__ void fc4_rider_run(const DraFc4Rider& r, int rb) {
           reinterpret_cast<float4*>(r.p_copy)[r.begin4 + i] = P[v];
         }
       }
-      reinterpret_cast<float4*>(r.s1)[r.begin4 + i] = S[v];
-      if (r.centered) reinterpret_cast<float4*>(r.s2)[r.begin4 + i] = A[v];
-#endif
+      if constexpr (WT >= 2) {
+        mega_st4<true>(r.s1, off, sv);
+        if (r.centered) mega_st4<true>(r.s2, off, av);
+      } else {
+        reinterpret_cast<float4*>(r.s1)[r.begin4 + i] = S[v];
+        if (r.centered) reinterpret_cast<float4*>(r.s2)[r.begin4 + i] = A[v];
+      }
     }
   }
 }
@@ -206,62 +277,6 @@ template <bool COH> __device__ __forceinline__ void mega_st(float* p, float v) {
   else *p = v;
 }
 
-
-// ---- 16-byte hand-over accesses (round 6) -------------------------------------------------------------------------------------
-// A 4-byte write-through store is one fabric write of its own and an 8-byte agent-scope load runs at 0.54-0.70x the 16-byte
-// rate; a 16-byte write-through store costs what a plain one does.  mega_ld4<true> / mega_st4<true> are ONE
-// buffer_load_dwordx4 ... sc1 / buffer_store_dwordx4 ... sc1 (the raw-buffer builtins with the sc1 bit: the compiler counts
-// them in vmcnt like any other access).  `base` is WAVE-UNIFORM (it becomes the buffer resource, in scalar registers), the
-// per-lane part is a 32-bit index: every buffer handed over inside a launch is far below 4 GB.
-// DRA_EXP_WIDE_HANDOVER is the A/B switch of every site that uses them (`make exp EXPFLAGS=-DDRA_EXP_WIDE_HANDOVER=0` builds
-// the 4- / 8-byte forms): bit 0 = 16-byte loads (slab folds, dy staging), bit 1 = the forward chain's conv1 -> conv2 planes
-// (conv_v2.hip).  (The weight-gradient slab stores as 16-byte stores -- each MFMA register group transposed inside its quad of
-// lanes -- measured slower than the 4-byte ones and were removed: DESIGN_HISTORY.md round 6, row 29.)
-#ifndef DRA_EXP_WIDE_HANDOVER
-#define DRA_EXP_WIDE_HANDOVER 3
-#endif
-constexpr bool kWideLd4 = (DRA_EXP_WIDE_HANDOVER & 1) != 0;
-constexpr bool kWideFwdPlanes = (DRA_EXP_WIDE_HANDOVER & 2) != 0;
-typedef float dra_f4 __attribute__((ext_vector_type(4)));
-typedef unsigned dra_u4 __attribute__((ext_vector_type(4)));
-constexpr int kBufSc1 = 16;             // aux bit of the raw-buffer builtins that sets sc1 on gfx950
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t mega_rsrc(const void* base) {
-  // raw buffer (stride 0), no bound (the callers clamp their indices).  Word 3 = 0x00020000 (DATA_FORMAT 32) with the dst-sel /
-  // num-format fields left zero: only the untyped raw_buffer_load / store builtins use this resource, which ignore them
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, -1, 0x00020000);
-}
-// float4 number `idx4` behind the wave-uniform, 16-byte aligned `base`.  The 16-byte coherent form addresses with a 32-bit byte
-// offset: idx4 < 2^27 there (the launchers of the chained kernels check what is not a compile-time size); the other forms keep
-// 64-bit pointer arithmetic
-template <bool COH> __device__ __forceinline__ dra_f4 mega_ld4(const dra_f4* base, int64_t idx4) {
-  if constexpr (COH && kWideLd4) {
-    const dra_u4 u = __builtin_amdgcn_raw_buffer_load_b128(mega_rsrc(base), (int)idx4 * 16, 0, kBufSc1);
-    dra_f4 v;
-    v.x = __uint_as_float(u.x); v.y = __uint_as_float(u.y); v.z = __uint_as_float(u.z); v.w = __uint_as_float(u.w);
-    return v;
-  } else if constexpr (COH) {   // two 8-byte relaxed atomic loads
-    const unsigned long long* q = reinterpret_cast<const unsigned long long*>(base + idx4);
-    const unsigned long long a = __hip_atomic_load(q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const unsigned long long b = __hip_atomic_load(q + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    dra_f4 v;
-    v.x = __uint_as_float((unsigned)a); v.y = __uint_as_float((unsigned)(a >> 32));
-    v.z = __uint_as_float((unsigned)b); v.w = __uint_as_float((unsigned)(b >> 32));
-    return v;
-  } else {
-    return base[idx4];
-  }
-}
-// v to the four floats that start `off` floats (a multiple of 4, < 2^29) behind the wave-uniform, 16-byte aligned `base`.  (A
-// primitive: which sites store 16 bytes is decided by the caller's DRA_EXP_WIDE_HANDOVER bit, not here.)
-template <bool COH> __device__ __forceinline__ void mega_st4(float* base, int off, dra_f4 v) {
-  if constexpr (COH) {
-    dra_u4 u;
-    u.x = __float_as_uint(v.x); u.y = __float_as_uint(v.y); u.z = __float_as_uint(v.z); u.w = __float_as_uint(v.w);
-    __builtin_amdgcn_raw_buffer_store_b128(u, mega_rsrc(base), off * 4, 0, kBufSc1);
-  } else {
-    *reinterpret_cast<dra_f4*>(base + off) = v;
-  }
-}
 
 // What a ROLE of a chained launch (oneshot.h / oneshot_lin.h roles under fused.hip's bwd_chain_kernel) needs to know about its
 // place in the chain: the counters its workgroups wait on / count themselves on, one 128-byte line per sample (stride in

@@ -1615,6 +1615,7 @@ int dra_conv_fwd_chain(const void* frames, const int64_t* idx, int64_t* idx_copy
   a.n_riders = 0; a.rider_after = 0;
   if (rider) {
     if (!rider_count || !rider_pending || !rider_valid) return DRA_EINVAL;
+    if (!fc4_rider_wt_ok(*rider)) return DRA_EINVAL;   // (16-byte write-through stores behind a 32-bit offset: common.h DRA_EXP_RIDER_WT)
     a.rider = *rider; a.n_riders = fc4_rider_blocks(rider->count4);
     a.rider_count = rider_count; a.rider_pending = rider_pending; a.rider_valid = rider_valid;
   }

@@ -1276,6 +1276,23 @@ static DraFc4Rider fc4_rider(const dra_dqn_learner* l, float* p_copy) {
 }
 
 __global__ void __launch_bounds__(256) fc4_flush_kernel(const DraFc4Rider r) { fc4_rider_run(r, (int)blockIdx.x); }
+// the rider code as it runs in the chained forward launch (common.h DRA_EXP_RIDER_WT), as a launch of its own: dra_fc4_rider_test
+__global__ void __launch_bounds__(256) fc4_rider_wt_kernel(const DraFc4Rider r) { fc4_rider_run<true>(r, (int)blockIdx.x); }
+DRA_API int dra_fc4_rider_test(float* p, const float* g, float* s1, float* s2, float* p_copy, int64_t begin4, int64_t count4,
+                               const float* coef, const int* pending, float lr, float alpha, float eps, int centered,
+                               int write_through, void* stream) {
+  if (!p || !g || !s1 || (centered && !s2) || !coef || !pending || begin4 < 0 || count4 < 1) return DRA_EINVAL;
+  DraFc4Rider r;
+  memset(&r, 0, sizeof(r));
+  r.p = p; r.g = const_cast<float*>(g); r.s1 = s1; r.s2 = s2; r.p_copy = p_copy;
+  r.begin4 = begin4; r.count4 = count4; r.coef = coef; r.pending = pending;
+  r.lr = lr; r.alpha = alpha; r.eps = eps; r.centered = centered;
+  if (!fc4_rider_wt_ok(r)) return DRA_EINVAL;     // (the plain form needs the aligned bases too: float4 accesses)
+  if (write_through) hipLaunchKernelGGL(fc4_rider_wt_kernel, dim3(fc4_rider_blocks(count4)), dim3(256), 0, dra_stream(stream), r);
+  else hipLaunchKernelGGL(fc4_flush_kernel, dim3(fc4_rider_blocks(count4)), dim3(256), 0, dra_stream(stream), r);
+  DRA_LAUNCH_CHECK();
+  return DRA_OK;
+}
 __global__ void fc4_flush_done_kernel(int* pending, int* valid) {
   __hip_atomic_store(pending, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   __hip_atomic_store(valid, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);

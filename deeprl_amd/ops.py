@@ -1139,6 +1139,16 @@ def rmsprop_step(param, grad, square_avg, grad_avg, partials, n_partials, max_no
                          int(bool(centered)), ptr(out_norm), stream_ptr())
 
 
+def fc4_rider_step(param, grad, square_avg, grad_avg, param_copy, begin4, count4, coef, pending, lr, alpha, eps, centered,
+                   write_through):
+    """The deferred fc4 step's rider code alone, as one launch (dra_fc4_rider_test, a test aid): float4s [begin4, begin4 +
+    count4) of the flat buffers are stepped if the device int32 `pending` is non-zero.  write_through: the form the chained
+    forward launch carries, else the plain form of the flush; coef: device f32 clip coefficient; param_copy may be None."""
+    lib.dra_fc4_rider_test(ptr(param), ptr(grad), ptr(square_avg), ptr(grad_avg), ptr(param_copy), int(begin4), int(count4),
+                           ptr(coef), ptr(pending), float(lr), float(alpha), float(eps), int(bool(centered)),
+                           int(bool(write_through)), stream_ptr())
+
+
 OPT_RMSPROP, OPT_ADAM = 0, 1      # DRA_OPT_RMSPROP / DRA_OPT_ADAM (include/deeprl_amd.h)
 
 

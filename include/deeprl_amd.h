@@ -655,6 +655,15 @@ int dra_dqn_learner_set_actor_cus(dra_dqn_learner* learner, int n_cus);
  * Call before reading parameters / optimizer state / actor copies from outside the library (a synchronise alone does not
  * complete the step); a no-op when nothing is pending.  DQN_agent.py:133 (optimizer.step() is ONE call in the reference). */
 int dra_dqn_learner_flush(dra_dqn_learner* learner, void* stream);
+/* test aid: the rider code that steps a deferred fc4 segment (RMSprop, csrc/common.h fc4_rider_run) ALONE, as one launch on the
+ * caller's flat f32 buffers: elements [4 * begin4, 4 * (begin4 + count4)) of p / s1 / (centered) s2 are stepped with gradient g and
+ * the clip coefficient *coef, and the new parameters also go to p_copy (may be NULL) -- if *pending (device int) is non-zero,
+ * otherwise nothing is written.  write_through != 0: the form the chained forward launch carries (DRA_VAR_FWD_CHAIN: the stores
+ * are written through), 0: the plain form of dra_dqn_learner_flush; same bits.  Bases 16-byte aligned and 4 * (begin4 + count4)
+ * < 2^29, else DRA_EINVAL before anything is launched.  DQN_agent.py:133 */
+int dra_fc4_rider_test(float* p, const float* g, float* s1, float* s2, float* p_copy, int64_t begin4, int64_t count4,
+                       const float* coef, const int* pending, float lr, float alpha, float eps, int centered, int write_through,
+                       void* stream);
 /* measurement aid: kernel group `kernel` (index as in _kernel_name) of the update ALONE, `reps` dependent launches in ONE
  * captured graph between two events: out_us[0] = microseconds per launch (kernel + one in-graph launch boundary), out_us[1] =
  * the same for an empty kernel (the boundary alone).  Their difference is the kernel's own duration -- the quantity rocprofv3
