@@ -2401,11 +2401,33 @@ class _DeterministicPolicyAgent(BaseAgent):
         t_flat, s_flat = self._flat_pair(target, src)
         ops.soft_update(t_flat, s_flat, self.config.target_network_mix)
 
+    def _fused_dpg(self):
+        """dpg_mlp.Update when `config.fused_dpg_update` is on and the agent is eligible (csrc/dpg_mlp.hip: the update as 4-5
+        launches, the acting forward as one), else None: the module path below, unchanged.  Decided once, at first use; an
+        agent that asked for the fused path and cannot have it says why in ONE warning."""
+        fused = getattr(self, '_dpg', False)
+        if fused is False:
+            fused = None
+            if getattr(self.config, 'fused_dpg_update', False) is True:
+                from . import dpg_mlp
+                why = dpg_mlp.why_not(self)
+                if why is None:
+                    fused = dpg_mlp.Update(self)
+                else:
+                    self.logger.warning('fused_dpg_update is on but this agent keeps the module path: %s' % why)
+            self._dpg = fused
+        return fused
+
+    def _policy_step(self):
+        """Whether this update also steps the actor and the targets (DDPG: always)."""
+        return True
+
     def eval_step(self, state):
         norm = self.config.state_normalizer
         norm.set_read_only()
+        fused = self._fused_dpg()
         with torch.no_grad():
-            action = self.network(norm(state))
+            action = fused.act(norm(state)) if fused is not None else self.network(norm(state))
         norm.unset_read_only()
         return to_np(action)
 
@@ -2414,8 +2436,9 @@ class _DeterministicPolicyAgent(BaseAgent):
         if self.total_steps < self.config.warm_up:
             action = [space.sample()]
         else:
+            fused = self._fused_dpg()
             with torch.no_grad():
-                action = to_np(self.network(self.state))
+                action = to_np(fused.act(self.state) if fused is not None else self.network(self.state))
             action = action + self.random_process.sample()
         return np.clip(action, space.low, space.high)
 
@@ -2436,6 +2459,15 @@ class _DeterministicPolicyAgent(BaseAgent):
         self.state = next_state
         self.total_steps += 1
         if self.warm():
+            fused = self._fused_dpg()
+            if fused is not None:
+                # the same index draw as replay.sample(); the fields in the ring's stored dtype (the kernel narrows fp64 as it
+                # loads: no cast launches), reward and mask as the gather's own fp32 outputs
+                ring = getattr(self.replay, 'replay', self.replay)
+                g = ring.gather(ring.draw_indices(), want_f32=True)
+                fused.learn(g['state'], g['action'], g['reward_f32'], g['next_state'], g['mask_f32'],
+                            policy_step=self._policy_step())
+                return
             tr = self.replay.sample()
             self.learn(_f32(tr.state), _f32(tr.action), _f32(tr.reward).unsqueeze(-1), _f32(tr.next_state),
                        _f32(tr.mask).unsqueeze(-1))
@@ -2472,13 +2504,18 @@ class TD3Agent(_DeterministicPolicyAgent):
     def warm(self):
         return self.total_steps >= self.config.warm_up
 
+    def _policy_step(self):
+        return bool(self.total_steps % self.config.td3_delay)
+
     def learn(self, states, actions, rewards, next_states, mask):
         config, net, tgt = self.config, self.network, self.target_network
         space = self.task.action_space
         with torch.no_grad():
             a_next = tgt(next_states)
             noise = torch.randn_like(a_next).mul(config.td3_noise).clamp(-config.td3_noise_clip, config.td3_noise_clip)
-            a_next = (a_next + noise).clamp(float(space.low[0]), float(space.high[0]))
+            # (bounds as gym's Box gives them, one per dimension, or as one scalar: envs.Box of the synthetic tasks)
+            low, high = (float(np.asarray(b).reshape(-1)[0]) for b in (space.low, space.high))
+            a_next = (a_next + noise).clamp(low, high)
             y = rewards + config.discount * mask * torch.min(*tgt.q(next_states, a_next))
         q_1, q_2 = net.q(states, actions)
         critic_loss = F.mse_loss(q_1, y) + F.mse_loss(q_2, y)

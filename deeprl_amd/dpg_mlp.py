@@ -1,0 +1,257 @@
+"""Host side of csrc/dpg_mlp.hip: the DDPG / TD3 update (DDPG_agent.py:75-100, TD3_agent.py:72-108) and the one-row acting
+forward as a few eager launches, behind the opt-in switch `config.fused_dpg_update`.
+
+`shape(network)` says whether a network is one the kernels walk (DeterministicActorCriticNet / TD3Net, identity phi_body,
+two-layer FCBody stacks of one (H1, H2) and one relu or tanh gate, plain Linear layers with biases); `why_not(agent)` adds the
+agent-side conditions and names the first one that fails; `Update(agent)` owns the workspace, the Adam moments over the online
+flat parameter buffer and the step counts, builds the structs and issues the launches on the current stream.
+There is no CPU / eager implementation here: without the HIP library every call raises.
+"""
+import ctypes
+
+import numpy as np
+import torch
+
+from ._lib import lib, stream_ptr
+from .a2c_mlp import GATES
+
+_I6 = ctypes.c_int32 * 6
+
+
+class Net(ctypes.Structure):
+    """Mirror of dra_dpg_net (include/deeprl_amd.h)."""
+    _fields_ = [("param", ctypes.c_void_p), ("actor", _I6), ("critic", _I6 * 2),
+                ("state_dim", ctypes.c_int32), ("action_dim", ctypes.c_int32), ("h1", ctypes.c_int32), ("h2", ctypes.c_int32),
+                ("gate", ctypes.c_int32), ("n_critics", ctypes.c_int32)]
+
+
+class Batch(ctypes.Structure):
+    """Mirror of dra_dpg_batch."""
+    _fields_ = [("state", ctypes.c_void_p), ("next_state", ctypes.c_void_p), ("action", ctypes.c_void_p),
+                ("reward", ctypes.c_void_p), ("mask", ctypes.c_void_p), ("noise", ctypes.c_void_p),
+                ("state_stride", ctypes.c_int64), ("next_state_stride", ctypes.c_int64), ("action_stride", ctypes.c_int64),
+                ("batch", ctypes.c_int32), ("in_f64", ctypes.c_int32)]
+
+
+class Step(ctypes.Structure):
+    """Mirror of dra_dpg_step."""
+    _fields_ = [("exp_avg", ctypes.c_void_p), ("exp_avg_sq", ctypes.c_void_p),
+                ("step_size", ctypes.c_float), ("inv_sqrt_bc2", ctypes.c_float),
+                ("beta1", ctypes.c_float), ("beta2", ctypes.c_float), ("eps", ctypes.c_float), ("discount", ctypes.c_float),
+                ("td3_noise", ctypes.c_float), ("td3_noise_clip", ctypes.c_float),
+                ("action_low", ctypes.c_float), ("action_high", ctypes.c_float),
+                ("noise_seed", ctypes.c_uint64), ("noise_counter", ctypes.c_int64)]
+
+
+def _mlp_dims(body, head, gate_out):
+    """(in, h1, h2, out) of FCBody(in, (h1, h2)) + Linear head, or None."""
+    from .nets import FCBody, Linear
+    if type(body) is not FCBody or body.noisy_linear or body.gate not in GATES or len(body.layers) != 2:
+        return None
+    if any(type(layer) is not Linear or layer.bias is None for layer in body.layers):
+        return None
+    if type(head) is not Linear or head.bias is None:
+        return None
+    w1, w2 = body.layers[0].weight, body.layers[1].weight
+    if w2.shape[1] != w1.shape[0] or head.weight.shape[1] != w2.shape[0]:
+        return None
+    gate_out.append(GATES[body.gate])
+    return int(w1.shape[1]), int(w1.shape[0]), int(w2.shape[0]), int(head.weight.shape[0])
+
+
+def modules(network):
+    """[(actor_body, fc_action), (critic_body, fc_critic), ...] of a DeterministicActorCriticNet / TD3Net, or None."""
+    from .nets import DeterministicActorCriticNet, DummyBody, TD3Net
+    if type(network) is DeterministicActorCriticNet:
+        if type(network.phi_body) is not DummyBody:
+            return None
+        return [(network.actor_body, network.fc_action), (network.critic_body, network.fc_critic)]
+    if type(network) is TD3Net:
+        return [(network.actor_body, network.fc_action), (network.critic_body_1, network.fc_critic_1),
+                (network.critic_body_2, network.fc_critic_2)]
+    return None
+
+
+def shape(network):
+    """(state_dim, action_dim, h1, h2, gate code, n_critics) when `network` is a DeterministicActorCriticNet (identity phi_body)
+    or a TD3Net whose actor and critic bodies are two-layer FCBody stacks of ONE (h1, h2) with ONE relu or tanh gate, plain
+    Linear layers with biases; else None."""
+    mods = modules(network)
+    if mods is None:
+        return None
+    gates = []
+    dims = [_mlp_dims(b, h, gates) for b, h in mods]
+    if any(d is None for d in dims) or len(set(gates)) != 1:
+        return None
+    (s_dim, h1, h2, a_dim), critics = dims[0], dims[1:]
+    if any(c != (s_dim + a_dim, h1, h2, 1) for c in critics):
+        return None
+    return s_dim, a_dim, h1, h2, gates[0], len(critics)
+
+
+def supported(batch, state_dim, action_dim, h1, h2, gate, n_critics):
+    """dra_dpg_supported: the shapes the kernels are built for (host-only: no GPU needed)."""
+    return lib.dra_dpg_supported.raw(int(batch), int(state_dim), int(action_dim), int(h1), int(h2), int(gate), int(n_critics)) == 0
+
+
+def _plain_adam(opt):
+    if type(opt) is not torch.optim.Adam or len(opt.param_groups) != 1:
+        return False
+    g = opt.param_groups[0]
+    return not (g.get('amsgrad') or g.get('weight_decay') or g.get('maximize') or g.get('capturable') or g.get('differentiable'))
+
+
+def why_not(agent, supported_fn=supported):
+    """None when `agent` (a DDPGAgent / TD3Agent) may take the fused path, else the reason it may not, in words."""
+    cfg = agent.config
+    if getattr(cfg, 'fused_dpg_update', False) is not True:
+        return "config.fused_dpg_update is off"
+    shp = shape(agent.network)
+    if shp is None or shape(agent.target_network) != shp:
+        return ("the network is not an actor S -> H1 -> H2 -> A with critics S + A -> H1 -> H2 -> 1 of plain Linear layers with "
+                "biases, one relu / tanh gate and an identity phi_body")
+    if not (_plain_adam(agent.network.actor_opt) and _plain_adam(agent.network.critic_opt)):
+        return "both optimisers must be plain torch.optim.Adam (no amsgrad, weight decay or maximize)"
+    from .replay import UniformReplay
+    ring = getattr(agent.replay, 'replay', agent.replay)
+    if type(ring) is not UniformReplay or ring.n_step != 1 or ring.history_length != 1:
+        return "the replay is not a one-step UniformReplay"
+    batch = ring.batch_size
+    if batch is None or not supported_fn(batch, *shp):
+        return "dra_dpg_supported refuses batch %r with (S, A, H1, H2, gate, critics) = %r" % (batch, shp)
+    space = agent.task.action_space
+    low, high = np.asarray(space.low, dtype=np.float64).reshape(-1), np.asarray(space.high, dtype=np.float64).reshape(-1)
+    if not (np.all(low == low[0]) and np.all(high == high[0])):
+        return "the action space bounds are not the same scalar in every dimension"
+    return None
+
+
+def eligible(agent, supported_fn=supported):
+    return why_not(agent, supported_fn) is None
+
+
+def net_struct(network, flat, shp):
+    """dra_dpg_net over `network`'s parameters inside the FlatParams `flat`."""
+    n = Net()
+    n.param = flat.flat.data_ptr()
+    off = flat.offset_of
+    for i, (body, head) in enumerate(modules(network)):
+        six = _I6(off(body.layers[0].weight), off(body.layers[0].bias), off(body.layers[1].weight), off(body.layers[1].bias),
+                  off(head.weight), off(head.bias))
+        if i == 0:
+            n.actor = six
+        else:
+            n.critic[i - 1] = six
+    n.state_dim, n.action_dim, n.h1, n.h2, n.gate, n.n_critics = shp
+    return n
+
+
+def workspace_floats(batch, shp):
+    out = ctypes.c_int64(0)
+    lib.dra_dpg_workspace_floats(int(batch), shp[0], shp[1], shp[2], shp[3], shp[5], ctypes.byref(out))
+    return out.value
+
+
+class Update:
+    """The fused update and acting forward of one DDPGAgent / TD3Agent (eligible: `why_not(agent) is None`)."""
+
+    def __init__(self, agent):
+        self.agent = agent
+        self.shape = shp = shape(agent.network)
+        t_flat, s_flat = agent._flat_pair(agent.target_network, agent.network)
+        tf, sf = agent._soft_flat[0], agent._soft_flat[1]
+        self.online, self.target = net_struct(agent.network, sf, shp), net_struct(agent.target_network, tf, shp)
+        self.flat, self.target_flat = s_flat, t_flat
+        self.exp_avg, self.exp_avg_sq = torch.zeros_like(s_flat), torch.zeros_like(s_flat)
+        self.t_critic = self.t_actor = 0
+        self.updates = 0                      # position of TD3's smoothing-noise stream
+        self.launches = 0
+        # seed of the smoothing-noise stream: configured, else the run's torch seed (read without consuming any generator, as
+        # dist.DataParallel does for the on-policy agents' action noise)
+        seed = getattr(agent.config, 'dp_noise_seed', None)
+        self.noise_seed = int(seed) if seed is not None else int(torch.initial_seed()) & 0x3fffffff
+        self.batch_size = getattr(agent.replay, 'replay', agent.replay).batch_size
+        dev = s_flat.device
+        self.workspace = torch.zeros(workspace_floats(self.batch_size, shp), dtype=torch.float32, device=dev)
+        self._act_in = torch.zeros(128 * shp[0], dtype=torch.float64, device=dev)
+        space = agent.task.action_space
+        self.low, self.high = float(np.asarray(space.low).reshape(-1)[0]), float(np.asarray(space.high).reshape(-1)[0])
+
+    # ---- structs
+    def _step(self, opt, t):
+        g = opt.param_groups[0]
+        hp = (ctypes.c_float * 2)()
+        lib.dra_adam_hyper(float(g['lr']), float(g['betas'][0]), float(g['betas'][1]), int(t), hp)
+        cfg = self.agent.config
+        s = Step()
+        s.exp_avg, s.exp_avg_sq = self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr()
+        s.step_size, s.inv_sqrt_bc2 = hp[0], hp[1]
+        s.beta1, s.beta2, s.eps = float(g['betas'][0]), float(g['betas'][1]), float(g['eps'])
+        s.discount = float(cfg.discount)
+        if self.shape[5] == 2:
+            s.td3_noise, s.td3_noise_clip = float(cfg.td3_noise), float(cfg.td3_noise_clip)
+            s.action_low, s.action_high = self.low, self.high
+        s.noise_seed, s.noise_counter = self.noise_seed, self.updates
+        return s
+
+    @staticmethod
+    def batch_struct(state, action, reward, next_state, mask, noise=None):
+        """dra_dpg_batch over device tensors: state / next_state / action fp32 or fp64 (one dtype; rows may be strided views of
+        the replay's block), reward / mask fp32 [B]."""
+        b = Batch()
+        f64 = state.dtype == torch.float64
+        for t in (state, next_state, action):
+            if t.dtype != state.dtype or t.dim() != 2 or t.stride(1) != 1 or t.dtype not in (torch.float32, torch.float64):
+                raise ValueError("dpg batch: state, next_state and action are [B, n] fp32 or fp64 of one dtype, unit inner stride")
+        for t in (reward, mask):
+            if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != state.shape[0]:
+                raise ValueError("dpg batch: reward and mask are contiguous fp32 [B]")
+        b.state, b.next_state, b.action = state.data_ptr(), next_state.data_ptr(), action.data_ptr()
+        b.reward, b.mask = reward.data_ptr(), mask.data_ptr()
+        b.noise = None if noise is None else noise.data_ptr()
+        b.state_stride, b.next_state_stride, b.action_stride = state.stride(0), next_state.stride(0), action.stride(0)
+        b.batch, b.in_f64 = state.shape[0], 1 if f64 else 0
+        return b
+
+    # ---- launches
+    def learn(self, state, action, reward, next_state, mask, policy_step=True, noise=None):
+        """One agent update on the current stream: critic (2 launches), then -- on a policy step -- actor (2) and the soft
+        target update (1).  The tensors must stay alive until the stream has run them (the caller holds the minibatch)."""
+        a, net = self.agent, self.agent.network
+        b = self.batch_struct(state, action, reward, next_state, mask, noise)
+        self.t_critic += 1
+        st = self._step(net.critic_opt, self.t_critic)
+        lib.dra_dpg_critic_update(ctypes.byref(self.online), ctypes.byref(self.target), ctypes.byref(b), ctypes.byref(st),
+                                  self.workspace.data_ptr(), stream_ptr())
+        self.updates += 1
+        self.launches += 2
+        if policy_step:
+            self.t_actor += 1
+            st = self._step(net.actor_opt, self.t_actor)
+            lib.dra_dpg_actor_update(ctypes.byref(self.online), ctypes.byref(b), ctypes.byref(st), self.workspace.data_ptr(),
+                                     stream_ptr())
+            a.soft_update(a.target_network, net)
+            self.launches += 3
+
+    def act(self, state):
+        """tanh(actor(state)) for [n <= 128, S] observations (numpy or tensor) -> fp32 device tensor [n, A]."""
+        s_dim, a_dim = self.shape[0], self.shape[1]
+        if isinstance(state, torch.Tensor):
+            x = state.to(self.flat.device).reshape(-1, s_dim)
+            if x.dtype not in (torch.float32, torch.float64) or x.stride(1) != 1:
+                x = x.float().contiguous()
+        else:
+            host = np.ascontiguousarray(np.asarray(state, dtype=np.float64).reshape(-1, s_dim))
+            x = self._act_in[:host.size].view(-1, s_dim)
+            x.copy_(torch.from_numpy(host))
+        out = torch.empty((x.shape[0], a_dim), dtype=torch.float32, device=self.flat.device)
+        lib.dra_dpg_act(ctypes.byref(self.online), x.data_ptr(), x.stride(0), 1 if x.dtype == torch.float64 else 0, x.shape[0],
+                        out.data_ptr(), stream_ptr())
+        self.launches += 1
+        return out
+
+    # ---- views for tests / logging (the head of the workspace: y, q [2], per-row loss)
+    def last(self):
+        n = self.batch_size
+        w = self.workspace
+        return dict(y=w[:n], q=w[n:3 * n].view(2, n)[:self.shape[5]], loss=w[3 * n:4 * n])

@@ -915,6 +915,56 @@ int dra_gauss_head_fwd(const float* z, const float* std, const float* action, in
 int dra_gauss_head_bwd(const float* z, const float* std, const float* action, const float* g_log_pi_a, const float* g_entropy,
                        int n, int a_dim, float* dz, float* dstd, void* stream);
 
+/* ---- dpg_mlp: the DDPG / TD3 update (DDPG_agent.py:62-100, TD3_agent.py:62-108) as a few eager launches ("dpg": deterministic
+ * policy gradient).  Networks: an actor S -> H1 -> H2 -> A with tanh on the head and n_critics (1: DDPG, 2: TD3) critics
+ * S + A -> H1 -> H2 -> 1, one gate (1 relu, 2 tanh) on every hidden layer, plain Linear layers with biases, all parameters of a
+ * network in ONE flat fp32 buffer.  1 <= batch <= 128, S <= 64, A <= 16, H1, H2 <= 512; no size needs to be a multiple of
+ * anything.  Every entry point returns -EINVAL outside that range. */
+typedef struct dra_dpg_net {
+  float* param;              /* flat parameter buffer (device); stepped in place by the two *_update calls (online network) */
+  int32_t actor[6];          /* float offsets into param of w1 [H1][S], b1, w2 [H2][H1], b2, w3 [A][H2], b3; any order, gaps allowed */
+  int32_t critic[2][6];      /* per critic: w1 [H1][S + A], b1, w2 [H2][H1], b2, w3 [1][H2], b3; critic[1] is ignored when n_critics == 1 */
+  int32_t state_dim, action_dim, h1, h2;
+  int32_t gate, n_critics;
+} dra_dpg_net;
+typedef struct dra_dpg_batch {
+  const void* state;         /* [batch][state_dim], rows state_stride elements apart; fp32, or fp64 when in_f64 != 0 (narrowed to */
+  const void* next_state;    /*   fp32 when loaded: the replay ring hands back the stored dtype) */
+  const void* action;        /* [batch][action_dim], same dtype */
+  const float* reward;       /* [batch] */
+  const float* mask;         /* [batch]  1 - done */
+  const float* noise;        /* optional [batch][action_dim] standard normals for TD3's target-policy smoothing; NULL: the counter-
+                              * hash stream gauss_noise(noise_seed, noise_counter, batch, row, dim) of csrc/cont_env.h */
+  int64_t state_stride, next_state_stride, action_stride;
+  int32_t batch, in_f64;
+} dra_dpg_batch;
+typedef struct dra_dpg_step {
+  float* exp_avg;            /* Adam moments, laid out like the ONLINE flat parameter buffer (the actor's and the critics' */
+  float* exp_avg_sq;         /*   optimisers own disjoint ranges of it) */
+  float step_size, inv_sqrt_bc2;   /* dra_adam_hyper(lr, beta1, beta2, t) of the optimiser this call steps */
+  float beta1, beta2, eps;
+  float discount;
+  float td3_noise, td3_noise_clip, action_low, action_high;   /* n_critics == 2 only */
+  uint64_t noise_seed;
+  int64_t noise_counter;     /* position t of the smoothing-noise stream (the caller's update counter) */
+} dra_dpg_step;
+int dra_dpg_supported(int batch, int state_dim, int action_dim, int h1, int h2, int gate, int n_critics);   /* 0 = yes */
+/* floats of workspace the update calls need.  Its head is fixed: y [batch], q [2][batch] (online Q_i(s, a) before the step), the
+ * per-row critic loss [batch] (0.5 (q - y)^2, or (q1 - y)^2 + (q2 - y)^2); activations and dz of every layer follow. */
+int dra_dpg_workspace_floats(int batch, int state_dim, int action_dim, int h1, int h2, int n_critics, int64_t* out);
+/* two launches: [target actor + critics -> y; online critics forward, dq = (q - y) / batch (x 2 for two critics: mse + mse), dz
+ * chain] over 16-row tiles, then [weight / bias gradient over all rows + Adam in place] per 16 x 16 parameter tile. */
+int dra_dpg_critic_update(const dra_dpg_net* online, const dra_dpg_net* target, const dra_dpg_batch* batch,
+                          const dra_dpg_step* step, float* workspace, void* stream);
+/* two launches, after dra_dpg_critic_update on the same batch and workspace (the states are read from it): [a = actor(s),
+ * critic 1 on (s, a), dq = -1 / batch back to da, the actor's dz chain], then the actor's gradient + Adam.  Critic parameters
+ * are not touched.  `step` carries the ACTOR optimiser's scalars. */
+int dra_dpg_actor_update(const dra_dpg_net* online, const dra_dpg_batch* batch, const dra_dpg_step* step, float* workspace,
+                         void* stream);
+/* out_action [n][action_dim] = tanh(actor(state)) for n <= 128 rows: one launch */
+int dra_dpg_act(const dra_dpg_net* net, const void* state, int64_t state_stride, int in_f64, int n, float* out_action,
+                void* stream);
+
 #ifdef __cplusplus
 }
 #endif

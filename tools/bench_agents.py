@@ -14,6 +14,9 @@ after a warm-up.  Prints one JSON object per line: agent steps/s, env steps/s, g
   config 5  a2c_pixel examples.py:361-381 (16 workers), ppo_pixel examples.py:525-550 (8 workers)
             a2c_continuous examples.py:384-404 (16 workers; `_host` = config.device_env False: python environments, module head)
             n_step_dqn_pixel examples.py:427-447 (16 workers), option_critic_pixel examples.py:471-492 (16 workers)
+  ddpg_continuous examples.py:554-583, td3_continuous examples.py:587-617 (one host environment, (400, 300) relu MLPs, Adam 1e-3,
+            minibatch 100, a 1M ring; warm_up shortened to 1000 so that the timed window is all updates; the default is
+            config.fused_dpg_update True: csrc/dpg_mlp.hip; `_modules` = the switch off: torch modules and optimisers)
 """
 import argparse
 import json
@@ -118,6 +121,30 @@ def a2c_continuous(workers=16, device=True, **switches):
     c.discount, c.use_gae, c.gae_tau, c.entropy_weight, c.rollout_length, c.gradient_clip = 0.99, True, 1.0, 0.01, 5, 5
     c.max_steps = int(2e7)
     return d.A2CAgent(c), dict(env_per_step=5 * workers, updates_per_step=1)
+
+
+def dpg_continuous(kind, fused=True):
+    c = d.Config()
+    c.merge(dict(game="synthetic-continuous-HalfCheetah", log_level=0, tag="bench", fused_dpg_update=fused))
+    c.task_fn = lambda: d.Task(c.game, seed=1)
+    c.eval_env = d.Task(c.game, seed=2)
+    adam = lambda p: torch.optim.Adam(p, lr=1e-3)
+    body = lambda n: d.FCBody(n, (400, 300), gate=torch.relu)
+    if kind == "ddpg":
+        c.network_fn = lambda: d.DeterministicActorCriticNet(c.state_dim, c.action_dim, actor_body=body(c.state_dim),
+                                                             critic_body=body(c.state_dim + c.action_dim), actor_opt_fn=adam,
+                                                             critic_opt_fn=adam)
+        c.replay_fn = lambda: d.UniformReplay(memory_size=int(1e6), batch_size=100)
+        c.random_process_fn = lambda: d.OrnsteinUhlenbeckProcess(size=(c.action_dim,), std=d.LinearSchedule(0.2))
+    else:
+        c.network_fn = lambda: d.TD3Net(c.action_dim, actor_body_fn=lambda: body(c.state_dim),
+                                        critic_body_fn=lambda: body(c.state_dim + c.action_dim), actor_opt_fn=adam, critic_opt_fn=adam)
+        c.replay_fn = lambda: d.ReplayWrapper(d.UniformReplay, dict(memory_size=int(1e6), batch_size=100))
+        c.random_process_fn = lambda: d.GaussianProcess(size=(c.action_dim,), std=d.LinearSchedule(0.1))
+        c.td3_noise, c.td3_noise_clip, c.td3_delay = 0.2, 0.5, 2
+    c.discount, c.warm_up, c.target_network_mix, c.max_steps = 0.99, 1000, 5e-3, int(1e6)
+    agent = (d.DDPGAgent if kind == "ddpg" else d.TD3Agent)(c)
+    return agent, dict(env_per_step=1, updates_per_step=1, warm=1100)
 
 
 def n_step_dqn_pixel(workers=16, device=True, **switches):
@@ -226,6 +253,10 @@ CASES = {
     "ppo_continuous_16": lambda: ppo_continuous(16),                                  # device environments + persistent kernels
     "ppo_continuous_16_host": lambda: ppo_continuous(16, device=False),               # host environments, persistent update kernel
     "ppo_continuous_16_generic": lambda: ppo_continuous(16, device=False, fused=False),   # round-4 path
+    "ddpg_continuous": lambda: dpg_continuous("ddpg"),                          # fused update + acting forward (csrc/dpg_mlp.hip)
+    "ddpg_continuous_modules": lambda: dpg_continuous("ddpg", fused=False),     # torch modules, two torch.optim.Adam
+    "td3_continuous": lambda: dpg_continuous("td3"),
+    "td3_continuous_modules": lambda: dpg_continuous("td3", fused=False),
 }
 
 
@@ -241,6 +272,7 @@ def main():
         try:
             agent, meta = CASES[name]()
             warm = 120 if "dqn" in name or "c51" in name or "rainbow" in name else 4      # DQN family: past exploration_steps; on-policy: past graph capture
+            warm = meta.get("warm", warm)                                                 # (replay actor-critics: past warm_up)
             for _ in range(warm):
                 agent.step()
             torch.cuda.synchronize()
