@@ -466,6 +466,20 @@ class DQNAgent(BaseAgent):
         env = self._device_env()
         if env is not None:
             self._attach_device_pipeline(env)
+        self._noisy_actor = self._device_noisy_actor()
+
+    def _device_noisy_actor(self):
+        """noisy_actor.NoisyActor when `config.device_noisy_actor` is on and the agent is eligible (Rainbow over one synthetic
+        Atari environment: the transitions of an agent step as one batched, sync-free block on the device), else None: the
+        host-stepped actor -- an opted-in agent that does not qualify says why, once."""
+        if getattr(self.config, 'device_noisy_actor', False) is not True or self._pipe is not None:
+            return None
+        from . import noisy_actor
+        why = noisy_actor.why_not(self)
+        if why is not None:
+            self.logger.warning('device_noisy_actor is on but this agent keeps the host-stepped actor: %s' % why)
+            return None
+        return noisy_actor.NoisyActor(self, noisy_actor._env_of(self))
 
     # -- fused fast path ---------------------------------------------------------------------------------
     def _inner_replay(self):
@@ -670,6 +684,10 @@ class DQNAgent(BaseAgent):
         (tests/test_gpu_resume.py).  Device-resident pipeline (the benchmarked dqn_pixel-family configurations) only."""
         import pickle
         import random as pyrandom
+        if getattr(self, '_noisy_actor', None) is not None:
+            raise NotImplementedError("save_full: the device-resident noisy actor (config.device_noisy_actor) has no full resume "
+                                      "-- its episode shadow and noise staging are not checkpointed; save() / load() keep the "
+                                      "weights and the normaliser")
         if self._pipe is None or self._learner is None:
             raise NotImplementedError("save_full: this agent runs a host environment / the generic update path; only the "
                                       "device-resident pipeline (config.device_env, synthetic Atari) has a full resume")
@@ -699,6 +717,8 @@ class DQNAgent(BaseAgent):
         """Into a freshly constructed agent of the same Config (same network / replay / pipeline shape), before its first step."""
         import pickle
         import random as pyrandom
+        if getattr(self, '_noisy_actor', None) is not None:
+            raise NotImplementedError("load_full: the device-resident noisy actor (config.device_noisy_actor) has no full resume")
         if self._pipe is None or self._learner is None:
             raise NotImplementedError("load_full needs the device-resident pipeline (see save_full)")
         with open(filename + '.resume', 'rb') as f:
@@ -848,6 +868,8 @@ class DQNAgent(BaseAgent):
                                       "lr needs config.fused_learner = False (generic path)")
         if self._pipe is not None:
             return self._step_device()
+        if self._noisy_actor is not None:
+            return self._step_noisy_device()
         if self._learner is not None:   # ring feeds, actor forwards and updates share the learner's stream
             with torch.cuda.stream(self._learner.stream):
                 if self._host_async:
@@ -871,6 +893,19 @@ class DQNAgent(BaseAgent):
                 reward=[config.reward_normalizer(r) for r in rewards],
                 mask=1 - np.asarray(dones, dtype=np.int32),
             ))
+        self._update_and_sync()
+
+    def _step_noisy_device(self):
+        """DQN_agent.py:101-138 with the transitions produced, acted on and fed on the device (noisy_actor.NoisyActor); the
+        update is the generic path's."""
+        for info in self._noisy_actor.step():
+            self.record_online_return(info)
+            self.total_steps += 1
+        self._update_and_sync()
+
+    def _update_and_sync(self):
+        """DQN_agent.py:114-138: the update of an agent step and the target synchronisation."""
+        config = self.config
         if self.total_steps > config.exploration_steps:
             if self._learner is not None:
                 rp = self._inner_replay()

@@ -189,6 +189,106 @@ noisy_fwd_col_kernel(const float* __restrict__ x, const float* __restrict__ wmu,
   }
 }
 
+// ------------------------------------------------------------------------------------------------ forward, one noise draw per row
+// noisy_fwd_col_kernel with row r of x under ITS OWN noise (e_in / e_out / e_b rows `noise_stride` floats apart): the transitions
+// of one agent step see the same parameters and differ only in their draws (DQN_agent.py:28-29), so ONE pass over the column's
+// two weight rows serves all of them.  Per row the arithmetic is the column kernel's, operation for operation (per-thread k order,
+// wave butterfly, waves in LDS in wave order, m + fo * s + bias): row r has the bits of a rows = 1 launch with row r's noise.
+template <int RB, bool VEC>
+__global__ void __launch_bounds__(256)
+noisy_fwd_rows_kernel(const float* __restrict__ x, const float* __restrict__ wmu, const float* __restrict__ wsig,
+                      const float* __restrict__ bmu, const float* __restrict__ bsig, const float* __restrict__ e_in,
+                      const float* __restrict__ e_out, const float* __restrict__ e_b, int64_t stride_in, int64_t stride_out,
+                      int rows, int K, int N, int act, float* __restrict__ y) {
+  __shared__ float red[kWaves][RB][2];
+  const int n = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const float* wm_row = wmu + (size_t)n * K;
+  const float* ws_row = wsig + (size_t)n * K;
+  float am[RB], as[RB];
+#pragma unroll
+  for (int r = 0; r < RB; ++r) am[r] = as[r] = 0.f;
+  if constexpr (VEC) {
+    for (int k = 4 * threadIdx.x; k < K; k += 4 * 256) {
+      const float4 wm = ld4(wm_row + k), ws = ld4(ws_row + k);
+#pragma unroll
+      for (int r = 0; r < RB; ++r) {
+        const int rr = min(r, rows - 1);
+        const float4 xv = ld4(x + (size_t)rr * K + k), fe = noise_f4(e_in + (size_t)rr * stride_in, k);
+        am[r] += xv.x * wm.x; am[r] += xv.y * wm.y; am[r] += xv.z * wm.z; am[r] += xv.w * wm.w;
+        as[r] += (xv.x * fe.x) * ws.x; as[r] += (xv.y * fe.y) * ws.y; as[r] += (xv.z * fe.z) * ws.z; as[r] += (xv.w * fe.w) * ws.w;
+      }
+    }
+  } else {
+    for (int k = threadIdx.x; k < K; k += 256) {
+      const float wm = wm_row[k], ws = ws_row[k];
+#pragma unroll
+      for (int r = 0; r < RB; ++r) {
+        const int rr = min(r, rows - 1);
+        const float xv = x[(size_t)rr * K + k], fe = noise_f(e_in[(size_t)rr * stride_in + k]);
+        am[r] += xv * wm;
+        as[r] += (xv * fe) * ws;
+      }
+    }
+  }
+#pragma unroll
+  for (int r = 0; r < RB; ++r) {
+    const float m = wave_sum(am[r]), s = wave_sum(as[r]);
+    if (lane == 0) { red[wave][r][0] = m; red[wave][r][1] = s; }
+  }
+  __syncthreads();
+  if (threadIdx.x < RB && threadIdx.x < rows) {
+    const int r = threadIdx.x;
+    float m = red[0][r][0], s = red[0][r][1];
+#pragma unroll
+    for (int w = 1; w < kWaves; ++w) { m += red[w][r][0]; s += red[w][r][1]; }
+    const float fo = noise_f(e_out[(size_t)r * stride_out + n]);
+    const float bias = bmu[n] + bsig[n] * noise_f(e_b[(size_t)r * stride_out + n]);
+    float v = m + fo * s + bias;
+    if (act == DRA_ACT_RELU) v = fmaxf(v, 0.f);
+    y[(size_t)r * N + n] = v;
+  }
+}
+
+// ------------------------------------------------------------------------------------------------ Rainbow's greedy action per row
+// One workgroup per row: logits[a][z] = value[z] + (adv[a][z] - mean_a adv[.][z]) (dueling_atoms_fwd_kernel's expression: ascending
+// a, mean = sum / A) into LDS, then one thread per action: softmax over the atoms (max, sum of exp, both ascending z) and
+// q[a] = sum_z p[a][z] atoms[z] in ascending z; thread 0 takes the FIRST maximum (np.argmax).  A, Z <= 64.
+constexpr int kActMax = 64;
+__global__ void __launch_bounds__(256)
+rainbow_act_rows_kernel(const float* __restrict__ value, const float* __restrict__ adv, const float* __restrict__ atoms, int A, int Z,
+                        int64_t* __restrict__ action, float* __restrict__ q_out) {
+  __shared__ float logit[kActMax * kActMax];
+  __shared__ float sq[kActMax];
+  const int b = blockIdx.x;
+  const float* ap = adv + (size_t)b * A * Z;
+  for (int z = threadIdx.x; z < Z; z += 256) {
+    float s = 0.f;
+    for (int a = 0; a < A; ++a) s += ap[(size_t)a * Z + z];
+    const float mean = s / (float)A, v = value[(size_t)b * Z + z];
+    for (int a = 0; a < A; ++a) logit[a * Z + z] = v + (ap[(size_t)a * Z + z] - mean);
+  }
+  __syncthreads();
+  if (threadIdx.x < A) {
+    const float* l = logit + threadIdx.x * Z;
+    float m = l[0];
+    for (int z = 1; z < Z; ++z) m = fmaxf(m, l[z]);
+    float se = 0.f;
+    for (int z = 0; z < Z; ++z) se += expf(l[z] - m);
+    float q = 0.f;
+    for (int z = 0; z < Z; ++z) q += (expf(l[z] - m) / se) * atoms[z];
+    sq[threadIdx.x] = q;
+    if (q_out) q_out[(size_t)b * A + threadIdx.x] = q;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    int best = 0;
+    float bq = sq[0];
+    for (int a = 1; a < A; ++a)
+      if (sq[a] > bq) { bq = sq[a]; best = a; }
+    action[b] = (int64_t)best;
+  }
+}
+
 // ------------------------------------------------------------------------------------------------ weight / bias gradients
 // grid (ceil(K / (V blockDim)), ceil(N / 8)).  A thread owns V consecutive inputs k of 8 outputs n: acc[i][e] = sum_b g[b][n0 + i]
 // x[b][k + e] in ascending b; the rows of g are staged through LDS 32 at a time.  dW_mu and dW_sigma = dW_mu * (f(e_out) f(e_in))
@@ -474,6 +574,38 @@ DRA_API int dra_noisy_linear_fwd(const float* x, const float* w_mu, const float*
   if (rows == 1) { if (vec) DRA_NOISY_COL(1, true); else DRA_NOISY_COL(1, false); }
   else           { if (vec) DRA_NOISY_COL(4, true); else DRA_NOISY_COL(4, false); }
 #undef DRA_NOISY_COL
+  DRA_LAUNCH_CHECK();
+  return DRA_OK;
+}
+
+DRA_API int dra_noisy_linear_fwd_rows(const float* x, const float* w_mu, const float* w_sigma, const float* b_mu, const float* b_sigma,
+                                      const float* noise_in, const float* noise_out_weight, const float* noise_out_bias,
+                                      int64_t noise_stride, float* y, int rows, int in_features, int out_features, int act,
+                                      void* stream) {
+  if (!x || !w_mu || !w_sigma || !b_mu || !b_sigma || !noise_in || !noise_out_weight || !noise_out_bias || !y) return DRA_EINVAL;
+  if (rows < 1 || rows > 8 || in_features < 1 || out_features < 1 || (act != DRA_ACT_NONE && act != DRA_ACT_RELU)) return DRA_EINVAL;
+  if (noise_stride < 0 || (noise_stride > 0 && (noise_stride < in_features || noise_stride < out_features))) return DRA_EINVAL;
+  const int K = in_features, N = out_features;
+  const int64_t s_in = noise_stride ? noise_stride : K, s_out = noise_stride ? noise_stride : N;
+  hipStream_t st = dra_stream(stream);
+  const bool vec = K % 4 == 0 && aligned16(x) && aligned16(w_mu) && aligned16(w_sigma);
+#define DRA_NOISY_ROWS(RB, VEC)                                                                                                 \
+  hipLaunchKernelGGL((noisy_fwd_rows_kernel<RB, VEC>), dim3(N), dim3(256), 0, st, x, w_mu, w_sigma, b_mu, b_sigma, noise_in,    \
+                     noise_out_weight, noise_out_bias, s_in, s_out, rows, K, N, act, y)
+  if (rows == 1)      { if (vec) DRA_NOISY_ROWS(1, true); else DRA_NOISY_ROWS(1, false); }
+  else if (rows <= 4) { if (vec) DRA_NOISY_ROWS(4, true); else DRA_NOISY_ROWS(4, false); }
+  else                { if (vec) DRA_NOISY_ROWS(8, true); else DRA_NOISY_ROWS(8, false); }
+#undef DRA_NOISY_ROWS
+  DRA_LAUNCH_CHECK();
+  return DRA_OK;
+}
+
+DRA_API int dra_rainbow_act_rows(const float* value, const float* advantage, const float* atoms, int rows, int n_actions, int n_atoms,
+                                 int64_t* action, float* q, void* stream) {
+  if (!value || !advantage || !atoms || !action) return DRA_EINVAL;
+  if (rows < 1 || rows > 8 || n_actions < 1 || n_actions > kActMax || n_atoms < 1 || n_atoms > kActMax) return DRA_EINVAL;
+  hipLaunchKernelGGL(rainbow_act_rows_kernel, dim3(rows), dim3(256), 0, dra_stream(stream), value, advantage, atoms, n_actions,
+                     n_atoms, action, q);
   DRA_LAUNCH_CHECK();
   return DRA_OK;
 }

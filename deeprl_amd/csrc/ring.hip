@@ -139,6 +139,51 @@ DRA_API int dra_ring_put(dra_ring* r, int64_t slot0, int64_t count, const void* 
   return DRA_OK;
 }
 
+// put_rows: the transitions of ONE agent step of a device-resident actor (replay.py:75-90, `count` <= 8 feeds).  The first slot is
+// a device word (slot0_dev; the launch can sit in a captured graph) or, when that is null, the by-value slot0; slots wrap at
+// `capacity`.  Frame k is read frame_stride bytes behind frame k - 1 (the newest frame of each [history][frame] stack); actions
+// i64, rewards f64, masks i32 are device arrays.  One workgroup per slot, ring_put_kernel's two copy paths.  A device word outside
+// [0, capacity) writes nothing.
+__global__ void __launch_bounds__(256)
+ring_put_rows_kernel(uint8_t* __restrict__ frames, int64_t* __restrict__ actions, double* __restrict__ rewards,
+                     int32_t* __restrict__ masks, int64_t capacity, int64_t frame_bytes, const int64_t* __restrict__ slot0_dev,
+                     int64_t slot0_val, const uint8_t* __restrict__ fsrc, int64_t frame_stride, const int64_t* __restrict__ asrc,
+                     const double* __restrict__ rsrc, const int32_t* __restrict__ msrc, int vec16) {
+  const int64_t k = blockIdx.x;
+  const int64_t s0 = slot0_dev ? *slot0_dev : slot0_val;
+  if (s0 < 0 || s0 >= capacity) return;          // (block-uniform)
+  const int64_t slot = (s0 + k) % capacity;
+  uint8_t* dst = frames + slot * frame_bytes;
+  const uint8_t* src = fsrc + k * frame_stride;
+  if (vec16) {
+    const int64_t nv = frame_bytes >> 4;
+    const uint4* s4 = reinterpret_cast<const uint4*>(src);
+    uint4* d4 = reinterpret_cast<uint4*>(dst);
+    for (int64_t i = threadIdx.x; i < nv; i += blockDim.x) d4[i] = s4[i];
+  } else {
+    for (int64_t i = threadIdx.x; i < frame_bytes; i += blockDim.x) dst[i] = src[i];
+  }
+  if (threadIdx.x == 0) {
+    actions[slot] = asrc[k];
+    rewards[slot] = rsrc[k];
+    masks[slot] = msrc[k];
+  }
+}
+
+DRA_API int dra_ring_put_rows(dra_ring* r, const int64_t* slot0_dev, int64_t slot0, int count, const void* frame_src,
+                              int64_t frame_stride, const int64_t* action_src, const double* reward_src, const int32_t* mask_src,
+                              void* stream) {
+  if (!r || !frame_src || !action_src || !reward_src || !mask_src || count < 1 || count > 8 || count > r->capacity) return DRA_EINVAL;
+  if (!slot0_dev && (slot0 < 0 || slot0 >= r->capacity)) return DRA_EINVAL;
+  if (r->action_bytes != 8 || frame_stride < r->frame_bytes) return DRA_EINVAL;
+  int vec16 = (r->frame_bytes % 16 == 0) && (frame_stride % 16 == 0) && aligned16(frame_src) && aligned16(r->frames);
+  hipLaunchKernelGGL(ring_put_rows_kernel, dim3((unsigned)count), dim3(256), 0, dra_stream(stream), r->frames,
+                     reinterpret_cast<int64_t*>(r->actions), r->rewards, r->masks, r->capacity, r->frame_bytes, slot0_dev, slot0,
+                     (const uint8_t*)frame_src, frame_stride, action_src, reward_src, mask_src, vec16);
+  DRA_LAUNCH_CHECK();
+  return DRA_OK;
+}
+
 // Host-side feed (replay.py:75-90 for one env): stage through pinned memory, then the put kernel
 // reads the staging slot over the host link.  Never blocks except once per staging wrap.
 DRA_API int dra_ring_put_host(dra_ring* r, int64_t slot, const void* frame_host, const void* action_host,

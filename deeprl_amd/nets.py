@@ -798,6 +798,49 @@ class _NoiseBlock:
         for _, m in self.layers:
             m.noise_changed()
 
+    def _rows_buffers(self, rows):
+        """Static [rows][numel] device block + its rotating pinned staging (built on first use, per row count)."""
+        bufs = getattr(self, '_rows', None)
+        if bufs is None:
+            bufs = self._rows = {}
+        if rows not in bufs:
+            pin = self.device.type == 'cuda'
+            stage = [torch.zeros((rows, self.numel), dtype=torch.float32) for _ in range(self.SLOTS if pin else 1)]
+            bufs[rows] = dict(dev=torch.zeros((rows, self.numel), dtype=torch.float32, device=self.device),
+                              stage=[s.pin_memory() for s in stage] if pin else stage, events=[None] * len(stage), k=0)
+        return bufs[rows]
+
+    def draw_rows(self, rows):
+        """`rows` successive draw()s -- the reset_noise() calls of the transitions of one agent step (DQN_agent.py:28-29) -- into
+        one pinned [rows][numel] block that reaches a static device block with ONE asynchronous copy: the generator ends where
+        `rows` draw() calls leave it, row r holds what the r-th of them would have uploaded.  The layers' own buffers (self.flat)
+        get row rows - 1, as after the last of those calls.  Returns the device block (dra_noisy_linear_fwd_rows reads the rows
+        self.numel floats apart; a layer's vectors start at self.slices[...][0] of each row)."""
+        rows = int(rows)
+        b = self._rows_buffers(rows)
+        k = b['k']
+        b['k'] = (k + 1) % len(b['stage'])
+        if b['events'][k] is not None:
+            b['events'][k].synchronize()
+        host = b['stage'][k]
+        std = Config.NOISY_LAYER_STD
+        for r in range(rows):
+            row = host[r]
+            for lname, _ in self.layers:
+                for bname in NoisyLinear.NOISE_NAMES:
+                    o, n = self.slices[(lname, bname)]
+                    row[o:o + n].normal_(std=std)
+        self.host = host[rows - 1]
+        b['dev'].copy_(host, non_blocking=True)
+        self.flat.copy_(b['dev'][rows - 1])
+        if self.device.type == 'cuda':
+            if b['events'][k] is None:
+                b['events'][k] = torch.cuda.Event()
+            b['events'][k].record()
+        for _, m in self.layers:
+            m.noise_changed()
+        return b['dev']
+
 
 # ---------------------------------------------------------------------------------------------------- bodies
 class NatureConvBody(nn.Module):

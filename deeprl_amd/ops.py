@@ -73,6 +73,17 @@ class Ring:
         lib.dra_ring_put(self.h, int(slot0), int(count), ptr(_c(frames)), ptr(actions), int(action_val), ptr(rewards),
                          float(reward_val), ptr(masks), int(mask_val), stream_ptr())
 
+    def put_rows(self, count, frames, frame_stride, actions, rewards, masks, slot0_dev=None, slot0=0):
+        """The `count` <= 8 transitions of one agent step (dra_ring_put_rows): first slot from the device word slot0_dev (int64
+        tensor) or by value, wrapping at the capacity; frame k starts frame_stride bytes behind frame k - 1 of `frames`."""
+        if actions.dtype != torch.int64 or rewards.dtype != torch.float64 or masks.dtype != torch.int32 or \
+                (slot0_dev is not None and slot0_dev.dtype != torch.int64):
+            raise DraError("put_rows: actions int64, rewards float64, masks int32, slot0_dev int64")
+        if min(actions.numel(), rewards.numel(), masks.numel()) < count:
+            raise DraError("put_rows: %d transitions need %d actions / rewards / masks" % (count, count))
+        lib.dra_ring_put_rows(self.h, ptr(slot0_dev), int(slot0), int(count), ptr(_dev(frames)), int(frame_stride), ptr(_dev(actions)),
+                              ptr(_dev(rewards)), ptr(_dev(masks)), stream_ptr())
+
     def fill_synthetic(self, slot0, count, counter0, seed, n_actions=4, done_period=800):
         lib.dra_ring_fill_synthetic(self.h, int(slot0), int(count), int(counter0), int(seed), int(n_actions),
                                     int(done_period), stream_ptr())
@@ -1053,6 +1064,53 @@ def noisy_linear_fwd(x, w_mu, w_sigma, b_mu, b_sigma, noise_in, noise_out_weight
                              ptr(_c(noise_out_weight, _f32)), ptr(_c(noise_out_bias, _f32)), ptr(y), rows, fin, fout, ACT[act],
                              ptr(ws), ws.numel(), stream_ptr())
     return y
+
+
+def noisy_linear_fwd_rows(x, w_mu, w_sigma, b_mu, b_sigma, noise_in, noise_out_weight, noise_out_bias, act=None, out=None):
+    """noisy_linear_fwd for the rows <= 8 transitions of one agent step, row r under its own noise draw: noise_in [rows, in],
+    noise_out_weight / noise_out_bias [rows, out] -- dense, or three column slices of ONE [rows, numel] block (nets._NoiseBlock.
+    draw_rows).  Row r has the bits of noisy_linear_fwd(x[r:r + 1], ..., noise row r)."""
+    x, w_mu, w_sigma = _c(x, _f32), _c(w_mu, _f32), _c(w_sigma, _f32)
+    rows, fin = x.shape
+    fout = w_mu.shape[0]
+    if w_mu.shape != (fout, fin) or w_sigma.shape != (fout, fin) or b_mu.numel() != fout or b_sigma.numel() != fout \
+            or tuple(noise_in.shape) != (rows, fin) or tuple(noise_out_weight.shape) != (rows, fout) \
+            or tuple(noise_out_bias.shape) != (rows, fout):
+        raise DraError("noisy_linear_fwd_rows: shapes do not agree")
+    noise = (noise_in, noise_out_weight, noise_out_bias)
+    for e in noise:
+        _dev(e)
+        if e.dtype != _f32 or e.stride(1) != 1:
+            raise DraError("noisy_linear_fwd_rows: noise rows must be contiguous f32")
+    if all(e.is_contiguous() for e in noise):
+        stride = 0
+    else:
+        stride = noise_in.stride(0) if rows > 1 else max(fin, fout)
+        if rows > 1 and any(e.stride(0) != stride for e in noise):
+            raise DraError("noisy_linear_fwd_rows: the three noise blocks must share one row stride")
+    y = torch.empty((rows, fout), dtype=_f32, device=x.device) if out is None else out
+    lib.dra_noisy_linear_fwd_rows(ptr(x), ptr(w_mu), ptr(w_sigma), ptr(_c(b_mu, _f32)), ptr(_c(b_sigma, _f32)), ptr(noise_in),
+                                  ptr(noise_out_weight), ptr(noise_out_bias), int(stride), ptr(y), rows, fin, fout, ACT[act],
+                                  stream_ptr())
+    return y
+
+
+def rainbow_act_rows(value, advantage, atoms, want_q=False, action=None):
+    """Greedy actions of rows <= 8 Rainbow forwards in one launch: dueling combination, softmax over the atoms, expected value,
+    first maximum.  value [rows, Z], advantage [rows, A, Z], atoms [Z]; -> (action int64 [rows] -- `action` when given --, q [rows, A]
+    or None)."""
+    value, advantage, atoms = _c(value, _f32), _c(advantage, _f32), _c(atoms, _f32)
+    b, a, z = advantage.shape
+    if value.shape != (b, z) or atoms.numel() != z:
+        raise DraError("rainbow_act_rows: value %s / atoms %d do not fit advantage %s" % (tuple(value.shape), atoms.numel(),
+                                                                                         tuple(advantage.shape)))
+    if action is None:
+        action = torch.empty(b, dtype=torch.int64, device=value.device)
+    elif action.dtype != torch.int64 or action.numel() != b or not action.is_contiguous():
+        raise DraError("rainbow_act_rows: action must be a contiguous int64 tensor of %d elements" % b)
+    q = torch.empty((b, a), dtype=_f32, device=value.device) if want_q else None
+    lib.dra_rainbow_act_rows(ptr(value), ptr(advantage), ptr(atoms), b, a, z, ptr(_dev(action)), ptr(q), stream_ptr())
+    return action, q
 
 
 def noisy_linear_bwd(g, x, w_mu, w_sigma, noise_in, noise_out_weight, noise_out_bias, x_relu=False, want_dx=True, dw_mu=None,

@@ -41,6 +41,14 @@ int dra_ring_pointers(dra_ring* ring, void** frames, void** actions, void** rewa
 int dra_ring_put(dra_ring* ring, int64_t slot0, int64_t count, const void* frame_src, const void* action_src,
                  int64_t action_val, const double* reward_src, double reward_val, const int32_t* mask_src,
                  int32_t mask_val, void* stream);
+/* replay.py:75-90 for the `count` <= 8 transitions of ONE agent step of a device-resident actor (DQN_agent.py:103-113: one feed
+ * per transition).  The first slot is read from the device word slot0_dev (so that the launch replays from a captured graph) or,
+ * when slot0_dev is NULL, is slot0; slots wrap at the capacity.  Frame k lies frame_stride bytes behind frame k - 1 (the newest
+ * frame of each [history][frame] stack); actions i64 (action_bytes == 8), rewards f64, masks i32: device arrays of `count`.  A
+ * by-value slot outside [0, capacity) or a count outside [1, 8] is refused; a device word outside the ring writes nothing. */
+int dra_ring_put_rows(dra_ring* ring, const int64_t* slot0_dev, int64_t slot0, int count, const void* frame_src,
+                      int64_t frame_stride, const int64_t* action_src, const double* reward_src, const int32_t* mask_src,
+                      void* stream);
 /* replay.py:75-90 from pageable HOST memory (staged through the handle's pinned buffer). */
 int dra_ring_put_host(dra_ring* ring, int64_t slot, const void* frame_host, const void* action_host, double reward,
                       int32_t mask, void* stream);
@@ -269,6 +277,19 @@ int dra_noisy_workspace_floats(int rows, int in_features, int out_features, int6
 int dra_noisy_linear_fwd(const float* x, const float* w_mu, const float* w_sigma, const float* b_mu, const float* b_sigma,
                          const float* noise_in, const float* noise_out_weight, const float* noise_out_bias, float* y, int rows,
                          int in_features, int out_features, int act, float* workspace, int64_t workspace_floats, void* stream);
+/* DQN_agent.py:26-33 for the `rows` <= 8 transitions of one agent step: reset_noise() runs before each forward, the parameters
+ * are the same, so row r of x goes through the layer under ITS OWN draw: noise_in [rows][in], noise_out_weight / noise_out_bias
+ * [rows][out], rows noise_stride floats apart (0: dense).  One pass over w_mu / w_sigma serves every row; row r has the bits of
+ * dra_noisy_linear_fwd(rows = 1) on row r with row r's noise. */
+int dra_noisy_linear_fwd_rows(const float* x, const float* w_mu, const float* w_sigma, const float* b_mu, const float* b_sigma,
+                              const float* noise_in, const float* noise_out_weight, const float* noise_out_bias,
+                              int64_t noise_stride, float* y, int rows, int in_features, int out_features, int act, void* stream);
+/* network_heads.py:79-86 + CategoricalDQN_agent.py:21-24 + torch_utils.py:51-58 at epsilon = 0 (DQN_agent.py:34-35), per row:
+ * dueling combination (dra_dueling_atoms_fwd's expression), softmax over the atoms, q[a] = sum_z prob[a][z] atoms[z] (ascending z),
+ * action = first maximum of q (np.argmax).  value [rows][atoms], advantage [rows][actions][atoms], rows <= 8, actions and atoms
+ * <= 64; action i64 [rows]; q [rows][actions] or NULL. */
+int dra_rainbow_act_rows(const float* value, const float* advantage, const float* atoms, int rows, int n_actions, int n_atoms,
+                         int64_t* action, float* q, void* stream);
 /* backward of the same from g = dL/d(pre-activation) [rows][out]: dw_mu = g^T x, dw_sigma = dw_mu * weight_epsilon (one contraction,
  * two stores), db_mu = sum_rows g, db_sigma = db_mu * f(noise_out_bias), dx = g w_mu + ((g * f(noise_out_weight)) w_sigma) *
  * f(noise_in), plus dx_add [rows][in] when given (the input gradient of another head on the same features), times [x_relu > 0]

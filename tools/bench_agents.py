@@ -225,6 +225,8 @@ CASES = {
     "c51_pixel_per": lambda: dqn_family("c51", d.PrioritizedReplay),
     "qr_dqn_pixel_uniform": lambda: dqn_family("qr", d.UniformReplay),
     "rainbow_pixel_per": lambda: dqn_family("rainbow", d.PrioritizedReplay),      # noisy layers on csrc/noisy.hip, captured actor forward + PER update
+    # environment, actor forward (batch 4, one noise draw per row), argmax and ring feed on the device: deeprl_amd/noisy_actor.py
+    "rainbow_pixel_per_device": lambda: dqn_family("rainbow", d.PrioritizedReplay, device=True, device_noisy_actor=True),
     "rainbow_pixel_per_modules": lambda: dqn_family("rainbow", d.PrioritizedReplay, fused_noisy=False, graph_update=False),
     "dqn_pixel_per_device": lambda: dqn_family("dqn", d.PrioritizedReplay, device=True),
     "dqn_pixel_per_device_sync": lambda: dqn_family("dqn", d.PrioritizedReplay, device=True, async_actor=False),
