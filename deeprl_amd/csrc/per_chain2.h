@@ -243,6 +243,17 @@ __device__ __forceinline__ void per_chain2_body(const PerChain2Args& a, char* sm
             chain_node_store(tree + node, __dadd_rn(chain_node_load(tree + node), change));
           }
         }
+        // the adds too as the reference's walk (add is update, sum_tree.py:39-60): after an ordered round outside the
+        // exactness regime the heap is not left + right everywhere, and a recomputed ancestor would leave its values
+        for (int k = 0; k < add_n; ++k) {
+          int64_t node = (write0 + k) % capacity + capacity - 1;
+          const double change = __dsub_rn(s_max, chain_node_load(tree + node));
+          chain_node_store(tree + node, s_max);
+          while (node > 0) {
+            node = (node - 1) >> 1;
+            chain_node_store(tree + node, __dadd_rn(chain_node_load(tree + node), change));
+          }
+        }
       }
       __threadfence_block();
     } else {
@@ -262,9 +273,9 @@ __device__ __forceinline__ void per_chain2_body(const PerChain2Args& a, char* sm
       }
     }
     __syncthreads();
-    // adds of the next agent step's transitions at max_priority
+    // adds of the next agent step's transitions at max_priority (exact regime: recomputed sums are the walk's sums)
     int64_t node = -1;
-    if (tid < add_n) {
+    if (!s_ordered && tid < add_n) {
       node = (write0 + tid) % capacity + capacity - 1;
       chain_node_store(tree + node, s_max);
     }

@@ -112,11 +112,12 @@ ring_put_kernel(uint8_t* __restrict__ frames, uint8_t* __restrict__ actions, dou
   } else {
     for (int64_t i = threadIdx.x; i < frame_bytes; i += blockDim.x) dst[i] = src[i];
   }
-  if (threadIdx.x < action_bytes) {
+  // (an action record may be longer than the workgroup: dra_ring_create takes any action_bytes > 0)
+  for (int64_t t = threadIdx.x; t < action_bytes; t += blockDim.x) {
     uint8_t v;
-    if (asrc) v = asrc[k * action_bytes + threadIdx.x];
-    else v = (threadIdx.x < 8) ? (uint8_t)((uint64_t)action_val >> (8 * threadIdx.x)) : 0;
-    actions[slot * action_bytes + threadIdx.x] = v;
+    if (asrc) v = asrc[k * action_bytes + t];
+    else v = (t < 8) ? (uint8_t)((uint64_t)action_val >> (8 * t)) : 0;
+    actions[slot * action_bytes + t] = v;
   }
   if (threadIdx.x == 0) {
     rewards[slot] = rsrc ? rsrc[k] : reward_val;
@@ -315,8 +316,9 @@ ring_gather_kernel(const uint8_t* __restrict__ frames, const uint8_t* __restrict
     }
   }
   if (j == 0) {
-    if (out_action && threadIdx.x < action_bytes)
-      out_action[(int64_t)b * action_bytes + threadIdx.x] = actions[i * action_bytes + threadIdx.x];
+    if (out_action)
+      for (int64_t t = threadIdx.x; t < action_bytes; t += blockDim.x)
+        out_action[(int64_t)b * action_bytes + t] = actions[i * action_bytes + t];
     if (threadIdx.x == 0) {
       double cum_r = 0.0;
       int32_t cum_m = 1;

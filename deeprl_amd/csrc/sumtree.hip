@@ -12,6 +12,11 @@
 //             node sum is exact, hence identical to the reference's incremental `+= change`.
 //   ordered   one lane replays the reference's `tree[parent] += change` walk update by update;
 //             bit-identical for ANY fp64 priorities, ~50x slower (dependent L2 round trips).
+// Adds (set / set_from / set_many_from, the add step of per_chain2) follow the reference's own delta walk --
+// add is update: tree[ancestor] += (p - old), sum_tree.py:39-60 -- wherever the ordered walk is or would be chosen: once an
+// ordered round has run outside the exactness regime the heap is no longer left + right everywhere, and an add that
+// recomputed its ancestors from their children would leave the reference's values.  Inside the regime both forms are
+// bit-identical, so the single-leaf adds always take the delta walk; set_many_from decides from `stat` as the commit does.
 // pending_idx gating, first-writer-wins de-duplication and max_priority live on the host
 // mirror (deeprl_amd/component/replay.py), which passes only the effective updates.
 #include "common.h"
@@ -117,21 +122,20 @@ DRA_API int dra_sumtree_update(dra_sumtree* t, const int64_t* leaf_idx_dev, cons
   return DRA_OK;
 }
 
-// Single-leaf variant with by-value arguments (PrioritizedReplay.feed -> SumTree.add, sum_tree.py:39-51):
-// one wave walks leaf -> root recomputing each ancestor from its children.
+// Single-leaf variant with by-value arguments (PrioritizedReplay.feed -> SumTree.add, sum_tree.py:39-51): one lane walks
+// leaf -> root adding (prio - old leaf) to every ancestor, the reference's own arithmetic for ANY tree contents.
+__device__ __forceinline__ void sumtree_delta_walk(double* __restrict__ tree, int64_t node, double p) {
+  const double change = __dsub_rn(p, tree[node]);
+  tree[node] = p;
+  while (node > 0) {
+    node = (node - 1) >> 1;
+    tree[node] = __dadd_rn(tree[node], change);
+  }
+}
+
 __global__ void sumtree_set_kernel(double* __restrict__ tree, int64_t leaf, double prio) {
   if (threadIdx.x != 0) return;
-  int64_t node = leaf;
-  tree[node] = prio;
-  double below = prio;
-  while (node > 0) {
-    const int64_t parent = (node - 1) >> 1;
-    const int64_t sib = (node & 1) ? node + 1 : node - 1;  // odd index = left child
-    const double s = (node & 1) ? __dadd_rn(below, tree[sib]) : __dadd_rn(tree[sib], below);
-    tree[parent] = s;
-    below = s;
-    node = parent;
-  }
+  sumtree_delta_walk(tree, leaf, prio);
 }
 
 DRA_API int dra_sumtree_set(dra_sumtree* t, int64_t leaf_idx, double prio, void* stream) {
@@ -145,18 +149,7 @@ DRA_API int dra_sumtree_set(dra_sumtree* t, int64_t leaf_idx, double prio, void*
 // replay.py:161; the running maximum lives in stat_dev[0] once the priorities are written back on device)
 __global__ void sumtree_set_from_kernel(double* __restrict__ tree, int64_t leaf, const double* __restrict__ prio) {
   if (threadIdx.x != 0) return;
-  int64_t node = leaf;
-  const double p = *prio;
-  tree[node] = p;
-  double below = p;
-  while (node > 0) {
-    const int64_t parent = (node - 1) >> 1;
-    const int64_t sib = (node & 1) ? node + 1 : node - 1;
-    const double s = (node & 1) ? __dadd_rn(below, tree[sib]) : __dadd_rn(tree[sib], below);
-    tree[parent] = s;
-    below = s;
-    node = parent;
-  }
+  sumtree_delta_walk(tree, leaf, *prio);
 }
 
 DRA_API int dra_sumtree_set_from(dra_sumtree* t, int64_t leaf_idx, const double* prio_dev, void* stream) {
@@ -167,12 +160,25 @@ DRA_API int dra_sumtree_set_from(dra_sumtree* t, int64_t leaf_idx, const double*
 }
 
 // n consecutive adds (write cursor write0, write0+1, ... mod capacity) at the SAME device-resident priority: what
-// PrioritizedReplay.feed does for the n transitions a device producer wrote in one agent step.  One lane per leaf,
-// ancestors recomputed level by level as in sumtree_update_parallel_kernel (one walk of `levels` barriers instead of n
-// dependent leaf-to-root walks of ~20 L2 round trips each).
+// PrioritizedReplay.feed does for the n transitions a device producer wrote in one agent step.  Inside the exactness regime
+// (stat = {max_priority, smallest priority offered}, the bound sumtree_commit_kernel checks): one lane per leaf, ancestors
+// recomputed level by level as in sumtree_update_parallel_kernel (one walk of `levels` barriers instead of n dependent
+// leaf-to-root walks of ~20 L2 round trips each).  Outside it -- or without a stat to tell -- one lane replays the
+// reference's n delta walks in its order.
 __global__ void __launch_bounds__(64)
 sumtree_set_many_from_kernel(double* __restrict__ tree, int levels, int64_t capacity, int64_t write0, int n,
-                             const double* __restrict__ prio) {
+                             const double* __restrict__ prio, const double* __restrict__ stat) {
+  int ordered = 1;                                 // (uniform: every lane reads the same two words)
+  if (stat) {
+    const double hi = fmax(stat[0], *prio), lo = fmin(stat[1], *prio);
+    ordered = !(lo > 0.0) || !(hi < INFINITY) || (double)capacity * hi > ldexp(1.0, 53 + ilogb(lo) - 23);
+  }
+  if (ordered) {
+    if (threadIdx.x != 0) return;
+    const double p = *prio;
+    for (int k = 0; k < n; ++k) sumtree_delta_walk(tree, (write0 + k) % capacity + capacity - 1, p);
+    return;
+  }
   int64_t node = -1;
   if ((int)threadIdx.x < n) {
     node = (write0 + threadIdx.x) % capacity + capacity - 1;
@@ -189,10 +195,11 @@ sumtree_set_many_from_kernel(double* __restrict__ tree, int levels, int64_t capa
   }
 }
 
-DRA_API int dra_sumtree_set_many_from(dra_sumtree* t, int64_t write0, int n, const double* prio_dev, void* stream) {
+DRA_API int dra_sumtree_set_many_from(dra_sumtree* t, int64_t write0, int n, const double* prio_dev, const double* stat_dev,
+                                      void* stream) {
   if (!t || !prio_dev || write0 < 0 || write0 >= t->capacity || n < 1 || n > 64 || n > t->capacity) return DRA_EINVAL;
   hipLaunchKernelGGL(sumtree_set_many_from_kernel, dim3(1), dim3(64), 0, dra_stream(stream), t->tree, t->levels, t->capacity,
-                     write0, n, prio_dev);
+                     write0, n, prio_dev, stat_dev);
   DRA_LAUNCH_CHECK();
   return DRA_OK;
 }

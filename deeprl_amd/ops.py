@@ -184,9 +184,11 @@ class SumTree:
         """set() with the priority read from device memory (f64 tensor, first element)."""
         lib.dra_sumtree_set_from(self.h, int(leaf_idx), ptr(prio_dev), stream_ptr())
 
-    def set_many_from(self, write0, n, prio_dev, stream=None):
-        """n consecutive adds at write cursor write0.. (mod capacity), all at the device-resident priority prio_dev[0]."""
-        lib.dra_sumtree_set_many_from(self.h, int(write0), int(n), ptr(prio_dev), stream_ptr(stream))
+    def set_many_from(self, write0, n, prio_dev, stat=None, stream=None):
+        """n consecutive adds at write cursor write0.. (mod capacity), all at the device-resident priority prio_dev[0].  stat:
+        commit_f32's f64[2] {running max, running min}; inside its exactness bound the adds run level-parallel, outside it (or
+        without a stat) as the reference's delta walks one after another."""
+        lib.dra_sumtree_set_many_from(self.h, int(write0), int(n), ptr(prio_dev), ptr(stat), stream_ptr(stream))
 
     def sample_into(self, u, out_idx, out_p, out_total, stream=None):
         """sample() into caller-provided buffers (e.g. pinned host memory the kernel writes directly; `u` may be pinned too)."""

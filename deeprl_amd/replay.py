@@ -461,7 +461,7 @@ class PrioritizedReplay(UniformReplay):
         for i in range(n):
             self._pending.discard((self._write + i) % self.memory_size + self.memory_size - 1)
         with self._on_device():
-            self.tree.set_many_from(self._write, n, self._stat, stream=stream)   # one launch for the whole agent step's adds
+            self.tree.set_many_from(self._write, n, self._stat, stat=self._stat, stream=stream)   # one launch for the whole agent step's adds
         self._write = (self._write + n) % self.memory_size
 
     def draw_begin(self, batch_size=None, stream=None):

@@ -85,8 +85,11 @@ int dra_sumtree_update(dra_sumtree* tree, const int64_t* leaf_idx_dev, const dou
                        void* stream);
 int dra_sumtree_set(dra_sumtree* tree, int64_t leaf_idx, double prio, void* stream); /* sum_tree.py:39-51 (add) */
 int dra_sumtree_set_from(dra_sumtree* tree, int64_t leaf_idx, const double* prio_dev, void* stream); /* same, *prio_dev */
-/* n (<= 64) consecutive adds at write cursor write0, write0+1, ... (mod capacity), all at *prio_dev */
-int dra_sumtree_set_many_from(dra_sumtree* tree, int64_t write0, int n, const double* prio_dev, void* stream);
+/* n (<= 64) consecutive adds at write cursor write0, write0+1, ... (mod capacity), all at *prio_dev.  stat_dev = the
+ * {max_priority, smallest priority offered} pair dra_sumtree_commit_f32 keeps: inside its exactness bound the adds run
+ * level-parallel, outside it (or with stat_dev null) as the reference's n delta walks in order: bit-identical always. */
+int dra_sumtree_set_many_from(dra_sumtree* tree, int64_t write0, int n, const double* prio_dev, const double* stat_dev,
+                              void* stream);
 /* replay.py:193-196 with the new priorities still on the device: leaf_idx_dev[i] <- f64(prio_f32_dev[pos_dev[i]]), i < n
  * (the host picks the pending, first-occurrence entries); stat_dev = {max_priority, smallest priority offered} is kept
  * over all `batch` offered values.  Falls back by itself to the reference's ordered walk when the level-parallel update

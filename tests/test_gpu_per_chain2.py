@@ -15,6 +15,7 @@ import torch
 pytestmark = pytest.mark.gpu
 
 from oracle.sumtree_oracle import SumTreeOracle  # noqa: E402
+from replay_edge_cases import mt_words, valid_index as _valid  # noqa: E402  (shared with tests/test_gpu_replay_edges.py)
 
 
 @pytest.fixture(scope="module")
@@ -24,10 +25,6 @@ def dra():
     import deeprl_amd as d
     d.select_device(0)
     return d
-
-
-def _valid(di, pos, size, h, n):       # replay.py:122-127
-    return (di - h + 1 >= 0 and di + n < pos) or (di - h + 1 >= pos and di + n < size)
 
 
 @pytest.mark.parametrize("cap,batch,add_n,ordered", [(300, 32, 4, 0), (4096, 32, 4, 0), (100003, 64, 8, 0), (300, 32, 4, 1),
@@ -81,10 +78,8 @@ def test_per_chain2_kernel_equals_oracle(dra, cap, batch, add_n, ordered):
     lib.dra_sumtree_per_chain2_state_set(ctypes.c_void_p(state.data_ptr()), 0, 0,
                                          np.asarray(cur_idx, dtype=np.int64).ctypes.data_as(ctypes.c_void_p), batch)
     # the word ring: the generator's next outputs, exactly as replay.DeviceDraw produces them
-    st0 = random.getstate()
     n_words = 40000
-    words[:n_words] = np.frombuffer(random.getrandbits(32 * n_words).to_bytes(4 * n_words, "little"), dtype="<u4")
-    random.setstate(st0)
+    words[:n_words] = mt_words(n_words)
     consumed = 0
     write = orc.write
     beta = 0.4
