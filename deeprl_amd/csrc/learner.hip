@@ -277,6 +277,10 @@ struct dra_dqn_learner {
   int late_nprior;                  // partials written before the optimizer launch
   int late_nfold;                   // fold workgroups of the optimizer launch (their partial slots double as arrival flags)
   bool captured;                    // some graph has been captured (the decision above is baked into it)
+  // dra_dqn_learner_path_flags (read-only, for checkers): what the most recently issued or captured head launch of the VanillaNet
+  // update was, how many were issued, and whether the last prioritized one-graph capture let the draw ride in the backward launches
+  int q_head_chain, q_head_pf, q_per2_ride;
+  int64_t q_head_launches;
 };
 
 struct HeadSpec;
@@ -1568,6 +1572,7 @@ static int run_body(dra_dqn_learner* l, hipStream_t st, int per, float beta, int
     const bool pf = (l->variant & DRA_VAR_ONESHOT_DGRAD) && B % 8 == 0 && B <= 32 && dra_xcd_order_enabled();
     const float* pf_w4 = pf ? P + o[P_W4] : nullptr;
     const int hb = B + (pf ? 3136 / 32 : 0);
+    l->q_head_chain = head_chain ? 1 : 0; l->q_head_pf = (!head_chain && pf) ? 1 : 0; l->q_head_launches++;
     if (head_chain) {
       HeadArgs ha;
       ha.slabs = l->fc4_slabs; ha.nz = nz; ha.B = B; ha.A = A; ha.b4_on = P + o[P_B4]; ha.b4_tg = T + o[P_B4]; ha.wh_on = P + o[P_WH];
@@ -1842,6 +1847,7 @@ static int capture_per2(dra_dqn_learner* l, hipStream_t st, int q, bool rd, hipG
   const int both = DRA_VAR_ONESHOT_WGRAD | DRA_VAR_ONESHOT_DGRAD;
   l->per2_ride = l->c.batch <= 256 && (l->variant & both) == both;
   l->per2_split = l->per2_ride && l->late;
+  l->q_per2_ride = l->per2_ride ? 1 : 0;
   if (rc == DRA_OK && l->per2_ride)
     rc = dra_sumtree_per_chain2_args(l->per_tree, l->per2_io[q & 3], l->delta, l->c.replay_eps, l->c.replay_alpha, l->prio,
                                      l->per_stat, l->per2_dev, l->per2_words, l->per2_idx + (size_t)((q + 1) & 3) * 1024,
@@ -3852,6 +3858,14 @@ DRA_API int dra_dqn_learner_ahead_stats(dra_dqn_learner* l, int64_t* out) {
   if (!l || !out) return DRA_EINVAL;
   for (int i = 0; i < 4; ++i) out[i] = l->ah_stat[i];
   out[4] = l->ah ? 1 : 0;
+  return DRA_OK;
+}
+
+DRA_API int dra_dqn_learner_path_flags(dra_dqn_learner* l, int64_t* out) {
+  if (!l || !out) return DRA_EINVAL;
+  const int64_t v[12] = {l->late, l->defer, l->fchain, l->bchain, l->fs, l->ah, l->q_per2_ride, l->q_head_chain, l->q_head_pf,
+                         l->q_head_launches, (int64_t)l->variant, (l->timeout_flag && *l->timeout_flag) ? 1 : 0};
+  for (int i = 0; i < 12; ++i) out[i] = v[i];
   return DRA_OK;
 }
 

@@ -434,6 +434,18 @@ class DQNLearner:
                                      "update_launches": out[6] / n / 1e3, "actor_launch": out[7] / n / 1e3,
                                      "whole_call": out[8] / n / 1e3}}
 
+    def path_flags(self):
+        """The code paths this learner resolved (dra_dqn_learner_path_flags; read-only, for checkers): `late`, `defer`, `fchain`,
+        `bchain`, `fs`, `ah` as decided at creation; `per2_ride`, `head_chain`, `head_pf` as of the last launch issued or captured;
+        `head_launches` VanillaNet head launches issued or captured so far; `variant` the resolved DRA_VAR_* mask; `timed_out` a
+        bounded device-side wait gave up (what the next step / update reports as DRA_ETIMEDOUT)."""
+        out = (ctypes.c_int64 * 12)()
+        lib.dra_dqn_learner_path_flags(self.h, out)
+        keys = ("late", "defer", "fchain", "bchain", "fs", "ah", "per2_ride", "head_chain", "head_pf")
+        res = {k: bool(out[i]) for i, k in enumerate(keys)}
+        res["head_launches"], res["variant"], res["timed_out"] = int(out[9]), int(out[10]), bool(out[11])
+        return res
+
     def invalidate_actor_copy(self):
         """The parameters were changed from outside (checkpoint load): the async actor's copies are reseeded on the next step."""
         lib.dra_dqn_learner_invalidate_actor_copy(self.h)

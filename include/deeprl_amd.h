@@ -779,6 +779,14 @@ int dra_dqn_learner_ahead_stats(dra_dqn_learner* learner, int64_t* out);
  * out[4..8] host nanoseconds inside those calls: pacing wait + hazard checks, index staging (+ the tagged copy command), the update's
  * launches, the actor launch, the whole call; out[9..11] reserved (0). */
 int dra_dqn_learner_lane_stats(dra_dqn_learner* learner, int64_t* out);
+/* Read-only, for checkers: the code paths this learner resolved, out[12].  Decided at creation: out[0] late fold (no gradient-norm
+ * launch), out[1] deferred fc4 step, out[2] chained conv forward, out[3] chained conv backward, out[4] event-free lane, out[5]
+ * target-ahead (after dra_dqn_learner_set_ahead_stream).  As of the last launch issued or captured: out[6] the prioritized draw
+ * rode in the backward launches, out[7] the VanillaNet head launch was the chained one (head + fc4 backward roles), out[8] it
+ * carried the spare workgroups that prefetch fc4's weights, out[9] VanillaNet head launches issued or captured since creation;
+ * out[10] the resolved DRA_VAR_* mask; out[11] 1 once a bounded device-side wait gave up (every later step / update returns
+ * DRA_ETIMEDOUT).  Changes nothing an update does. */
+int dra_dqn_learner_path_flags(dra_dqn_learner* learner, int64_t* out);
 
 /* HIP stream restricted to the compute units whose bit is set in cu_mask (n_words x 32 bits): the async agent step
  * gives the actor chain and the update chain disjoint CU partitions (DRA_VAR_CU_PARTITION, host side). */

@@ -48,14 +48,17 @@ class AsyncDqnScheduleOracle:
 
     def __init__(self, params, target_params, cap, batch, seed, n_actions=4, epsilon=0.01, done_period=800, gamma=0.99,
                  clip=5.0, lr=0.00025, alpha=0.95, eps=0.01, double_q=False, head="vanilla", n_atoms=51, v_min=-10.0,
-                 v_max=10.0, betas=(0.9, 0.999)):
+                 v_max=10.0, betas=(0.9, 0.999), dtype=torch.float32):
+        """dtype=torch.float64: the same schedule with every tensor (parameters, observations, rewards, optimizer state) widened
+        from its float32 value to float64 -- the high-precision reference of the edge-shape suite (tests/learner_edge_cases.py)."""
+        self.dtype = dtype
         torch.set_num_threads(max(1, min(8, torch.get_num_threads())))
         self.head, self.n_atoms, self.v_min, self.v_max, self.betas = head, int(n_atoms), float(v_min), float(v_max), betas
         self.opt_step = 0
         if head == "c51":     # np.linspace in fp64, then fp32 (CategoricalDQN_agent.py:33, tensor())
-            self.atoms = torch.tensor(np.linspace(v_min, v_max, n_atoms), dtype=torch.float32)
-        self.p = {k: torch.tensor(v, requires_grad=True) for k, v in params.items()}
-        self.pt = {k: torch.tensor(v) for k, v in target_params.items()}
+            self.atoms = torch.tensor(np.linspace(v_min, v_max, n_atoms), dtype=torch.float32).to(dtype)
+        self.p = {k: torch.tensor(v).to(dtype).requires_grad_(True) for k, v in params.items()}
+        self.pt = {k: torch.tensor(v).to(dtype) for k, v in target_params.items()}
         self.names = list(self.p)
         self.sq = {k: torch.zeros_like(v) for k, v in self.p.items()}
         self.ga = {k: torch.zeros_like(v) for k, v in self.p.items()}
@@ -78,8 +81,8 @@ class AsyncDqnScheduleOracle:
         with torch.no_grad():
             for k in self.names:
                 self.p[k].copy_(state["params"][k])
-                self.sq[k] = state["square_avg"][k].clone()      # (Adam heads: exp_avg / exp_avg_sq under the same keys)
-                self.ga[k] = state["grad_avg"][k].clone()
+                self.sq[k] = state["square_avg"][k].to(self.dtype).clone()      # (Adam heads: exp_avg / exp_avg_sq under the same keys)
+                self.ga[k] = state["grad_avg"][k].to(self.dtype).clone()
 
     def _snapshot(self):
         return {k: v.detach().clone() for k, v in self.p.items()}
@@ -97,18 +100,19 @@ class AsyncDqnScheduleOracle:
             slot = rep.pos
             # the observation the actor acts on: the 3 newest ring frames + the new frame
             stack = np.stack([rep.state[(slot - 3 + j) % self.cap] for j in range(3)] + [frame[0].reshape(84, 84)])
-            x = torch.from_numpy(NUM.image_normalize_sync(stack[None]))
+            x = torch.from_numpy(NUM.image_normalize_sync(stack[None])).to(self.dtype)
             with torch.no_grad():
                 q = self._action_values(theta, N.nature_conv_body(theta, x)).numpy()[0]
             greedy = int(np.argmax(q))
             srt = np.sort(q)
+            gap = float(srt[-1] - srt[-2]) if q.size > 1 else float("inf")      # (one action: nothing to tie with)
             action = ra if dice < self.epsilon else greedy
             if not (dice < self.epsilon):
-                self.q_gaps.append(float(srt[-1] - srt[-2]))
+                self.q_gaps.append(gap)
             stored = action if override_actions is None else int(override_actions[e])
             rep.feed_one(frame[0].reshape(84, 84), np.int64(stored), rew[0], msk[0])
             self.counter += 1
-            out.append((action, float(srt[-1] - srt[-2]), dice < self.epsilon))
+            out.append((action, gap, dice < self.epsilon))
             self.actions.append(action)
         return out
 
@@ -130,9 +134,10 @@ class AsyncDqnScheduleOracle:
         """One update of a distributional head: per-sample loss vector, its (importance-weighted) mean, clipped gradients, Adam."""
         st, ac, rw, ns, mk = batch
         p, pt = self.p, self.pt
-        x = torch.from_numpy(NUM.image_normalize_sync(st))
-        xn = torch.from_numpy(NUM.image_normalize_sync(ns))
-        a_t, r_t, m_t = torch.from_numpy(ac), torch.from_numpy(rw.astype(np.float32)), torch.from_numpy(mk.astype(np.float32))
+        x = torch.from_numpy(NUM.image_normalize_sync(st)).to(self.dtype)
+        xn = torch.from_numpy(NUM.image_normalize_sync(ns)).to(self.dtype)
+        a_t = torch.from_numpy(ac)
+        r_t, m_t = torch.from_numpy(rw.astype(np.float32)).to(self.dtype), torch.from_numpy(mk.astype(np.float32)).to(self.dtype)
         phi, self.relu_margin = N.nature_conv_body_margin(p, x)
         if self.head == "c51":
             with torch.no_grad():
@@ -167,15 +172,15 @@ class AsyncDqnScheduleOracle:
             return self._update_dist(batch, weights)
         st, ac, rw, ns, mk = batch
         p, pt = self.p, self.pt
-        x = torch.from_numpy(NUM.image_normalize_sync(st))
-        xn = torch.from_numpy(NUM.image_normalize_sync(ns))
+        x = torch.from_numpy(NUM.image_normalize_sync(st)).to(self.dtype)
+        xn = torch.from_numpy(NUM.image_normalize_sync(ns)).to(self.dtype)
         with torch.no_grad():
             qn = N.vanilla_head(pt, N.nature_conv_body(pt, xn))
             qno = N.vanilla_head(p, N.nature_conv_body(p, xn)) if self.double_q else None
         phi, self.relu_margin = N.nature_conv_body_margin(p, x)    # smallest |ReLU input| of the differentiated forward
         q = N.vanilla_head(p, phi)
-        delta = L.dqn_td_error(q, qn, torch.from_numpy(ac), torch.from_numpy(rw.astype(np.float32)),
-                               torch.from_numpy(mk.astype(np.float32)), self.gamma, q_next_online=qno)
+        delta = L.dqn_td_error(q, qn, torch.from_numpy(ac), torch.from_numpy(rw.astype(np.float32)).to(self.dtype),
+                               torch.from_numpy(mk.astype(np.float32)).to(self.dtype), self.gamma, q_next_online=qno)
         # PER: the importance weights multiply the TD-error VECTOR compute_loss returns (DQN_agent.py:98-99,126), and
         # reduce_loss squares afterwards (:78-79): mean(0.5 * (delta * w)^2)
         loss = L.dqn_reduce(delta) if weights is None else L.dqn_reduce(delta.mul(weights))

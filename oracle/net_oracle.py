@@ -115,8 +115,9 @@ def clip_grad_norm(grads, max_norm):
     over all grads (per-tensor 2-norms, then the 2-norm of those, as torch does);
     scale by max_norm/(norm+1e-6) when that is < 1.  Returns the norm and the scaled
     grads.  fp32 summation order differs between torch versions / thread counts, so
-    callers compare the norm at 5e-5 relative."""
-    total = torch.linalg.vector_norm(torch.stack([torch.linalg.vector_norm(g.detach().float()) for g in grads]))
+    callers compare the norm at 5e-5 relative.  (float64 gradients keep their width: the float64 references.)"""
+    wide = all(g.dtype == torch.float64 for g in grads)
+    total = torch.linalg.vector_norm(torch.stack([torch.linalg.vector_norm(g.detach() if wide else g.detach().float()) for g in grads]))
     coef = max_norm / (total + 1e-6)
     if coef < 1:
         grads = [g * coef for g in grads]
