@@ -56,6 +56,47 @@ __device__ __forceinline__ float softplus_grad(float x) {
   const float z = expf(x);
   return z / (z + 1.f);
 }
+// fp64 helpers of the actor's once-per-step scale block (below): a dozen fused multiply-adds each where the library's log1p / exp /
+// log / division are some hundred instructions on the sequential chain.  Relative error < 1e-12, far inside what the block's float
+// results keep.
+__device__ __forceinline__ double rcp_f64(double x) {      // hardware seed, two Newton steps
+  double r = __builtin_amdgcn_rcp(x);
+  r = __builtin_fma(__builtin_fma(-x, r, 1.0), r, r);
+  return __builtin_fma(__builtin_fma(-x, r, 1.0), r, r);
+}
+__device__ __forceinline__ double log_f64(double x) {      // x = m 2^e, m in [0.75, 1.5): log m = 2 atanh(u), u = (m - 1) / (m + 1), |u| <= 0.2
+  int e = __builtin_amdgcn_frexp_exp(x);
+  double m = __builtin_amdgcn_frexp_mant(x);               // [0.5, 1)
+  if (m < 0.75) { m *= 2.0; e -= 1; }
+  const double u = (m - 1.0) * rcp_f64(m + 1.0), u2 = u * u;
+  double p = 1.0 / 17.0;
+  p = __builtin_fma(p, u2, 1.0 / 15.0);
+  p = __builtin_fma(p, u2, 1.0 / 13.0);
+  p = __builtin_fma(p, u2, 1.0 / 11.0);
+  p = __builtin_fma(p, u2, 1.0 / 9.0);
+  p = __builtin_fma(p, u2, 1.0 / 7.0);
+  p = __builtin_fma(p, u2, 1.0 / 5.0);
+  p = __builtin_fma(p, u2, 1.0 / 3.0);
+  p = __builtin_fma(p, u2, 1.0);
+  return __builtin_fma((double)e, 0.69314718055994530942, 2.0 * u * p);
+}
+__device__ __forceinline__ double exp_f64(double x) {      // x <= 20: 2^n e^r, |r| <= ln 2 / 2, Taylor to r^11
+  const double n = __builtin_rint(x * 1.4426950408889634074);
+  const double r = __builtin_fma(-n, 0.69314718055994530942, x);
+  double p = 1.0 / 39916800.0;
+  p = __builtin_fma(p, r, 1.0 / 3628800.0);
+  p = __builtin_fma(p, r, 1.0 / 362880.0);
+  p = __builtin_fma(p, r, 1.0 / 40320.0);
+  p = __builtin_fma(p, r, 1.0 / 5040.0);
+  p = __builtin_fma(p, r, 1.0 / 720.0);
+  p = __builtin_fma(p, r, 1.0 / 120.0);
+  p = __builtin_fma(p, r, 1.0 / 24.0);
+  p = __builtin_fma(p, r, 1.0 / 6.0);
+  p = __builtin_fma(p, r, 0.5);
+  p = __builtin_fma(p, r, 1.0);
+  p = __builtin_fma(p, r, 1.0);
+  return __builtin_amdgcn_ldexp(p, (int)n);
+}
 // batch row of contraction step s for lane group g in the weight-gradient contractions: a bijection (s < 4 MT, g < 4) -> rows
 // whose four rows per step lie 4 apart, so the 4 x 16-float reads of one ds_read_b32 fall on 4 distinct bank groups
 __device__ __forceinline__ int row_of(int s, int g) { return ((s >> 2) << 4) + (g << 2) + (s & 3); }
@@ -251,8 +292,7 @@ __device__ __forceinline__ void ppo_update_role(const dra_ppo_mlp_cfg& cfg, cons
   __syncthreads();
 
   int64_t applied = 0;
-  float sd = 1.f, log_sd = 0.f, std_raw = 0.f, inv_sd = 1.f, inv_var = 1.f;
-  bool std_dirty = true;
+  float lp_c = kLogSqrt2Pi, lp_c_lo = 0.f, std_raw = 0.f, inv_sd = 1.f, inv_var = 1.f;   // lp_c (+ lp_c_lo): log(scale) + log sqrt(2 pi)
   for (int q = 0; q < total; ++q) {
     const int kq = q % per_epoch;
     const int rows = min(MB, n - kq * MB);
@@ -373,14 +413,7 @@ __device__ __forceinline__ void ppo_update_role(const dra_ppo_mlp_cfg& cfg, cons
         else ret4[r] = sAux[row * kLd3 + kAuxRet];
       }
       const float b3 = sB3[c16];
-      if (ACTOR && std_dirty) {      // scale = softplus(std) and what the row loop needs of it, once per actor step
-        std_raw = sStd[c16];
-        sd = std_raw > 20.f ? std_raw : fast_log(1.f + fast_exp(std_raw));
-        log_sd = fast_log(sd);
-        inv_sd = __builtin_amdgcn_rcpf(sd);
-        inv_var = inv_sd * inv_sd;
-        std_dirty = false;
-      }
+      if (ACTOR) std_raw = sStd[c16];
       __builtin_amdgcn_sched_barrier(0);
       f32x4 acc = {0.f, 0.f, 0.f, 0.f}, acc_b = {0.f, 0.f, 0.f, 0.f};     // two chains: a dependent MFMA waits 40 cycles
 #pragma unroll
@@ -389,6 +422,20 @@ __device__ __forceinline__ void ppo_update_role(const dra_ppo_mlp_cfg& cfg, cons
         acc_b = MFMA16(av[tk][1], bv[tk][1], acc_b);
         acc = MFMA16(av[tk][2], bv[tk][2], acc);
         acc_b = MFMA16(av[tk][3], bv[tk][3], acc_b);
+      }
+      if (ACTOR) {      // scale = softplus(std) and what the row loop needs of it (branch-free; 0.3 us of a 10 us minibatch)
+        // In fp64, handed to the row loop as float pairs: log(scale) enters every row's log-probability, so an error in it does not
+        // average out over the rows.  v_log_f32's absolute error is an ulp of log2(scale) (3e-7 once |log2 scale| >= 4, and
+        // 1 + exp(std) loses exp(std)'s low bits below std = -2): with six dimensions of one std it stood as 2e-6 in approx_kl.
+        const double z = exp_f64(fmin((double)std_raw, 20.0));
+        const double sp = z < 1e-4 ? z * (1.0 - z * (0.5 - z * (1.0 / 3.0))) : log_f64(1.0 + z);     // (1 + z keeps 1e-16 / z of z)
+        const double sdd = std_raw > 20.f ? (double)std_raw : sp;
+        const double lcd = log_f64(sdd) + 0.91893853320467274178;
+        const double isd = rcp_f64(sdd);
+        lp_c = (float)lcd;
+        lp_c_lo = (float)(lcd - (double)lp_c);
+        inv_sd = (float)isd;
+        inv_var = (float)(isd * isd);
       }
       acc += acc_b;
       const bool col_ok = c16 < A;
@@ -402,7 +449,7 @@ __device__ __forceinline__ void ppo_update_role(const dra_ppo_mlp_cfg& cfg, cons
         if (ACTOR) {
           const float mean = fast_tanh(acc[r] + b3);
           const float diff = aux[r] - mean;
-          const float lpe = col_ok ? (-(diff * diff) * (0.5f * inv_var) - log_sd - kLogSqrt2Pi) : 0.f;
+          const float lpe = col_ok ? ((-(diff * diff) * (0.5f * inv_var) - lp_c) - lp_c_lo) : 0.f;
           const float lp = group16_sum(lpe);
           // losses.hip ppo_loss_kernel's arithmetic (PPO_agent.py:78-86), row by row
           const float ratio = fast_exp(lp - lp_old[r]);
@@ -544,7 +591,9 @@ __device__ __forceinline__ void ppo_update_role(const dra_ppo_mlp_cfg& cfg, cons
         if (dump) {
 #pragma unroll
           for (int r = 0; r < 4; ++r) dbg[kDbgW3 + c16 * 64 + 16 * w + 4 * g + r] = gw3[r];
-          if (w == 0 && g == 0) { dbg[kDbgB3 + c16] = gb3; dbg[kDbgStd + c16] = gstd; }
+          // (lanes c16 >= A hold the entropy term of a std that does not exist -- softplus(0) of the zero padding; Adam never
+          // sees it, and the dump shows padded positions as zero)
+          if (w == 0 && g == 0) { dbg[kDbgB3 + c16] = gb3; dbg[kDbgStd + c16] = c16 < A ? gstd : 0.f; }
         }
       }
       stamp(7);
@@ -704,7 +753,6 @@ __device__ __forceinline__ void ppo_update_role(const dra_ppo_mlp_cfg& cfg, cons
         adam_elem(b1p, gb1, b1m, b1v, ad);
       }
       ++applied;
-      std_dirty = true;
     }
     stamp(12);
     __syncthreads();          // the next image, the published weights and every read of this minibatch's buffers are complete
