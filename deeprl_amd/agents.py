@@ -21,6 +21,7 @@ Differences that are the point of the rewrite (results unchanged):
     the IS-weight / priority kernel and runs the chain eagerly) and one C call per actor forward;
     `config.fused_learner = False` keeps the generic autograd path.
 """
+import collections
 import pickle
 import os
 
@@ -1406,25 +1407,116 @@ class A2CAgent(BaseAgent):
                 self.states = None
                 self.network.fused_gauss_head = True
                 self._mlp_rollout = a2c_mlp.Rollout(self, shape)
+        self._cat_rollout, self._cat_sig, self._cat_steps = None, None, 0
+        self._ep_anchor, self._ep_log = None, collections.deque(maxlen=16384)
+        from .device_env import DeviceCartPoleVec
+        if DeviceCartPoleVec.eligible(self.task, config):
+            # cart-pole environments under CategoricalActorCriticNet over a small FCBody (a2c_feature, examples.py:340-358): the
+            # environments move to the device, a rollout is one launch (csrc/cat_mlp.hip), episode ends come back through the
+            # device's episode ring (_step_device_cat)
+            from . import cat_mlp
+            why = cat_mlp.why_not(self)
+            if why is None:
+                self.task = DeviceCartPoleVec(self.task)
+                self.states = None
+                if self.dp.step_dev is None:      # the rank-invariant sampler's position: the kernel reads and advances it
+                    self.dp.step_dev = torch.zeros(1, dtype=torch.int64, device=Config.DEVICE)
+                self._sampler_host = int(self.dp.step_dev.item())
+                self._cat_rollout = cat_mlp.Rollout(self, cat_mlp.shape(self.network))
+            elif getattr(config, 'fused_a2c_cat', True) is not False:
+                getattr(self.logger, 'warning', self.logger.info)(
+                    'the cart-pole environments stay on the host and this agent keeps the module path: %s' % why)
 
     def close(self):
+        self.drain_episodes()
         close_obj(self.task)
         self.dp.close()
 
+    def eval_episodes(self):
+        self.drain_episodes()
+        return BaseAgent.eval_episodes(self)
+
     def save(self, filename):
-        """The reference's two files (BaseAgent.py:24-27); on the device rollout path also `<filename>.sampler`: seed and position
-        of the counter-hash action noise (as PPOAgent.save)."""
+        """The reference's two files (BaseAgent.py:24-27); on the device rollout paths also `<filename>.sampler`: seed and position
+        of the counter-hash action noise (as PPOAgent.save) and, over DeviceCartPoleVec, the environments' arrays (state, counters,
+        episode steps, returns, the episode ring), so that a loaded run continues bit for bit."""
+        self.drain_episodes()
         BaseAgent.save(self, filename)
-        if self._mlp_rollout is not None and self.dp.is_main:
+        if (self._mlp_rollout is not None or self._cat_rollout is not None) and self.dp.is_main:
+            state = self.dp.sampler_state()
+            if self._cat_rollout is not None:
+                state['envs'] = self.task.state_dict()
             with open(filename + '.sampler', 'wb') as f:
-                pickle.dump(self.dp.sampler_state(), f)
+                pickle.dump(state, f)
 
     def load(self, filename):
         BaseAgent.load(self, filename)
-        if self._mlp_rollout is not None and os.path.isfile(filename + '.sampler'):
+        if (self._mlp_rollout is not None or self._cat_rollout is not None) and os.path.isfile(filename + '.sampler'):
             with open(filename + '.sampler', 'rb') as f:
-                self.dp.load_sampler_state(pickle.load(f), Config.DEVICE)
+                state = pickle.load(f)
+            self.dp.load_sampler_state(state, Config.DEVICE)
             self._noise_seed = self.dp.noise_seed
+            if self._cat_rollout is not None:
+                self.drain_episodes()
+                self._sampler_host, self._ep_anchor = int(state['step']), None
+                if 'envs' in state:
+                    self.task.load_state_dict(state['envs'])
+
+    # -- a2c_feature over device-resident cart-pole environments ------------------------------------------------------------
+    def drain_episodes(self):
+        """Fetches the episodes that ended on the device since the last drain (DeviceCartPoleVec.drain: one copy) and emits the
+        reference's 'episodic_return_train' lines for them, with the step numbers the host path logs -- total_steps at the start
+        of the episode's rollout + t * N + environment.  The lines arrive late (up to config.episode_drain_interval agent steps),
+        otherwise unchanged.  Returns the (step, return) pairs of this drain."""
+        if getattr(self, '_cat_rollout', None) is None or self._ep_anchor is None:
+            return []
+        s0, total0, t_len = self._ep_anchor
+        n = self.dp.global_workers
+        out = []
+        for s, i, ret in self.task.drain():
+            k, t = divmod(s - s0, t_len + 1)
+            at = total0 + (k * t_len + t) * n + i
+            self.logger.add_scalar('episodic_return_train', ret, at)
+            self.logger.info('steps %d, episodic_return_train %s' % (at, ret))
+            out.append((at, ret))
+        self._ep_log.extend(out)
+        return out
+
+    def episodes(self):
+        """(step, episodic return) of the training episodes that ended since the previous call (the newest 16384 at most), after
+        a drain.  Empty on the host-stepped paths, whose episodes are only logged."""
+        self.drain_episodes()
+        out = list(self._ep_log)
+        self._ep_log.clear()
+        return out
+
+    def _step_device_cat(self):
+        """step() over device_env.DeviceCartPoleVec: A2C_agent.py:22-41 is ONE launch (dra_cat_mlp_rollout: per step the forward,
+        the Gumbel-max action, the environment step), then _learn_stacked on the rollout's buffers -- after _OnPolicyGraph.WARMUP
+        eager rollouts both are replayed from one captured graph (a single stream, no parallel branches).  Nothing comes back to
+        the host inside a step; the episodes that ended are drained every config.episode_drain_interval agent steps."""
+        from collections import namedtuple
+        config, task, dp = self.config, self.task, self.dp
+        t_len = int(config.rollout_length)
+        if self._ep_anchor is None or self._ep_anchor[2] != t_len:
+            self.drain_episodes()       # (what is pending was appended under the old rollout length)
+            self._ep_anchor = (self._sampler_host, self.total_steps, t_len)
+        self._sampler_host += t_len + 1
+        self.total_steps += t_len * dp.global_workers
+        sig = int(self._noise_seed)     # what the captured launch has baked in besides the optimizer's hyper-parameters
+        if sig != self._cat_sig:
+            self._dev_graph.graph, self._cat_sig = None, sig
+        plan = namedtuple('CatPlan', ['counters', 't_len'])(task.env_counter, t_len)
+        self.last_loss = self._dev_graph.run(plan, self._cat_compute)
+        self._cat_steps += 1
+        if self._cat_steps % max(1, int(getattr(config, 'episode_drain_interval', 64))) == 0:
+            self.drain_episodes()
+
+    def _cat_compute(self, plan):
+        b = self._cat_rollout.run(plan.t_len)
+        self._rollout_step += plan.t_len
+        rows = plan.t_len * self.task.num_envs
+        return self._learn_stacked(b['state'].view(rows, -1), b['action'].view(rows), b['v'], b['reward'], b['mask'])
 
     def _step_device_mlp(self):
         """step() over device_env.DeviceContinuousVec: A2C_agent.py:22-41 is ONE launch (dra_a2c_mlp_rollout: per step the
@@ -1563,6 +1655,8 @@ class A2CAgent(BaseAgent):
         if getattr(self.task, 'on_device', False):
             if self._mlp_rollout is not None:
                 return self._step_device_mlp()
+            if self._cat_rollout is not None:
+                return self._step_device_cat()
             return self._step_device()
         config = self.config
         states = self.states

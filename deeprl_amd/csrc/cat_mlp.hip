@@ -1,0 +1,299 @@
+// cat_mlp: a2c_feature (examples.py:340-358: 5 workers, rollout length 5, CategoricalActorCriticNet over FCBody(state_dim, gate =
+// tanh), ONE RMSprop optimiser) over device-resident cart-pole environments (cartpole_env.h).
+//
+//   cat_mlp_rollout_kernel   A2C_agent.py:22-41 as ONE launch of one workgroup: per step the observation narrowed to float32 (what
+//                            tensor() uploads), the body (4 -> H -> H, tanh or relu), logits and v, the action by the rank-invariant
+//                            Gumbel-max stream (gumbel_noise.h: dra_gumbel_sample's bits), the environment step, reward, mask and --
+//                            the environment's terminals depend on the actions, so no host shadow can know them -- one appended row
+//                            of the episode ring per episode that ended; then the bootstrap forward.  Parameters are read from the
+//                            optimiser's ONE flat buffer; nothing is updated here.
+//   cartpole_step_kernel     one environment step, stand-alone (what the parity test calls)
+//
+// The update stays on the module path (dra_gae, nets.linear, dra_policy_heads_given / _bwd, dra_a2c_loss, the fused RMSprop step),
+// replayed from a captured graph by agents.A2CAgent.
+//
+// The rollout is a chain of (T + 1) x 3 dependent layers over <= 64 rows: latency-bound, nothing to spread over 256 CUs.  Plain
+// VALU code as in a2c_mlp.hip: weights are copied to LDS once per launch (transposed: consecutive lanes read consecutive units),
+// activations are kept TRANSPOSED ([unit][row]) so that a thread's 8 rows of one input unit are two 16-byte LDS reads, and every
+// dot product is one fp32 FMA chain in ascending k.  The environments live in the registers of wave 0 (lane e = environment e:
+// four fp64 state components, counters, the running return) for the whole launch; the ring position of an ending episode is the
+// rank of its lane in the wave's ballot, so rows land in (step, environment) order without a serial pass.
+#include "common.h"
+#include "cartpole_env.h"
+#include "gumbel_noise.h"
+#include <math.h>
+
+namespace {
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+constexpr int kS = kCartPoleS, kA = kCartPoleA, kMaxN = 64;
+constexpr int kRB = 8;                        // rows a thread carries through one pass over k
+constexpr int kGateRelu = 1, kGateTanh = 2;   // ops.ACT
+constexpr int kOut = kA + 1;                  // logits and the value
+
+__host__ __device__ constexpr int round_up8(int n) { return (n + 7) & ~7; }
+__host__ __device__ constexpr int round_up4(int n) { return (n + 3) & ~3; }
+
+// LDS of the rollout kernel, in floats; every region starts at a multiple of 4 floats (16 bytes)
+__host__ __device__ constexpr size_t rollout_lds_floats(int H, int N) {
+  return (size_t)kS * H + (size_t)H * H + 2 * (size_t)H       // W1^T [S][H], W2^T [H][H], b1, b2
+         + round_up4(kOut * (H + 1)) + 4                      // heads [3][H + 1], their biases
+         + round_up4(kA * kMaxN)                              // logits [N][A]
+         + (size_t)kS * round_up8(N) + 2 * (size_t)H * round_up8(N);   // x^T [S][NP], h1^T, h2^T [H][NP]
+}
+
+template <int GATE>
+__device__ __forceinline__ float gate_f(float x) {
+  if constexpr (GATE == kGateRelu) return fmaxf(x, 0.f);
+  else return tanhf(x);
+}
+
+// one hidden layer for the rows this thread carries: out^T[u][e] = gate(b[u] + sum_k in^T[k][e] W^T[k][u]).
+// unit u = tid % H, row-block group rg = tid / H; row blocks of kRB rows go round the 256 / H groups.
+template <int H, int GATE>
+__device__ __forceinline__ void hidden_layer(const float* __restrict__ inT, const float* __restrict__ wT, const float* __restrict__ b,
+                                             float* __restrict__ outT, int K, int NP, int tid) {
+  constexpr int G = 256 / H;
+  const int u = tid & (H - 1), rg = tid / H;
+  const float bias = b[u];
+  for (int e0 = rg * kRB; e0 < NP; e0 += G * kRB) {
+    float acc[kRB];
+#pragma unroll
+    for (int r = 0; r < kRB; ++r) acc[r] = 0.f;
+#pragma unroll 4
+    for (int k = 0; k < K; ++k) {
+      const float w = wT[k * H + u];
+      const f32x4 x0 = *reinterpret_cast<const f32x4*>(&inT[k * NP + e0]);
+      const f32x4 x1 = *reinterpret_cast<const f32x4*>(&inT[k * NP + e0 + 4]);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        acc[r] = fmaf(x0[r], w, acc[r]);
+        acc[4 + r] = fmaf(x1[r], w, acc[4 + r]);
+      }
+    }
+    f32x4 y0, y1;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      y0[r] = gate_f<GATE>(acc[r] + bias);
+      y1[r] = gate_f<GATE>(acc[4 + r] + bias);
+    }
+    *reinterpret_cast<f32x4*>(&outT[u * NP + e0]) = y0;
+    *reinterpret_cast<f32x4*>(&outT[u * NP + e0 + 4]) = y1;
+  }
+}
+
+template <int H, int GATE>
+__global__ void __launch_bounds__(256)
+cat_mlp_rollout_kernel(dra_cat_mlp_net net, dra_cat_mlp_rollout_io io) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  const int tid = threadIdx.x;
+  const int N = io.n_env, T = io.t_len, NP = round_up8(N);
+  const float* __restrict__ P = net.param;
+
+  float* sW1 = lds;                                   // [S][H]  (transposed: [k][unit])
+  float* sW2 = sW1 + kS * H;                          // [H][H]
+  float* sB1 = sW2 + H * H;                           // [H]
+  float* sB2 = sB1 + H;                               // [H]
+  float* sWh = sB2 + H;                               // [3][H + 1]: fc_action's two rows, fc_critic's one
+  float* sBh = sWh + round_up4(kOut * (H + 1));       // [3] (+ pad)
+  float* sLogit = sBh + 4;                            // [N][A]
+  float* sXT = sLogit + round_up4(kA * kMaxN);        // [S][NP]
+  float* sH1T = sXT + kS * NP;                        // [H][NP]
+  float* sH2T = sH1T + H * NP;                        // [H][NP]
+  const int total = (int)(sH2T + H * NP - lds);
+  for (int i = tid; i < total; i += 256) lds[i] = 0.f;
+  const int64_t t0 = *io.sampler_step;                // (rewritten by thread 0 behind the last barrier)
+  __syncthreads();
+
+  // ---- weights, once per launch
+  for (int i = tid; i < kS * H; i += 256) {
+    const int k = i / H, u = i - k * H;
+    sW1[i] = P[net.w1 + u * kS + k];
+  }
+  for (int i = tid; i < H * H; i += 256) {
+    const int k = i / H, u = i - k * H;
+    sW2[i] = P[net.w2 + u * H + k];
+  }
+  for (int i = tid; i < H; i += 256) {
+    sB1[i] = P[net.b1 + i];
+    sB2[i] = P[net.b2 + i];
+  }
+  for (int i = tid; i < kOut * H; i += 256) {
+    const int c = i / H, k = i - c * H;
+    sWh[c * (H + 1) + k] = c < kA ? P[net.wa + c * H + k] : P[net.wc + k];
+  }
+  if (tid < kOut) sBh[tid] = tid < kA ? P[net.ba + tid] : P[net.bc];
+
+  // ---- the environments: lane e of wave 0 carries environment e
+  const bool env_lane = tid < N;
+  CartPoleState st = {0.0, 0.0, 0.0, 0.0};
+  int64_t counter = 0;
+  int32_t ep_steps = 0;
+  double ep_return = 0.0;
+  uint64_t seed = 0;
+  int64_t ring_count = 0;
+  if (env_lane) {
+    st.x = io.env_state[tid * kS + 0];
+    st.xd = io.env_state[tid * kS + 1];
+    st.th = io.env_state[tid * kS + 2];
+    st.thd = io.env_state[tid * kS + 3];
+    counter = io.env_counter[tid];
+    ep_steps = io.ep_steps[tid];
+    ep_return = io.ep_return[tid];
+    seed = (uint64_t)io.env_seed[tid];
+  }
+  if (tid < 64) ring_count = *io.ep_count;
+  const float reward = (float)(1.0 * io.reward_coef);       // what tensor(reward_normalizer(rewards)) uploads
+
+  for (int t = 0; t <= T; ++t) {
+    // ---- the observation: float32 of the fp64 state (torch_utils.py:23)
+    if (env_lane) {
+      const float x[kS] = {(float)st.x, (float)st.xd, (float)st.th, (float)st.thd};
+#pragma unroll
+      for (int j = 0; j < kS; ++j) {
+        sXT[j * NP + tid] = x[j];
+        if (t < T) io.out_state[((int64_t)t * N + tid) * kS + j] = x[j];
+      }
+    }
+    __syncthreads();
+    hidden_layer<H, GATE>(sXT, sW1, sB1, sH1T, kS, NP, tid);
+    __syncthreads();
+    hidden_layer<H, GATE>(sH1T, sW2, sB2, sH2T, H, NP, tid);
+    __syncthreads();
+    // ---- heads: one output per thread -- (environment e, logit c) or (e, the value); the bootstrap step needs the value alone
+    if (tid < N * kOut) {
+      const int e = tid / kOut, c = tid - e * kOut;
+      if (c == kA || t < T) {
+        const float* hT = sH2T + e;
+        const float* w = sWh + c * (H + 1);
+        float acc = 0.f;
+#pragma unroll 8
+        for (int k = 0; k < H; ++k) acc = fmaf(hT[k * NP], w[k], acc);
+        acc += sBh[c];
+        if (c == kA) io.out_v[(int64_t)t * N + e] = acc;
+        else sLogit[e * kA + c] = acc;
+      }
+    }
+    if (t == T) break;
+    __syncthreads();
+    // ---- action (gumbel_sample_kernel's loop, bit for bit), environment step, ring append: wave 0
+    if (tid < 64) {
+      bool done = false;
+      double ended = 0.0;
+      if (env_lane) {
+        const uint64_t base = gs_step_base(io.noise_seed, t0 + t);
+        float best = -INFINITY;
+        int arg = 0;
+#pragma unroll
+        for (int a = 0; a < kA; ++a) {
+          const float v = gs_perturbed(base, io.env0 + tid, a, sLogit[tid * kA + a]);
+          if (v > best) { best = v; arg = a; }
+        }
+        done = cartpole_step(st, counter, ep_steps, ep_return, seed, arg, io.horizon, ended);
+        const int64_t o = (int64_t)t * N + tid;
+        io.out_action[o] = arg;
+        io.out_reward[o] = reward;
+        io.out_mask[o] = done ? 0.f : 1.f;
+      }
+      const unsigned long long ends = __ballot(done ? 1 : 0);
+      if (done) {
+        const int before = __popcll(ends & ((1ull << tid) - 1ull));
+        double* row = io.ep_ring + ((ring_count + before) % io.ring_cap) * 3;
+        row[0] = (double)(t0 + t);
+        row[1] = (double)(io.env0 + tid);
+        row[2] = ended;
+      }
+      ring_count += __popcll(ends);
+    }
+    // (wave 0 writes the next observation into x^T next: layer 1 of this step, its only reader, is three barriers back)
+  }
+  __syncthreads();
+  if (env_lane) {
+    io.env_state[tid * kS + 0] = st.x;
+    io.env_state[tid * kS + 1] = st.xd;
+    io.env_state[tid * kS + 2] = st.th;
+    io.env_state[tid * kS + 3] = st.thd;
+    io.env_counter[tid] = counter;
+    io.ep_steps[tid] = ep_steps;
+    io.ep_return[tid] = ep_return;
+  }
+  if (tid == 0) {
+    *io.sampler_step = t0 + T + 1;
+    *io.ep_count = ring_count;
+  }
+}
+
+__global__ void __launch_bounds__(64)
+cartpole_step_kernel(double* __restrict__ state, int64_t* __restrict__ counter, int32_t* __restrict__ ep_steps,
+                     double* __restrict__ ep_return, const int64_t* __restrict__ seed, const int64_t* __restrict__ action, int n,
+                     int64_t horizon, double* __restrict__ out_reward, int32_t* __restrict__ out_done) {
+  const int i = blockIdx.x * 64 + threadIdx.x;
+  if (i >= n) return;
+  CartPoleState st = {state[i * kS + 0], state[i * kS + 1], state[i * kS + 2], state[i * kS + 3]};
+  int64_t c = counter[i];
+  int32_t steps = ep_steps[i];
+  double ret = ep_return[i], ended = 0.0;
+  const bool done = cartpole_step(st, c, steps, ret, (uint64_t)seed[i], action[i] == 1 ? 1 : 0, horizon, ended);
+  state[i * kS + 0] = st.x;
+  state[i * kS + 1] = st.xd;
+  state[i * kS + 2] = st.th;
+  state[i * kS + 3] = st.thd;
+  counter[i] = c;
+  ep_steps[i] = steps;
+  ep_return[i] = ret;
+  out_reward[i] = 1.0;
+  out_done[i] = done ? 1 : 0;
+}
+
+template <int H, int GATE>
+int launch_rollout(const dra_cat_mlp_net* net, const dra_cat_mlp_rollout_io* io, void* stream) {
+  const size_t bytes = rollout_lds_floats(H, io->n_env) * sizeof(float);
+  static DraLdsAttr lds_attr;
+  if (int rc = dra_grant_lds(lds_attr, reinterpret_cast<const void*>(&cat_mlp_rollout_kernel<H, GATE>), bytes)) return rc;
+  hipLaunchKernelGGL((cat_mlp_rollout_kernel<H, GATE>), dim3(1), dim3(256), bytes, dra_stream(stream), *net, *io);
+  DRA_LAUNCH_CHECK();
+  return DRA_OK;
+}
+
+template <int H>
+int launch_gate(const dra_cat_mlp_net* net, const dra_cat_mlp_rollout_io* io, void* stream) {
+  return net->gate == kGateRelu ? launch_rollout<H, kGateRelu>(net, io, stream) : launch_rollout<H, kGateTanh>(net, io, stream);
+}
+
+}  // namespace
+
+DRA_API int dra_cat_mlp_supported(int state_dim, int n_actions, int hidden, int n_env, int gate) {
+  if (state_dim != kS || n_actions != kA) return DRA_EINVAL;
+  if (hidden != 16 && hidden != 32 && hidden != 64) return DRA_EINVAL;
+  if (n_env < 1 || n_env > kMaxN || (gate != kGateRelu && gate != kGateTanh)) return DRA_EINVAL;
+  return DRA_OK;
+}
+
+DRA_API int dra_cat_mlp_rollout(const dra_cat_mlp_net* net, const dra_cat_mlp_rollout_io* io, void* stream) {
+  if (!net || !io || !net->param) return DRA_EINVAL;
+  if (dra_cat_mlp_supported(net->state_dim, net->n_actions, net->hidden, io->n_env, net->gate)) return DRA_EINVAL;
+  const int32_t offs[8] = {net->w1, net->b1, net->w2, net->b2, net->wa, net->ba, net->wc, net->bc};
+  for (int i = 0; i < 8; ++i)
+    if (offs[i] < 0) return DRA_EINVAL;
+  if (io->t_len < 1 || io->horizon < 1 || io->ring_cap < 1 || io->n_global < io->n_env || io->env0 < 0 ||
+      io->env0 + io->n_env > io->n_global)
+    return DRA_EINVAL;
+  if ((int64_t)(io->t_len + 1) * io->n_env * kS > 0x7fffffff) return DRA_EINVAL;
+  if (!io->env_state || !io->env_counter || !io->ep_steps || !io->ep_return || !io->env_seed || !io->sampler_step || !io->ep_count ||
+      !io->ep_ring || !io->out_state || !io->out_action || !io->out_v || !io->out_reward || !io->out_mask)
+    return DRA_EINVAL;
+  if (net->hidden == 16) return launch_gate<16>(net, io, stream);
+  if (net->hidden == 32) return launch_gate<32>(net, io, stream);
+  return launch_gate<64>(net, io, stream);
+}
+
+DRA_API int dra_cartpole_step(double* state, int64_t* counter, int32_t* ep_steps, double* ep_return, const int64_t* seed,
+                              const int64_t* action, int n, int64_t horizon, double* out_reward, int32_t* out_done, void* stream) {
+  if (!state || !counter || !ep_steps || !ep_return || !seed || !action || !out_reward || !out_done || n < 1 || horizon < 1)
+    return DRA_EINVAL;
+  hipLaunchKernelGGL(cartpole_step_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, dra_stream(stream), state, counter, ep_steps,
+                     ep_return, seed, action, n, horizon, out_reward, out_done);
+  DRA_LAUNCH_CHECK();
+  return DRA_OK;
+}

@@ -7,6 +7,7 @@
 // reference's 15-30 ATen ops, and never materialises the [B,N,N] / [N,B,N] intermediates.
 // Actions arrive as the ring's raw int64 records or as f32 (what `tensor()` makes of them).
 #include "common.h"
+#include "gumbel_noise.h"
 
 // (clamped to [0, n_actions): an action record that was never written -- a sampling bug upstream -- must show up as a wrong
 // number, not turn into a wild pointer and a GPU fault)
@@ -575,26 +576,17 @@ DRA_API int dra_weighted_mean(const float* x, const float* w, int n, float* out,
 // network_heads.py:249-252 in distribution).  The rollout step lives in DEVICE memory and is advanced by the kernel itself,
 // so the launch has constant arguments and replays from a captured rollout graph (round 2 reseeded a host generator per
 // step, which kept every data-parallel rollout on the eager path).  One workgroup; rows strided over its threads.
-__device__ __forceinline__ uint64_t gs_mix64(uint64_t z) {
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
 __global__ void __launch_bounds__(256)
 gumbel_sample_kernel(const float* __restrict__ logits, int n_local, int n_actions, uint64_t seed, int64_t* __restrict__ step_dev,
                      int64_t lo, int64_t* __restrict__ action_out) {
   const int64_t step = *step_dev;
   __syncthreads();                    // every thread has read the step before thread 0 advances it
-  const uint64_t base = gs_mix64(seed * 0x9E3779B97F4A7C15ull + (uint64_t)step);
+  const uint64_t base = gs_step_base(seed, step);
   for (int i = threadIdx.x; i < n_local; i += blockDim.x) {
     float best = -INFINITY;
     int arg = 0;
     for (int a = 0; a < n_actions; ++a) {
-      const uint64_t h = gs_mix64(base + (uint64_t)(lo + i) * 64ull + (uint64_t)a);
-      // 23 bits: k + 0.5 is exact in fp32 for every k < 2^23, so u lies STRICTLY inside (0, 1) (with 24 bits the largest k
-      // rounded up to 2^24 and u == 1 made -log(-log u) = +inf: that action won whatever the logits, 2^-24 per draw)
-      const float u = ((float)(h >> 41) + 0.5f) * (1.0f / 8388608.0f);
-      const float v = logits[(int64_t)i * n_actions + a] - logf(-logf(u));
+      const float v = gs_perturbed(base, lo + i, a, logits[(int64_t)i * n_actions + a]);      // gumbel_noise.h
       if (v > best) { best = v; arg = a; }
     }
     action_out[i] = arg;

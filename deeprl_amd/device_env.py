@@ -265,3 +265,102 @@ class DeviceContinuousVec:
 
     def close(self):
         return
+
+
+class DeviceCartPoleVec:
+    """The envs.CartPole environments of a Task, resident on the device (a2c_feature, examples.py:340-358): fp64 state, total
+    step counters, episode steps and running returns live in HBM and one launch (dra_cat_mlp_rollout) walks a whole rollout --
+    forward, action, environment step -- without a host round trip.  Same arithmetic as envs.CartPole stepped from python
+    (csrc/cartpole_env.h; tests/test_gpu_a2c_feature.py compares the two).
+
+    The terminals depend on the actions, so the host cannot shadow them (DeviceContinuousVec.shadow has no counterpart here).
+    Episode ends are REPORTED by the device instead: the rollout kernel appends one row (sampler step of the end, global
+    environment, episodic return) per finished episode to `ep_ring` [RING_CAP][3] and counts them in `ep_count`; `drain()`
+    fetches what is new with one device-to-host copy."""
+    on_device = True
+    RING_CAP = 4096
+
+    def __init__(self, task):
+        envs = task.env.envs
+        dev = Config.DEVICE
+        self.task = task
+        self.name, self.state_dim, self.action_dim = task.name, task.state_dim, task.action_dim
+        self.observation_space, self.action_space = task.observation_space, task.action_space
+        self.num_envs, self.horizon = len(envs), int(envs[0].horizon)
+        self.ring_cap = int(self.RING_CAP)
+        self.env_state = torch.from_numpy(np.stack([np.asarray(e.s, dtype=np.float64) for e in envs])).to(dev)
+        self.env_counter = torch.tensor([e.c for e in envs], dtype=torch.int64, device=dev)
+        self.ep_steps = torch.tensor([e.steps for e in envs], dtype=torch.int32, device=dev)
+        self.ep_return = torch.tensor([e.ret for e in envs], dtype=torch.float64, device=dev)
+        self.env_seed = torch.tensor([e.seed for e in envs], dtype=torch.int64, device=dev)
+        # [0:3 cap] the ring's rows, [3 cap] the count (as fp64 bits of an int64 view): ONE buffer, so that drain() is one copy
+        self._ring_buf = torch.zeros(3 * self.ring_cap + 1, dtype=torch.float64, device=dev)
+        self.ep_ring = self._ring_buf[:3 * self.ring_cap].view(self.ring_cap, 3)
+        self.ep_count = self._ring_buf[3 * self.ring_cap:].view(torch.int64)
+        self._ring_host = torch.zeros(3 * self.ring_cap + 1, dtype=torch.float64).pin_memory()
+        self.drained = 0
+        for e in envs:
+            e.s = "device"          # the host objects are retired: stepping them too would fork the streams
+        self._bufs = {}
+
+    @staticmethod
+    def eligible(task, config):
+        from .envs import CartPole, DummyVecEnv, Task
+        from .normalizers import RescaleNormalizer
+        if Config.DEVICE.type != 'cuda' or getattr(config, 'device_env', True) is False or type(task) is not Task:
+            return False
+        env = getattr(task, 'env', None)
+        if type(env) is not DummyVecEnv or not env.envs or len(env.envs) > 64:
+            return False
+        e0 = env.envs[0]
+        if not all(type(e) is CartPole and e.horizon == e0.horizon for e in env.envs):
+            return False
+        sn, rn = config.state_normalizer, config.reward_normalizer
+        return type(sn) is RescaleNormalizer and sn.coef == 1.0 and type(rn) is RescaleNormalizer
+
+    def buffers(self, t_len):
+        if t_len not in self._bufs:
+            n, s, dev = self.num_envs, self.state_dim, Config.DEVICE
+            f = lambda *shape: torch.zeros(shape, dtype=torch.float32, device=dev)
+            self._bufs[t_len] = dict(state=f(t_len, n, s), action=torch.zeros((t_len, n), dtype=torch.int64, device=dev),
+                                     v=f(t_len + 1, n, 1), reward=f(t_len, n, 1), mask=f(t_len, n, 1))
+        return self._bufs[t_len]
+
+    def drain(self):
+        """The episodes that ended since the last drain -> list of (sampler step, global environment, episodic return) in the
+        order they were appended ((step, environment) order).  One device-to-host copy; raises when more than RING_CAP rows were
+        pending (the oldest have been overwritten)."""
+        self._ring_host.copy_(self._ring_buf, non_blocking=True)
+        torch.cuda.current_stream().synchronize()
+        host = self._ring_host.numpy()
+        count = int(host[3 * self.ring_cap:].view(np.int64)[0])
+        pending = count - self.drained
+        if pending > self.ring_cap:
+            raise RuntimeError("DeviceCartPoleVec: %d episodes ended since the last drain, the ring holds %d: drain more often "
+                               "(config.episode_drain_interval)" % (pending, self.ring_cap))
+        rows = host[:3 * self.ring_cap].reshape(self.ring_cap, 3)
+        out = [(int(r[0]), int(r[1]), float(r[2])) for r in (rows[k % self.ring_cap] for k in range(self.drained, count))]
+        self.drained = count
+        return out
+
+    def state_dict(self):
+        """Everything a loaded run needs to continue bit for bit (host copies)."""
+        torch.cuda.current_stream().synchronize()
+        keys = ("env_state", "env_counter", "ep_steps", "ep_return", "env_seed", "_ring_buf")
+        d = {k: getattr(self, k).cpu().numpy().copy() for k in keys}
+        d["drained"] = int(self.drained)
+        return d
+
+    def load_state_dict(self, d):
+        for k in ("env_state", "env_counter", "ep_steps", "ep_return", "env_seed", "_ring_buf"):
+            getattr(self, k).copy_(torch.from_numpy(np.asarray(d[k])))
+        self.drained = int(d["drained"])
+
+    def reset(self):
+        return None
+
+    def step(self, actions):
+        raise RuntimeError("DeviceCartPoleVec is driven through A2CAgent's device rollout; its environments are not steppable")
+
+    def close(self):
+        return

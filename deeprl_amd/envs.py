@@ -203,6 +203,89 @@ class SyntheticContinuous:
         return self.s.copy(), reward, done, info
 
 
+_M64 = (1 << 64) - 1
+_PSIN = (1.0, -0.16666666666666666, 0.008333333333333333, -0.0001984126984126984, 2.7557319223985893e-06,
+         -2.505210838544172e-08, 1.6059043836821613e-10, -7.647163731819816e-13)
+_PCOS = (1.0, -0.5, 0.041666666666666664, -0.001388888888888889, 2.48015873015873e-05, -2.755731922398589e-07,
+         2.08767569878681e-09, -1.1470745597729725e-11, 4.779477332387385e-14)
+
+
+def psin(th):
+    """sin(th) = th P(th^2): Horner over the coefficients (-1)^k / (2k + 1)!, k = 0..7, one rounding per operation
+    (csrc/cartpole_env.h cartpole_psin, the same literals).  Within 1.2e-16 of libm for |th| <= 0.45."""
+    z = th * th
+    p = _PSIN[7]
+    for k in (6, 5, 4, 3, 2, 1, 0):
+        p = _PSIN[k] + z * p
+    return th * p
+
+
+def pcos(th):
+    """cos(th) = Q(th^2): coefficients (-1)^k / (2k)!, k = 0..8 (cartpole_pcos)."""
+    z = th * th
+    q = _PCOS[8]
+    for k in (7, 6, 5, 4, 3, 2, 1, 0):
+        q = _PCOS[k] + z * q
+    return q
+
+
+def _mix64_int(z):
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & _M64
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & _M64
+    return z ^ (z >> 31)
+
+
+def cenv_reset_state(seed, c, j):
+    """csrc/cont_env.h cenv_reset_state on python integers: -0.05 + 0.1 U(stream 3, counter c, component j)."""
+    h = _mix64_int((((seed * 8 + 4) & _M64) * 0x9E3779B97F4A7C15 + c * 64 + j) & _M64)
+    return -0.05 + 0.1 * (float(h >> 11) * 1.1102230246251565e-16)
+
+
+class CartPole:
+    """Cart-pole: the published equations with the constants of gym's CartPole-v0 (gravity 9.8, cart 1.0, pole 0.1, half length
+    0.5, force 10, tau 0.02, Euler; +-2.4 / +-12 degrees; 200 steps; reward 1 on every step) -- the host statement of
+    csrc/cartpole_env.h, bit for bit: python fp64 scalars in the same operation order, sine and cosine as the fixed polynomials
+    psin / pcos, reset states from the counter hash cenv_reset_state(seed, c, j) with c the environment's total step counter.  So
+    the same environments can live on the device (device_env.DeviceCartPoleVec) and a device rollout can be compared with this
+    class stepped from python.  Parity with gym's own CartPole is not pinned.  Action 1 pushes right, anything
+    else left."""
+    THETA, X = 0.20943951023931953, 2.4
+    state_dim, n_actions = 4, 2
+
+    def __init__(self, seed=0, horizon=200):
+        self.seed, self.horizon = int(seed), int(horizon)
+        self.c = 0
+        self.s = None
+        self.steps = 0
+        self.ret = 0.0
+
+    def reset(self):
+        sd, c = self.seed & _M64, self.c
+        self.s = np.asarray([cenv_reset_state(sd, c, j) for j in range(4)], dtype=np.float64)
+        self.steps = 0
+        self.ret = 0.0
+        return self.s.copy()
+
+    def step(self, action):
+        x, xd, th, thd = (float(v) for v in self.s)
+        force = 10.0 if int(np.asarray(action).reshape(-1)[0]) == 1 else -10.0
+        c, s = pcos(th), psin(th)
+        temp = (force + ((0.05 * thd) * thd) * s) / 1.1
+        thacc = (9.8 * s - c * temp) / (0.5 * (1.3333333333333333 - ((0.1 * c) * c) / 1.1))
+        xacc = temp - ((0.05 * thacc) * c) / 1.1
+        x = x + 0.02 * xd
+        xd = xd + 0.02 * xacc
+        th = th + 0.02 * thd
+        thd = thd + 0.02 * thacc
+        self.s = np.asarray([x, xd, th, thd], dtype=np.float64)
+        self.c += 1
+        self.steps += 1
+        self.ret += 1.0
+        done = bool(x < -self.X or x > self.X or th < -self.THETA or th > self.THETA or self.steps >= self.horizon)
+        info = {'episodic_return': self.ret if done else None}
+        return self.s.copy(), 1.0, done, info
+
+
 class DummyVecEnv:
     """envs.py:126-150: serial vector env with auto-reset on done."""
 
@@ -387,6 +470,12 @@ class Task:
         if seed is None:
             seed = np.random.randint(int(1e9))
         self.name = name
+        if name == 'classic-CartPole-v0':
+            # the cart-pole stated in this package (CartPole above): a real environment by an explicit name, no stand-in and no warning
+            self.env = DummyVecEnv([CartPole(seed + i, horizon=synthetic_done_period or 200) for i in range(num_envs)])
+            self.observation_space, self.action_space = Box(-np.inf, np.inf, (4,)), Discrete(2)
+            self.state_dim, self.action_dim = 4, 2
+            return
         explicit = name.startswith('synthetic-')
         real = None if explicit else _real_task_envs(name, num_envs, seed, episode_life)
         if real is not None:

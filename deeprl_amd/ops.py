@@ -1326,6 +1326,22 @@ def gumbel_sample(logits, seed, step_dev, lo):
     return out
 
 
+def cartpole_step(state, counter, ep_steps, ep_return, seed, action, horizon):
+    """One step of n device-resident cart-pole environments with auto reset (dra_cartpole_step; csrc/cartpole_env.h): state f64
+    [n, 4], counter i64 [n], ep_steps i32 [n] and ep_return f64 [n] are updated in place; action i64 [n] -> (reward f64 [n],
+    done i32 [n])."""
+    n = int(_c(state, torch.float64).shape[0])
+    for t, dt in ((state, torch.float64), (counter, torch.int64), (ep_steps, torch.int32), (ep_return, torch.float64),
+                  (seed, torch.int64), (action, torch.int64)):
+        if _dev(t).dtype != dt or not t.is_contiguous() or t.numel() != n * (4 if t is state else 1):
+            raise DraError("cartpole_step: contiguous state f64 [n, 4], counter i64, ep_steps i32, ep_return f64, seed i64, action i64 [n]")
+    reward = torch.empty(n, dtype=torch.float64, device=state.device)
+    done = torch.empty(n, dtype=torch.int32, device=state.device)
+    lib.dra_cartpole_step(ptr(state), ptr(counter), ptr(ep_steps), ptr(ep_return), ptr(seed), ptr(action), n, int(horizon),
+                          ptr(reward), ptr(done), stream_ptr())
+    return reward, done
+
+
 def categorical_bwd(logits, action, g_lp, g_ent):
     logits = _c(logits, _f32)
     b, a = logits.shape

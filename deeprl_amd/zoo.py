@@ -83,6 +83,13 @@ ZOO = {
                     exploration_steps=20000, sgd_update_frequency=4, double_q=True, async_actor=True, gradient_clip=10),
         normalizers=(ImageNormalizer, SignNormalizer),
         replay=dict(memory_size=int(1e6), with_n_step=True), eps=(1, 0.01, 25e4), beta=(0.4, 1.0)),
+    # examples.py:340-358
+    "a2c_feature": dict(
+        agent="A2CAgent", kw=dict(log_level=0), pre_fields=dict(num_workers=5),
+        task=lambda c: Task(c.game, num_envs=c.num_workers), eval_task=lambda c: Task(c.game),
+        optimizer=_rmsprop(lr=0.001),
+        network=lambda c: N.CategoricalActorCriticNet(c.state_dim, c.action_dim, N.FCBody(c.state_dim, gate=F.tanh)),
+        fields=dict(discount=0.99, use_gae=True, gae_tau=0.95, entropy_weight=0.01, rollout_length=5, gradient_clip=0.5)),
     # examples.py:361-381
     "a2c_pixel": dict(
         agent="A2CAgent", kw=dict(log_level=0), pre_fields=dict(num_workers=16),

@@ -997,6 +997,52 @@ int dra_dpg_actor_update(const dra_dpg_net* online, const dra_dpg_batch* batch, 
 int dra_dpg_act(const dra_dpg_net* net, const void* state, int64_t state_stride, int in_f64, int n, float* out_action,
                 void* stream);
 
+/* ---- cat_mlp: a2c_feature (examples.py:340-358) over device-resident cart-pole environments (csrc/cartpole_env.h,
+ * deeprl_amd/envs.py CartPole: the same function bit for bit).
+ * one step of n environments with DummyVecEnv's auto reset: state f64 [n][4] (x, x', theta, theta'), counter i64 [n] (total
+ * steps: the reset stream's position), ep_steps i32 [n] and ep_return f64 [n] are updated in place; action i64 [n] (1 pushes
+ * right, anything else left); out_reward f64 [n] (1.0), out_done i32 [n]. */
+int dra_cartpole_step(double* state, int64_t* counter, int32_t* ep_steps, double* ep_return, const int64_t* seed,
+                      const int64_t* action, int n, int64_t horizon, double* out_reward, int32_t* out_done, void* stream);
+/* CategoricalActorCriticNet (network_heads.py:217-255) over a two-layer FCBody phi_body of one width (tanh or relu), identity
+ * actor / critic bodies, biased Linear heads; every parameter in ONE flat buffer (one optimiser).  state_dim 4, 2 actions,
+ * hidden in {16, 32, 64}, n_env <= 64. */
+typedef struct dra_cat_mlp_net {
+  const float* param;                /* the optimiser's flat parameter buffer (device); read only */
+  int32_t w1, b1, w2, b2;            /* phi_body.layers[0..1]: float offsets into param */
+  int32_t wa, ba, wc, bc;            /* fc_action [n_actions][hidden], fc_critic [1][hidden] */
+  int32_t gate;                      /* 1 relu, 2 tanh */
+  int32_t state_dim, n_actions, hidden;
+} dra_cat_mlp_net;
+/* A2C_agent.py:22-41 in ONE launch of one workgroup: for t < t_len [observation narrowed to float32 and stored, body, logits
+ * and v, action = argmax_a (logit_a + Gumbel noise of (noise_seed, *sampler_step + t, env0 + env, a)) -- dra_gumbel_sample's
+ * stream, bit for bit --, environment step, reward * reward_coef, mask = 1 - done, and for every episode that ended one
+ * appended row of ep_ring], then the bootstrap observation's value.  *sampler_step advances by t_len + 1.
+ * ep_ring row (*ep_count mod ring_cap) = (sampler step of the end, global environment, episodic return); *ep_count counts
+ * every episode ever ended.  Rows are appended in (step, environment) order with vector stores. */
+typedef struct dra_cat_mlp_rollout_io {
+  double* env_state;        /* [n_env][4] (in/out) */
+  int64_t* env_counter;     /* [n_env] (in/out) */
+  int32_t* ep_steps;        /* [n_env] (in/out) */
+  double* ep_return;        /* [n_env] (in/out) */
+  const int64_t* env_seed;  /* [n_env] */
+  int64_t* sampler_step;    /* [1] (in/out) */
+  int64_t* ep_count;        /* [1] (in/out) */
+  double* ep_ring;          /* [ring_cap][3] */
+  float* out_state;         /* [t_len][n_env][4] */
+  int64_t* out_action;      /* [t_len][n_env] */
+  float* out_v;             /* [t_len + 1][n_env] */
+  float* out_reward;        /* [t_len][n_env] */
+  float* out_mask;          /* [t_len][n_env] */
+  int64_t env0, n_global;   /* first GLOBAL environment of this rollout, global environment count */
+  uint64_t noise_seed;
+  int64_t horizon, ring_cap;
+  double reward_coef;
+  int32_t t_len, n_env;
+} dra_cat_mlp_rollout_io;
+int dra_cat_mlp_supported(int state_dim, int n_actions, int hidden, int n_env, int gate);   /* 0 = yes */
+int dra_cat_mlp_rollout(const dra_cat_mlp_net* net, const dra_cat_mlp_rollout_io* io, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

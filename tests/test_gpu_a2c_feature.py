@@ -1,0 +1,548 @@
+"""GPU tests of a2c_feature on device-resident cart-pole environments: dra_cartpole_step against envs.CartPole bit for bit, the
+rollout kernel of csrc/cat_mlp.hip against the restatement (tests/a2c_feature_restatement.py, pinned to the reference's own run by
+tests/test_a2c_feature_host.py, which also asserts the Gumbel margins the action comparisons rest on), one update against the
+reference's recorded A2CAgent.step, A2CAgent's device path against the host-stepped path, graph replay against eager, save /
+load, the episode ring's drain, and a closed loop that has to LEARN.
+Bars: exact for everything the fp64 environment determines once the actions are equal (observations, states, counters, masks,
+ring rows); 1e-5 of a tensor's largest magnitude (floor 1) for fp32 values."""
+import ctypes
+import json
+import os
+
+import numpy as np
+import pytest
+import torch
+from parity_log import record_parity
+
+import a2c_feature_cases as K
+import a2c_feature_restatement as R
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+GOLDEN = os.path.join(ROOT, "tests", "golden", "a2c_feature")
+FIXTURE = os.path.join(GOLDEN, "a2c_feature_step.npz")
+GAME = "classic-CartPole-v0"
+
+
+@pytest.fixture(scope="module")
+def dra():
+    if not torch.cuda.is_available():
+        pytest.skip("GPU tests need an MI355X")
+    import deeprl_amd as d
+    d.select_device(0)
+    return d
+
+
+class _Rec:
+    """A logger that keeps the episodic-return lines."""
+
+    def __init__(self):
+        self.lines = []
+
+    def info(self, msg, *a, **k):
+        self.lines.append(str(msg))
+
+    def add_scalar(self, *a, **k):
+        pass
+    add_histogram = warning = add_scalar
+
+
+def _within(got, want, what):
+    """1e-5 of the tensor's largest magnitude, floor 1.0."""
+    got, want = np.asarray(got, dtype=np.float64), np.asarray(want, dtype=np.float64)
+    assert got.shape == want.shape, (what, got.shape, want.shape)
+    err = float(np.max(np.abs(got - want))) if want.size else 0.0
+    bar = 1e-5 * max(float(np.abs(want).max()) if want.size else 0.0, 1.0)
+    print("%s: max abs error %.3e (bar %.3e)" % (what, err, bar))
+    assert err <= bar, (what, err, bar)
+    return err / bar
+
+
+def _bits(x):
+    x = np.ascontiguousarray(x)
+    return x.view({4: np.uint32, 8: np.uint64}[x.dtype.itemsize])
+
+
+# ------------------------------------------------------------------------------------------ the environment kernel
+@pytest.mark.parametrize("horizon", [200, 7])
+@pytest.mark.parametrize("n", [1, 5, 64])
+def test_cartpole_step_matches_host_bit_for_bit(dra, n, horizon):
+    """300 steps of seeded random actions through dra_cartpole_step and through envs.CartPole under DummyVecEnv: state, counters,
+    episode steps, returns, reward and done equal to the bit at every step (horizon 7: time-limit ends and resets everywhere)."""
+    from deeprl_amd import ops
+    from deeprl_amd.envs import CartPole, DummyVecEnv
+    dev = dra.Config.DEVICE
+    steps = 300
+    envs = [CartPole(50 + i, horizon) for i in range(n)]
+    vec = DummyVecEnv(envs)
+    first = np.stack(vec.reset())
+    actions = np.random.RandomState(1000 * n + horizon).randint(0, 2, size=(steps, n)).astype(np.int64)
+    state = torch.from_numpy(first.copy()).to(dev)
+    counter = torch.zeros(n, dtype=torch.int64, device=dev)
+    ep_steps = torch.zeros(n, dtype=torch.int32, device=dev)
+    ep_return = torch.zeros(n, dtype=torch.float64, device=dev)
+    seed = torch.tensor([e.seed for e in envs], dtype=torch.int64, device=dev)
+    act = torch.from_numpy(actions).to(dev)
+    got = []
+    for t in range(steps):
+        reward, done = ops.cartpole_step(state, counter, ep_steps, ep_return, seed, act[t], horizon)
+        got.append([x.clone() for x in (state, counter, ep_steps, ep_return, reward, done)])
+    torch.cuda.synchronize()
+    ends = 0
+    for t in range(steps):
+        obs, rew, done, info = vec.step(actions[t])
+        g = [x.cpu().numpy() for x in got[t]]
+        assert np.array_equal(_bits(g[0]), _bits(np.stack(obs))), t
+        assert np.array_equal(g[1], [e.c for e in envs]) and np.array_equal(g[2], [e.steps for e in envs]), t
+        assert np.array_equal(_bits(g[3]), _bits(np.asarray([e.ret for e in envs]))), t
+        assert np.array_equal(g[4], rew) and np.array_equal(g[5], done.astype(np.int32)), t
+        ends += int(done.sum())
+    assert ends >= (n * (steps // 7) if horizon == 7 else n * 5)        # (random actions: episodes of about 22 steps)
+
+
+# ------------------------------------------------------------------------------------------ rollout kernel
+GUARD = 8       # elements behind every buffer's stated size, filled with a sentinel that must survive
+
+
+def _guarded(shape, dtype, dev, fill):
+    n = int(np.prod(shape))
+    full = torch.full((n + GUARD,), fill, dtype=dtype, device=dev)
+    return full, full[:n].view(*shape)
+
+
+def _net_struct(params, dev, hidden, gate, padded):
+    from deeprl_amd import cat_mlp
+    offs, chunks, off = {}, [], 0
+    if padded:          # (a leading gap: the offsets are not assumed to start at zero; NaN between the tensors)
+        chunks.append(np.full(3, np.nan, dtype=np.float32))
+        off = 3
+    for k in R.KEYS:
+        v = params[k].reshape(-1)
+        offs[k] = off
+        pad = ((-v.size) % 4 + 1) if padded else 0
+        chunks += [v, np.full(pad, np.nan, dtype=np.float32)]
+        off += v.size + pad
+    flat = torch.from_numpy(np.concatenate(chunks)).to(dev)
+    net = cat_mlp.Net()
+    net.param = flat.data_ptr()
+    net.w1, net.b1, net.w2, net.b2, net.wa, net.ba, net.wc, net.bc = [offs[k] for k in R.KEYS]
+    net.state_dim, net.n_actions, net.hidden, net.gate = 4, 2, hidden, {"relu": 1, "tanh": 2}[gate]
+    return net, flat
+
+
+def _launch(dra, case, start):
+    """One dra_cat_mlp_rollout from the case's start -> dict of host arrays (guards included) and the return code."""
+    from deeprl_amd import cat_mlp
+    from deeprl_amd._lib import lib, stream_ptr
+    dev = dra.Config.DEVICE
+    hidden, gate, n, t_len, horizon, padded, _ = case
+    net, flat = _net_struct(start["params"], dev, hidden, gate, padded)
+    nan = float("nan")
+    spec = dict(env_state=((n, 4), torch.float64, nan), env_counter=((n,), torch.int64, -7), ep_steps=((n,), torch.int32, -7),
+                ep_return=((n,), torch.float64, nan), env_seed=((n,), torch.int64, -7), sampler=((1,), torch.int64, -7),
+                ep_count=((1,), torch.int64, -7), ep_ring=((K.RING_CAP, 3), torch.float64, nan),
+                state=((t_len, n, 4), torch.float32, nan), action=((t_len, n), torch.int64, -7), v=((t_len + 1, n), torch.float32, nan),
+                reward=((t_len, n), torch.float32, nan), mask=((t_len, n), torch.float32, nan))
+    full, view = {}, {}
+    for k, (shape, dt, fill) in spec.items():
+        full[k], view[k] = _guarded(shape, dt, dev, fill)
+    view["env_state"].copy_(torch.from_numpy(start["raw"]))
+    view["env_counter"].zero_(); view["ep_steps"].zero_(); view["ep_return"].zero_()
+    view["env_seed"].copy_(torch.tensor(start["seeds"], dtype=torch.int64))
+    view["sampler"].fill_(K.SAMPLER0); view["ep_count"].fill_(K.RING_COUNT0)
+    io = cat_mlp.RolloutIO()
+    io.env_state, io.env_counter, io.ep_steps = view["env_state"].data_ptr(), view["env_counter"].data_ptr(), view["ep_steps"].data_ptr()
+    io.ep_return, io.env_seed, io.sampler_step = view["ep_return"].data_ptr(), view["env_seed"].data_ptr(), view["sampler"].data_ptr()
+    io.ep_count, io.ep_ring = view["ep_count"].data_ptr(), view["ep_ring"].data_ptr()
+    io.out_state, io.out_action, io.out_v = view["state"].data_ptr(), view["action"].data_ptr(), view["v"].data_ptr()
+    io.out_reward, io.out_mask = view["reward"].data_ptr(), view["mask"].data_ptr()
+    io.env0, io.n_global, io.noise_seed, io.horizon = K.ENV0_EXTRA, n + K.ENV0_EXTRA + 1, K.NOISE_SEED, horizon
+    io.ring_cap, io.reward_coef, io.t_len, io.n_env = K.RING_CAP, 1.0, t_len, n
+    flat_before = flat.cpu().numpy().copy()
+    rc = lib.dra_cat_mlp_rollout.raw(ctypes.byref(net), ctypes.byref(io), stream_ptr())
+    torch.cuda.synchronize()
+    out = {k: v.cpu().numpy() for k, v in full.items()}
+    out["rc"], out["spec"] = rc, spec
+    assert np.array_equal(_bits(flat.cpu().numpy()), _bits(flat_before))        # (the parameter buffer is read only)
+    return out, (net, io, full, view)
+
+
+def _body(out, k):
+    shape = out["spec"][k][0]
+    return out[k][:int(np.prod(shape))].reshape(shape)
+
+
+@pytest.mark.parametrize("case", K.ROLLOUT_CASES, ids=K.case_id)
+def test_rollout_kernel_matches_restatement(dra, case):
+    """dra_cat_mlp_rollout against the restatement: actions equal (the host suite asserts a Gumbel margin >= 1e-4 for every case);
+    stored observations, final environment state, counters, episode steps and returns, rewards, masks, the sampler position and
+    the ring's rows and count equal to the bit; v within 1e-5 of scale; the guard elements behind every buffer untouched; a
+    second launch from the same start gives the same bits everywhere."""
+    hidden, gate, n, t_len, horizon, padded, _ = case
+    want, envs, start = K.restated_rollout(case)
+    out, _ = _launch(dra, case, start)
+    assert out["rc"] == 0
+    assert np.array_equal(_body(out, "action"), want["action"])
+    assert np.array_equal(_bits(_body(out, "state")), _bits(want["state"]))
+    assert np.array_equal(_bits(_body(out, "env_state")), _bits(want["raw_states"]))
+    assert np.array_equal(_body(out, "env_counter"), [e.c for e in envs])
+    assert np.array_equal(_body(out, "ep_steps"), [e.steps for e in envs])
+    assert np.array_equal(_bits(_body(out, "ep_return")), _bits(np.asarray([e.ret for e in envs])))
+    assert np.array_equal(_bits(_body(out, "reward")), _bits(want["reward"])) and np.array_equal(_bits(_body(out, "mask")), _bits(want["mask"]))
+    assert int(_body(out, "sampler")[0]) == K.SAMPLER0 + t_len + 1
+    assert int(_body(out, "ep_count")[0]) == K.RING_COUNT0 + len(want["events"])
+    ring = np.full((K.RING_CAP, 3), np.nan)
+    for i, ev in enumerate(want["events"]):
+        ring[(K.RING_COUNT0 + i) % K.RING_CAP] = ev
+    assert np.array_equal(_bits(_body(out, "ep_ring")), _bits(ring))
+    err = _within(_body(out, "v"), want["v"], "v")
+    record_parity("cat_mlp rollout kernel vs restatement %s (fraction of the bar)" % K.case_id(case), v=err)
+    for k, (shape, dt, fill) in out["spec"].items():
+        tail = out[k][int(np.prod(shape)):]
+        assert tail.size == GUARD and (np.isnan(tail).all() if fill != fill else (tail == fill).all()), k
+    again, _ = _launch(dra, case, start)
+    for k in out["spec"]:
+        assert np.array_equal(_bits(out[k]), _bits(again[k])), k
+
+
+def test_rollout_refuses_unsupported_shapes_and_launches_nothing(dra):
+    from deeprl_amd import cat_mlp
+    from deeprl_amd._lib import lib, stream_ptr
+    case = K.ROLLOUT_CASES[0]
+    _, _, start = K.restated_rollout(case)
+    out, (net, io, full, view) = _launch(dra, case, start)
+    before = {k: v.clone() for k, v in full.items()}
+
+    def refused(**change):
+        n2, io2 = cat_mlp.Net.from_buffer_copy(net), cat_mlp.RolloutIO.from_buffer_copy(io)
+        for k, v in change.items():
+            setattr(n2 if hasattr(n2, k) else io2, k, v)
+        rc = lib.dra_cat_mlp_rollout.raw(ctypes.byref(n2), ctypes.byref(io2), stream_ptr())
+        torch.cuda.synchronize()
+        return rc == -22 and all(torch.equal(_as_int(before[k]), _as_int(full[k])) for k in full)
+
+    assert refused(hidden=48) and refused(hidden=128) and refused(state_dim=5) and refused(n_actions=3) and refused(gate=3)
+    assert refused(n_env=65) and refused(n_env=0) and refused(t_len=0) and refused(horizon=0) and refused(ring_cap=0)
+    assert refused(w2=-1) and refused(n_global=case[2] - 1) and refused(out_v=None) and refused(ep_ring=None)
+
+
+def _as_int(t):
+    return t.view(torch.int64) if t.dtype == torch.float64 else (t.view(torch.int32) if t.dtype == torch.float32 else t)
+
+
+# ------------------------------------------------------------------------------------------ update against the reference
+def _bare_agent(d, g, tag):
+    """An A2CAgent with everything _learn_stacked reads and nothing else (no task: the rollout comes from the fixture)."""
+    import torch.nn.functional as F
+    from deeprl_amd.dist import DataParallel
+    from deeprl_amd.optim import FusedOptimizer
+    discount, tau, ent_w, v_w, clip, lr, t_len, n, _ = [float(x) for x in g[tag + "_cfg"]]
+    cfg = d.Config()
+    cfg.discount, cfg.use_gae, cfg.gae_tau, cfg.entropy_weight, cfg.value_loss_weight = discount, True, tau, ent_w, v_w
+    cfg.gradient_clip, cfg.rollout_length, cfg.num_workers = clip, int(t_len), int(n)
+    agent = d.A2CAgent.__new__(d.A2CAgent)
+    agent.config, agent.grad_hook = cfg, None
+    agent.dp = DataParallel(cfg)
+    agent.network = d.CategoricalActorCriticNet(4, 2, d.FCBody(4, gate=F.tanh))
+    pre = tag + "_init_"
+    agent.network.load_state_dict({k[len(pre):]: torch.from_numpy(g[k]) for k in g.files if k.startswith(pre)})
+    agent.optimizer = torch.optim.RMSprop(agent.network.parameters(), lr)
+    agent._fused = FusedOptimizer.adopt(agent.optimizer)
+    return agent
+
+
+@pytest.mark.parametrize("tag", ["t5n5", "t3n2"])
+def test_update_on_the_device_path_matches_reference_step(dra, tag):
+    """The fixture's initial parameters, states, actions, values, rewards and masks through A2CAgent._learn_stacked, laid out as
+    the rollout kernel leaves them: the parameters after the update against the reference's own A2CAgent.step (rtol 2e-5 / atol
+    2e-6)."""
+    dev = dra.Config.DEVICE
+    g = np.load(FIXTURE)
+    agent = _bare_agent(dra, g, tag)
+    t_len, n = g[tag + "_reward"].shape[:2]
+    up = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to(dev)
+    states = up(g[tag + "_states"][:t_len].reshape(t_len * n, -1))
+    actions = up(g[tag + "_action"].astype(np.int64).reshape(t_len * n))
+    out4 = agent._learn_stacked(states, actions, up(g[tag + "_v"]), up(g[tag + "_reward"]), up(g[tag + "_mask"]))
+    torch.cuda.synchronize()
+    assert np.isfinite(out4.cpu().numpy()).all()
+    worst = 0.0
+    for k, v in agent.network.state_dict().items():
+        got, want = v.cpu().numpy(), g["%s_final_%s" % (tag, k)]
+        worst = max(worst, float(np.max(np.abs(got - want) / (2e-6 + 2e-5 * np.abs(want)))))
+    print("%s: worst parameter error as a fraction of atol + rtol |want|: %.3f" % (tag, worst))
+    record_parity("a2c_feature update vs reference step %s (fraction of the bar)" % tag, params=worst)
+    for k, v in agent.network.state_dict().items():
+        np.testing.assert_allclose(v.cpu().numpy(), g["%s_final_%s" % (tag, k)], rtol=2e-5, atol=2e-6, err_msg=k)
+    agent.dp.close()
+
+
+# ------------------------------------------------------------------------------------------ the agent
+A = K.AGENT
+
+
+def _config(d, device_env, graph=True, horizon=A["horizon"], n_env=A["n_env"], **extra):
+    from deeprl_amd import zoo
+    c = zoo.config("a2c_feature", game=GAME, tag="a2c_feat%d%d" % (device_env, graph), device_env=device_env,
+                   dp_invariant_sampling=True, dp_noise_seed=A["noise_seed"], graph_update=graph,
+                   overrides=dict(num_workers=n_env, rollout_length=A["t_len"], **extra))
+    c.task_fn = lambda: d.Task(c.game, num_envs=c.num_workers, seed=A["task_seed"], synthetic_done_period=horizon)
+    c.log_interval = 10 ** 9
+    return c
+
+
+def _make_agent(d, monkeypatch, device_env, graph=True, **kw):
+    import deeprl_amd.agents as agents_mod
+    rec = _Rec()
+    monkeypatch.setattr(agents_mod, "get_logger", lambda *a, **k: rec)
+    d.random_seed(9)
+    torch.manual_seed(9)
+    torch.cuda.manual_seed_all(9)
+    agent = d.A2CAgent(_config(d, device_env, graph, **kw))
+    # the case's parameters (numpy-seeded: the same on every machine), copied into the optimiser's flat buffer through the views
+    init = K.restated_agent_run()["init"]
+    with torch.no_grad():
+        for k, p in agent.network.state_dict().items():
+            p.copy_(torch.from_numpy(init[k]))
+    return agent, rec
+
+
+def _watch_host(agent, log):
+    raw = agent.task.step
+
+    def step(actions):
+        o = raw(actions)
+        log['actions'].append(np.asarray(actions).copy())
+        log['masks'].append(1.0 - np.asarray(o[2], dtype=np.float32))
+        return o
+    agent.task.step = step
+
+
+def _snapshot(agent, rec):
+    torch.cuda.synchronize()
+    return dict(params={k: v.detach().cpu().numpy().copy() for k, v in agent.network.state_dict().items()},
+                total=agent.total_steps, lines=list(rec.lines), sampler=agent.dp.sampler_state(),
+                rng=np.random.randint(0, 1 << 30, size=3))
+
+
+def _run(d, monkeypatch, device_env, graph=True, steps=A["steps"], **kw):
+    from deeprl_amd.device_env import DeviceCartPoleVec
+    agent, rec = _make_agent(d, monkeypatch, device_env, graph, **kw)
+    assert isinstance(agent.task, DeviceCartPoleVec) == bool(device_env) and (agent._cat_rollout is not None) == bool(device_env)
+    log = dict(actions=[], masks=[])
+    if not device_env:
+        _watch_host(agent, log)
+    for _ in range(steps):
+        agent.step()
+        if device_env:
+            b = agent.task.buffers(A["t_len"])
+            log['actions'] += list(b['action'].cpu().numpy())
+            log['masks'] += list(b['mask'].cpu().numpy().reshape(A["t_len"], -1))
+    events = agent.episodes()
+    out = _snapshot(agent, rec)
+    out.update(actions=np.stack(log['actions']), masks=np.stack(log['masks']), events=events,
+               graphed=agent._dev_graph.graph is not None, launches=agent._cat_rollout.launches if device_env else 0)
+    agent.close()
+    return out
+
+
+@pytest.fixture(scope="module")
+def device_run(dra):
+    """Six steps of the device path with graph replay: shared by the tests below, left unchanged."""
+    mp = pytest.MonkeyPatch()
+    try:
+        return _run(dra, mp, True, True)
+    finally:
+        mp.undo()
+
+
+def _line_events(lines):
+    out = []
+    for ln in lines:
+        if 'episodic_return_train' in ln:
+            w = ln.replace(',', '').split()
+            out.append((int(w[1]), float(w[3])))
+    return out
+
+
+def test_agent_device_rollout_equals_host_environments(dra, monkeypatch, device_run):
+    """A2CAgent on the a2c_feature configuration (4 environments, rollout length 5, episodes of at most 7 steps) over
+    DeviceCartPoleVec -- one rollout launch, graph replay from the third step -- against the same agent stepping envs.CartPole
+    from python with the rank-invariant sampler (the parent commit's path), and against the fp64 restatement: actions, masks,
+    total_steps, the episodic-return log lines (late on the device path, otherwise the same) and the np.random tail equal;
+    parameters within 2e-4 of each tensor's largest magnitude (floor 1e-2)."""
+    a, b = device_run, _run(dra, monkeypatch, False)
+    want = K.restated_agent_run()
+    steps, t_len, n = A["steps"], A["t_len"], A["n_env"]
+    assert a['graphed'] and not b['graphed'] and b['launches'] == 0
+    assert a['launches'] == 3          # two eager rollouts and the capture pass; the replays launch from the graph
+    assert a['total'] == b['total'] == steps * t_len * n
+    assert np.array_equal(a['actions'], b['actions']) and np.array_equal(a['masks'], b['masks'])
+    assert np.array_equal(a['actions'], want['actions'].reshape(steps * t_len, n))
+    assert np.array_equal(a['masks'], want['masks'].reshape(steps * t_len, n))
+    assert a['lines'] == b['lines'] and len(a['lines']) >= 8
+    assert a['events'] == _line_events(b['lines']) and b['events'] == []
+    assert [r for _, r in a['events']] == [r for _, _, r in want['events']]
+    assert np.array_equal(a['rng'], b['rng'])
+    assert a['sampler'] == b['sampler'] == dict(noise_seed=A["noise_seed"], step=steps * (t_len + 1))
+    worst = 0.0
+    for k in a['params']:
+        scale = max(np.abs(b['params'][k]).max(), 1e-2)
+        worst = max(worst, float(np.max(np.abs(a['params'][k] - b['params'][k])) / (2e-4 * scale)))
+    print("device vs host parameters: worst fraction of the bar %.3f" % worst)
+    record_parity("a2c_feature agent device vs host path (fraction of the bar)", params=worst)
+    for k in a['params']:
+        scale = max(np.abs(b['params'][k]).max(), 1e-2)
+        assert np.max(np.abs(a['params'][k] - b['params'][k])) <= 2e-4 * scale, k
+
+
+def test_graph_replay_equals_eager(dra, monkeypatch):
+    """config.graph_update = False keeps every step eager: after 8 steps parameters, actions and events are equal to the bit."""
+    a = _run(dra, monkeypatch, True, graph=True, steps=8)
+    b = _run(dra, monkeypatch, True, graph=False, steps=8)
+    assert a['graphed'] and not b['graphed'] and a['launches'] == 3 and b['launches'] == 8
+    assert a['total'] == b['total'] and a['lines'] == b['lines'] and a['sampler'] == b['sampler'] and a['events'] == b['events']
+    assert np.array_equal(a['actions'], b['actions']) and np.array_equal(a['masks'], b['masks'])
+    for k in a['params']:
+        assert np.array_equal(_bits(a['params'][k]), _bits(b['params'][k])), k
+
+
+def test_save_load_continues_the_run(dra, monkeypatch, device_run, tmp_path):
+    """3 steps, save, load into a fresh agent, 3 more steps == 6 uninterrupted steps, bit for bit.  save() writes what the
+    reference's checkpoint holds plus the noise stream's seed and position and the environments' arrays; the optimiser's running
+    averages and total_steps are no part of a checkpoint, so the test carries them over by hand."""
+    first, rec = _make_agent(dra, monkeypatch, True)
+    for _ in range(3):
+        first.step()
+    name = str(tmp_path / "ckpt")
+    first.save(name)
+    assert os.path.isfile(name + ".sampler")
+    second, rec2 = _make_agent(dra, monkeypatch, True)
+    assert second.dp.sampler_state()['step'] == 0
+    second.load(name)
+    assert second.dp.sampler_state() == dict(noise_seed=A["noise_seed"], step=3 * (A["t_len"] + 1))
+    for key in ("env_state", "env_counter", "ep_steps", "ep_return"):
+        assert torch.equal(getattr(second.task, key), getattr(first.task, key)), key
+    second._fused.state1.copy_(first._fused.state1)
+    second._fused.state2.copy_(first._fused.state2)
+    second._fused.steps, second.total_steps = first._fused.steps, first.total_steps
+    for _ in range(3):
+        second.step()
+    second.drain_episodes()
+    got = _snapshot(second, rec2)
+    first.close()
+    second.close()
+    assert got['total'] == device_run['total'] and got['sampler'] == device_run['sampler']
+    assert rec.lines + got['lines'] == device_run['lines']
+    for k in got['params']:
+        assert np.array_equal(_bits(got['params'][k]), _bits(device_run['params'][k])), k
+
+
+def test_other_agents_keep_their_host_paths(dra, monkeypatch):
+    """PPOAgent and NStepDQNAgent on the new Task step envs.CartPole on the host, as before."""
+    import torch.nn.functional as F
+    import deeprl_amd.agents as agents_mod
+    d = dra
+    monkeypatch.setattr(agents_mod, "get_logger", lambda *a, **k: _Rec())
+
+    def base(tag):
+        c = d.Config()
+        c.merge(dict(game=GAME, log_level=0, tag=tag))
+        c.num_workers = 4
+        c.task_fn = lambda: d.Task(c.game, num_envs=c.num_workers, seed=3, synthetic_done_period=7)
+        c.eval_env = d.Task(c.game, seed=4)
+        c.optimizer_fn = lambda p: torch.optim.RMSprop(p, 0.001)
+        c.discount, c.gradient_clip, c.rollout_length = 0.99, 0.5, 5
+        c.log_interval = 10 ** 9
+        return c
+
+    c = base("a2c_feat_ppo_guard")
+    c.network_fn = lambda: d.CategoricalActorCriticNet(c.state_dim, c.action_dim, d.FCBody(c.state_dim, gate=F.tanh))
+    c.shared_repr, c.use_gae, c.gae_tau, c.entropy_weight = True, True, 0.95, 0.01
+    c.optimization_epochs, c.mini_batch_size, c.ppo_ratio_clip, c.max_steps = 2, 10, 0.2, 1e6
+    d.random_seed(9)
+    agent = d.PPOAgent(c)
+    assert type(agent.task) is d.Task and not getattr(agent.task, 'on_device', False)
+    agent.step()
+    torch.cuda.synchronize()
+    assert agent.total_steps == 5 * 4 and [e.c for e in agent.task.env.envs] == [5] * 4
+    agent.close()
+
+    c = base("a2c_feat_nstep_guard")
+    c.network_fn = lambda: d.VanillaNet(c.action_dim, d.FCBody(c.state_dim))
+    c.random_action_prob = d.LinearSchedule(1.0, 0.05, 1e4)
+    c.target_network_update_freq = 200
+    d.random_seed(9)
+    agent = d.NStepDQNAgent(c)
+    assert type(agent.task) is d.Task and not getattr(agent.task, 'on_device', False)
+    agent.step()
+    torch.cuda.synchronize()
+    assert agent.total_steps == 5 * 4 and [e.c for e in agent.task.env.envs] == [5] * 4
+    agent.close()
+
+
+# ------------------------------------------------------------------------------------------ drain
+def test_drain_reports_what_the_host_path_logs(dra, monkeypatch):
+    """Horizon 3 over 40 agent steps of 5 environments (an episode ends on three steps of every five): the drained events --
+    every 16 agent steps here, and at close -- carry the step numbers and returns of the host path's log lines."""
+    kw = dict(horizon=3, n_env=5, steps=40, episode_drain_interval=16)
+    a, b = _run(dra, monkeypatch, True, **kw), _run(dra, monkeypatch, False, **kw)
+    assert np.array_equal(a['actions'], b['actions']) and np.array_equal(a['masks'], b['masks'])
+    want = _line_events(b['lines'])
+    assert len(want) >= 300
+    assert a['events'] == want and a['lines'] == b['lines']
+    assert all(r == 3.0 for _, r in want)
+
+
+def test_ring_overflow_raises(dra, monkeypatch):
+    from deeprl_amd.device_env import DeviceCartPoleVec
+    monkeypatch.setattr(DeviceCartPoleVec, "RING_CAP", 8)
+    agent, _ = _make_agent(dra, monkeypatch, True, horizon=3, n_env=5, episode_drain_interval=10 ** 9)
+    assert agent.task.ring_cap == 8
+    agent.step()
+    assert len(agent.episodes()) == 5          # 5 environments x 5 steps, horizon 3: one end each (steps 3), within the ring
+    for _ in range(2):
+        agent.step()                           # 15 or more rows pending in a ring of 8
+    with pytest.raises(RuntimeError, match="drain more often"):
+        agent.drain_episodes()
+    agent.task.drained = int(agent.task.ep_count.item())      # (acknowledged: close() drains once more)
+    agent.close()
+
+
+# ------------------------------------------------------------------------------------------ the closed loop
+def test_closed_loop_learns(dra, monkeypatch):
+    """zoo.agent('a2c_feature') on the device path for N_learn environment steps and three fixed seeds: the median over the seeds
+    of the mean return of the last 100 drained episodes must reach 2 x the random policy's mean return.  N_learn is the length at
+    which the REFERENCE's own A2CAgent over envs.CartPole reaches twice that bar in the median of 5 seeds
+    (tests/golden/a2c_feature/learning_reference.json); the random policy's mean is computed by the host suite."""
+    import deeprl_amd.agents as agents_mod
+    from deeprl_amd import zoo
+    from deeprl_amd.device_env import DeviceCartPoleVec
+    rec = json.load(open(os.path.join(GOLDEN, "learning_reference.json")))
+    bar = 2.0 * json.load(open(os.path.join(GOLDEN, "random_policy.json")))["mean"]
+    n_learn = int(rec["n_learn"])
+    assert rec["bar"] == bar
+    monkeypatch.setattr(agents_mod, "get_logger", lambda *a, **k: _Rec())
+    means = []
+    for seed in K.LEARN_SEEDS:
+        dra.random_seed(seed)
+        torch.manual_seed(seed)
+        torch.cuda.manual_seed_all(seed)
+        agent = zoo.agent("a2c_feature", game=GAME, tag="a2c_feat_learn%d" % seed)
+        assert isinstance(agent.task, DeviceCartPoleVec)
+        returns = []
+        while agent.total_steps < n_learn:
+            agent.step()
+            if agent._cat_steps % 512 == 0:
+                returns += [r for _, r in agent.episodes()]
+        returns += [r for _, r in agent.episodes()]
+        assert agent._dev_graph.graph is not None
+        agent.close()
+        means.append(float(np.mean(returns[-K.LAST_EPISODES:])))
+        print("seed %d: %d episodes, mean return of the last %d: %.1f" % (seed, len(returns), K.LAST_EPISODES, means[-1]))
+    median = float(np.median(means))
+    print("median %.1f, bar %.1f (random policy x 2), reference median at %d steps %.1f" % (median, bar, n_learn, rec["medians"][str(n_learn)]))
+    record_parity("a2c_feature closed loop: last-100 mean returns per seed, median, bar", median=median, bar=bar,
+                  **{"seed_%d" % s: m for s, m in zip(K.LEARN_SEEDS, means)})
+    assert median >= bar

@@ -13,6 +13,8 @@ after a warm-up.  Prints one JSON object per line: agent steps/s, env steps/s, g
             config.graph_update False: materialised noisy weights through the plain GEMM, eager launches)
   config 5  a2c_pixel examples.py:361-381 (16 workers), ppo_pixel examples.py:525-550 (8 workers)
             a2c_continuous examples.py:384-404 (16 workers; `_host` = config.device_env False: python environments, module head)
+            a2c_feature examples.py:340-358 (5 workers, classic-CartPole-v0; `_host` = config.device_env False: python
+            environments, one module forward per step)
             n_step_dqn_pixel examples.py:427-447 (16 workers), option_critic_pixel examples.py:471-492 (16 workers)
   ddpg_continuous examples.py:554-583, td3_continuous examples.py:587-617 (one host environment, (400, 300) relu MLPs, Adam 1e-3,
             minibatch 100, a 1M ring; warm_up shortened to 1000 so that the timed window is all updates; the default is
@@ -120,6 +122,19 @@ def a2c_continuous(workers=16, device=True, **switches):
                                                     critic_body=d.FCBody(c.state_dim))
     c.discount, c.use_gae, c.gae_tau, c.entropy_weight, c.rollout_length, c.gradient_clip = 0.99, True, 1.0, 0.01, 5, 5
     c.max_steps = int(2e7)
+    return d.A2CAgent(c), dict(env_per_step=5 * workers, updates_per_step=1)
+
+
+def a2c_feature(workers=5, device=True, **switches):
+    import torch.nn.functional as F
+    c = d.Config()
+    c.merge(dict(game="classic-CartPole-v0", log_level=0, tag="bench", device_env=device, **switches))
+    c.num_workers = workers
+    c.task_fn = lambda: d.Task(c.game, num_envs=c.num_workers, seed=1)
+    c.eval_env = d.Task(c.game, seed=2)
+    c.optimizer_fn = lambda p: torch.optim.RMSprop(p, 0.001)
+    c.network_fn = lambda: d.CategoricalActorCriticNet(c.state_dim, c.action_dim, d.FCBody(c.state_dim, gate=F.tanh))
+    c.discount, c.use_gae, c.gae_tau, c.entropy_weight, c.rollout_length, c.gradient_clip = 0.99, True, 0.95, 0.01, 5, 0.5
     return d.A2CAgent(c), dict(env_per_step=5 * workers, updates_per_step=1)
 
 
@@ -251,6 +266,8 @@ CASES = {
     "ppo_pixel_8_host": lambda: ppo_pixel(8, device=False),
     "a2c_continuous": lambda: a2c_continuous(16),                      # device-resident rollout (csrc/a2c_mlp.hip) + one captured graph
     "a2c_continuous_host": lambda: a2c_continuous(16, device=False),   # 16 python environments stepped one by one, module head
+    "a2c_feature": lambda: a2c_feature(5),                      # device-resident cart-poles (csrc/cat_mlp.hip) + one captured graph
+    "a2c_feature_host": lambda: a2c_feature(5, device=False),   # 5 python cart-poles stepped one by one, one module forward per step
     "ppo_continuous_1": lambda: ppo_continuous(1),
     "ppo_continuous_16": lambda: ppo_continuous(16),                                  # device environments + persistent kernels
     "ppo_continuous_16_host": lambda: ppo_continuous(16, device=False),               # host environments, persistent update kernel
