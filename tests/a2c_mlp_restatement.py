@@ -9,7 +9,7 @@ import math
 import numpy as np
 import torch
 
-from oracle.numerics_oracle import MeanStdNormalizerOracle  # noqa: F401  (re-exported for the tests)
+from oracle.numerics_oracle import MeanStdNormalizerOracle, RunningMeanStdOracle  # noqa: F401  (re-exported for the tests)
 from oracle.ppo_mlp_oracle import ContinuousEnvOracle, gauss_noise  # noqa: F401
 
 F64 = torch.float64
@@ -17,8 +17,8 @@ _GATES = {"relu": torch.relu, "tanh": torch.tanh}
 HALF_LOG_2PI = 0.5 * math.log(2.0 * math.pi)
 
 
-def to64(params, requires_grad=False):
-    return {k: torch.as_tensor(np.asarray(v), dtype=F64).clone().requires_grad_(requires_grad) for k, v in params.items()}
+def to64(params, requires_grad=False, dtype=F64):
+    return {k: torch.as_tensor(np.asarray(v), dtype=dtype).clone().requires_grad_(requires_grad) for k, v in params.items()}
 
 
 def init_params(state_dim, action_dim, hidden, seed):
@@ -64,16 +64,17 @@ def head_grads(z, std, action, g_lp, g_ent):
     return z.grad.numpy(), std.grad.numpy()
 
 
-def forward(p, obs, action=None, noise=None, gate="relu"):
-    """network_heads.py:198-214; `noise`: the standard normals of dist.sample() (action = mean + scale * noise)."""
-    obs = torch.as_tensor(np.asarray(obs), dtype=F64)
+def forward(p, obs, action=None, noise=None, gate="relu", dtype=F64):
+    """network_heads.py:198-214; `noise`: the standard normals of dist.sample() (action = mean + scale * noise).  `dtype`: the
+    type the forward runs in (the parameters `p` are expected in it)."""
+    obs = torch.as_tensor(np.asarray(obs), dtype=dtype)
     z = torch.nn.functional.linear(_body(p, "actor_body", obs, gate), p["fc_action.weight"], p["fc_action.bias"])
     v = torch.nn.functional.linear(_body(p, "critic_body", obs, gate), p["fc_critic.weight"], p["fc_critic.bias"])
     if action is None:
         with torch.no_grad():
-            action = torch.tanh(z) + softplus(p["std"]) * torch.as_tensor(np.asarray(noise), dtype=F64)
+            action = torch.tanh(z) + softplus(p["std"]) * torch.as_tensor(np.asarray(noise), dtype=dtype)
     else:
-        action = torch.as_tensor(np.asarray(action), dtype=F64)
+        action = torch.as_tensor(np.asarray(action), dtype=dtype)
     mean, lp, ent = head(z, p["std"], action)
     return dict(action=action, log_pi_a=lp, entropy=ent, mean=mean, v=v, z=z)
 
@@ -122,14 +123,40 @@ def a2c_update(params, states, actions, reward, mask, discount, tau, entropy_wei
     return new, keep
 
 
+def start_envs(seeds, state_dim, action_dim, horizon, pre_steps=None):
+    """(environments, their raw observations [n, S]) after reset() and, for environment i, pre_steps[i] steps with zero actions:
+    a start whose step counters differ from one environment to the next.  pre_steps None: fresh environments."""
+    envs = [ContinuousEnvOracle(s, state_dim, action_dim, horizon) for s in seeds]
+    raw = []
+    for i, e in enumerate(envs):
+        s = e.reset()
+        for _ in range(pre_steps[i] if pre_steps is not None else 0):
+            s, _, _ = e.step(np.zeros(action_dim, dtype=np.float32))
+        raw.append(s)
+    return envs, np.stack(raw)
+
+
+def warm_normalizer(kind, state_dim, warm_rows, clip=10.0):
+    """(normaliser, statistics [2 S + 1] = mean, var, count) for `kind`: "identity" (None, and the statistics a fresh
+    RunningMeanStd holds), or a MeanStdNormalizerOracle clipping at +-clip that has seen `warm_rows` rows, updating
+    ("meanstd-update") or read-only ("meanstd-readonly") from here on."""
+    if kind == "identity":
+        return None, np.concatenate([np.zeros(state_dim), np.ones(state_dim), [0.0]])
+    norm = MeanStdNormalizerOracle(clip=clip)
+    norm.rms = RunningMeanStdOracle(shape=(1, state_dim))
+    norm(np.random.RandomState(5).randn(warm_rows, state_dim) * 0.05 + 0.01)
+    norm.read_only = kind == "meanstd-readonly"
+    return norm, np.concatenate([norm.rms.mean.reshape(-1), norm.rms.var.reshape(-1), [norm.rms.count]])
+
+
 def rollout(params, envs, raw_states, normalizer, t_len, noise_seed, sampler_step0, gate="relu", n_global=None, env0=0,
-            reward_coef=1.0):
+            reward_coef=1.0, dtype=F64):
     """A2C_agent.py:22-41 over ContinuousEnvOracle environments: per step the normaliser is called on the CURRENT raw observation
     (it folds it into its statistics unless read-only), the policy acts on the float32 result, the environments step; the
     bootstrap observation is normalised (and folded) too.  normalizer None: the identity.  Returns float arrays state [T, N, S],
     action [T, N, A], v [T + 1, N], reward / mask [T, N], cur_state (the normalised bootstrap observation), raw_states, and
-    the number of terminals."""
-    p = to64(params)
+    the number of terminals.  `dtype`: the type both forwards run in (environments and normaliser stay fp64)."""
+    p = to64(params, dtype=dtype)
     n = len(envs)
     n_global = n_global or n
     a_dim = p["fc_action.weight"].shape[0]
@@ -140,7 +167,7 @@ def rollout(params, envs, raw_states, normalizer, t_len, noise_seed, sampler_ste
         for t in range(t_len):
             x = norm(raw)
             noise = gauss_noise(noise_seed, sampler_step0 + t, n_global, env0 + np.arange(n), a_dim)
-            pred = forward(p, x, noise=noise, gate=gate)
+            pred = forward(p, x, noise=noise, gate=gate, dtype=dtype)
             acts = pred["action"].numpy()
             nxt, rew, done = [], [], []
             for i, e in enumerate(envs):
@@ -151,7 +178,7 @@ def rollout(params, envs, raw_states, normalizer, t_len, noise_seed, sampler_ste
             out["mask"].append(np.asarray(1 - np.asarray(done), dtype=np.float32))
             raw = np.stack(nxt)
         x = norm(raw)
-        out["v"].append(forward(p, x, noise=np.zeros((n, a_dim)), gate=gate)["v"].numpy().reshape(-1))
+        out["v"].append(forward(p, x, noise=np.zeros((n, a_dim)), gate=gate, dtype=dtype)["v"].numpy().reshape(-1))
     res = {k: np.stack(v) for k, v in out.items()}
     res["cur_state"], res["raw_states"] = x, raw
     res["terminals"] = int((res["mask"] == 0).sum())

@@ -13,6 +13,7 @@ from parity_log import record_parity
 
 import a2c_mlp_cases as K
 import a2c_mlp_restatement as R
+from a2c_mlp_edge_cases import STD_VALUES, head_case as _head_case  # noqa: F401  (one generator for both head suites)
 
 pytestmark = pytest.mark.gpu
 
@@ -55,23 +56,6 @@ def _within(got, want, what):
 
 
 # ------------------------------------------------------------------------------------------ head kernels
-STD_VALUES = (-8.0, 0.0, 3.0, 19.9, 20.1, 30.0)       # both sides of softplus's threshold; scale from 3e-4 to 30
-
-
-def _head_case(n, a):
-    rs = np.random.RandomState(100 * n + a)
-    std = np.asarray([STD_VALUES[(i + n) % len(STD_VALUES)] for i in range(a)], dtype=np.float32)
-    z = rs.randn(n, a) * 1.5
-    sat = rs.rand(n, a) < 0.4                           # means near +-1: the tanh saturates
-    z = np.where(sat, np.sign(z) * rs.uniform(3.0, 9.0, size=(n, a)), z).astype(np.float32)
-    scale = R.softplus(torch.tensor(std, dtype=torch.float64)).numpy()
-    k = rs.uniform(-6.0, 6.0, size=(n, a))
-    k.flat[0], k.flat[-1] = 6.0, -6.0                   # up to 6 sigma from the mean
-    action = (np.tanh(z.astype(np.float64)) + k * scale).astype(np.float32)
-    g_lp, g_ent = rs.randn(n, 1).astype(np.float32), rs.randn(n, 1).astype(np.float32)
-    return z, std, action, g_lp, g_ent
-
-
 @pytest.mark.parametrize("n,a", [(1, 1), (67, 7), (80, 6), (256, 16)])
 def test_gauss_head_kernels_match_restatement(dra, n, a):
     """dra_gauss_head_fwd / _bwd against the fp64 restatement: mean, log_pi_a, entropy, dz and dstd within 1e-5 of each tensor's
@@ -117,13 +101,14 @@ def _forward_backward(net, obs, action, g):
             {k: p.grad.detach().cpu().numpy().copy() for k, p in net.named_parameters()})
 
 
-def test_fused_head_function_matches_module_path(dra):
+@pytest.mark.parametrize("n", [80, 320])
+def test_fused_head_function_matches_module_path(dra, n):
     """GaussianActorCriticNet.forward(obs, action) with fused_gauss_head on against the same network with it off (torch's
-    tanh / softplus / Normal): all five outputs and every parameter's gradient within 1e-5 of scale."""
+    tanh / softplus / Normal): all five outputs and every parameter's gradient within 1e-5 of scale.  80 rows are the
+    a2c_continuous update; 320 rows (64 workers x 5 steps) take the head kernels past one workgroup of rows."""
     dev = dra.Config.DEVICE
     net = _gauss_net(dra)
     rs = np.random.RandomState(8)
-    n = 80
     obs = torch.from_numpy(rs.randn(n, 17).astype(np.float32)).to(dev)
     with torch.no_grad():
         action = net(obs)['action'].clone()
@@ -136,7 +121,7 @@ def test_fused_head_function_matches_module_path(dra):
     assert sorted(got_out) == sorted(want_out) == ['action', 'entropy', 'log_pi_a', 'mean', 'v']
     errs = {k: _within(got_out[k], want_out[k], k) for k in want_out}
     errs.update({"grad " + k: _within(got_grad[k], want_grad[k], "grad " + k) for k in want_grad})
-    record_parity("fused gauss head Function vs module path (fraction of the bar)", **errs)
+    record_parity("fused gauss head Function vs module path [%d rows] (fraction of the bar)" % n, **errs)
     assert np.abs(want_grad['std']).max() > 1e-3 and np.abs(want_grad['actor_body.layers.0.weight']).max() > 1e-4
 
 
