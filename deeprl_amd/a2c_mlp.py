@@ -9,11 +9,12 @@ There is no CPU / eager implementation here: without the HIP library every call 
 import ctypes
 
 import torch
-import torch.nn.functional as F
 
-from ._lib import lib, stream_ptr
-
-GATES = {F.relu: 1, torch.relu: 1, torch.tanh: 2, F.tanh: 2}      # ops.ACT codes
+from . import mlp_rollout
+from ._lib import lib
+from .device_env import DeviceContinuousVec
+from .mlp_rollout import GATES, body_params, fc_body, head_out      # noqa: F401  (GATES: this module's public name)
+from .support import Config
 
 
 class Net(ctypes.Structure):
@@ -44,28 +45,17 @@ def shape(network):
     """(state_dim, action_dim, hidden, gate code) when `network` is a GaussianActorCriticNet whose phi_body is the identity and
     whose actor / critic bodies are two-layer FCBody stacks of one width with the same relu or tanh gate, plain Linear layers
     with biases; else None."""
-    from .nets import DummyBody, FCBody, GaussianActorCriticNet, Linear
+    from .nets import DummyBody, GaussianActorCriticNet
     if type(network) is not GaussianActorCriticNet or type(network.phi_body) is not DummyBody:
         return None
-    bodies = (network.actor_body, network.critic_body)
-    for b in bodies:
-        if type(b) is not FCBody or b.noisy_linear or b.gate not in GATES or len(b.layers) != 2:
-            return None
-        if any(type(layer) is not Linear or layer.bias is None for layer in b.layers):
-            return None
-    a, c = bodies
-    if GATES[a.gate] != GATES[c.gate]:
+    actor, critic = fc_body(network.actor_body), fc_body(network.critic_body)
+    if actor is None or actor != critic or actor[1] != actor[2]:
         return None
-    s_dim, hidden = a.layers[0].weight.shape[1], a.layers[0].weight.shape[0]
-    if not all(tuple(b.layers[0].weight.shape) == (hidden, s_dim) and tuple(b.layers[1].weight.shape) == (hidden, hidden)
-               for b in bodies):
+    s_dim, hidden, _, gate = actor
+    a_dim = head_out(network.fc_action, hidden)
+    if a_dim is None or head_out(network.fc_critic, hidden) != 1:
         return None
-    heads = (network.fc_action, network.fc_critic)
-    if any(type(h) is not Linear or h.bias is None for h in heads):
-        return None
-    if network.fc_action.weight.shape[1] != hidden or tuple(network.fc_critic.weight.shape) != (1, hidden):
-        return None
-    return int(s_dim), int(network.fc_action.weight.shape[0]), int(hidden), GATES[a.gate]
+    return s_dim, a_dim, hidden, gate
 
 
 def supported(state_dim, action_dim, hidden, n_env, gate):
@@ -73,66 +63,43 @@ def supported(state_dim, action_dim, hidden, n_env, gate):
     return lib.dra_a2c_mlp_supported.raw(int(state_dim), int(action_dim), int(hidden), int(n_env), int(gate)) == 0
 
 
+def _fields(net):
+    a, c = body_params(net.actor_body), body_params(net.critic_body)
+    return list(zip(("a_w1", "a_b1", "a_w2", "a_b2", "a_w3", "a_b3", "c_w1", "c_b1", "c_w2", "c_b2", "c_w3", "c_b3", "off_std"),
+                    a + [net.fc_action.weight, net.fc_action.bias] + c + [net.fc_critic.weight, net.fc_critic.bias, net.std]))
+
+
 def eligible(agent, supported_fn=supported):
-    """The network shape when A2CAgent may move `agent.task` to the device (None: it keeps the host path).  Everything but
-    the task itself (device_env.DeviceContinuousVec.eligible) is decided here."""
-    cfg = agent.config
-    if getattr(cfg, 'fused_a2c_mlp', True) is False or agent.dp.active or agent.grad_hook is not None:
-        return None
-    shp = shape(agent.network)
-    if shp is None:
-        return None
-    flat = agent._fused.flat
-    net = agent.network
-    need = [l.weight for b in (net.actor_body, net.critic_body) for l in b.layers] + \
-           [l.bias for b in (net.actor_body, net.critic_body) for l in b.layers] + \
-           [net.fc_action.weight, net.fc_action.bias, net.fc_critic.weight, net.fc_critic.bias, net.std]
-    if any(all(p is not q for q in flat.params) for p in need):      # one optimiser over every parameter the kernel reads
-        return None
-    if not supported_fn(shp[0], shp[1], shp[2], int(cfg.num_workers), shp[3]):
-        return None
-    return shp
+    """The network shape when A2CAgent may move `agent.task` to the device (None: it keeps the host path, silently).  Everything
+    but the task itself (device_env.DeviceContinuousVec.eligible) is decided here."""
+    return shape(agent.network) if mlp_rollout.why_not(Rollout, agent, supported_fn) is None else None
 
 
-class Rollout:
+class Rollout(mlp_rollout.Rollout):
     """dra_a2c_mlp_rollout over a DeviceContinuousVec and the agent's flat parameter buffer."""
+    SWITCH, ENTRY, VEC = 'fused_a2c_mlp', 'dra_a2c_mlp_rollout', DeviceContinuousVec
+    NETWORK = "GaussianActorCriticNet over two two-layer relu / tanh FCBody stacks of one width with plain heads"
+    Net, IO, DIMS, ACTION_VIEW = Net, RolloutIO, ("state_dim", "action_dim", "hidden", "gate"), (-1,)
+    network_shape, fields, supported = staticmethod(shape), staticmethod(_fields), staticmethod(supported)
 
-    def __init__(self, agent, shp):
-        self.agent = agent
-        self.shape = shp
-        self.launches = 0
-
-    def net_struct(self):
+    def attach(self):
+        """Observations, counters and the observation statistics move to the device; the update's Gaussian head becomes one
+        kernel each way."""
         a = self.agent
-        net, flat = a.network, a._fused.flat
-        n = Net()
-        n.param = flat.flat.data_ptr()
-        ab, cb = net.actor_body.layers, net.critic_body.layers
-        off = flat.offset_of
-        n.a_w1, n.a_b1, n.a_w2, n.a_b2 = off(ab[0].weight), off(ab[0].bias), off(ab[1].weight), off(ab[1].bias)
-        n.a_w3, n.a_b3 = off(net.fc_action.weight), off(net.fc_action.bias)
-        n.c_w1, n.c_b1, n.c_w2, n.c_b2 = off(cb[0].weight), off(cb[0].bias), off(cb[1].weight), off(cb[1].bias)
-        n.c_w3, n.c_b3 = off(net.fc_critic.weight), off(net.fc_critic.bias)
-        n.off_std = off(net.std)
-        n.state_dim, n.action_dim, n.hidden, n.gate = self.shape
-        return n
+        a.task = DeviceContinuousVec(a.task, a.states, a.config.state_normalizer)
+        a.network.fused_gauss_head = True
 
-    def run(self, t_len, read_only):
-        """One rollout launch on the current stream; returns the task's buffers (state, action, v, reward, mask)."""
+    def begin_step(self, t_len):
+        """Episode reporting: rewards and terminals are hashes of the counters, so the host's shadow of them knows the episodes
+        that end inside this rollout before it is launched (BaseAgent.record_online_return at the step the episode ended)."""
         a = self.agent
-        task, dp, config = a.task, a.dp, a.config
-        b = task.buffers(t_len)
-        io = RolloutIO()
-        io.env_state, io.env_counter, io.env_seed = task.env_state.data_ptr(), task.env_counter.data_ptr(), task.env_seed.data_ptr()
-        io.rms, io.cur_state, io.sampler_step = task.rms.data_ptr(), task.cur_state.data_ptr(), dp.step_dev.data_ptr()
-        io.out_state, io.out_action, io.out_v = b['state'].data_ptr(), b['action'].data_ptr(), b['v'].data_ptr()
-        io.out_reward, io.out_mask = b['reward'].data_ptr(), b['mask'].data_ptr()
-        io.env0, io.n_global, io.noise_seed, io.horizon = dp.lo, dp.global_workers, a._noise_seed, task.horizon
-        io.reward_coef, io.rms_epsilon, io.rms_clip = float(config.reward_normalizer.coef), task.rms_epsilon, task.rms_clip
-        io.rms_update = 1 if (task.rms_kind == 'meanstd' and not read_only) else 0
-        io.t_len, io.n_env = int(t_len), task.num_envs
-        net = self.net_struct()
-        lib.dra_a2c_mlp_rollout(ctypes.byref(net), ctypes.byref(io), stream_ptr())
-        self.launches += 1
-        return b
+        events = a.task.shadow(t_len)
+        if a.dp.step_dev is None:
+            a.dp.step_dev = torch.zeros(1, dtype=torch.int64, device=Config.DEVICE)
+        for t, i, ret in events:
+            a.log_train_return(ret, a.total_steps + t * a.dp.global_workers + i)
 
+    def signature(self):
+        """What the captured launch has baked in besides the optimizer's hyper-parameters (_OnPolicyGraph's own key): whether the
+        normaliser's statistics are left alone (fill_io's read_only), and the seed of the noise stream."""
+        return bool(getattr(self.agent.config.state_normalizer, 'read_only', False)), int(self.agent._noise_seed)

@@ -132,9 +132,12 @@ class BaseAgent:
             raise NotImplementedError
         ret = info['episodic_return']
         if ret is not None:
-            at = self.total_steps + offset
-            self.logger.add_scalar('episodic_return_train', ret, at)
-            self.logger.info('steps %d, episodic_return_train %s' % (at, ret))
+            self.log_train_return(ret, self.total_steps + offset)
+
+    def log_train_return(self, ret, at):
+        """The reference's two 'episodic_return_train' lines for an episode that ended at step `at`."""
+        self.logger.add_scalar('episodic_return_train', ret, at)
+        self.logger.info('steps %d, episodic_return_train %s' % (at, ret))
 
     def switch_task(self):
         """config.tasks: consecutive equal shares of max_steps per task."""
@@ -1394,38 +1397,28 @@ class A2CAgent(BaseAgent):
         self.network.rollout_fc4_slices = bool(getattr(config, 'rollout_fc4_slices', True))
         # action noise of the device rollout: the rank-invariant stream when one is configured, else a seed of its own
         self._noise_seed = self.dp.noise_seed
-        self._mlp_rollout, self._mlp_sig = None, None
-        from .device_env import DeviceContinuousVec
-        if DeviceContinuousVec.eligible(self.task, config):
-            # synthetic continuous-control environments under GaussianActorCriticNet over two small MLPs (a2c_continuous,
-            # examples.py:384-404): observations, counters and the observation statistics move to the device; a rollout is one
-            # launch (csrc/a2c_mlp.hip) and the update's Gaussian head one kernel each way (_step_device_mlp)
-            from . import a2c_mlp
-            shape = a2c_mlp.eligible(self)
-            if shape is not None:
-                self.task = DeviceContinuousVec(self.task, self.states, config.state_normalizer)
-                self.states = None
-                self.network.fused_gauss_head = True
-                self._mlp_rollout = a2c_mlp.Rollout(self, shape)
-        self._cat_rollout, self._cat_sig, self._cat_steps = None, None, 0
-        self._ep_anchor, self._ep_log = None, collections.deque(maxlen=16384)
-        from .device_env import DeviceCartPoleVec
-        if DeviceCartPoleVec.eligible(self.task, config):
-            # cart-pole environments under CategoricalActorCriticNet over a small FCBody (a2c_feature, examples.py:340-358): the
-            # environments move to the device, a rollout is one launch (csrc/cat_mlp.hip), episode ends come back through the
-            # device's episode ring (_step_device_cat)
-            from . import cat_mlp
-            why = cat_mlp.why_not(self)
-            if why is None:
-                self.task = DeviceCartPoleVec(self.task)
-                self.states = None
-                if self.dp.step_dev is None:      # the rank-invariant sampler's position: the kernel reads and advances it
-                    self.dp.step_dev = torch.zeros(1, dtype=torch.int64, device=Config.DEVICE)
-                self._sampler_host = int(self.dp.step_dev.item())
-                self._cat_rollout = cat_mlp.Rollout(self, cat_mlp.shape(self.network))
-            elif getattr(config, 'fused_a2c_cat', True) is not False:
-                getattr(self.logger, 'warning', self.logger.info)(
-                    'the cart-pole environments stay on the host and this agent keeps the module path: %s' % why)
+        self._cat_steps, self._ep_anchor, self._ep_log = 0, None, collections.deque(maxlen=16384)
+        # one launch per rollout over device-resident environments (_step_device_rollout) -- a2c_continuous, examples.py:384-404:
+        # synthetic continuous-control environments under GaussianActorCriticNet over two small MLPs (csrc/a2c_mlp.hip);
+        # a2c_feature, examples.py:340-358: cart-poles under CategoricalActorCriticNet over a small FCBody (csrc/cat_mlp.hip)
+        from . import a2c_mlp, cat_mlp
+        self._mlp_rollout = self._adopt_rollout(a2c_mlp.Rollout)
+        self._cat_rollout = self._adopt_rollout(cat_mlp.Rollout)
+
+    def _adopt_rollout(self, kind):
+        """A `kind` rollout with self.task moved to the device when the task, the configuration and this agent allow it; else
+        None (the host path)."""
+        from .mlp_rollout import why_not
+        if not kind.VEC.eligible(self.task, self.config):
+            return None
+        why = why_not(kind, self)
+        if why is not None:
+            kind.stays_on_host(self, why)
+            return None
+        rollout = kind(self, kind.network_shape(self.network))
+        rollout.attach()
+        self.states = None
+        return rollout
 
     def close(self):
         self.drain_episodes()
@@ -1442,7 +1435,7 @@ class A2CAgent(BaseAgent):
         episode steps, returns, the episode ring), so that a loaded run continues bit for bit."""
         self.drain_episodes()
         BaseAgent.save(self, filename)
-        if (self._mlp_rollout is not None or self._cat_rollout is not None) and self.dp.is_main:
+        if self._device_rollout() is not None and self.dp.is_main:
             state = self.dp.sampler_state()
             if self._cat_rollout is not None:
                 state['envs'] = self.task.state_dict()
@@ -1451,7 +1444,7 @@ class A2CAgent(BaseAgent):
 
     def load(self, filename):
         BaseAgent.load(self, filename)
-        if (self._mlp_rollout is not None or self._cat_rollout is not None) and os.path.isfile(filename + '.sampler'):
+        if self._device_rollout() is not None and os.path.isfile(filename + '.sampler'):
             with open(filename + '.sampler', 'rb') as f:
                 state = pickle.load(f)
             self.dp.load_sampler_state(state, Config.DEVICE)
@@ -1476,8 +1469,7 @@ class A2CAgent(BaseAgent):
         for s, i, ret in self.task.drain():
             k, t = divmod(s - s0, t_len + 1)
             at = total0 + (k * t_len + t) * n + i
-            self.logger.add_scalar('episodic_return_train', ret, at)
-            self.logger.info('steps %d, episodic_return_train %s' % (at, ret))
+            self.log_train_return(ret, at)
             out.append((at, ret))
         self._ep_log.extend(out)
         return out
@@ -1490,63 +1482,33 @@ class A2CAgent(BaseAgent):
         self._ep_log.clear()
         return out
 
-    def _step_device_cat(self):
-        """step() over device_env.DeviceCartPoleVec: A2C_agent.py:22-41 is ONE launch (dra_cat_mlp_rollout: per step the forward,
-        the Gumbel-max action, the environment step), then _learn_stacked on the rollout's buffers -- after _OnPolicyGraph.WARMUP
-        eager rollouts both are replayed from one captured graph (a single stream, no parallel branches).  Nothing comes back to
-        the host inside a step; the episodes that ended are drained every config.episode_drain_interval agent steps."""
-        from collections import namedtuple
-        config, task, dp = self.config, self.task, self.dp
-        t_len = int(config.rollout_length)
-        if self._ep_anchor is None or self._ep_anchor[2] != t_len:
-            self.drain_episodes()       # (what is pending was appended under the old rollout length)
-            self._ep_anchor = (self._sampler_host, self.total_steps, t_len)
-        self._sampler_host += t_len + 1
-        self.total_steps += t_len * dp.global_workers
-        sig = int(self._noise_seed)     # what the captured launch has baked in besides the optimizer's hyper-parameters
-        if sig != self._cat_sig:
-            self._dev_graph.graph, self._cat_sig = None, sig
-        plan = namedtuple('CatPlan', ['counters', 't_len'])(task.env_counter, t_len)
-        self.last_loss = self._dev_graph.run(plan, self._cat_compute)
-        self._cat_steps += 1
-        if self._cat_steps % max(1, int(getattr(config, 'episode_drain_interval', 64))) == 0:
-            self.drain_episodes()
+    def _device_rollout(self):
+        return self._mlp_rollout or self._cat_rollout
 
-    def _cat_compute(self, plan):
-        b = self._cat_rollout.run(plan.t_len)
+    def _step_device_rollout(self):
+        """step() over device_env.DeviceContinuousVec / DeviceCartPoleVec: A2C_agent.py:22-41 is ONE launch (dra_a2c_mlp_rollout /
+        dra_cat_mlp_rollout: per step the forwards, the action, the environment step), then _learn_stacked on the rollout's
+        buffers -- after _OnPolicyGraph.WARMUP eager rollouts both are replayed from one captured graph (a single stream, no
+        parallel branches).  Nothing comes back to the host inside a step.  What differs is the rollout's own: the episodes come
+        from the host's shadow of rewards / terminals ahead of the launch (a2c_mlp.Rollout.begin_step) or from the device's
+        ring, drained every config.episode_drain_interval agent steps (cat_mlp.Rollout.begin_step / end_step)."""
+        from .mlp_rollout import Plan
+        rollout = self._device_rollout()
+        t_len = int(self.config.rollout_length)
+        rollout.begin_step(t_len)
+        self.total_steps += t_len * self.dp.global_workers
+        sig = rollout.signature()
+        if sig != rollout.sig:
+            self._dev_graph.graph, rollout.sig = None, sig
+        self.last_loss = self._dev_graph.run(Plan(self.task.env_counter, t_len), self._rollout_learn)
+        rollout.end_step()
+
+    def _rollout_learn(self, plan):
+        rollout = self._device_rollout()
+        b = rollout.run(plan.t_len)
         self._rollout_step += plan.t_len
         rows = plan.t_len * self.task.num_envs
-        return self._learn_stacked(b['state'].view(rows, -1), b['action'].view(rows), b['v'], b['reward'], b['mask'])
-
-    def _step_device_mlp(self):
-        """step() over device_env.DeviceContinuousVec: A2C_agent.py:22-41 is ONE launch (dra_a2c_mlp_rollout: per step the
-        normalised observation, both forwards, action = mean + softplus(std) * noise, environment step), then _learn_stacked on
-        the rollout's buffers -- after _OnPolicyGraph.WARMUP eager rollouts both are replayed from one captured graph (a single
-        stream, no parallel branches).  The host keeps a shadow of rewards / terminals for the episodic-return log lines."""
-        from collections import namedtuple
-        config, task, dp = self.config, self.task, self.dp
-        t_len = int(config.rollout_length)
-        events = task.shadow(t_len)
-        if dp.step_dev is None:
-            dp.step_dev = torch.zeros(1, dtype=torch.int64, device=Config.DEVICE)
-        for t, i, ret in events:        # BaseAgent.record_online_return at the step the episode ended
-            at = self.total_steps + t * dp.global_workers + i
-            self.logger.add_scalar('episodic_return_train', ret, at)
-            self.logger.info('steps %d, episodic_return_train %s' % (at, ret))
-        self.total_steps += t_len * dp.global_workers
-        # what the captured launch has baked in besides the optimizer's hyper-parameters (_OnPolicyGraph's own key): whether
-        # the normaliser's statistics are updated, and the seed of the noise stream
-        sig = (bool(getattr(config.state_normalizer, 'read_only', False)), int(self._noise_seed))
-        if sig != self._mlp_sig:
-            self._dev_graph.graph, self._mlp_sig = None, sig
-        plan = namedtuple('MlpPlan', ['counters', 't_len'])(task.env_counter, t_len)
-        self.last_loss = self._dev_graph.run(plan, self._mlp_compute)
-
-    def _mlp_compute(self, plan):
-        b = self._mlp_rollout.run(plan.t_len, self._mlp_sig[0])
-        self._rollout_step += plan.t_len
-        rows = plan.t_len * self.task.num_envs
-        return self._learn_stacked(b['state'].view(rows, -1), b['action'].view(rows, -1), b['v'], b['reward'], b['mask'])
+        return self._learn_stacked(b['state'].view(rows, -1), b['action'].view(rows, *rollout.ACTION_VIEW), b['v'], b['reward'], b['mask'])
 
     def _step_device(self):
         """step() over device-resident environments: the host lays the rollout out (counters, rewards, terminals of every
@@ -1653,10 +1615,8 @@ class A2CAgent(BaseAgent):
 
     def step(self):
         if getattr(self.task, 'on_device', False):
-            if self._mlp_rollout is not None:
-                return self._step_device_mlp()
-            if self._cat_rollout is not None:
-                return self._step_device_cat()
+            if self._device_rollout() is not None:
+                return self._step_device_rollout()
             return self._step_device()
         config = self.config
         states = self.states
@@ -2063,20 +2023,11 @@ class PPOAgent(BaseAgent):
         cfg, actor, critic = self._mlp.structs()
         self._mlp.sync_counts()
         io = RolloutIO()
-        io.env_state, io.env_counter, io.env_seed = task.env_state.data_ptr(), task.env_counter.data_ptr(), task.env_seed.data_ptr()
-        io.rms, io.cur_state, io.sampler_step = task.rms.data_ptr(), task.cur_state.data_ptr(), dp.step_dev.data_ptr()
-        io.out_state, io.out_action, io.out_log_pi_a = b['state'].data_ptr(), b['action'].data_ptr(), b['log_pi_a'].data_ptr()
-        io.out_v, io.out_reward, io.out_mask = b['v'].data_ptr(), b['reward'].data_ptr(), b['mask'].data_ptr()
-        io.env0, io.n_global, io.noise_seed, io.horizon = dp.lo, dp.global_workers, self._noise_seed, task.horizon
-        io.reward_coef, io.rms_epsilon, io.rms_clip = float(config.reward_normalizer.coef), task.rms_epsilon, task.rms_clip
-        io.rms_update = 1 if (task.rms_kind == 'meanstd' and not config.state_normalizer.read_only) else 0
-        io.t_len, io.n_env = t_len, n
+        task.fill_io(io, self, t_len, config.state_normalizer.read_only)
         lib.dra_ppo_mlp_rollout(ctypes.byref(cfg), ctypes.byref(actor), ctypes.byref(critic), ctypes.byref(io), stream_ptr())
         self._rollout_step += t_len + 1
         for t, i, ret in events:        # BaseAgent.record_online_return at the step the episode ended
-            at = self.total_steps + t * dp.global_workers + i
-            self.logger.add_scalar('episodic_return_train', ret, at)
-            self.logger.info('steps %d, episodic_return_train %s' % (at, ret))
+            self.log_train_return(ret, self.total_steps + t * dp.global_workers + i)
         self.total_steps += t_len * dp.global_workers
         adv, ret = ops.gae(b['reward'], b['mask'], b['v'], config.discount, config.gae_tau, config.use_gae)
         entry_cls = namedtuple('Entry', ['state', 'action', 'log_pi_a', 'ret', 'advantage'])

@@ -9,11 +9,12 @@ parameter buffer and launches a rollout (A2C_agent.py:22-41: one launch instead 
 import ctypes
 
 import torch
-import torch.nn.functional as F
 
-from ._lib import lib, stream_ptr
-
-GATES = {F.relu: 1, torch.relu: 1, torch.tanh: 2, F.tanh: 2}      # ops.ACT codes
+from . import mlp_rollout
+from ._lib import lib
+from .device_env import DeviceCartPoleVec
+from .mlp_rollout import GATES, body_params, fc_body, head_out      # noqa: F401  (GATES: this module's public name)
+from .support import Config
 
 
 class Net(ctypes.Structure):
@@ -41,25 +42,21 @@ def shape(network):
     """(state_dim, n_actions, hidden, gate code) when `network` is a CategoricalActorCriticNet whose phi_body is a two-layer FCBody
     of one width with a relu or tanh gate, whose actor / critic bodies are identities and whose heads are plain Linear layers
     with biases; else None."""
-    from .nets import CategoricalActorCriticNet, DummyBody, FCBody, Linear
+    from .nets import CategoricalActorCriticNet, DummyBody
     if type(network) is not CategoricalActorCriticNet:
         return None
     if type(network.actor_body) is not DummyBody or type(network.critic_body) is not DummyBody:
         return None
-    b = network.phi_body
-    if type(b) is not FCBody or b.noisy_linear or b.gate not in GATES or len(b.layers) != 2:
+    body = fc_body(network.phi_body)
+    if body is None or body[1] != body[2]:
         return None
-    if any(type(layer) is not Linear or layer.bias is None for layer in b.layers):
+    s_dim, hidden, _, gate = body
+    n_actions = head_out(network.fc_action, hidden)
+    if n_actions is None or head_out(network.fc_critic, hidden) != 1:
         return None
-    hidden, s_dim = b.layers[0].weight.shape
-    if tuple(b.layers[1].weight.shape) != (hidden, hidden):
+    if network.fc_action.fused_act is not None or network.fc_critic.fused_act is not None:
         return None
-    heads = (network.fc_action, network.fc_critic)
-    if any(type(h) is not Linear or h.bias is None or h.fused_act is not None for h in heads):
-        return None
-    if network.fc_action.weight.shape[1] != hidden or tuple(network.fc_critic.weight.shape) != (1, hidden):
-        return None
-    return int(s_dim), int(network.fc_action.weight.shape[0]), int(hidden), GATES[b.gate]
+    return s_dim, n_actions, hidden, gate
 
 
 def supported(state_dim, n_actions, hidden, n_env, gate):
@@ -67,32 +64,15 @@ def supported(state_dim, n_actions, hidden, n_env, gate):
     return lib.dra_cat_mlp_supported.raw(int(state_dim), int(n_actions), int(hidden), int(n_env), int(gate)) == 0
 
 
-def _params(net):
-    b = net.phi_body.layers
-    return [b[0].weight, b[0].bias, b[1].weight, b[1].bias, net.fc_action.weight, net.fc_action.bias, net.fc_critic.weight,
-            net.fc_critic.bias]
+def _fields(net):
+    return list(zip(("w1", "b1", "w2", "b2", "wa", "ba", "wc", "bc"),
+                    body_params(net.phi_body) + [net.fc_action.weight, net.fc_action.bias, net.fc_critic.weight, net.fc_critic.bias]))
 
 
 def why_not(agent, supported_fn=supported):
     """None when A2CAgent may run `agent` on the rollout kernel, else the first reason it may not (everything but the task
     itself, which device_env.DeviceCartPoleVec.eligible decides)."""
-    cfg = agent.config
-    if getattr(cfg, 'fused_a2c_cat', True) is False:
-        return "config.fused_a2c_cat is off"
-    if agent.dp.active:
-        return "the agent is data parallel"
-    if agent.grad_hook is not None:
-        return "a grad_hook is installed"
-    shp = shape(agent.network)
-    if shp is None:
-        return "the network is not CategoricalActorCriticNet over a two-layer relu / tanh FCBody with plain heads"
-    flat = agent._fused.flat
-    if any(all(p is not q for q in flat.params) for p in _params(agent.network)):
-        return "one optimiser does not own every parameter the kernel reads"
-    if not supported_fn(shp[0], shp[1], shp[2], int(cfg.num_workers), shp[3]):
-        return "dra_cat_mlp_rollout is not built for state_dim %d, %d actions, hidden %d, %d environments" % (
-            shp[0], shp[1], shp[2], int(cfg.num_workers))
-    return None
+    return mlp_rollout.why_not(Rollout, agent, supported_fn)
 
 
 def eligible(agent, supported_fn=supported):
@@ -100,38 +80,42 @@ def eligible(agent, supported_fn=supported):
     return shape(agent.network) if why_not(agent, supported_fn) is None else None
 
 
-class Rollout:
+class Rollout(mlp_rollout.Rollout):
     """dra_cat_mlp_rollout over a DeviceCartPoleVec and the agent's flat parameter buffer."""
+    SWITCH, ENTRY, VEC = 'fused_a2c_cat', 'dra_cat_mlp_rollout', DeviceCartPoleVec
+    NETWORK = "CategoricalActorCriticNet over a two-layer relu / tanh FCBody with plain heads"
+    Net, IO, DIMS, ACTION_VIEW = Net, RolloutIO, ("state_dim", "n_actions", "hidden", "gate"), ()
+    network_shape, fields, supported = staticmethod(shape), staticmethod(_fields), staticmethod(supported)
 
-    def __init__(self, agent, shp):
-        self.agent = agent
-        self.shape = shp
-        self.launches = 0
-
-    def net_struct(self):
+    def attach(self):
+        """The environments move to the device; episode ends come back through the device's episode ring."""
         a = self.agent
-        flat = a._fused.flat
-        n = Net()
-        n.param = flat.flat.data_ptr()
-        n.w1, n.b1, n.w2, n.b2, n.wa, n.ba, n.wc, n.bc = [flat.offset_of(p) for p in _params(a.network)]
-        n.state_dim, n.n_actions, n.hidden, n.gate = self.shape
-        return n
+        a.task = DeviceCartPoleVec(a.task)
+        if a.dp.step_dev is None:      # the rank-invariant sampler's position: the kernel reads and advances it
+            a.dp.step_dev = torch.zeros(1, dtype=torch.int64, device=Config.DEVICE)
+        a._sampler_host = int(a.dp.step_dev.item())
 
-    def run(self, t_len):
-        """One rollout launch on the current stream; returns the task's buffers (state, action, v, reward, mask)."""
+    @staticmethod
+    def stays_on_host(agent, why):
+        if getattr(agent.config, 'fused_a2c_cat', True) is not False:
+            getattr(agent.logger, 'warning', agent.logger.info)(
+                'the cart-pole environments stay on the host and this agent keeps the module path: %s' % why)
+
+    def begin_step(self, t_len):
+        """Episode reporting: the terminals depend on the actions, so the episodes that end come back through the device's ring
+        (A2CAgent.drain_episodes); what the host keeps is the anchor that turns a ring row's sampler step into a step number."""
         a = self.agent
-        task, dp = a.task, a.dp
-        b = task.buffers(t_len)
-        io = RolloutIO()
-        io.env_state, io.env_counter, io.ep_steps = task.env_state.data_ptr(), task.env_counter.data_ptr(), task.ep_steps.data_ptr()
-        io.ep_return, io.env_seed, io.sampler_step = task.ep_return.data_ptr(), task.env_seed.data_ptr(), dp.step_dev.data_ptr()
-        io.ep_count, io.ep_ring = task.ep_count.data_ptr(), task.ep_ring.data_ptr()
-        io.out_state, io.out_action, io.out_v = b['state'].data_ptr(), b['action'].data_ptr(), b['v'].data_ptr()
-        io.out_reward, io.out_mask = b['reward'].data_ptr(), b['mask'].data_ptr()
-        io.env0, io.n_global, io.noise_seed, io.horizon = dp.lo, dp.global_workers, a._noise_seed, task.horizon
-        io.ring_cap, io.reward_coef = task.ring_cap, float(a.config.reward_normalizer.coef)
-        io.t_len, io.n_env = int(t_len), task.num_envs
-        net = self.net_struct()
-        lib.dra_cat_mlp_rollout(ctypes.byref(net), ctypes.byref(io), stream_ptr())
-        self.launches += 1
-        return b
+        if a._ep_anchor is None or a._ep_anchor[2] != t_len:
+            a.drain_episodes()       # (what is pending was appended under the old rollout length)
+            a._ep_anchor = (a._sampler_host, a.total_steps, t_len)
+        a._sampler_host += t_len + 1
+
+    def signature(self):
+        """What the captured launch has baked in besides the optimizer's hyper-parameters: the seed of the noise stream."""
+        return (int(self.agent._noise_seed),)
+
+    def end_step(self):
+        a = self.agent
+        a._cat_steps += 1
+        if a._cat_steps % max(1, int(getattr(a.config, 'episode_drain_interval', 64))) == 0:
+            a.drain_episodes()

@@ -22,19 +22,14 @@
 // (PPO's kernel folds AFTER the environment step, as PPO_agent.py:39 does).
 #include "common.h"
 #include "cont_env.h"
+#include "mlp_rollout.h"
 #include <math.h>
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int kMaxS = 64, kMaxA = 16, kMaxN = 64;
-constexpr int kRB = 8;                        // rows a thread carries through one pass over k
-constexpr int kGateRelu = 1, kGateTanh = 2;   // ops.ACT
 constexpr size_t kLdsBytesMax = 160 * 1024;
 constexpr double kHalfLog2Pi = 0.91893853320467274178;
-
-__host__ __device__ constexpr int round_up8(int n) { return (n + 7) & ~7; }
 
 // LDS of the rollout kernel, in floats (the fp64 statistics first: mean, var, divisor [S] and the count)
 __host__ __device__ constexpr size_t rollout_lds_floats(int S, int A, int H, int N) {
@@ -45,52 +40,11 @@ __host__ __device__ constexpr size_t rollout_lds_floats(int S, int A, int H, int
          + (size_t)N * A;                                            // actions [N][A]
 }
 
-// F.softplus (beta 1, threshold 20)
-__device__ __forceinline__ float softplus_f(float x) { return x > 20.f ? x : log1pf(expf(x)); }
 __device__ __forceinline__ double softplus_d(double x) { return x > 20.0 ? x : log1p(exp(x)); }
 __device__ __forceinline__ double softplus_grad_d(double x) {     // as autograd forms it: z / (z + 1), z = exp(x)
   if (x > 20.0) return 1.0;
   const double z = exp(x);
   return z / (z + 1.0);
-}
-template <int GATE>
-__device__ __forceinline__ float gate_f(float x) {
-  if constexpr (GATE == kGateRelu) return fmaxf(x, 0.f);
-  else return tanhf(x);
-}
-
-// one hidden layer of ONE network for the rows this thread carries: out^T[u][e] = gate(b[u] + sum_k in^T[k][e] W^T[k][u]).
-// Threads t7 < 128 of a role: unit u = t7 % H, row-block group rg = t7 / H; row blocks of kRB rows go round the 128 / H groups.
-template <int H, int GATE>
-__device__ __forceinline__ void hidden_layer(const float* __restrict__ inT, const float* __restrict__ wT, const float* __restrict__ b,
-                                             float* __restrict__ outT, int K, int NP, int t7) {
-  constexpr int G = 128 / H;
-  const int u = t7 & (H - 1), rg = t7 / H;
-  const float bias = b[u];
-  for (int e0 = rg * kRB; e0 < NP; e0 += G * kRB) {
-    float acc[kRB];
-#pragma unroll
-    for (int r = 0; r < kRB; ++r) acc[r] = 0.f;
-#pragma unroll 4
-    for (int k = 0; k < K; ++k) {
-      const float w = wT[k * H + u];
-      const f32x4 x0 = *reinterpret_cast<const f32x4*>(&inT[k * NP + e0]);
-      const f32x4 x1 = *reinterpret_cast<const f32x4*>(&inT[k * NP + e0 + 4]);
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        acc[r] = fmaf(x0[r], w, acc[r]);
-        acc[4 + r] = fmaf(x1[r], w, acc[4 + r]);
-      }
-    }
-    f32x4 y0, y1;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      y0[r] = gate_f<GATE>(acc[r] + bias);
-      y1[r] = gate_f<GATE>(acc[4 + r] + bias);
-    }
-    *reinterpret_cast<f32x4*>(&outT[u * NP + e0]) = y0;
-    *reinterpret_cast<f32x4*>(&outT[u * NP + e0 + 4]) = y1;
-  }
 }
 
 template <int H, int GATE>
@@ -198,9 +152,9 @@ a2c_mlp_rollout_kernel(dra_a2c_mlp_net net, dra_a2c_mlp_rollout_io io) {
     __syncthreads();
     // ---- F1, F2: threads 0-127 the policy network, 128-255 the value network (the bootstrap step needs the value alone)
     const bool live = role == 1 || t < T;
-    if (live) hidden_layer<H, GATE>(sXT, sW1 + role * S * H, sB1 + role * H, sH1T + role * H * NP, S, NP, t7);
+    if (live) hidden_layer<H, GATE, 128>(sXT, sW1 + role * S * H, sB1 + role * H, sH1T + role * H * NP, S, NP, t7);
     __syncthreads();
-    if (live) hidden_layer<H, GATE>(sH1T + role * H * NP, sW2 + role * H * H, sB2 + role * H, sH2T + role * H * NP, H, NP, t7);
+    if (live) hidden_layer<H, GATE, 128>(sH1T + role * H * NP, sW2 + role * H * H, sB2 + role * H, sH2T + role * H * NP, H, NP, t7);
     __syncthreads();
     // ---- heads: one output per thread -- (environment e, action dimension c) or (e, the value)
     for (int i = tid; i < N * (A + 1); i += 256) {
@@ -312,11 +266,7 @@ gauss_head_bwd_kernel(const float* __restrict__ z, const float* __restrict__ std
 template <int H, int GATE>
 int launch_rollout(const dra_a2c_mlp_net* net, const dra_a2c_mlp_rollout_io* io, void* stream) {
   const size_t bytes = (rollout_lds_floats(net->state_dim, net->action_dim, H, io->n_env) + 4) * sizeof(float);
-  static DraLdsAttr lds_attr;
-  if (int rc = dra_grant_lds(lds_attr, reinterpret_cast<const void*>(&a2c_mlp_rollout_kernel<H, GATE>), bytes)) return rc;
-  hipLaunchKernelGGL((a2c_mlp_rollout_kernel<H, GATE>), dim3(1), dim3(256), bytes, dra_stream(stream), *net, *io);
-  DRA_LAUNCH_CHECK();
-  return DRA_OK;
+  return launch_one_workgroup<&a2c_mlp_rollout_kernel<H, GATE>>(bytes, net, io, stream);
 }
 
 }  // namespace

@@ -21,19 +21,13 @@
 #include "common.h"
 #include "cartpole_env.h"
 #include "gumbel_noise.h"
+#include "mlp_rollout.h"
 #include <math.h>
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int kS = kCartPoleS, kA = kCartPoleA, kMaxN = 64;
-constexpr int kRB = 8;                        // rows a thread carries through one pass over k
-constexpr int kGateRelu = 1, kGateTanh = 2;   // ops.ACT
 constexpr int kOut = kA + 1;                  // logits and the value
-
-__host__ __device__ constexpr int round_up8(int n) { return (n + 7) & ~7; }
-__host__ __device__ constexpr int round_up4(int n) { return (n + 3) & ~3; }
 
 // LDS of the rollout kernel, in floats; every region starts at a multiple of 4 floats (16 bytes)
 __host__ __device__ constexpr size_t rollout_lds_floats(int H, int N) {
@@ -41,46 +35,6 @@ __host__ __device__ constexpr size_t rollout_lds_floats(int H, int N) {
          + round_up4(kOut * (H + 1)) + 4                      // heads [3][H + 1], their biases
          + round_up4(kA * kMaxN)                              // logits [N][A]
          + (size_t)kS * round_up8(N) + 2 * (size_t)H * round_up8(N);   // x^T [S][NP], h1^T, h2^T [H][NP]
-}
-
-template <int GATE>
-__device__ __forceinline__ float gate_f(float x) {
-  if constexpr (GATE == kGateRelu) return fmaxf(x, 0.f);
-  else return tanhf(x);
-}
-
-// one hidden layer for the rows this thread carries: out^T[u][e] = gate(b[u] + sum_k in^T[k][e] W^T[k][u]).
-// unit u = tid % H, row-block group rg = tid / H; row blocks of kRB rows go round the 256 / H groups.
-template <int H, int GATE>
-__device__ __forceinline__ void hidden_layer(const float* __restrict__ inT, const float* __restrict__ wT, const float* __restrict__ b,
-                                             float* __restrict__ outT, int K, int NP, int tid) {
-  constexpr int G = 256 / H;
-  const int u = tid & (H - 1), rg = tid / H;
-  const float bias = b[u];
-  for (int e0 = rg * kRB; e0 < NP; e0 += G * kRB) {
-    float acc[kRB];
-#pragma unroll
-    for (int r = 0; r < kRB; ++r) acc[r] = 0.f;
-#pragma unroll 4
-    for (int k = 0; k < K; ++k) {
-      const float w = wT[k * H + u];
-      const f32x4 x0 = *reinterpret_cast<const f32x4*>(&inT[k * NP + e0]);
-      const f32x4 x1 = *reinterpret_cast<const f32x4*>(&inT[k * NP + e0 + 4]);
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        acc[r] = fmaf(x0[r], w, acc[r]);
-        acc[4 + r] = fmaf(x1[r], w, acc[4 + r]);
-      }
-    }
-    f32x4 y0, y1;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      y0[r] = gate_f<GATE>(acc[r] + bias);
-      y1[r] = gate_f<GATE>(acc[4 + r] + bias);
-    }
-    *reinterpret_cast<f32x4*>(&outT[u * NP + e0]) = y0;
-    *reinterpret_cast<f32x4*>(&outT[u * NP + e0 + 4]) = y1;
-  }
 }
 
 template <int H, int GATE>
@@ -157,9 +111,9 @@ cat_mlp_rollout_kernel(dra_cat_mlp_net net, dra_cat_mlp_rollout_io io) {
       }
     }
     __syncthreads();
-    hidden_layer<H, GATE>(sXT, sW1, sB1, sH1T, kS, NP, tid);
+    hidden_layer<H, GATE, 256>(sXT, sW1, sB1, sH1T, kS, NP, tid);
     __syncthreads();
-    hidden_layer<H, GATE>(sH1T, sW2, sB2, sH2T, H, NP, tid);
+    hidden_layer<H, GATE, 256>(sH1T, sW2, sB2, sH2T, H, NP, tid);
     __syncthreads();
     // ---- heads: one output per thread -- (environment e, logit c) or (e, the value); the bootstrap step needs the value alone
     if (tid < N * kOut) {
@@ -248,12 +202,7 @@ cartpole_step_kernel(double* __restrict__ state, int64_t* __restrict__ counter, 
 
 template <int H, int GATE>
 int launch_rollout(const dra_cat_mlp_net* net, const dra_cat_mlp_rollout_io* io, void* stream) {
-  const size_t bytes = rollout_lds_floats(H, io->n_env) * sizeof(float);
-  static DraLdsAttr lds_attr;
-  if (int rc = dra_grant_lds(lds_attr, reinterpret_cast<const void*>(&cat_mlp_rollout_kernel<H, GATE>), bytes)) return rc;
-  hipLaunchKernelGGL((cat_mlp_rollout_kernel<H, GATE>), dim3(1), dim3(256), bytes, dra_stream(stream), *net, *io);
-  DRA_LAUNCH_CHECK();
-  return DRA_OK;
+  return launch_one_workgroup<&cat_mlp_rollout_kernel<H, GATE>>(rollout_lds_floats(H, io->n_env) * sizeof(float), net, io, stream);
 }
 
 template <int H>

@@ -19,17 +19,16 @@
 // needs to be a multiple of 16 or 4: every operand outside a tensor is replaced by zero where it is loaded.
 #include "common.h"
 #include "cont_env.h"
+#include "mlp_rollout.h"
 #include <math.h>
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 #define MFMA16(a, b, c) __builtin_amdgcn_mfma_f32_16x16x4f32((a), (b), (c), 0, 0, 0)
 
 constexpr int kMaxB = 128, kMaxS = 64, kMaxA = 16, kMaxH = 512;
 constexpr int kRows = 16;                     // minibatch rows of a row-tiled workgroup
 constexpr int kLdX = kMaxS + kMaxA + 4;       // stride of the [rows][state | action] tile
-constexpr int kGateRelu = 1, kGateTanh = 2;   // ops.ACT
 constexpr int kActNone = 0;
 constexpr int kMaxJobs = 6;
 constexpr int kThreads = 512, kWaves = kThreads / 64;    // of a row-tiled workgroup: 8 waves walk a layer's unit tiles

@@ -1,0 +1,73 @@
+// What the one-workgroup rollout kernels over small MLPs share (a2c_mlp.hip, cat_mlp.hip): gate codes, row rounding, one hidden
+// layer over TRANSPOSED activations and the launch; ppo_mlp.hip and dpg_mlp.hip take the vector type, the gate codes and softplus_f.
+// The device functions are __forceinline__ and compile to the instructions the kernels had with the text in place.  The weight
+// staging and the heads' dot products do NOT (as functions they perturb these latency-bound chains): each kernel keeps its own.
+#pragma once
+#include "common.h"
+#include <math.h>
+
+namespace {
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+constexpr int kRB = 8;                        // rows a thread carries through one pass over k
+constexpr int kGateRelu = 1, kGateTanh = 2;   // ops.ACT
+
+__host__ __device__ constexpr int round_up8(int n) { return (n + 7) & ~7; }
+__host__ __device__ constexpr int round_up4(int n) { return (n + 3) & ~3; }
+
+// F.softplus (beta 1, threshold 20)
+__device__ __forceinline__ float softplus_f(float x) { return x > 20.f ? x : log1pf(expf(x)); }
+
+template <int GATE>
+__device__ __forceinline__ float gate_f(float x) {
+  if constexpr (GATE == kGateRelu) return fmaxf(x, 0.f);
+  else return tanhf(x);
+}
+
+// one hidden layer of ONE network for the rows this thread carries: out^T[u][e] = gate(b[u] + sum_k in^T[k][e] W^T[k][u]).
+// THREADS threads work on the layer, t is this one's index among them: unit u = t % H, row-block group rg = t / H; row blocks of
+// kRB rows go round the THREADS / H groups.
+template <int H, int GATE, int THREADS>
+__device__ __forceinline__ void hidden_layer(const float* __restrict__ inT, const float* __restrict__ wT, const float* __restrict__ b,
+                                             float* __restrict__ outT, int K, int NP, int t) {
+  constexpr int G = THREADS / H;
+  const int u = t & (H - 1), rg = t / H;
+  const float bias = b[u];
+  for (int e0 = rg * kRB; e0 < NP; e0 += G * kRB) {
+    float acc[kRB];
+#pragma unroll
+    for (int r = 0; r < kRB; ++r) acc[r] = 0.f;
+#pragma unroll 4
+    for (int k = 0; k < K; ++k) {
+      const float w = wT[k * H + u];
+      const f32x4 x0 = *reinterpret_cast<const f32x4*>(&inT[k * NP + e0]);
+      const f32x4 x1 = *reinterpret_cast<const f32x4*>(&inT[k * NP + e0 + 4]);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        acc[r] = fmaf(x0[r], w, acc[r]);
+        acc[4 + r] = fmaf(x1[r], w, acc[4 + r]);
+      }
+    }
+    f32x4 y0, y1;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      y0[r] = gate_f<GATE>(acc[r] + bias);
+      y1[r] = gate_f<GATE>(acc[4 + r] + bias);
+    }
+    *reinterpret_cast<f32x4*>(&outT[u * NP + e0]) = y0;
+    *reinterpret_cast<f32x4*>(&outT[u * NP + e0 + 4]) = y1;
+  }
+}
+
+// KERNEL(net, io) as one workgroup of 256 threads with `bytes` of dynamic LDS
+template <auto KERNEL, typename Net, typename Io>
+int launch_one_workgroup(size_t bytes, const Net* net, const Io* io, void* stream) {
+  static DraLdsAttr lds_attr;
+  if (int rc = dra_grant_lds(lds_attr, reinterpret_cast<const void*>(KERNEL), bytes)) return rc;
+  hipLaunchKernelGGL(KERNEL, dim3(1), dim3(256), bytes, dra_stream(stream), *net, *io);
+  DRA_LAUNCH_CHECK();
+  return DRA_OK;
+}
+
+}  // namespace

@@ -25,11 +25,11 @@
 // only the transposed use (dh = dz W) needs a copy in LDS.
 #include "common.h"
 #include "cont_env.h"
+#include "mlp_rollout.h"
 #include <math.h>
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 #define MFMA16(a, b, c) __builtin_amdgcn_mfma_f32_16x16x4f32((a), (b), (c), 0, 0, 0)
 
 constexpr int kRows = 64;              // rows a workgroup holds at once: 4 M tiles
@@ -49,8 +49,7 @@ __device__ __forceinline__ float fast_tanh(float x) {
 }
 __device__ __forceinline__ float fast_exp(float x) { return __builtin_amdgcn_exp2f(x * 1.4426950408889634f); }
 __device__ __forceinline__ float fast_log(float x) { return __builtin_amdgcn_logf(x) * 0.6931471805599453f; }
-// F.softplus (beta 1, threshold 20) and its derivative as autograd forms it (z / (z + 1), z = exp(x))
-__device__ __forceinline__ float softplus_f(float x) { return x > 20.f ? x : log1pf(expf(x)); }
+// the derivative of F.softplus (mlp_rollout.h) as autograd forms it (z / (z + 1), z = exp(x))
 __device__ __forceinline__ float softplus_grad(float x) {
   if (x > 20.f) return 1.f;
   const float z = expf(x);

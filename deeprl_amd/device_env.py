@@ -164,7 +164,66 @@ class DeviceAtariVec:
         return
 
 
-class DeviceContinuousVec:
+class _RolloutVec:
+    """What the device-resident vector environments behind a one-launch rollout share (DeviceContinuousVec, DeviceCartPoleVec):
+    the Task surface, the task's own eligibility, the output buffers per rollout length and the environment-independent fields
+    of a rollout_io struct."""
+    on_device = True
+
+    def __init__(self, task):
+        envs = task.env.envs
+        self.task = task
+        self.name, self.state_dim, self.action_dim = task.name, task.state_dim, task.action_dim
+        self.observation_space, self.action_space = task.observation_space, task.action_space
+        self.num_envs, self.horizon = len(envs), int(envs[0].horizon)
+        self._bufs = {}
+
+    def _retire_host(self):
+        for e in self.task.env.envs:
+            e.s = "device"          # the host objects are retired: stepping them too would fork the streams
+
+    @staticmethod
+    def _host_envs(task, config):
+        """The environments of an envs.Task over a DummyVecEnv of at most 64, with a device and config.device_env on; else None."""
+        from .envs import DummyVecEnv, Task
+        if Config.DEVICE.type != 'cuda' or getattr(config, 'device_env', True) is False or type(task) is not Task:
+            return None
+        env = getattr(task, 'env', None)
+        if type(env) is not DummyVecEnv or not env.envs or len(env.envs) > 64:
+            return None
+        return env.envs
+
+    def buffers(self, t_len):
+        if t_len not in self._bufs:
+            dev = Config.DEVICE
+            self._bufs[t_len] = self._new_buffers(t_len, lambda *shape: torch.zeros(shape, dtype=torch.float32, device=dev))
+        return self._bufs[t_len]
+
+    def fill_io(self, io, agent, t_len):
+        """The fields every rollout_io struct over these environments has (an out_* pointer per buffer it takes); returns the buffers."""
+        dp = agent.dp
+        b = self.buffers(t_len)
+        io.env_state, io.env_counter, io.env_seed = self.env_state.data_ptr(), self.env_counter.data_ptr(), self.env_seed.data_ptr()
+        io.sampler_step = dp.step_dev.data_ptr()
+        for k, v in b.items():
+            if hasattr(io, 'out_' + k):
+                setattr(io, 'out_' + k, v.data_ptr())
+        io.env0, io.n_global, io.noise_seed, io.horizon = dp.lo, dp.global_workers, agent._noise_seed, self.horizon
+        io.reward_coef = float(agent.config.reward_normalizer.coef)
+        io.t_len, io.n_env = int(t_len), self.num_envs
+        return b
+
+    def reset(self):
+        return None
+
+    close = reset
+
+    def step(self, actions):
+        raise RuntimeError("%s is driven through %s's device rollout; its environments are not steppable"
+                           % (type(self).__name__, self.DRIVER))
+
+
+class DeviceContinuousVec(_RolloutVec):
     """The SyntheticContinuous environments of a Task, resident on the device (BASELINE configs[2]: PPO, 16 HalfCheetah-shaped
     workers): raw fp64 observations, step counters and the observation normaliser's running statistics live in HBM and one
     launch (dra_ppo_mlp_rollout) walks a whole rollout -- normalise, both forwards, sample, environment step -- without a host
@@ -172,18 +231,15 @@ class DeviceContinuousVec:
     one pass per rollout) for the episodic-return log lines; observations depend on the actions and exist only on the device.
     Same arithmetic as envs.SyntheticContinuous + normalizers.MeanStdNormalizer stepped from python (csrc/cont_env.h;
     tests/test_gpu_ppo_mlp.py compares the two paths)."""
-    on_device = True
+    DRIVER = "PPOAgent"
 
     def __init__(self, task, agent_states, normalizer):
         """task: the envs.Task whose (already reset) environments move to the device; agent_states: the normalised observations
         the agent holds (what config.state_normalizer(task.reset()) returned); normalizer: config.state_normalizer."""
         from .normalizers import MeanStdNormalizer
+        _RolloutVec.__init__(self, task)
         envs = task.env.envs
         dev = Config.DEVICE
-        self.task = task
-        self.name, self.state_dim, self.action_dim = task.name, task.state_dim, task.action_dim
-        self.observation_space, self.action_space = task.observation_space, task.action_space
-        self.num_envs, self.horizon = len(envs), int(envs[0].horizon)
         self.seeds_host = np.asarray([e.seed for e in envs], dtype=np.int64)
         self.counters_host = np.asarray([e.c for e in envs], dtype=np.int64)
         self.ret_host = np.asarray([e.ret for e in envs], dtype=np.float64)
@@ -203,34 +259,35 @@ class DeviceContinuousVec:
         self.rms = torch.from_numpy(rms).to(dev)
         if self.rms_kind == 'meanstd':
             normalizer.attach_device(self.rms, s)
-        for e in envs:
-            e.s = "device"          # the host objects are retired: stepping them too would fork the streams
-        self._bufs = {}
+        self._retire_host()
 
     @staticmethod
     def eligible(task, config):
-        from .envs import DummyVecEnv, SyntheticContinuous, Task
+        from .envs import SyntheticContinuous
         from .normalizers import MeanStdNormalizer, RescaleNormalizer
-        if Config.DEVICE.type != 'cuda' or getattr(config, 'device_env', True) is False or type(task) is not Task:
+        envs = _RolloutVec._host_envs(task, config)
+        if envs is None:
             return False
-        env = getattr(task, 'env', None)
-        if type(env) is not DummyVecEnv or not env.envs or len(env.envs) > 64:
-            return False
-        e0 = env.envs[0]
+        e0 = envs[0]
         if not all(type(e) is SyntheticContinuous and e.horizon == e0.horizon and e.state_dim == e0.state_dim and
-                   e.action_dim == e0.action_dim for e in env.envs):
+                   e.action_dim == e0.action_dim for e in envs):
             return False
         sn, rn = config.state_normalizer, config.reward_normalizer
         state_ok = type(sn) is MeanStdNormalizer or (type(sn) is RescaleNormalizer and sn.coef == 1.0)
         return state_ok and type(rn) is RescaleNormalizer
 
-    def buffers(self, t_len):
-        if t_len not in self._bufs:
-            n, s, a, dev = self.num_envs, self.state_dim, self.action_dim, Config.DEVICE
-            f = lambda *shape: torch.zeros(shape, dtype=torch.float32, device=dev)
-            self._bufs[t_len] = dict(state=f(t_len, n, s), action=f(t_len, n, a), log_pi_a=f(t_len, n, 1), v=f(t_len + 1, n, 1),
-                                     reward=f(t_len, n, 1), mask=f(t_len, n, 1))
-        return self._bufs[t_len]
+    def _new_buffers(self, t_len, f):
+        n, s, a = self.num_envs, self.state_dim, self.action_dim
+        return dict(state=f(t_len, n, s), action=f(t_len, n, a), log_pi_a=f(t_len, n, 1), v=f(t_len + 1, n, 1),
+                    reward=f(t_len, n, 1), mask=f(t_len, n, 1))
+
+    def fill_io(self, io, agent, t_len, read_only):
+        """_RolloutVec.fill_io and the observation normaliser's fields (a2c_mlp.RolloutIO, ppo_mlp.RolloutIO)."""
+        b = _RolloutVec.fill_io(self, io, agent, t_len)
+        io.rms, io.cur_state = self.rms.data_ptr(), self.cur_state.data_ptr()
+        io.rms_epsilon, io.rms_clip = self.rms_epsilon, self.rms_clip
+        io.rms_update = 1 if (self.rms_kind == 'meanstd' and not read_only) else 0
+        return b
 
     def shadow(self, t_len):
         """Advances the host shadow by t_len steps of every environment -> list of (t, env, episodic_return) for the episodes
@@ -257,17 +314,8 @@ class DeviceContinuousVec:
         events.sort()
         return events
 
-    def reset(self):
-        return None
 
-    def step(self, actions):
-        raise RuntimeError("DeviceContinuousVec is driven through PPOAgent's device rollout; its environments are not steppable")
-
-    def close(self):
-        return
-
-
-class DeviceCartPoleVec:
+class DeviceCartPoleVec(_RolloutVec):
     """The envs.CartPole environments of a Task, resident on the device (a2c_feature, examples.py:340-358): fp64 state, total
     step counters, episode steps and running returns live in HBM and one launch (dra_cat_mlp_rollout) walks a whole rollout --
     forward, action, environment step -- without a host round trip.  Same arithmetic as envs.CartPole stepped from python
@@ -277,16 +325,13 @@ class DeviceCartPoleVec:
     Episode ends are REPORTED by the device instead: the rollout kernel appends one row (sampler step of the end, global
     environment, episodic return) per finished episode to `ep_ring` [RING_CAP][3] and counts them in `ep_count`; `drain()`
     fetches what is new with one device-to-host copy."""
-    on_device = True
+    DRIVER = "A2CAgent"
     RING_CAP = 4096
 
     def __init__(self, task):
+        _RolloutVec.__init__(self, task)
         envs = task.env.envs
         dev = Config.DEVICE
-        self.task = task
-        self.name, self.state_dim, self.action_dim = task.name, task.state_dim, task.action_dim
-        self.observation_space, self.action_space = task.observation_space, task.action_space
-        self.num_envs, self.horizon = len(envs), int(envs[0].horizon)
         self.ring_cap = int(self.RING_CAP)
         self.env_state = torch.from_numpy(np.stack([np.asarray(e.s, dtype=np.float64) for e in envs])).to(dev)
         self.env_counter = torch.tensor([e.c for e in envs], dtype=torch.int64, device=dev)
@@ -299,32 +344,29 @@ class DeviceCartPoleVec:
         self.ep_count = self._ring_buf[3 * self.ring_cap:].view(torch.int64)
         self._ring_host = torch.zeros(3 * self.ring_cap + 1, dtype=torch.float64).pin_memory()
         self.drained = 0
-        for e in envs:
-            e.s = "device"          # the host objects are retired: stepping them too would fork the streams
-        self._bufs = {}
+        self._retire_host()
 
     @staticmethod
     def eligible(task, config):
-        from .envs import CartPole, DummyVecEnv, Task
+        from .envs import CartPole
         from .normalizers import RescaleNormalizer
-        if Config.DEVICE.type != 'cuda' or getattr(config, 'device_env', True) is False or type(task) is not Task:
-            return False
-        env = getattr(task, 'env', None)
-        if type(env) is not DummyVecEnv or not env.envs or len(env.envs) > 64:
-            return False
-        e0 = env.envs[0]
-        if not all(type(e) is CartPole and e.horizon == e0.horizon for e in env.envs):
+        envs = _RolloutVec._host_envs(task, config)
+        if envs is None or not all(type(e) is CartPole and e.horizon == envs[0].horizon for e in envs):
             return False
         sn, rn = config.state_normalizer, config.reward_normalizer
         return type(sn) is RescaleNormalizer and sn.coef == 1.0 and type(rn) is RescaleNormalizer
 
-    def buffers(self, t_len):
-        if t_len not in self._bufs:
-            n, s, dev = self.num_envs, self.state_dim, Config.DEVICE
-            f = lambda *shape: torch.zeros(shape, dtype=torch.float32, device=dev)
-            self._bufs[t_len] = dict(state=f(t_len, n, s), action=torch.zeros((t_len, n), dtype=torch.int64, device=dev),
-                                     v=f(t_len + 1, n, 1), reward=f(t_len, n, 1), mask=f(t_len, n, 1))
-        return self._bufs[t_len]
+    def _new_buffers(self, t_len, f):
+        n = self.num_envs
+        return dict(state=f(t_len, n, self.state_dim), action=torch.zeros((t_len, n), dtype=torch.int64, device=Config.DEVICE),
+                    v=f(t_len + 1, n, 1), reward=f(t_len, n, 1), mask=f(t_len, n, 1))
+
+    def fill_io(self, io, agent, t_len):
+        """_RolloutVec.fill_io and the episode bookkeeping's fields (cat_mlp.RolloutIO)."""
+        b = _RolloutVec.fill_io(self, io, agent, t_len)
+        io.ep_steps, io.ep_return = self.ep_steps.data_ptr(), self.ep_return.data_ptr()
+        io.ep_count, io.ep_ring, io.ring_cap = self.ep_count.data_ptr(), self.ep_ring.data_ptr(), self.ring_cap
+        return b
 
     def drain(self):
         """The episodes that ended since the last drain -> list of (sampler step, global environment, episodic return) in the
@@ -355,12 +397,3 @@ class DeviceCartPoleVec:
         for k in ("env_state", "env_counter", "ep_steps", "ep_return", "env_seed", "_ring_buf"):
             getattr(self, k).copy_(torch.from_numpy(np.asarray(d[k])))
         self.drained = int(d["drained"])
-
-    def reset(self):
-        return None
-
-    def step(self, actions):
-        raise RuntimeError("DeviceCartPoleVec is driven through A2CAgent's device rollout; its environments are not steppable")
-
-    def close(self):
-        return

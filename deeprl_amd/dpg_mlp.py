@@ -13,7 +13,7 @@ import numpy as np
 import torch
 
 from ._lib import lib, stream_ptr
-from .a2c_mlp import GATES
+from .mlp_rollout import fc_body, head_out
 
 _I6 = ctypes.c_int32 * 6
 
@@ -43,22 +43,6 @@ class Step(ctypes.Structure):
                 ("noise_seed", ctypes.c_uint64), ("noise_counter", ctypes.c_int64)]
 
 
-def _mlp_dims(body, head, gate_out):
-    """(in, h1, h2, out) of FCBody(in, (h1, h2)) + Linear head, or None."""
-    from .nets import FCBody, Linear
-    if type(body) is not FCBody or body.noisy_linear or body.gate not in GATES or len(body.layers) != 2:
-        return None
-    if any(type(layer) is not Linear or layer.bias is None for layer in body.layers):
-        return None
-    if type(head) is not Linear or head.bias is None:
-        return None
-    w1, w2 = body.layers[0].weight, body.layers[1].weight
-    if w2.shape[1] != w1.shape[0] or head.weight.shape[1] != w2.shape[0]:
-        return None
-    gate_out.append(GATES[body.gate])
-    return int(w1.shape[1]), int(w1.shape[0]), int(w2.shape[0]), int(head.weight.shape[0])
-
-
 def modules(network):
     """[(actor_body, fc_action), (critic_body, fc_critic), ...] of a DeterministicActorCriticNet / TD3Net, or None."""
     from .nets import DeterministicActorCriticNet, DummyBody, TD3Net
@@ -79,14 +63,15 @@ def shape(network):
     mods = modules(network)
     if mods is None:
         return None
-    gates = []
-    dims = [_mlp_dims(b, h, gates) for b, h in mods]
-    if any(d is None for d in dims) or len(set(gates)) != 1:
+    bodies = [fc_body(b) for b, _ in mods]
+    if any(b is None for b in bodies):
         return None
-    (s_dim, h1, h2, a_dim), critics = dims[0], dims[1:]
-    if any(c != (s_dim + a_dim, h1, h2, 1) for c in critics):
+    s_dim, h1, h2, gate = bodies[0]
+    outs = [head_out(h, h2) for _, h in mods]
+    a_dim = outs[0]
+    if a_dim is None or any(b != (s_dim + a_dim, h1, h2, gate) for b in bodies[1:]) or any(o != 1 for o in outs[1:]):
         return None
-    return s_dim, a_dim, h1, h2, gates[0], len(critics)
+    return s_dim, a_dim, h1, h2, gate, len(mods) - 1
 
 
 def supported(batch, state_dim, action_dim, h1, h2, gate, n_critics):

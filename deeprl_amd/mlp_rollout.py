@@ -1,0 +1,109 @@
+"""What the host sides of the small-MLP kernels share (a2c_mlp.py, cat_mlp.py, ppo_mlp.py, dpg_mlp.py): the gate codes, the ONE
+check that a body is a two-layer FCBody the kernels walk and that a head is a plain Linear, the agent-side conditions of a
+device rollout (`why_not`) and the `Rollout` base of a2c_mlp.Rollout / cat_mlp.Rollout: the kernel's two structs over the agent's
+ONE flat parameter buffer and its device-resident environments, one launch per rollout.
+There is no CPU / eager implementation here: without the HIP library every call raises.
+"""
+import ctypes
+from collections import namedtuple
+
+import torch
+import torch.nn.functional as F
+
+from ._lib import lib, stream_ptr
+
+GATES = {F.relu: 1, torch.relu: 1, torch.tanh: 2, F.tanh: 2}      # ops.ACT codes
+
+Plan = namedtuple('Plan', ['counters', 't_len'])      # what _OnPolicyGraph.run reads of a rollout plan
+
+
+def fc_body(body):
+    """(in, h1, h2, gate code) when `body` is a two-layer FCBody of plain Linear layers with biases under a relu or tanh gate, not
+    noisy; else None."""
+    from .nets import FCBody, Linear
+    if type(body) is not FCBody or body.noisy_linear or body.gate not in GATES or len(body.layers) != 2:
+        return None
+    if any(type(layer) is not Linear or layer.bias is None for layer in body.layers):
+        return None
+    w1, w2 = body.layers[0].weight, body.layers[1].weight
+    if w2.shape[1] != w1.shape[0]:
+        return None
+    return int(w1.shape[1]), int(w1.shape[0]), int(w2.shape[0]), GATES[body.gate]
+
+
+def head_out(head, in_features):
+    """The output width when `head` is a plain Linear layer with a bias over `in_features` inputs; else None."""
+    from .nets import Linear
+    if type(head) is not Linear or head.bias is None or head.weight.shape[1] != in_features:
+        return None
+    return int(head.weight.shape[0])
+
+
+def body_params(body):
+    a, b = body.layers
+    return [a.weight, a.bias, b.weight, b.bias]
+
+
+def why_not(kind, agent, supported_fn=None):
+    """None when A2CAgent may run `agent` on the rollout kernel of `kind` (a Rollout subclass), else the first reason it may not
+    (everything but the task itself, which the device_env class decides)."""
+    cfg = agent.config
+    if getattr(cfg, kind.SWITCH, True) is False:
+        return "config.%s is off" % kind.SWITCH
+    if agent.dp.active:
+        return "the agent is data parallel"
+    if agent.grad_hook is not None:
+        return "a grad_hook is installed"
+    shp = kind.network_shape(agent.network)
+    if shp is None:
+        return "the network is not %s" % kind.NETWORK
+    owned = agent._fused.flat.params
+    if any(all(p is not q for q in owned) for _, p in kind.fields(agent.network)):
+        return "one optimiser does not own every parameter the kernel reads"
+    if not (supported_fn or kind.supported)(shp[0], shp[1], shp[2], int(cfg.num_workers), shp[3]):
+        return "%s is not built for state_dim %d, %d actions, hidden %d, %d environments" % (
+            kind.ENTRY, shp[0], shp[1], shp[2], int(cfg.num_workers))
+    return None
+
+
+class Rollout:
+    """One launch per rollout over the agent's device-resident environments (agent.task: a device_env class with fill_io) and its
+    flat parameter buffer.  A subclass names its kernel: the config switch, the library entry, the two struct mirrors, the
+    struct's four shape fields, `network_shape(network)`, `fields(network)` -- the (offset field, parameter) pairs -- and
+    `supported(...)`; how the task moves to the device (`VEC`, `attach`, `stays_on_host`); and where A2CAgent's device step
+    differs between them: `begin_step` / `end_step` (episode reporting), `signature()` (what a captured launch has baked in: the
+    arguments fill_io takes behind t_len, then the noise seed; kept in `sig`) and `ACTION_VIEW` (the stored actions' shape
+    behind the row axis)."""
+    SWITCH = ENTRY = VEC = NETWORK = Net = IO = DIMS = ACTION_VIEW = None
+
+    def __init__(self, agent, shp):
+        self.agent = agent
+        self.shape = shp
+        self.launches = 0
+        self.sig = None         # signature() of the captured launch
+
+    def net_struct(self):
+        flat = self.agent._fused.flat
+        n = self.Net()
+        n.param = flat.flat.data_ptr()
+        for field, p in self.fields(self.agent.network):
+            setattr(n, field, flat.offset_of(p))
+        for field, v in zip(self.DIMS, self.shape):
+            setattr(n, field, v)
+        return n
+
+    def run(self, t_len):
+        """One rollout launch on the current stream; returns the task's buffers (state, action, v, reward, mask)."""
+        io = self.IO()
+        b = self.agent.task.fill_io(io, self.agent, t_len, *self.sig[:-1])
+        net = self.net_struct()
+        getattr(lib, self.ENTRY)(ctypes.byref(net), ctypes.byref(io), stream_ptr())
+        self.launches += 1
+        return b
+
+    @staticmethod
+    def stays_on_host(agent, why):
+        return
+
+    def end_step(self):
+        return

@@ -16,6 +16,7 @@ import numpy as np
 import torch
 
 from ._lib import DraError, lib, ptr, stream_ptr
+from .mlp_rollout import body_params
 from .support import Config
 
 DBG_FLOATS = 65536          # DRA_PPO_MLP_DBG_FLOATS
@@ -52,25 +53,11 @@ class RolloutIO(ctypes.Structure):
 def _mlp_shape(network):
     """(state_dim, action_dim, hidden) when `network` is a GaussianActorCriticNet whose phi_body is the identity and whose
     actor / critic bodies are two-layer tanh FCBody stacks of one width; else None."""
-    from .nets import DummyBody, FCBody, GaussianActorCriticNet, Linear
-    if type(network) is not GaussianActorCriticNet or type(network.phi_body) is not DummyBody:
+    from .a2c_mlp import shape
+    shp = shape(network)
+    if shp is None or network.actor_body.gate is not torch.tanh or network.critic_body.gate is not torch.tanh:
         return None
-    bodies = (network.actor_body, network.critic_body)
-    for b in bodies:
-        if type(b) is not FCBody or b.noisy_linear or b.gate is not torch.tanh or len(b.layers) != 2:
-            return None
-        if any(type(layer) is not Linear or layer.bias is None for layer in b.layers):
-            return None
-    a, c = bodies
-    s_dim = a.layers[0].weight.shape[1]
-    hidden = a.layers[0].weight.shape[0]
-    shapes_ok = all(tuple(b.layers[0].weight.shape) == (hidden, s_dim) and tuple(b.layers[1].weight.shape) == (hidden, hidden)
-                    for b in bodies)
-    if not shapes_ok or network.fc_action.weight.shape[1] != hidden or tuple(network.fc_critic.weight.shape) != (1, hidden):
-        return None
-    if network.fc_action.bias is None or network.fc_critic.bias is None:
-        return None
-    return int(s_dim), int(network.fc_action.weight.shape[0]), int(hidden)
+    return shp[:3]
 
 
 def _net_struct(fused, body, head, std, step_dev):
@@ -80,8 +67,7 @@ def _net_struct(fused, body, head, std, step_dev):
     n = Net()
     n.param, n.exp_avg, n.exp_avg_sq = flat.flat.data_ptr(), fused.state1.data_ptr(), fused.state2.data_ptr()
     n.step_dev = step_dev.data_ptr()
-    n.off_w1, n.off_b1 = flat.offset_of(body.layers[0].weight), flat.offset_of(body.layers[0].bias)
-    n.off_w2, n.off_b2 = flat.offset_of(body.layers[1].weight), flat.offset_of(body.layers[1].bias)
+    n.off_w1, n.off_b1, n.off_w2, n.off_b2 = [flat.offset_of(p) for p in body_params(body)]
     n.off_w3, n.off_b3 = flat.offset_of(head.weight), flat.offset_of(head.bias)
     n.off_std = flat.offset_of(std) if std is not None else -1
     n.lr, n.beta1, n.beta2, n.eps = float(fused.hyper['lr']), float(b1), float(b2), float(fused.hyper['eps'])
@@ -119,10 +105,8 @@ class MlpPPO:
         if any(o.kind != 'adam' for o in opts):
             return None
         net = agent.network
-        expect_a = [net.actor_body.layers[0].weight, net.actor_body.layers[0].bias, net.actor_body.layers[1].weight,
-                    net.actor_body.layers[1].bias, net.fc_action.weight, net.fc_action.bias, net.std]
-        expect_c = [net.critic_body.layers[0].weight, net.critic_body.layers[0].bias, net.critic_body.layers[1].weight,
-                    net.critic_body.layers[1].bias, net.fc_critic.weight, net.fc_critic.bias]
+        expect_a = body_params(net.actor_body) + [net.fc_action.weight, net.fc_action.bias, net.std]
+        expect_c = body_params(net.critic_body) + [net.fc_critic.weight, net.fc_critic.bias]
         for o, expect in zip(opts, (expect_a, expect_c)):
             if len(o.flat.params) != len(expect) or any(all(p is not q for q in o.flat.params) for p in expect):
                 return None
