@@ -1012,7 +1012,7 @@ def test_policy_heads_sample_equals_heads_then_categorical(dev, b, k, a):
 
 
 @pytest.mark.parametrize("b,k,a,relu", [(80, 512, 4, True), (256, 512, 18, True), (1, 512, 6, False), (33, 64, 3, True), (5, 17, 1, False),
-                                        (1000, 512, 9, True)])
+                                        (1000, 512, 9, True), (39, 256, 5, True), (39, 257, 5, False)])
 def test_policy_heads_given_and_backward_equal_the_separate_launches(dev, b, k, a, relu):
     """dra_policy_heads_given == dra_linear_fwd_pair + dra_categorical_fwd(action) and dra_policy_heads_bwd == dra_categorical_bwd +
     dra_linear_bwd_pair (+ dra_act_bwd's ReLU mask on the input gradient): every output bit for bit -- the fused launches keep
@@ -1101,7 +1101,8 @@ def test_gather_rows_equals_indexing(dev, rows, n):
         assert o.dtype == f.dtype and torch.equal(o, f[idx])
 
 
-@pytest.mark.parametrize("b,k,o0,o1", [(80, 512, 4, 1), (256, 512, 18, 1), (1, 512, 6, 1), (33, 64, 3, 2), (5, 17, 1, 1)])
+@pytest.mark.parametrize("b,k,o0,o1", [(80, 512, 4, 1), (256, 512, 18, 1), (1, 512, 6, 1), (33, 64, 3, 2), (5, 17, 1, 1),
+                                       (39, 256, 3, 2), (39, 257, 3, 2)])
 def test_linear_bwd_pair_vs_fp64(dev, b, k, o0, o1):
     """dra_linear_bwd_pair (input gradient and both layers' weight / bias gradients of the paired heads in one launch) against
     float64: d x = g0 W0 + g1 W1, dW_h = g_h^T x, db_h = column sums, each at 1e-5 of its scale."""
