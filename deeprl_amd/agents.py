@@ -38,7 +38,10 @@ from .envs import LazyFrames
 from .optim import FlatParams, FusedOptimizer, nature_conv_weights
 from .replay import PrioritizedTransition, Storage
 from ._lib import DraError
-from .support import Config, LinearSchedule, close_obj, epsilon_greedy, get_logger, random_sample, range_tensor, tensor, to_np
+from .device_env import DeviceAtariVec
+from .pixel_rollout import _OCRollout, _PixelRollout, _QRollout, hand_over, k_major     # noqa: F401  (the rollouts: this module's names too)
+from .support import (Config, LinearSchedule, StagedUpload, close_obj, epsilon_greedy, get_logger, random_sample, range_tensor, tensor,
+                      to_np)
 
 
 
@@ -138,6 +141,20 @@ class BaseAgent:
         """The reference's two 'episodic_return_train' lines for an episode that ended at step `at`."""
         self.logger.add_scalar('episodic_return_train', ret, at)
         self.logger.info('steps %d, episodic_return_train %s' % (at, ret))
+
+    def _account_rollout(self, infos, stride):
+        """A rollout that was planned ahead (DeviceAtariVec.plan), on the host's books: per planned step the returns of the episodes
+        that end there, then total_steps advances by `stride`.  -> whether config.target_network_update_freq falls on one of the
+        steps (the per-step loops copy the target network there; the parameters do not change inside a rollout, so the caller
+        copies once, ahead of it)."""
+        freq = self.config.target_network_update_freq
+        sync = False
+        for info in infos:
+            self.record_online_return(info)
+            self.total_steps += stride
+            if freq is not None and self.total_steps // stride % freq == 0:
+                sync = True
+        return sync
 
     def switch_task(self):
         """config.tasks: consecutive equal shares of max_steps per task."""
@@ -271,9 +288,7 @@ class _GraphedQ:
         self.calls = 0
         self.graph = None
         self.static_in = self.static_out = None
-        self.stage = []
-        self.events = []
-        self.k = 0
+        self.upload = None
         self.failed = False
 
     def usable(self, state):
@@ -298,9 +313,8 @@ class _GraphedQ:
         dev = next(a._network.parameters()).device
         if self.graph is None:
             try:
-                self.static_in = torch.zeros(x.shape, dtype=torch.uint8, device=dev)
-                self.stage = [torch.empty(x.shape, dtype=torch.uint8).pin_memory() for _ in range(4)]
-                self.events = [None] * 4
+                self.upload = StagedUpload(x.shape, torch.uint8, dev)
+                self.static_in = self.upload.dev
                 with torch.no_grad():   # eager dry run of exactly what is captured: creates every lazily built
                     a.q_device(a._network(cfg.state_normalizer(self.static_in)))   # object (normaliser table, ...)
                 g = torch.cuda.CUDAGraph()
@@ -314,15 +328,7 @@ class _GraphedQ:
                 self.failed = True
                 self.graph = None
                 return None
-        k = self.k
-        self.k = (k + 1) % len(self.stage)
-        if self.events[k] is not None:
-            self.events[k].synchronize()
-        self.stage[k].numpy()[...] = x
-        self.static_in.copy_(self.stage[k], non_blocking=True)
-        ev = torch.cuda.Event()
-        ev.record()
-        self.events[k] = ev
+        self.upload.put(x)
         self.graph.replay()
         return to_np(self.static_out)
 
@@ -1130,93 +1136,6 @@ def _begin_rollout(agent, n_env):
     return slots
 
 
-class _PixelRollout:
-    """The no-grad forwards of one A2C / PPO rollout over CategoricalActorCriticNet(NatureConvBody) and device-resident synthetic
-    Atari environments as FOUR launches per step instead of five (csrc/conv_v2.hip: rollout_conv1_heads_kernel): [conv1 of step t
-    | fc4's finish + policy head of step t - 1], conv2, conv3, fc4's 28 K-slice partial sums -- every launch of such a step is a few dozen workgroups at its latency floor,
-    so the step costs what its launches cost.  The head of step t - 1 can share conv1's launch because the planned observations
-    do not depend on the actions (DeviceAtariVec.states_all).  Same device functions as the module path: the rollout's actions,
-    log-probabilities, entropies and values are bit-identical (tests/test_gpu_agents.py).  a2c_pixel 209 k -> 224 k, ppo_pixel
-    109 k -> 118 k env-steps/s (profiles/r05x_bench_agents_c3fc4_ab.jsonl; conv3 + fc4 as one launch was measured too and lost)."""
-
-    def __init__(self, agent):
-        self.agent = agent
-        self.bufs = None
-
-    def eligible(self):
-        from .device_env import DeviceAtariVec
-        from .nets import CategoricalActorCriticNet, Conv2d, DummyBody, Linear, NatureConvBody
-        a = self.agent
-        net, cfg = a.network, a.config
-        if getattr(cfg, 'fused_rollout', True) is False or Config.DEVICE.type != 'cuda' or not isinstance(a.task, DeviceAtariVec):
-            return False
-        if type(net) is not CategoricalActorCriticNet or getattr(net, 'sampler', None) is not None or not getattr(net, 'rollout_fc4_slices', True):
-            return False
-        body = net.phi_body
-        if type(body) is not NatureConvBody or type(net.actor_body) is not DummyBody or type(net.critic_body) is not DummyBody:
-            return False
-        convs = [body.conv1, body.conv2, body.conv3]
-        if not all(type(c) is Conv2d and c.bias is not None and c.weight.permute(1, 2, 3, 0).is_contiguous() for c in convs):
-            return False
-        if getattr(body.conv1, 'u8_coef', None) is None or a.task.history != 4:
-            return False
-        heads = [body.fc4, net.fc_action, net.fc_critic]
-        if not all(type(m) is Linear and m.bias is not None and m.weight.is_contiguous() for m in heads):
-            return False
-        return (body.fc4.fused_act == "relu" and tuple(body.fc4.weight.shape) == (512, 3136) and net.fc_action.fused_act is None
-                and net.fc_critic.fused_act is None and net.fc_action.weight.shape[0] <= 64 and net.fc_critic.weight.shape[0] == 1
-                and a.task.num_envs <= 32)
-
-    def run(self, frames, slots):
-        """frames: uint8 [T + 1, N, 4, 84, 84]; fills rows 0..T of `slots` (action, log_pi_a, entropy, v) from slots.uniform."""
-        import ctypes
-        from ._lib import lib, stream_ptr
-        a = self.agent
-        net = a.network
-        body = net.phi_body
-        rows, n = int(frames.shape[0]), int(frames.shape[1])
-        dev = frames.device
-        if self.bufs is None or self.bufs['n'] != n or self.bufs['rows'] < rows:
-            f = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
-            # (the activations of every step are kept: A2C's update backpropagates through them, as the reference does through the
-            # rollout's own forward graph -- config.reuse_rollout_activations)
-            self.bufs = dict(n=n, rows=rows, y1=f(rows, n, 32, 20, 20), y2=f(rows, n, 64, 9, 9), y3=f(rows, n, 64, 7, 7), slabs=f(28, n, 512),
-                             phi=f(rows, n, 512))
-            one = lambda t: (ctypes.c_void_p * 1)(t.data_ptr())
-            # (per-step pointer arguments built once: the rollout loop of PPO's 129 steps is host-side eager code)
-            self.bufs['args'] = [(ctypes.c_void_p(self.bufs['y1'][t].data_ptr()), one(self.bufs['y1'][t]), one(self.bufs['y2'][t]),
-                                  one(self.bufs['y3'][t]), ctypes.c_void_p(self.bufs['phi'][t].data_ptr())) for t in range(rows)]
-        b = self.bufs
-        p = lambda t: ctypes.c_void_p(t.data_ptr())
-        arr = lambda t: (ctypes.c_void_p * 1)(t.data_ptr())
-        st = stream_ptr()
-        w1, w2, w3 = body.conv1.weight, body.conv2.weight, body.conv3.weight       # [(c, kh, kw)][oc] storage (FlatParams)
-        wa, ba, wv, bv = net.fc_action.weight, net.fc_action.bias, net.fc_critic.weight, net.fc_critic.bias
-        n_act = int(wa.shape[0])
-        coef = float(body.conv1.u8_coef)
-        wt2, b2 = arr(w2), arr(body.conv2.bias)
-        wt3, b3, w4 = arr(w3), arr(body.conv3.bias), arr(body.fc4.weight)
-        b4, slabs = body.fc4.bias, b['slabs']
-        for t in range(rows):
-            prev = t > 0
-            y1p, x2, y2, y3, _ = b['args'][t]
-            # fc4 of step t - 1 left its 28 K-slice partial sums: the head that rides in this launch folds them (bias, ReLU) first
-            # (and leaves the folded features of step t - 1 in phi[t - 1]: fc4's forward output, for A2C's update)
-            lib.dra_rollout_conv1_heads_phi(p(frames[t]), p(w1), p(body.conv1.bias), y1p, n, coef,
-                                            p(slabs) if prev else None, p(b4) if prev else None, p(wa), p(ba), p(wv), p(bv),
-                                            p(slots.uniform[t - 1]) if prev else None, n_act,
-                                            p(slots.action[t - 1]) if prev else None, p(slots.log_pi_a[t - 1]) if prev else None,
-                                            p(slots.entropy[t - 1]) if prev else None, p(slots.v[t - 1]) if prev else None,
-                                            b['args'][t - 1][4] if prev else None, st)
-            lib.dra_conv_fwd_koc(2, 1, x2, wt2, b2, y2, n, 0, 1.0, ops.ACT["relu"], st)
-            lib.dra_conv_fwd_koc(3, 1, y2, wt3, b3, y3, n, 0, 1.0, ops.ACT["relu"], st)
-            lib.dra_linear_fwd_slabs_one(1, y3, w4, n, 3136, 512, 28, p(slabs), st)
-        t = rows - 1
-        lib.dra_policy_heads_sample_fold28(p(slabs), p(b4), p(wa), p(ba), p(wv), p(bv), p(slots.uniform[t]), n, n_act,
-                                           p(slots.action[t]), p(slots.log_pi_a[t]), p(slots.entropy[t]), p(slots.v[t]), st)
-        slots.end()
-
-
 def _install_sampler(agent):
     """Data-parallel agents (and config.dp_invariant_sampling) sample actions from per-step noise that is the same
     however the environments are spread over ranks (dist.DataParallel.uniforms); everything else keeps the reference's
@@ -1354,7 +1273,7 @@ def _device_state_fn(agent):
     body = getattr(agent.network, 'phi_body', None)
     conv1 = getattr(body, 'conv1', None)
     if (Config.DEVICE.type == 'cuda' and isinstance(norm, RescaleNormalizer) and type(body) is NatureConvBody
-            and isinstance(conv1, Conv2d) and conv1.weight.permute(1, 2, 3, 0).is_contiguous()
+            and isinstance(conv1, Conv2d) and k_major(conv1)
             and getattr(cfg, 'device_u8_states', True)):
         conv1.u8_coef = float(norm.coef)
 
@@ -1383,7 +1302,6 @@ class A2CAgent(BaseAgent):
         if self.dp.active:
             self.dp.set_weight(1.0 / self.dp.world)
         self.total_steps = 0
-        from .device_env import DeviceAtariVec
         if DeviceAtariVec.eligible(self.task, config):      # synthetic Atari emulators: the environments live on the device
             self.task = DeviceAtariVec(self.task)
         self.states = self.task.reset()
@@ -1517,9 +1435,7 @@ class A2CAgent(BaseAgent):
         optimizer -- is enqueued without a host round trip and, after two eager rollouts, replayed as ONE captured graph."""
         config = self.config
         plan = self.task.plan(config.rollout_length, config.reward_normalizer)
-        for t in range(config.rollout_length):
-            self.record_online_return(plan.infos[t])
-            self.total_steps += self.dp.global_workers
+        self._account_rollout(plan.infos, self.dp.global_workers)
         if self.dp.active:      # graph = [rollout + loss + backward]; the exchange and the step behind it stay eager
             out4 = self._dev_graph.run(plan, lambda pl: self._rollout_compute(pl, apply=False), tail=self._learn_apply)
         else:
@@ -1540,10 +1456,8 @@ class A2CAgent(BaseAgent):
                 # one batched forward take the rollout's stored outputs (same inputs, same parameters) instead of recomputing them
                 # -- 31 us of a 315 us agent step at 16 x 5.  (The recomputed forward runs the four-wave kernel shape, the rollout
                 # the eight-wave one: the two differ in fp32 summation order, parameters agree to ~1e-6 per update, not bit for bit.)
-                acts, body = self._pixel_rollout.bufs, self.network.phi_body
-                for conv, key in ((body.conv1, 'y1'), (body.conv2, 'y2'), (body.conv3, 'y3')):
-                    y = acts[key][:t_len]
-                    conv._y_pre = y.reshape((t_len * n,) + tuple(y.shape[2:]))
+                acts = self._pixel_rollout.bufs
+                hand_over(self.network.phi_body, acts, t_len, n)
                 # (and fc4's output: the folded features the rollout's head launches left -- the update's fc4 + head node runs the
                 # head launch alone)
                 self.network._phi_pre = acts['phi'][:t_len].reshape(t_len * n, 512)
@@ -1645,130 +1559,44 @@ class A2CAgent(BaseAgent):
         self.last_loss = self._learn(seen, actions, values, rewards_l, masks_l)
 
 
-class _QRollout:
-    """NStepDQNAgent's device path over VanillaNet(NatureConvBody) and device-resident synthetic Atari environments.  Per rollout
-    step the four launches of _PixelRollout with the Q head in conv1's launch (dra_rollout_conv1_qheads: [conv1 of step t | fc4's
-    fold + Q head + epsilon-greedy selection of step t - 1], conv2, conv3, fc4's 28 K-slice partial sums); step T is the TARGET
-    network's forward of the last observation (its conv1 launch carries the online head of step T - 1), then its max head
-    (dra_q_heads_fold28, NStepDQN_agent.py:56-57).  The update: returns, loss and the Q head's backward in one launch
-    (dra_nstep_q_loss_bwd), fc4 and the convolutions backpropagate through the activations the rollout stored (the reference keeps
-    the rollout's own forward graph, NStepDQN_agent.py:33-67), then the fused clip + optimizer step."""
+class _TargetRolloutAgent(BaseAgent):
+    """What NStepDQNAgent and OptionCriticAgent share: a target network in a flat buffer of its own and, over synthetic Atari
+    emulators, the device path of a pixel_rollout._TargetRollout."""
 
-    def __init__(self, agent):
-        self.agent = agent
-        self.bufs = None
-        self.stage, self.events, self.k = None, None, 0
+    def _sync_target(self):
+        ops.copy_f32(self._target_flat.flat, self._fused.flat.flat)
 
-    def eligible(self):
-        from .device_env import DeviceAtariVec
-        from .nets import Conv2d, Linear, NatureConvBody, VanillaNet
-        a = self.agent
-        net, cfg = a.network, a.config
-        if getattr(cfg, 'fused_rollout', True) is False or not DeviceAtariVec.eligible(a.task, cfg):
+    def _adopt_device(self, rollout):
+        """Moves the task to the device when `rollout` may run this agent (conv1 then takes the uint8 frames themselves) -> whether
+        it did."""
+        self._dev_graph = _OnPolicyGraph(self)
+        self.last_rollout = None
+        if not rollout.eligible():
             return False
-        if torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1:
-            return False        # data-parallel n-step DQN keeps the host path
-        if type(net) is not VanillaNet or type(net.body) is not NatureConvBody or getattr(net.body, 'noisy_linear', False):
-            return False
-        body = net.body
-        convs = [body.conv1, body.conv2, body.conv3]
-        if not all(type(c) is Conv2d and c.bias is not None and c.weight.permute(1, 2, 3, 0).is_contiguous() for c in convs):
-            return False
-        heads = [body.fc4, net.fc_head]
-        if not all(type(m) is Linear and m.bias is not None and m.weight.is_contiguous() for m in heads):
-            return False
-        envs = a.task.env.envs
-        n = len(envs)
-        return (body.fc4.fused_act == "relu" and tuple(body.fc4.weight.shape) == (512, 3136) and net.fc_head.fused_act is None
-                and 1 <= net.fc_head.weight.shape[0] <= 64 and envs[0].history == 4 and n <= 32
-                and int(cfg.rollout_length) * n <= 2048 and int(cfg.num_workers) == n)
+        self._rollout = rollout
+        self.task = DeviceAtariVec(self.task)
+        self.network.body.conv1.u8_coef = float(self.config.state_normalizer.coef)
+        return True
 
-    def upload_exploration(self, t_len):
-        """Draws the rollout's exploration (support.plan_epsilon_greedy) and stages it into the persistent device buffers the
-        Q-head launches read (fixed addresses: graph replays see the new values)."""
-        from .support import plan_epsilon_greedy
-        a = self.agent
-        n, n_act = a.task.num_envs, int(a.network.fc_head.weight.shape[0])
-        explore, rand = plan_epsilon_greedy(a.config.random_action_prob, t_len, n, n_act, a.config.num_workers)
-        if self.stage is None or self.stage[0][0].shape[0] != t_len:
-            dev = Config.DEVICE
-            self.explore = torch.zeros((t_len, n), dtype=torch.uint8, device=dev)
-            self.random_action = torch.zeros((t_len, n), dtype=torch.int64, device=dev)
-            self.stage = [(torch.zeros((t_len, n), dtype=torch.uint8).pin_memory(), torch.zeros((t_len, n), dtype=torch.int64).pin_memory())
-                          for _ in range(4)]
-            self.events = [None] * 4
-        k = self.k
-        self.k = (k + 1) % len(self.stage)
-        if self.events[k] is not None:
-            self.events[k].synchronize()
-        e_h, r_h = self.stage[k]
-        e_h.numpy()[...] = explore
-        r_h.numpy()[...] = rand
-        self.explore.copy_(e_h, non_blocking=True)
-        self.random_action.copy_(r_h, non_blocking=True)
-        ev = torch.cuda.Event()
-        ev.record()
-        self.events[k] = ev
-
-    def _buffers(self, t_len, n, n_act):
-        if self.bufs is None or self.bufs['key'] != (t_len, n, n_act):
-            dev = Config.DEVICE
-            f = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
-            self.bufs = dict(key=(t_len, n, n_act), y1=f(t_len + 1, n, 32, 20, 20), y2=f(t_len + 1, n, 64, 9, 9),
-                             y3=f(t_len + 1, n, 64, 7, 7), slabs=f(28, n, 512), phi=f(t_len, n, 512), q=f(t_len, n, n_act),
-                             action=torch.empty((t_len, n), dtype=torch.int64, device=dev), bootstrap=f(n))
-        return self.bufs
-
-    def compute(self, plan):
-        import ctypes
-        from ._lib import lib, stream_ptr
-        from .nets import _claim_direct, direct_param_grads, fc4_from_rollout
-        a = self.agent
-        cfg = a.config
-        net, tgt = a.network, a.target_network
-        t_len, n = plan.t_len, a.task.num_envs
-        head = net.fc_head
-        n_act = int(head.weight.shape[0])
-        b = self._buffers(t_len, n, n_act)
-        frames = a.task.states_all(plan)           # every observation of the planned rollout, one launch
-        coef = float(net.body.conv1.u8_coef)
-        arr = lambda t: (ctypes.c_void_p * 1)(t.data_ptr())
-        st = stream_ptr()
-        relu = ops.ACT["relu"]
-        online, target = net.body, tgt.body
-        for t in range(t_len + 1):
-            body = target if t == t_len else online
-            prev = t > 0
-            ops.rollout_conv1_qheads(frames[t], body.conv1.weight, body.conv1.bias, b['y1'][t], coef,
-                                     *((b['slabs'], online.fc4.bias, head.weight, head.bias, self.explore[t - 1],
-                                        self.random_action[t - 1], b['q'][t - 1], b['action'][t - 1], b['phi'][t - 1]) if prev else ()))
-            lib.dra_conv_fwd_koc(2, 1, arr(b['y1'][t]), arr(body.conv2.weight), arr(body.conv2.bias), arr(b['y2'][t]), n, 0, 1.0, relu, st)
-            lib.dra_conv_fwd_koc(3, 1, arr(b['y2'][t]), arr(body.conv3.weight), arr(body.conv3.bias), arr(b['y3'][t]), n, 0, 1.0, relu, st)
-            lib.dra_linear_fwd_slabs_one(1, arr(b['y3'][t]), arr(body.fc4.weight), n, 3136, 512, 28, ctypes.c_void_p(b['slabs'].data_ptr()), st)
-        ops.q_heads_fold28(b['slabs'], target.fc4.bias, tgt.fc_head.weight, tgt.fc_head.bias, out_max=b['bootstrap'])
-        a._rollout_step += t_len
-        # ---- the update over the rollout's own activations (the conv layers' _y_pre, fc4's stored output)
-        rows = t_len * n
-        for conv, key in ((online.conv1, 'y1'), (online.conv2, 'y2'), (online.conv3, 'y3')):
-            y = b[key][:t_len]
-            conv._y_pre = y.reshape((rows,) + tuple(y.shape[2:]))
-        y3 = online.conv3(online.conv2(online.conv1(frames[:t_len].reshape((rows,) + tuple(frames.shape[2:])))))
-        phi = fc4_from_rollout(online, y3.view(rows, -1), b['phi'].view(rows, 512))
-        a._fused.zero_grad(direct=True)
-        defer = a._fused if getattr(cfg, 'defer_conv_folds', True) else None
-        with direct_param_grads(True, defer_folds_to=defer, covers=[a._fused]):
-            _claim_direct((head.weight, head.bias))       # the loss launch writes the Q head's gradient in place
-            out = ops.nstep_q_loss_bwd(b['q'], b['action'], plan.reward, plan.mask, b['bootstrap'], cfg.discount, b['phi'].view(rows, 512),
-                                       head.weight, out=dict(ret=torch.empty((t_len, n), dtype=torch.float32, device=frames.device),
-                                                             loss=torch.empty(1, dtype=torch.float32, device=frames.device),
-                                                             dw=head.weight.grad, db=head.bias.grad,
-                                                             dphi=torch.empty((rows, 512), dtype=torch.float32, device=frames.device)))
-            torch.autograd.backward([phi], [out['dphi']])
-        a._fused.step(cfg.gradient_clip)
-        return dict(loss=out['loss'], ret=out['ret'], q=b['q'], action=b['action'], bootstrap=b['bootstrap'])
+    def _step_device(self):
+        """step() over device-resident environments: the host lays the rollout out (DeviceAtariVec.plan) and makes the rollout's
+        draws in the reference's order (the rollout's prepare()); the T head forwards with their choices, the target network's
+        bootstrap, the loss, the backward over the rollout's own activations, clip and optimizer step are enqueued without a host
+        round trip and, after two eager rollouts, replayed as ONE captured graph (the rollout's compute()).  The target copy of
+        NStepDQN_agent.py:48-50 / OptionCritic_agent.py:83-85 runs before the rollout: the parameters do not change inside one, so
+        copying then gives the bootstrap copying at step t gives."""
+        config = self.config
+        t_len = config.rollout_length
+        plan = self.task.plan(t_len, config.reward_normalizer)
+        self._rollout.prepare(t_len)
+        if self._account_rollout(plan.infos, config.num_workers):
+            self._sync_target()
+        out = self._dev_graph.run(plan, self._rollout.compute)
+        self.last_loss = out['loss']
+        self.last_rollout = out
 
 
-class NStepDQNAgent(BaseAgent):
+class NStepDQNAgent(_TargetRolloutAgent):
     """NStepDQN_agent.py:12-67: on-policy n-step Q-learning; returns via the scan kernel (use_gae off)."""
 
     def __init__(self, config):
@@ -1781,40 +1609,13 @@ class NStepDQNAgent(BaseAgent):
         self._fused = FusedOptimizer.adopt(self.optimizer)
         self._target_flat = FlatParams(list(self.target_network.parameters()),
                                        koc=nature_conv_weights(list(self.target_network.parameters())))
-        ops.copy_f32(self._target_flat.flat, self._fused.flat.flat)
+        self._sync_target()
         self.total_steps = 0
         self.grad_hook = None
         self._rollout_step = 0
         self._q_rollout = _QRollout(self)
-        if self._q_rollout.eligible():      # synthetic Atari emulators + VanillaNet(NatureConvBody): the rollout lives on the device
-            from .device_env import DeviceAtariVec
-            self.task = DeviceAtariVec(self.task)
-            self.network.body.conv1.u8_coef = float(config.state_normalizer.coef)
-        self._dev_graph = _OnPolicyGraph(self)
-        self.last_rollout = None
+        self._adopt_device(self._q_rollout)     # synthetic Atari emulators + VanillaNet(NatureConvBody): the rollout lives on the device
         self.states = self.task.reset()
-
-    def _step_device(self):
-        """step() over device-resident environments: the host lays the rollout out (DeviceAtariVec.plan) and draws its exploration
-        in the reference's order (support.plan_epsilon_greedy); the T Q-head forwards, the target network's bootstrap, the loss, the
-        backward over the rollout's own activations, clip and optimizer step are enqueued without a host round trip and, after two
-        eager rollouts, replayed as ONE captured graph (_QRollout.compute).  The target copy of NStepDQN_agent.py:48-50 runs
-        before the rollout: the parameters do not change inside one, so copying then gives the bootstrap copying at step t gives."""
-        config = self.config
-        t_len = config.rollout_length
-        plan = self.task.plan(t_len, config.reward_normalizer)
-        self._q_rollout.upload_exploration(t_len)
-        sync = False
-        for t in range(t_len):
-            self.record_online_return(plan.infos[t])
-            self.total_steps += config.num_workers
-            if self.total_steps // config.num_workers % config.target_network_update_freq == 0:
-                sync = True
-        if sync:
-            ops.copy_f32(self._target_flat.flat, self._fused.flat.flat)
-        out = self._dev_graph.run(plan, self._q_rollout.compute)
-        self.last_loss = out['loss']
-        self.last_rollout = out
 
     def step(self):
         if getattr(self.task, 'on_device', False):
@@ -1834,7 +1635,7 @@ class NStepDQNAgent(BaseAgent):
             states = next_states
             self.total_steps += config.num_workers
             if self.total_steps // config.num_workers % config.target_network_update_freq == 0:
-                ops.copy_f32(self._target_flat.flat, self._fused.flat.flat)
+                self._sync_target()
         self.states = states
         storage.placeholder()
         with torch.no_grad():
@@ -1887,7 +1688,7 @@ class PPOAgent(BaseAgent):
         if config.shared_repr:
             _dp_plan_exchange(self.dp, self.network, self._fused)
         self.total_steps = 0
-        from .device_env import DeviceAtariVec, DeviceContinuousVec
+        from .device_env import DeviceContinuousVec
         from .ppo_mlp import MlpPPO
         self.grad_hook = None
         self._mlp = MlpPPO(self)        # csrc/ppo_mlp.hip: two small tanh MLPs + two Adam optimisers as persistent kernels
@@ -1907,7 +1708,7 @@ class PPOAgent(BaseAgent):
         if config.shared_repr:
             self.lr_scheduler = torch.optim.lr_scheduler.LambdaLR(self.opt, lambda step: 1 - step / config.max_steps)
         self._graphed = _GraphedPPO(self)
-        self._rollout_graph = dict(calls=0, graph=None, failed=False, k=0)
+        self._rollout_graph = dict(calls=0, graph=None, failed=False)
         self._rollout_step = 0
         _install_sampler(self)
         self._pixel_rollout = _PixelRollout(self)
@@ -1941,9 +1742,7 @@ class PPOAgent(BaseAgent):
         captured graph whose outputs are the rollout entries; the optimisation phase is unchanged."""
         config = self.config
         plan = self.task.plan(config.rollout_length, config.reward_normalizer)
-        for t in range(config.rollout_length):
-            self.record_online_return(plan.infos[t])
-            self.total_steps += self.dp.global_workers
+        self._account_rollout(plan.infos, self.dp.global_workers)
         if self.dp.active:      # PPO_agent.py:66 over the GLOBAL rollout: three all-reduced scalars, outside the captured region
             from .dist import global_advantage_normalize_
 
@@ -2097,9 +1896,8 @@ class PPOAgent(BaseAgent):
                 if g['graph'] is None or g['in'].shape != x.shape:
                     validate = torch.distributions.Distribution._validate_args
                     try:
-                        g['in'] = torch.zeros(x.shape, dtype=torch.float32, device=Config.DEVICE)
-                        g['stage'] = [torch.empty(x.shape, dtype=torch.float32).pin_memory() for _ in range(4)]
-                        g['events'] = [None] * 4
+                        g['upload'] = StagedUpload(x.shape, torch.float32, Config.DEVICE)
+                        g['in'] = g['upload'].dev
                         torch.distributions.Distribution.set_default_validate_args(False)
                         graph = torch.cuda.CUDAGraph()
                         # (a categorical net reads its uniforms from the rollout's one draw: the captured forward reads a static
@@ -2122,15 +1920,7 @@ class PPOAgent(BaseAgent):
                         if getattr(self.network, 'rollout_slots', None) is not None:
                             self.network.rollout_slots.pin(None)
                 if not g['failed']:
-                    k = g['k']
-                    g['k'] = (k + 1) % 4
-                    if g['events'][k] is not None:
-                        g['events'][k].synchronize()
-                    g['stage'][k].numpy()[...] = x
-                    g['in'].copy_(g['stage'][k], non_blocking=True)
-                    ev = torch.cuda.Event()
-                    ev.record()
-                    g['events'][k] = ev
+                    g['upload'].put(x)
                     if g['u'] is not None:
                         u = self.network.rollout_slots.next_uniform()
                         if u is not None and u.numel() == g['u'].numel():
@@ -2611,159 +2401,7 @@ class TD3Agent(_DeterministicPolicyAgent):
 
 
 # ==================================================================================================== option-critic
-class _OCRollout:
-    """OptionCriticAgent's device path over OptionCriticNet(NatureConvBody) and device-resident synthetic Atari environments.  Per
-    rollout step the four launches of _PixelRollout with the option-critic head in conv1's launch (dra_rollout_conv1_ocheads:
-    [conv1 of step t | fc4's fold + q / beta / intra-option logits + option and action choice of step t - 1], conv2, conv3, fc4's
-    28 K-slice partial sums); step T is the TARGET network's forward of the last observation (its conv1 launch carries the online
-    head of step T - 1), then its bootstrap head (dra_oc_heads_fold28, OptionCritic_agent.py:87-93).  The update: returns,
-    advantages, the three losses and the heads' backward in one launch (dra_oc_loss_bwd), fc4 and the convolutions backpropagate
-    through the activations the rollout stored, then the fused clip + optimizer step.  The carried option state (prev_option,
-    is_initial) lives in persistent device buffers the head launches read and replace.  Random draws: one uniform_() [T, N, 3] per
-    rollout on torch's device generator (draw_uniforms, before the captured region), turned into options and actions by inverse
-    CDF -- the documented deviation of A2C's RolloutSlots: Categorical.sample()'s own stream is not reproduced."""
-
-    def __init__(self, agent):
-        self.agent = agent
-        self.bufs = None
-        self.stage, self.events, self.k = None, None, 0
-        self.uniform = None
-        self.eps = None
-
-    def eligible(self):
-        from .device_env import DeviceAtariVec
-        from .nets import Conv2d, Linear, NatureConvBody, OptionCriticNet
-        a = self.agent
-        net, cfg = a.network, a.config
-        if getattr(cfg, 'fused_rollout', True) is False or not DeviceAtariVec.eligible(a.task, cfg):
-            return False
-        if torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1:
-            return False        # data-parallel option-critic keeps the host path
-        if type(net) is not OptionCriticNet or type(net.body) is not NatureConvBody or getattr(net.body, 'noisy_linear', False):
-            return False
-        body = net.body
-        convs = [body.conv1, body.conv2, body.conv3]
-        if not all(type(c) is Conv2d and c.bias is not None and c.weight.permute(1, 2, 3, 0).is_contiguous() for c in convs):
-            return False
-        heads = [net.fc_q, net.fc_pi, net.fc_beta]
-        if not all(type(m) is Linear and m.bias is not None and m.weight.is_contiguous() and m.fused_act is None for m in heads):
-            return False
-        if not (type(body.fc4) is Linear and body.fc4.bias is not None and body.fc4.weight.is_contiguous()):
-            return False
-        n_opt, n_act = int(net.num_options), int(net.action_dim)
-        envs = a.task.env.envs
-        n = len(envs)
-        return (body.fc4.fused_act == "relu" and tuple(body.fc4.weight.shape) == (512, 3136) and 1 <= n_opt <= 8
-                and 1 <= n_act <= 18 and tuple(net.fc_q.weight.shape) == (n_opt, 512)
-                and tuple(net.fc_beta.weight.shape) == (n_opt, 512) and tuple(net.fc_pi.weight.shape) == (n_opt * n_act, 512)
-                and envs[0].history == 4 and n <= 32 and int(cfg.rollout_length) * n <= 2048 and int(cfg.num_workers) == n)
-
-    def state(self, n):
-        """The carried option state (OptionCritic_agent.py:26-27: ones at the start): persistent device buffers."""
-        dev = Config.DEVICE
-        self.prev_option = torch.ones(n, dtype=torch.int64, device=dev)
-        self.is_initial = torch.ones(n, dtype=torch.bool, device=dev)
-        return self.prev_option, self.is_initial
-
-    def upload_exploration(self, t_len):
-        """config.random_option_prob(num_workers) once per rollout step -- the reference's calls in its order -- staged into the
-        persistent [T] buffer the head launches read (a fixed address: graph replays see the new values).  -> the host values."""
-        a = self.agent
-        eps = np.asarray([a.config.random_option_prob(a.config.num_workers) for _ in range(t_len)], dtype=np.float64)
-        if self.stage is None or self.stage[0].shape[0] != t_len:
-            self.eps = torch.zeros(t_len, dtype=torch.float32, device=Config.DEVICE)
-            self.stage = [torch.zeros(t_len, dtype=torch.float32).pin_memory() for _ in range(4)]
-            self.events = [None] * 4
-        k = self.k
-        self.k = (k + 1) % len(self.stage)
-        if self.events[k] is not None:
-            self.events[k].synchronize()
-        self.stage[k].numpy()[...] = eps
-        self.eps.copy_(self.stage[k], non_blocking=True)
-        ev = torch.cuda.Event()
-        ev.record()
-        self.events[k] = ev
-        return eps
-
-    def draw_uniforms(self, t_len):
-        """One uniform_() [T, N, 3] on torch's device generator into a persistent buffer (columns: fresh option, continued option,
-        action).  Runs before the captured region, so replays read the new draw at the same address."""
-        n = self.agent.task.num_envs
-        if self.uniform is None or self.uniform.shape[0] != t_len:
-            self.uniform = torch.empty((t_len, n, 3), dtype=torch.float32, device=Config.DEVICE)
-        self.uniform.uniform_()
-
-    def _buffers(self, t_len, n, n_opt, n_act):
-        if self.bufs is None or self.bufs['key'] != (t_len, n, n_opt, n_act):
-            dev = Config.DEVICE
-            f = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
-            i = lambda *shape: torch.empty(shape, dtype=torch.int64, device=dev)
-            self.bufs = dict(key=(t_len, n, n_opt, n_act), y1=f(t_len + 1, n, 32, 20, 20), y2=f(t_len + 1, n, 64, 9, 9),
-                             y3=f(t_len + 1, n, 64, 7, 7), slabs=f(28, n, 512), phi=f(t_len, n, 512), q=f(t_len, n, n_opt),
-                             beta=f(t_len, n, n_opt), logits=f(t_len, n, n_act), option=i(t_len, n), action=i(t_len, n),
-                             log_pi_a=f(t_len, n), entropy=f(t_len, n), prev_option=i(t_len, n), init=f(t_len, n), boot=f(n))
-        return self.bufs
-
-    def compute(self, plan):
-        import ctypes
-        from ._lib import lib, stream_ptr
-        from .nets import _claim_direct, direct_param_grads, fc4_from_rollout
-        a = self.agent
-        cfg = a.config
-        net, tgt = a.network, a.target_network
-        t_len, n = plan.t_len, a.task.num_envs
-        n_opt, n_act = int(net.num_options), int(net.action_dim)
-        b = self._buffers(t_len, n, n_opt, n_act)
-        frames = a.task.states_all(plan)           # every observation of the planned rollout, one launch
-        coef = float(net.body.conv1.u8_coef)
-        arr = lambda t: (ctypes.c_void_p * 1)(t.data_ptr())
-        st = stream_ptr()
-        relu = ops.ACT["relu"]
-        online, target = net.body, tgt.body
-        heads = (net.fc_q.weight, net.fc_q.bias, net.fc_beta.weight, net.fc_beta.bias, net.fc_pi.weight, net.fc_pi.bias)
-        keys = ("q", "beta", "logits", "option", "action", "log_pi_a", "entropy", "prev_option", "init", "phi")
-        for t in range(t_len + 1):
-            body = target if t == t_len else online
-            if t > 0:
-                s = t - 1
-                ops.rollout_conv1_ocheads(frames[t], body.conv1.weight, body.conv1.bias, b['y1'][t], coef, b['slabs'], online.fc4.bias,
-                                          heads, self.uniform[s], self.eps[s:s + 1], plan.mask[s], self.prev_option, self.is_initial,
-                                          out={k: b[k][s] for k in keys})
-            else:
-                ops.rollout_conv1_ocheads(frames[t], body.conv1.weight, body.conv1.bias, b['y1'][t], coef)
-            lib.dra_conv_fwd_koc(2, 1, arr(b['y1'][t]), arr(body.conv2.weight), arr(body.conv2.bias), arr(b['y2'][t]), n, 0, 1.0, relu, st)
-            lib.dra_conv_fwd_koc(3, 1, arr(b['y2'][t]), arr(body.conv3.weight), arr(body.conv3.bias), arr(b['y3'][t]), n, 0, 1.0, relu, st)
-            lib.dra_linear_fwd_slabs_one(1, arr(b['y3'][t]), arr(body.fc4.weight), n, 3136, 512, 28, ctypes.c_void_p(b['slabs'].data_ptr()), st)
-        ops.oc_heads_fold28(b['slabs'], target.fc4.bias, tgt.fc_q.weight, tgt.fc_q.bias, tgt.fc_beta.weight, tgt.fc_beta.bias,
-                            prev_option=self.prev_option, boot=b['boot'])
-        a._rollout_step += t_len
-        # ---- the update over the rollout's own activations (the conv layers' _y_pre, fc4's stored output)
-        rows = t_len * n
-        for conv, key in ((online.conv1, 'y1'), (online.conv2, 'y2'), (online.conv3, 'y3')):
-            y = b[key][:t_len]
-            conv._y_pre = y.reshape((rows,) + tuple(y.shape[2:]))
-        y3 = online.conv3(online.conv2(online.conv1(frames[:t_len].reshape((rows,) + tuple(frames.shape[2:])))))
-        phi = fc4_from_rollout(online, y3.view(rows, -1), b['phi'].view(rows, 512))
-        a._fused.zero_grad(direct=True)
-        defer = a._fused if getattr(cfg, 'defer_conv_folds', True) else None
-        dev = frames.device
-        f = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
-        with direct_param_grads(True, defer_folds_to=defer, covers=[a._fused]):
-            _claim_direct(heads)       # the loss launch writes the three heads' gradients in place
-            out = ops.oc_loss_bwd(b, plan.reward, plan.mask, b['boot'], self.eps, cfg.discount, cfg.termination_regularizer,
-                                  cfg.entropy_weight, b['phi'].view(rows, 512), net.fc_q.weight, net.fc_pi.weight, net.fc_beta.weight,
-                                  out=dict(ret=f(t_len, n), adv=f(t_len, n), beta_adv=f(t_len, n), loss=f(4),
-                                           dw_q=net.fc_q.weight.grad, db_q=net.fc_q.bias.grad, dw_pi=net.fc_pi.weight.grad,
-                                           db_pi=net.fc_pi.bias.grad, dw_beta=net.fc_beta.weight.grad,
-                                           db_beta=net.fc_beta.bias.grad, dphi=f(rows, 512)))
-            torch.autograd.backward([phi], [out['dphi']])
-        a._fused.step(cfg.gradient_clip)
-        return dict(q=b['q'], beta=b['beta'], logits=b['logits'], option=b['option'], prev_option=b['prev_option'], init=b['init'],
-                    action=b['action'], log_pi_a=b['log_pi_a'], entropy=b['entropy'], boot=b['boot'], ret=out['ret'],
-                    advantage=out['adv'], beta_advantage=out['beta_adv'], loss=out['loss'][:1], losses=out['loss'])
-
-
-class OptionCriticAgent(BaseAgent):
+class OptionCriticAgent(_TargetRolloutAgent):
     """OptionCritic_agent.py:11-119: n-step option-critic over `num_workers` environments.  Per rollout step: one forward
     (q over options, termination beta, intra-option policies), an epsilon-soft option choice that keeps the previous
     option unless it terminates, an action from the chosen option's policy; per rollout: returns bootstrapped from the
@@ -2785,46 +2423,14 @@ class OptionCriticAgent(BaseAgent):
         self.worker_index = range_tensor(config.num_workers)
         self.grad_hook = None
         self._rollout_step = 0
-        self.last_rollout = None
         self._oc_rollout = _OCRollout(self)
-        if self._oc_rollout.eligible():     # synthetic Atari emulators + OptionCriticNet(NatureConvBody): the rollout lives on the device
-            from .device_env import DeviceAtariVec
-            self.task = DeviceAtariVec(self.task)
-            self.network.body.conv1.u8_coef = float(config.state_normalizer.coef)
-            self._dev_graph = _OnPolicyGraph(self)
+        if self._adopt_device(self._oc_rollout):    # synthetic Atari emulators + OptionCriticNet(NatureConvBody): the rollout lives on the device
             self.states = self.task.reset()
             self.prev_options, self.is_initial_states = self._oc_rollout.state(config.num_workers)
             return
         self.states = config.state_normalizer(self.task.reset())
         self.is_initial_states = torch.ones(config.num_workers, dtype=torch.bool, device=Config.DEVICE)
         self.prev_options = torch.ones(config.num_workers, dtype=torch.int64, device=Config.DEVICE)
-
-    def _sync_target(self):
-        ops.copy_f32(self._target_flat.flat, self._fused.flat.flat)
-
-    def _step_device(self):
-        """step() over device-resident environments: the host lays the rollout out (DeviceAtariVec.plan), calls the option
-        epsilon schedule once per rollout step in the reference's order and draws the rollout's uniforms (_OCRollout.draw_uniforms);
-        the T head forwards with their option / action choices, the target network's bootstrap, the loss, the backward over the
-        rollout's own activations, clip and optimizer step are enqueued without a host round trip and, after two eager rollouts,
-        replayed as ONE captured graph (_OCRollout.compute).  The target copy of OptionCritic_agent.py:83-85 runs before the
-        rollout: the parameters do not change inside one, so copying then gives the bootstrap copying at step t gives."""
-        config = self.config
-        t_len = config.rollout_length
-        plan = self.task.plan(t_len, config.reward_normalizer)
-        self._oc_rollout.upload_exploration(t_len)
-        self._oc_rollout.draw_uniforms(t_len)
-        sync = False
-        for t in range(t_len):
-            self.record_online_return(plan.infos[t])
-            self.total_steps += config.num_workers
-            if self.total_steps // config.num_workers % config.target_network_update_freq == 0:
-                sync = True
-        if sync:
-            self._sync_target()
-        out = self._dev_graph.run(plan, self._oc_rollout.compute)
-        self.last_loss = out['loss']
-        self.last_rollout = out
 
     def sample_option(self, prediction, epsilon, prev_option, is_initial):
         with torch.no_grad():

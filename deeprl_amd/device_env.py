@@ -16,7 +16,7 @@ import numpy as np
 import torch
 
 from ._lib import lib, stream_ptr
-from .support import Config
+from .support import Config, StagedUpload
 
 Plan = namedtuple("Plan", ["counters", "ages", "reward", "mask", "infos", "t_len"])
 
@@ -92,24 +92,18 @@ class DeviceAtariVec:
         return None     # observations come from states(plan, t); the first one is every stream's initial reset
 
     def _static(self, t_len):
-        """Persistent device buffers + rotating pinned staging of one rollout plan (graph replays read the same addresses)."""
+        """Persistent device buffer + rotating pinned staging of one rollout plan (graph replays read the same addresses)."""
         if t_len not in self._bufs:
-            n, dev = self.num_envs, Config.DEVICE
+            n = self.num_envs
             words = (t_len + 1) * n * 2 + (t_len + 1) * n + 2 * t_len * n      # i64 counters | i32 ages | f32 reward, mask
-            self._bufs[t_len] = dict(
-                dev=torch.zeros(words * 4 + 16, dtype=torch.uint8, device=dev),
-                stage=[torch.zeros(words * 4 + 16, dtype=torch.uint8).pin_memory() for _ in range(4)], events=[None] * 4, k=0)
+            self._bufs[t_len] = StagedUpload(words * 4 + 16, torch.uint8, Config.DEVICE)
         return self._bufs[t_len]
 
     def plan(self, t_len, reward_normalizer):
         """Advances every environment by t_len transitions on the host shadow and uploads what the device needs."""
         n = self.num_envs
-        b = self._static(t_len)
-        k = b['k']
-        b['k'] = (k + 1) % len(b['stage'])
-        if b['events'][k] is not None:
-            b['events'][k].synchronize()
-        raw = b['stage'][k].numpy()
+        up = self._static(t_len)
+        raw = up.stage().numpy()
         o1 = (t_len + 1) * n * 8
         o2 = o1 + (t_len + 1) * n * 4
         o3 = o2 + t_len * n * 4
@@ -126,11 +120,7 @@ class DeviceAtariVec:
             infos.append(tuple({'episodic_return': float(r) if d else None} for r, d in zip(ep_ret, done)) if done.any()
                          else self._no_info)
         counters[t_len], ages[t_len] = sh.c, sh.age   # the observation the NEXT rollout starts from (bootstrap value)
-        d = b['dev']
-        d.copy_(b['stage'][k], non_blocking=True)
-        ev = torch.cuda.Event()
-        ev.record()
-        b['events'][k] = ev
+        d = up.send()
         return Plan(counters=d[:o1].view(torch.int64).view(t_len + 1, n), ages=d[o1:o2].view(torch.int32).view(t_len + 1, n),
                     reward=d[o2:o3].view(torch.float32).view(t_len, n, 1), mask=d[o3:o3 + t_len * n * 4].view(torch.float32).view(t_len, n, 1),
                     infos=infos, t_len=t_len)

@@ -19,7 +19,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import ops
-from .support import Config, tensor
+from .support import Config, StagedUpload, tensor
 
 
 class BaseNet:
@@ -759,18 +759,15 @@ class _NoiseBlock:
         self.numel = off
         dev = self.layers[0][1].noise_in.device
         self.device = dev
-        self.flat = torch.zeros(off, dtype=torch.float32, device=dev)
+        self._up = StagedUpload(off, torch.float32, dev, self.SLOTS)
+        self.flat = self._up.dev
         for lname, m in self.layers:
             for bname in NoisyLinear.NOISE_NAMES:
                 o, n = self.slices[(lname, bname)]
                 self.flat[o:o + n].copy_(getattr(m, bname))
                 m._buffers[bname] = self.flat[o:o + n]
-        pin = dev.type == 'cuda'
-        self.stage = [torch.zeros(off, dtype=torch.float32).pin_memory() if pin else torch.zeros(off, dtype=torch.float32)
-                      for _ in range(self.SLOTS if pin else 1)]
-        self.events = [None] * len(self.stage)
-        self.k = 0
-        self.host = self.stage[0]                   # the staging block the last draw() filled
+        self._rows = {}                             # row count -> the staged [rows][numel] block of draw_rows
+        self.host = self._up.stages[0]              # the staging block the last draw() filled
 
     def intact(self):
         """The modules' buffers are still the views (Module.to() / .cuda() replace them by fresh tensors)."""
@@ -778,37 +775,19 @@ class _NoiseBlock:
         return all(getattr(m, b).data_ptr() == base + 4 * self.slices[(ln, b)][0] for ln, m in self.layers
                    for b in NoisyLinear.NOISE_NAMES)
 
-    def draw(self):
-        k = self.k
-        self.k = (k + 1) % len(self.stage)
-        if self.events[k] is not None:
-            self.events[k].synchronize()
-        host = self.stage[k]
+    def _draw_into(self, host):
         std = Config.NOISY_LAYER_STD
         for lname, _ in self.layers:
             for bname in NoisyLinear.NOISE_NAMES:
                 o, n = self.slices[(lname, bname)]
                 host[o:o + n].normal_(std=std)
-        self.host = host
-        self.flat.copy_(host, non_blocking=True)
-        if self.device.type == 'cuda':
-            if self.events[k] is None:
-                self.events[k] = torch.cuda.Event()
-            self.events[k].record()
+
+    def draw(self):
+        self.host = self._up.stage()
+        self._draw_into(self.host)
+        self._up.send()
         for _, m in self.layers:
             m.noise_changed()
-
-    def _rows_buffers(self, rows):
-        """Static [rows][numel] device block + its rotating pinned staging (built on first use, per row count)."""
-        bufs = getattr(self, '_rows', None)
-        if bufs is None:
-            bufs = self._rows = {}
-        if rows not in bufs:
-            pin = self.device.type == 'cuda'
-            stage = [torch.zeros((rows, self.numel), dtype=torch.float32) for _ in range(self.SLOTS if pin else 1)]
-            bufs[rows] = dict(dev=torch.zeros((rows, self.numel), dtype=torch.float32, device=self.device),
-                              stage=[s.pin_memory() for s in stage] if pin else stage, events=[None] * len(stage), k=0)
-        return bufs[rows]
 
     def draw_rows(self, rows):
         """`rows` successive draw()s -- the reset_noise() calls of the transitions of one agent step (DQN_agent.py:28-29) -- into
@@ -817,29 +796,18 @@ class _NoiseBlock:
         get row rows - 1, as after the last of those calls.  Returns the device block (dra_noisy_linear_fwd_rows reads the rows
         self.numel floats apart; a layer's vectors start at self.slices[...][0] of each row)."""
         rows = int(rows)
-        b = self._rows_buffers(rows)
-        k = b['k']
-        b['k'] = (k + 1) % len(b['stage'])
-        if b['events'][k] is not None:
-            b['events'][k].synchronize()
-        host = b['stage'][k]
-        std = Config.NOISY_LAYER_STD
+        if rows not in self._rows:
+            self._rows[rows] = StagedUpload((rows, self.numel), torch.float32, self.device, self.SLOTS)
+        up = self._rows[rows]
+        host = up.stage()
         for r in range(rows):
-            row = host[r]
-            for lname, _ in self.layers:
-                for bname in NoisyLinear.NOISE_NAMES:
-                    o, n = self.slices[(lname, bname)]
-                    row[o:o + n].normal_(std=std)
+            self._draw_into(host[r])
         self.host = host[rows - 1]
-        b['dev'].copy_(host, non_blocking=True)
-        self.flat.copy_(b['dev'][rows - 1])
-        if self.device.type == 'cuda':
-            if b['events'][k] is None:
-                b['events'][k] = torch.cuda.Event()
-            b['events'][k].record()
+        dev = up.send()
+        self.flat.copy_(dev[rows - 1])
         for _, m in self.layers:
             m.noise_changed()
-        return b['dev']
+        return dev
 
 
 # ---------------------------------------------------------------------------------------------------- bodies

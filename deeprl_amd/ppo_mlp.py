@@ -17,7 +17,7 @@ import torch
 
 from ._lib import DraError, lib, ptr, stream_ptr
 from .mlp_rollout import body_params
-from .support import Config
+from .support import Config, StagedUpload
 
 DBG_FLOATS = 65536          # DRA_PPO_MLP_DBG_FLOATS
 
@@ -152,22 +152,13 @@ class MlpPPO:
         dev = entries.state.device
         # PPO_agent.py:72 -> misc.py:55-62: one np.random.permutation per epoch (random_sample draws it when the epoch starts;
         # no other consumer of np.random sits between the epochs, so drawing them together leaves the stream where it was)
-        if self._perm is None or self._perm.numel() != epochs * n:
-            self._perm = torch.zeros(epochs * n, dtype=torch.int64, device=dev)
-            self._perm_up = [torch.zeros(epochs * n, dtype=torch.int64).pin_memory() for _ in range(2)]
-            self._perm_ev = [None, None]
-            self._perm_k = 0
-        k = self._perm_k
-        self._perm_k = 1 - k
-        if self._perm_ev[k] is not None:
-            self._perm_ev[k].synchronize()
-        stage = self._perm_up[k].numpy()
+        if self._perm_up is None or self._perm.numel() != epochs * n:
+            self._perm_up = StagedUpload(epochs * n, torch.int64, dev, slots=2)
+            self._perm = self._perm_up.dev
+        stage = self._perm_up.stage().numpy()
         for e in range(epochs):
             stage[e * n:(e + 1) * n] = a.dp.permutation(n)
-        self._perm.copy_(self._perm_up[k], non_blocking=True)
-        ev = torch.cuda.Event()
-        ev.record()
-        self._perm_ev[k] = ev
+        self._perm_up.send()
         floats = ctypes.c_int64()
         lib.dra_ppo_mlp_packed_floats(n, epochs, mb, s_dim, ctypes.byref(floats))
         if self._packed is None or self._packed.numel() != floats.value:

@@ -91,6 +91,45 @@ def tensor(x):
     return torch.from_numpy(x).to(Config.DEVICE)
 
 
+class StagedUpload:
+    """A persistent device tensor (`.dev`: a fixed address, so a captured graph reads whatever was sent last) refilled through
+    `slots` rotating pinned host stages, one event per stage guarding its reuse: `stage()` hands out the next host stage as a
+    torch tensor once the copy that last left it has finished, `send()` copies it into `.dev` asynchronously on the current
+    stream and records the stage's event.  On a CPU device: one unpinned stage, no events.  `event_cls` (tests) stands in for
+    torch.cuda.Event and keeps the `slots` stages on any device."""
+
+    def __init__(self, shape, dtype, device, slots=4, event_cls=None):
+        device = torch.device(device)
+        pin = device.type == 'cuda'
+        self._event_cls = event_cls if event_cls is not None else (torch.cuda.Event if pin else None)
+        self.dev = torch.zeros(shape, dtype=dtype, device=device)
+        stages = [torch.zeros(shape, dtype=dtype) for _ in range(slots if self._event_cls is not None else 1)]
+        self.stages = [s.pin_memory() for s in stages] if pin else stages
+        self.events = [None] * len(self.stages)
+        self.k = 0          # the stage stage() hands out and send() sends
+
+    def stage(self):
+        ev = self.events[self.k]
+        if ev is not None:
+            ev.synchronize()
+        return self.stages[self.k]
+
+    def send(self):
+        k = self.k
+        self.k = (k + 1) % len(self.stages)
+        self.dev.copy_(self.stages[k], non_blocking=True)
+        if self._event_cls is not None:
+            if self.events[k] is None:
+                self.events[k] = self._event_cls()
+            self.events[k].record()
+        return self.dev
+
+    def put(self, values):
+        """stage() filled with the numpy array `values`, then send()."""
+        self.stage().numpy()[...] = values
+        return self.send()
+
+
 def range_tensor(end):
     return torch.arange(end).long().to(Config.DEVICE)
 
