@@ -1615,9 +1615,137 @@ class NStepDQNAgent(_TargetRolloutAgent):
         self._rollout_step = 0
         self._q_rollout = _QRollout(self)
         self._adopt_device(self._q_rollout)     # synthetic Atari emulators + VanillaNet(NatureConvBody): the rollout lives on the device
+        # n_step_dqn_feature, examples.py:408-424 (opt-in, config.fused_nstep_feature): cart-poles under VanillaNet over a small
+        # FCBody live on the device, one launch per rollout and one per update (csrc/q_mlp.hip)
+        self._dev_steps, self._step_host, self._ep_anchor, self._ep_log = 0, 0, None, collections.deque(maxlen=16384)
         self.states = self.task.reset()
+        self._feature = self._adopt_feature()       # (the environments move as reset() left them)
+        if self._feature is not None:
+            self.states = None
+
+    def _adopt_feature(self):
+        """A q_mlp.Rollout with self.task moved to the device when config.fused_nstep_feature is True and the task, the
+        configuration and this agent allow it; else None (the host path; the first reason is logged when the switch was on)."""
+        if getattr(self.config, 'fused_nstep_feature', False) is not True:
+            return None
+        from . import q_mlp
+        kind = q_mlp.Rollout
+        if not kind.VEC.eligible(self.task, self.config):
+            why = "the task is not a vector of at most 64 envs.CartPole environments under RescaleNormalizer(1.0), or there is no device"
+        else:
+            why = q_mlp.why_not(self)
+        if why is not None:
+            kind.stays_on_host(self, why)
+            return None
+        rollout = kind(self, kind.network_shape(self.network))
+        rollout.attach()
+        return rollout
+
+    def close(self):
+        self.drain_episodes()
+        BaseAgent.close(self)
+
+    def eval_episodes(self):
+        self.drain_episodes()
+        return BaseAgent.eval_episodes(self)
+
+    def save(self, filename):
+        """The reference's two files (BaseAgent.py:24-27); on the cart-pole device path also `<filename>.envs`: the environments'
+        arrays (state, counters, episode steps, returns, the episode ring) and the device step counter, so that a loaded run
+        continues bit for bit."""
+        self.drain_episodes()
+        BaseAgent.save(self, filename)
+        if self._feature is not None:
+            torch.cuda.current_stream().synchronize()
+            with open(filename + '.envs', 'wb') as f:
+                pickle.dump(dict(envs=self.task.state_dict(), step=int(self._feature.step_dev.item())), f)
+
+    def load(self, filename):
+        BaseAgent.load(self, filename)
+        if self._feature is not None and os.path.isfile(filename + '.envs'):
+            with open(filename + '.envs', 'rb') as f:
+                state = pickle.load(f)
+            self.drain_episodes()
+            self.task.load_state_dict(state['envs'])
+            self._feature.step_dev.fill_(int(state['step']))
+            self._step_host, self._ep_anchor = int(state['step']), None
+
+    # -- n_step_dqn_feature over device-resident cart-pole environments --------------------------------------------------------
+    def drain_episodes(self):
+        """A2CAgent.drain_episodes' meaning: fetches the episodes that ended on the device since the last drain and emits the
+        reference's 'episodic_return_train' lines for them with the step numbers the host path logs -- total_steps at the start of
+        the episode's rollout + t * N + environment.  The lines arrive late (up to config.episode_drain_interval agent steps),
+        otherwise unchanged.  Returns the (step, return) pairs of this drain."""
+        if getattr(self, '_feature', None) is None or self._ep_anchor is None:
+            return []
+        s0, total0, t_len = self._ep_anchor
+        n = self.task.num_envs
+        out = []
+        for s, i, ret in self.task.drain():
+            at = total0 + (s - s0) * n + i
+            self.log_train_return(ret, at)
+            out.append((at, ret))
+        self._ep_log.extend(out)
+        return out
+
+    def episodes(self):
+        """(step, episodic return) of the training episodes that ended since the previous call (the newest 16384 at most), after
+        a drain.  Empty on the host-stepped paths, whose episodes are only logged."""
+        self.drain_episodes()
+        out = list(self._ep_log)
+        self._ep_log.clear()
+        return out
+
+    def _step_feature(self):
+        """step() over device_env.DeviceCartPoleVec: the host makes the rollout's exploration draws in the reference's order and
+        stages them; NStepDQN_agent.py:31-57 is ONE launch (dra_q_mlp_rollout), :58-65 with the backward a second one
+        (dra_q_mlp_update; config.fused_nstep_update False: the module path on the same buffers), then the fused clip + optimizer
+        step -- after _OnPolicyGraph.WARMUP eager steps all replayed from one captured graph (a single stream, no parallel
+        branches).  The target copy of NStepDQN_agent.py:48-50 runs before the launch when a step of this rollout reaches
+        target_network_update_freq: the parameters do not change inside a rollout (_TargetRolloutAgent._step_device)."""
+        from .mlp_rollout import Plan
+        config = self.config
+        t_len, n = int(config.rollout_length), config.num_workers
+        self._feature.prepare(t_len)
+        if self._ep_anchor is None or self._ep_anchor[2] != t_len:
+            self.drain_episodes()
+            self._ep_anchor = (self._step_host, self.total_steps, t_len)
+        self._step_host += t_len
+        freq, sync = config.target_network_update_freq, False
+        for _ in range(t_len):
+            self.total_steps += n
+            if freq is not None and self.total_steps // n % freq == 0:
+                sync = True
+        if sync:
+            self._sync_target()
+        self.last_loss = self._dev_graph.run(Plan(self.task.env_counter, t_len), self._feature_learn)
+        self._dev_steps += 1
+        if self._dev_steps % max(1, int(getattr(config, 'episode_drain_interval', 64))) == 0:
+            self.drain_episodes()
+
+    def _feature_learn(self, plan):
+        config = self.config
+        rollout = self._feature
+        b = rollout.run(plan.t_len)
+        self._rollout_step += plan.t_len
+        if getattr(config, 'fused_nstep_update', True) is not False:
+            loss = rollout.update(b, config.discount)
+        else:       # the module path on the rollout's buffers: returns by the scan kernel, one batched forward, autograd
+            t_len, n = b['action'].shape
+            value = torch.zeros((t_len + 1, n, 1), device=b['reward'].device)
+            value[t_len] = b['bootstrap'].view(n, 1)
+            _, rets = ops.gae(b['reward'].view(t_len, n, 1), b['mask'].view(t_len, n, 1), value, config.discount, 1.0, False)
+            q_a = self.network(b['state'].view(t_len * n, -1))['q'].gather(1, b['action'].view(t_len * n, 1))
+            diff = q_a.detach() - rets.view(t_len * n, 1)
+            loss = 0.5 * diff.pow(2).mean()
+            self._fused.zero_grad()
+            q_a.backward(diff / (t_len * n))
+        self._fused.step(config.gradient_clip)
+        return loss
 
     def step(self):
+        if self._feature is not None:
+            return self._step_feature()
         if getattr(self.task, 'on_device', False):
             return self._step_device()
         config = self.config

@@ -1,0 +1,471 @@
+// q_mlp: n_step_dqn_feature (examples.py:408-424: 5 workers, rollout length 5, VanillaNet over FCBody(state_dim), ONE RMSprop
+// optimiser, a target network copied every 200 steps) over device-resident cart-pole environments (cartpole_env.h).
+//
+//   q_mlp_rollout_kernel   NStepDQN_agent.py:31-57 as ONE launch of one workgroup: per step the observation narrowed to float32
+//                          (what tensor() uploads), the body (4 -> H -> H, relu or tanh), q, the epsilon-greedy action -- the
+//                          exploration draws are made by the host ahead of the launch, in the reference's order, and read from
+//                          fixed addresses --, the environment step, reward, mask and one appended row of the episode ring per
+//                          episode that ended; then the TARGET network's forward of the last observation and its max.
+//   q_mlp_update_kernel    NStepDQN_agent.py:58-65 and the whole backward as ONE launch of one workgroup: the return scan, the
+//                          forward recomputed from the stored observations (same inputs, same parameters: the graph the reference
+//                          kept), 0.5 mean (q_a - ret)^2 and its gradient with respect to all six tensors, written into the
+//                          optimiser's flat gradient buffer at the parameters' own offsets.
+//
+// Both are chains of dependent layers over a few rows: latency-bound, nothing to spread over 256 CUs.  Plain fp32 VALU code as in
+// cat_mlp.hip: weights are copied to LDS once per launch, activations are kept TRANSPOSED ([unit][row]) and read 16 bytes at a
+// time, every dot product is one FMA chain in ascending k.  The update walks the rows in blocks of 64; every gradient element is
+// owned by ONE thread that adds its rows in ascending order, block after block: no atomics, the same bits on every launch.
+#include "common.h"
+#include "cartpole_env.h"
+#include "mlp_rollout.h"
+#include <math.h>
+
+namespace {
+
+constexpr int kS = kCartPoleS, kA = kCartPoleA, kMaxN = 64;
+
+// ---------------------------------------------------------------------------------------------------- the rollout
+// one network's weights in LDS, in floats; every region starts at a multiple of 4 floats (16 bytes)
+__host__ __device__ constexpr size_t weight_floats(int H) {
+  return (size_t)kS * H + (size_t)H * H + 2 * (size_t)H + round_up4(kA * (H + 1)) + 4;
+}
+__host__ __device__ constexpr size_t rollout_lds_floats(int H, int N) {
+  return 2 * weight_floats(H)                                            // online, target
+         + round_up4(kA * kMaxN)                                         // q [N][A]
+         + (size_t)kS * round_up8(N) + 2 * (size_t)H * round_up8(N);     // x^T [S][NP], h1^T, h2^T [H][NP]
+}
+
+template <int H>
+struct Weights {
+  float *w1, *w2, *b1, *b2, *wq, *bq;       // W1^T [S][H], W2^T [H][H] (transposed: [k][unit]), b1, b2, head [A][H + 1], its bias
+  __device__ explicit Weights(float* base)
+      : w1(base), w2(w1 + kS * H), b1(w2 + H * H), b2(b1 + H), wq(b2 + H), bq(wq + round_up4(kA * (H + 1))) {}
+  __device__ void stage(const float* __restrict__ P, const dra_q_mlp_net& net, int tid) const {
+    for (int i = tid; i < kS * H; i += 256) {
+      const int k = i / H, u = i - k * H;
+      w1[i] = P[net.w1 + u * kS + k];
+    }
+    for (int i = tid; i < H * H; i += 256) {
+      const int k = i / H, u = i - k * H;
+      w2[i] = P[net.w2 + u * H + k];
+    }
+    for (int i = tid; i < H; i += 256) {
+      b1[i] = P[net.b1 + i];
+      b2[i] = P[net.b2 + i];
+    }
+    for (int i = tid; i < kA * H; i += 256) {
+      const int c = i / H, k = i - c * H;
+      wq[c * (H + 1) + k] = P[net.wq + c * H + k];
+    }
+    if (tid < kA) bq[tid] = P[net.bq + tid];
+  }
+};
+
+template <int H, int GATE>
+__global__ void __launch_bounds__(256)
+q_mlp_rollout_kernel(dra_q_mlp_net net, dra_q_mlp_rollout_io io) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  const int tid = threadIdx.x;
+  const int N = io.n_env, T = io.t_len, NP = round_up8(N);
+
+  const Weights<H> online(lds), target(lds + weight_floats(H));
+  float* sQ = lds + 2 * weight_floats(H);             // [N][A]
+  float* sXT = sQ + round_up4(kA * kMaxN);            // [S][NP]
+  float* sH1T = sXT + kS * NP;                        // [H][NP]
+  float* sH2T = sH1T + H * NP;                        // [H][NP]
+  const int total = (int)(sH2T + H * NP - lds);
+  for (int i = tid; i < total; i += 256) lds[i] = 0.f;
+  const int64_t t0 = *io.step_counter;                // (rewritten by thread 0 behind the last barrier)
+  __syncthreads();
+
+  // ---- both networks' weights, once per launch
+  online.stage(net.param, net, tid);
+  target.stage(net.target, net, tid);
+
+  // ---- the environments: lane e of wave 0 carries environment e
+  const bool env_lane = tid < N;
+  CartPoleState st = {0.0, 0.0, 0.0, 0.0};
+  int64_t counter = 0;
+  int32_t ep_steps = 0;
+  double ep_return = 0.0;
+  uint64_t seed = 0;
+  int64_t ring_count = 0;
+  if (env_lane) {
+    st.x = io.env_state[tid * kS + 0];
+    st.xd = io.env_state[tid * kS + 1];
+    st.th = io.env_state[tid * kS + 2];
+    st.thd = io.env_state[tid * kS + 3];
+    counter = io.env_counter[tid];
+    ep_steps = io.ep_steps[tid];
+    ep_return = io.ep_return[tid];
+    seed = (uint64_t)io.env_seed[tid];
+  }
+  if (tid < 64) ring_count = *io.ep_count;
+  const float reward = (float)(1.0 * io.reward_coef);       // what tensor(reward_normalizer(rewards)) uploads
+
+  for (int t = 0; t <= T; ++t) {
+    const Weights<H>& w = t < T ? online : target;          // NStepDQN_agent.py:56: the bootstrap is the TARGET network's
+    // ---- the observation: float32 of the fp64 state (torch_utils.py:23)
+    if (env_lane) {
+      const float x[kS] = {(float)st.x, (float)st.xd, (float)st.th, (float)st.thd};
+#pragma unroll
+      for (int j = 0; j < kS; ++j) {
+        sXT[j * NP + tid] = x[j];
+        if (t < T) io.out_state[((int64_t)t * N + tid) * kS + j] = x[j];
+      }
+    }
+    __syncthreads();
+    hidden_layer<H, GATE, 256>(sXT, w.w1, w.b1, sH1T, kS, NP, tid);
+    __syncthreads();
+    hidden_layer<H, GATE, 256>(sH1T, w.w2, w.b2, sH2T, H, NP, tid);
+    __syncthreads();
+    // ---- the head: one output per thread, (environment e, action c)
+    if (tid < N * kA) {
+      const int e = tid / kA, c = tid - e * kA;
+      const float* hT = sH2T + e;
+      const float* wr = w.wq + c * (H + 1);
+      float acc = 0.f;
+#pragma unroll 8
+      for (int k = 0; k < H; ++k) acc = fmaf(hT[k * NP], wr[k], acc);
+      acc += w.bq[c];
+      sQ[tid] = acc;
+      if (t < T) io.out_q[(int64_t)t * N * kA + tid] = acc;
+    }
+    __syncthreads();
+    if (t == T) {
+      if (env_lane) io.bootstrap[tid] = fmaxf(sQ[tid * kA], sQ[tid * kA + 1]);      // torch.max(q_target, dim=1)
+      break;
+    }
+    // ---- epsilon-greedy action (torch_utils.py:51-58 with the draws made ahead), environment step, ring append: wave 0
+    if (tid < 64) {
+      bool done = false;
+      double ended = 0.0;
+      if (env_lane) {
+        const int64_t o = (int64_t)t * N + tid;
+        int arg = sQ[tid * kA + 1] > sQ[tid * kA] ? 1 : 0;          // np.argmax: the first maximum
+        if (io.explore[o]) arg = io.random_action[o] == 1 ? 1 : 0;
+        done = cartpole_step(st, counter, ep_steps, ep_return, seed, arg, io.horizon, ended);
+        io.out_action[o] = arg;
+        io.out_reward[o] = reward;
+        io.out_mask[o] = done ? 0.f : 1.f;
+      }
+      const unsigned long long ends = __ballot(done ? 1 : 0);
+      if (done) {
+        const int before = __popcll(ends & ((1ull << tid) - 1ull));
+        double* row = io.ep_ring + ((ring_count + before) % io.ring_cap) * 3;
+        row[0] = (double)(t0 + t);
+        row[1] = (double)tid;
+        row[2] = ended;
+      }
+      ring_count += __popcll(ends);
+    }
+    // (wave 0 writes the next observation into x^T next: layer 1 of this step, its only reader, is three barriers back; q is
+    // rewritten behind the three barriers of the next step)
+  }
+  __syncthreads();
+  if (env_lane) {
+    io.env_state[tid * kS + 0] = st.x;
+    io.env_state[tid * kS + 1] = st.xd;
+    io.env_state[tid * kS + 2] = st.th;
+    io.env_state[tid * kS + 3] = st.thd;
+    io.env_counter[tid] = counter;
+    io.ep_steps[tid] = ep_steps;
+    io.ep_return[tid] = ep_return;
+  }
+  if (tid == 0) {
+    *io.step_counter = t0 + T;
+    *io.ep_count = ring_count;
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------- the update
+constexpr int kUB = 64;          // rows of one block
+constexpr int kLD = kUB + 4;     // row stride of the transposed activations: 16-byte aligned, consecutive units 4 banks apart
+constexpr int kMaxRows = 1024;   // ret [rows] stays in LDS
+
+__host__ __device__ constexpr size_t update_lds_floats(int H) {
+  return (size_t)kS * H + 2 * (size_t)H * H + 2 * (size_t)H + (size_t)kA * H + 4      // W1^T, W2^T, W2, b1, b2, head, its bias
+         + kMaxRows + 3 * kUB                                                         // ret, d, action, the loss partials
+         + (size_t)kS * kLD + 3 * (size_t)H * kLD;                                    // x^T, h1^T, h2^T (later dz1^T), dz2^T
+}
+
+template <int GATE>
+__device__ __forceinline__ float gate_back(float g, float h) {       // g * gate'(pre-activation), from the stored post-activation h
+  if constexpr (GATE == kGateRelu) return h > 0.f ? g : 0.f;
+  else return g * (1.f - h * h);
+}
+
+// hidden_layer (mlp_rollout.h) over one block of kUB rows with the row stride kLD.  BACK false: out = gate(b + in W); BACK true
+// (b unused): out = (in W) * gate'(post), post^T the stored post-activations of this layer's units.
+template <int H, int GATE, bool BACK>
+__device__ __forceinline__ void block_layer(const float* __restrict__ inT, const float* __restrict__ wT, const float* __restrict__ b,
+                                            const float* __restrict__ postT, float* __restrict__ outT, int K, int tid) {
+  constexpr int G = 256 / H;
+  const int u = tid & (H - 1), rg = tid / H;
+  const float bias = BACK ? 0.f : b[u];
+  for (int e0 = rg * kRB; e0 < kUB; e0 += G * kRB) {
+    float acc[kRB];
+#pragma unroll
+    for (int r = 0; r < kRB; ++r) acc[r] = 0.f;
+#pragma unroll 4
+    for (int k = 0; k < K; ++k) {
+      const float w = wT[k * H + u];
+      const f32x4 x0 = *reinterpret_cast<const f32x4*>(&inT[k * kLD + e0]);
+      const f32x4 x1 = *reinterpret_cast<const f32x4*>(&inT[k * kLD + e0 + 4]);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        acc[r] = fmaf(x0[r], w, acc[r]);
+        acc[4 + r] = fmaf(x1[r], w, acc[4 + r]);
+      }
+    }
+    f32x4 y0, y1;
+    if constexpr (BACK) {
+      const f32x4 p0 = *reinterpret_cast<const f32x4*>(&postT[u * kLD + e0]);
+      const f32x4 p1 = *reinterpret_cast<const f32x4*>(&postT[u * kLD + e0 + 4]);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        y0[r] = gate_back<GATE>(acc[r], p0[r]);
+        y1[r] = gate_back<GATE>(acc[4 + r], p1[r]);
+      }
+    } else {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        y0[r] = gate_f<GATE>(acc[r] + bias);
+        y1[r] = gate_f<GATE>(acc[4 + r] + bias);
+      }
+    }
+    *reinterpret_cast<f32x4*>(&outT[u * kLD + e0]) = y0;
+    *reinterpret_cast<f32x4*>(&outT[u * kLD + e0 + 4]) = y1;
+  }
+}
+
+template <int H, int GATE>
+__global__ void __launch_bounds__(256)
+q_mlp_update_kernel(dra_q_mlp_net net, dra_q_mlp_update_io io) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  constexpr int TPU = 256 / H;       // threads that share one unit's row of dW2
+  constexpr int KPT = H / TPU;       // columns of it each carries
+  const int tid = threadIdx.x;
+  const int N = io.n_env, T = io.t_len, R = T * N;
+  const float* __restrict__ P = net.param;
+
+  float* sW1 = lds;                       // [S][H]  (transposed: [k][unit])
+  float* sW2 = sW1 + kS * H;              // [H][H]  (transposed)
+  float* sW2N = sW2 + H * H;              // [H][H]  (as stored, [unit][k]: the backward's "transposed" operand)
+  float* sB1 = sW2N + H * H;              // [H]
+  float* sB2 = sB1 + H;                   // [H]
+  float* sWq = sB2 + H;                   // [A][H]
+  float* sBq = sWq + kA * H;              // [A] (+ pad)
+  float* sRet = sBq + 4;                  // [R]
+  float* sD = sRet + kMaxRows;            // [kUB]: (q_a - ret) / R of the block's rows, 0 behind the last row
+  int* sAct = reinterpret_cast<int*>(sD + kUB);      // [kUB]
+  float* sRed = sD + 2 * kUB;             // [kUB]: the loss partials
+  float* sXT = sRed + kUB;                // [S][kLD]
+  float* sH1T = sXT + kS * kLD;           // [H][kLD]
+  float* sH2T = sH1T + H * kLD;           // [H][kLD]: h2^T, then dz1^T
+  float* sG2T = sH2T + H * kLD;           // [H][kLD]: dz2^T
+
+  for (int i = tid; i < kS * H; i += 256) {
+    const int k = i / H, u = i - k * H;
+    sW1[i] = P[net.w1 + u * kS + k];
+  }
+  for (int i = tid; i < H * H; i += 256) {
+    const int k = i / H, u = i - k * H;
+    sW2[i] = P[net.w2 + u * H + k];
+    sW2N[i] = P[net.w2 + i];
+  }
+  for (int i = tid; i < H; i += 256) {
+    sB1[i] = P[net.b1 + i];
+    sB2[i] = P[net.b2 + i];
+  }
+  for (int i = tid; i < kA * H; i += 256) sWq[i] = P[net.wq + i];
+  if (tid < kA) sBq[tid] = P[net.bq + tid];
+  // ---- returns: NStepDQN_agent.py:58-60, one environment per thread, backwards from the bootstrap
+  const float gamma = (float)io.discount;
+  for (int e = tid; e < N; e += 256) {
+    float ret = io.bootstrap[e];
+    for (int t = T - 1; t >= 0; --t) {
+      const int r = t * N + e;
+      ret = __fadd_rn(io.reward[r], __fmul_rn(__fmul_rn(gamma, io.mask[r]), ret));
+      sRet[r] = ret;
+      io.out_ret[r] = ret;
+    }
+  }
+  __syncthreads();
+
+  // what this thread owns of the gradient
+  const int u2 = tid / TPU, k2 = (tid % TPU) * KPT;       // dW2 [u2][k2 .. k2 + KPT), db2 [u2] on the first of the unit's threads
+  float gW2[KPT], gB2 = 0.f;
+#pragma unroll
+  for (int i = 0; i < KPT; ++i) gW2[i] = 0.f;
+  const int u1 = tid / kS, j1 = tid % kS;                 // dW1 [u1][j1] (tid < S H), db1 [u1] where j1 == 0
+  float gW1 = 0.f, gB1 = 0.f;
+  const int aq = tid / H, kq = tid % H;                   // dWq [aq][kq] (tid < A H); dbq [tid - A H] on the two threads behind
+  float gWq = 0.f, gBq = 0.f;
+  float loss = 0.f;
+  const float inv_rows = 1.f / (float)R;
+
+  for (int r0 = 0; r0 < R; r0 += kUB) {
+    // ---- x^T of the block (256 threads: 64 rows x 4), zero behind the last row
+    {
+      const int row = tid / kS, j = tid % kS;
+      sXT[j * kLD + row] = r0 + row < R ? io.state[(int64_t)(r0 + row) * kS + j] : 0.f;
+    }
+    __syncthreads();
+    block_layer<H, GATE, false>(sXT, sW1, sB1, nullptr, sH1T, kS, tid);
+    __syncthreads();
+    block_layer<H, GATE, false>(sH1T, sW2, sB2, nullptr, sH2T, H, tid);
+    __syncthreads();
+    // ---- q of the action taken, dq = (q_a - ret) / R, the loss
+    if (tid < kUB) {
+      const int r = r0 + tid;
+      float d = 0.f;
+      int a = 0;
+      if (r < R) {
+        a = io.action[r] == 1 ? 1 : 0;
+        const float* wr = sWq + a * H;
+        float acc = 0.f;
+#pragma unroll 8
+        for (int k = 0; k < H; ++k) acc = fmaf(sH2T[k * kLD + tid], wr[k], acc);
+        const float diff = (acc + sBq[a]) - sRet[r];
+        loss = fmaf(diff, diff, loss);
+        d = diff * inv_rows;
+      }
+      sD[tid] = d;
+      sAct[tid] = a;
+    }
+    __syncthreads();
+    // ---- dz2 = dq wq[a] gate'(h2); the head's gradient
+    for (int i = tid; i < H * kUB; i += 256) {
+      const int k = i / kUB, r = i % kUB;
+      sG2T[k * kLD + r] = gate_back<GATE>(sD[r] * sWq[sAct[r] * H + k], sH2T[k * kLD + r]);
+    }
+    if (tid < kA * H) {
+#pragma unroll 1
+      for (int r = 0; r < kUB; r += 4) {
+        const f32x4 h = *reinterpret_cast<const f32x4*>(&sH2T[kq * kLD + r]);
+#pragma unroll
+        for (int c = 0; c < 4; ++c) gWq = fmaf(sAct[r + c] == aq ? sD[r + c] : 0.f, h[c], gWq);
+      }
+    } else if (tid < kA * H + kA) {
+#pragma unroll 1
+      for (int r = 0; r < kUB; ++r) gBq += sAct[r] == tid - kA * H ? sD[r] : 0.f;
+    }
+    __syncthreads();
+    // ---- dW2 += dz2 h1^T, db2 += dz2; dz1 = (dz2 W2) gate'(h1) into h2^T's place (its readers are behind the barrier)
+#pragma unroll 1
+    for (int r = 0; r < kUB; r += 4) {
+      const f32x4 dz = *reinterpret_cast<const f32x4*>(&sG2T[u2 * kLD + r]);
+#pragma unroll
+      for (int i = 0; i < KPT; ++i) {
+        const f32x4 h = *reinterpret_cast<const f32x4*>(&sH1T[(k2 + i) * kLD + r]);
+#pragma unroll
+        for (int c = 0; c < 4; ++c) gW2[i] = fmaf(dz[c], h[c], gW2[i]);
+      }
+      if (k2 == 0) {
+#pragma unroll
+        for (int c = 0; c < 4; ++c) gB2 += dz[c];
+      }
+    }
+    block_layer<H, GATE, true>(sG2T, sW2N, nullptr, sH1T, sH2T, H, tid);
+    __syncthreads();
+    // ---- dW1 += dz1 x^T, db1 += dz1
+    if (tid < kS * H) {
+#pragma unroll 1
+      for (int r = 0; r < kUB; r += 4) {
+        const f32x4 dz = *reinterpret_cast<const f32x4*>(&sH2T[u1 * kLD + r]);
+        const f32x4 x = *reinterpret_cast<const f32x4*>(&sXT[j1 * kLD + r]);
+#pragma unroll
+        for (int c = 0; c < 4; ++c) gW1 = fmaf(dz[c], x[c], gW1);
+        if (j1 == 0) {
+#pragma unroll
+          for (int c = 0; c < 4; ++c) gB1 += dz[c];
+        }
+      }
+    }
+    __syncthreads();       // (the next block rewrites x^T and h2^T)
+  }
+
+  // ---- every element of the six tensors, nothing between them
+  float* __restrict__ Gd = io.grad;
+#pragma unroll
+  for (int i = 0; i < KPT; ++i) Gd[net.w2 + u2 * H + k2 + i] = gW2[i];
+  if (k2 == 0) Gd[net.b2 + u2] = gB2;
+  if (tid < kS * H) {
+    Gd[net.w1 + tid] = gW1;
+    if (j1 == 0) Gd[net.b1 + u1] = gB1;
+  }
+  if (tid < kA * H) Gd[net.wq + tid] = gWq;
+  else if (tid < kA * H + kA) Gd[net.bq + tid - kA * H] = gBq;
+  if (tid < kUB) sRed[tid] = loss;
+  __syncthreads();
+  if (tid == 0) {
+    float s = 0.f;
+    for (int i = 0; i < kUB; ++i) s += sRed[i];
+    io.out_loss[0] = 0.5f * (s * inv_rows);
+  }
+}
+
+template <int H>
+int launch_rollout(const dra_q_mlp_net* net, const dra_q_mlp_rollout_io* io, void* stream) {
+  const size_t bytes = rollout_lds_floats(H, io->n_env) * sizeof(float);
+  return net->gate == kGateRelu ? launch_one_workgroup<&q_mlp_rollout_kernel<H, kGateRelu>>(bytes, net, io, stream)
+                                : launch_one_workgroup<&q_mlp_rollout_kernel<H, kGateTanh>>(bytes, net, io, stream);
+}
+
+template <int H>
+int launch_update(const dra_q_mlp_net* net, const dra_q_mlp_update_io* io, void* stream) {
+  const size_t bytes = update_lds_floats(H) * sizeof(float);
+  return net->gate == kGateRelu ? launch_one_workgroup<&q_mlp_update_kernel<H, kGateRelu>>(bytes, net, io, stream)
+                                : launch_one_workgroup<&q_mlp_update_kernel<H, kGateTanh>>(bytes, net, io, stream);
+}
+
+bool offsets_ok(const dra_q_mlp_net* net) {
+  const int32_t offs[6] = {net->w1, net->b1, net->w2, net->b2, net->wq, net->bq};
+  for (int i = 0; i < 6; ++i)
+    if (offs[i] < 0) return false;
+  return true;
+}
+
+}  // namespace
+
+DRA_API int dra_q_mlp_supported(int state_dim, int n_actions, int hidden, int n_env, int gate) {
+  if (state_dim != kS || n_actions != kA) return DRA_EINVAL;
+  if (hidden != 16 && hidden != 32 && hidden != 64) return DRA_EINVAL;
+  if (n_env < 1 || n_env > kMaxN || (gate != kGateRelu && gate != kGateTanh)) return DRA_EINVAL;
+  return DRA_OK;
+}
+
+DRA_API int dra_q_mlp_update_supported(int state_dim, int n_actions, int hidden, int rows, int gate) {
+  if (state_dim != kS || n_actions != kA) return DRA_EINVAL;
+  if (hidden != 16 && hidden != 32 && hidden != 64) return DRA_EINVAL;
+  if (rows < 1 || rows > kMaxRows || (gate != kGateRelu && gate != kGateTanh)) return DRA_EINVAL;
+  return DRA_OK;
+}
+
+DRA_API int dra_q_mlp_rollout(const dra_q_mlp_net* net, const dra_q_mlp_rollout_io* io, void* stream) {
+  if (!net || !io || !net->param || !net->target) return DRA_EINVAL;
+  if (dra_q_mlp_supported(net->state_dim, net->n_actions, net->hidden, io->n_env, net->gate)) return DRA_EINVAL;
+  if (!offsets_ok(net)) return DRA_EINVAL;
+  if (io->t_len < 1 || io->horizon < 1 || io->ring_cap < 1) return DRA_EINVAL;
+  if ((int64_t)(io->t_len + 1) * io->n_env * kS > 0x7fffffff) return DRA_EINVAL;
+  if (!io->env_state || !io->env_counter || !io->ep_steps || !io->ep_return || !io->env_seed || !io->step_counter || !io->ep_count ||
+      !io->ep_ring || !io->explore || !io->random_action || !io->out_state || !io->out_q || !io->out_action || !io->out_reward ||
+      !io->out_mask || !io->bootstrap)
+    return DRA_EINVAL;
+  if (net->hidden == 16) return launch_rollout<16>(net, io, stream);
+  if (net->hidden == 32) return launch_rollout<32>(net, io, stream);
+  return launch_rollout<64>(net, io, stream);
+}
+
+DRA_API int dra_q_mlp_update(const dra_q_mlp_net* net, const dra_q_mlp_update_io* io, void* stream) {
+  if (!net || !io || !net->param) return DRA_EINVAL;
+  if (io->t_len < 1 || io->n_env < 1 || (int64_t)io->t_len * io->n_env > kMaxRows) return DRA_EINVAL;
+  if (dra_q_mlp_update_supported(net->state_dim, net->n_actions, net->hidden, io->t_len * io->n_env, net->gate)) return DRA_EINVAL;
+  if (!offsets_ok(net)) return DRA_EINVAL;
+  if (!io->state || !io->action || !io->reward || !io->mask || !io->bootstrap || !io->grad || !io->out_ret || !io->out_loss)
+    return DRA_EINVAL;
+  if (net->hidden == 16) return launch_update<16>(net, io, stream);
+  if (net->hidden == 32) return launch_update<32>(net, io, stream);
+  return launch_update<64>(net, io, stream);
+}

@@ -1,0 +1,195 @@
+"""Host side of csrc/q_mlp.hip: n_step_dqn_feature (examples.py:408-424) over device-resident cart-pole environments.
+
+`shape(network)` says whether a network is one the kernels walk (VanillaNet over a two-layer FCBody of one width with a relu or
+tanh gate and a plain biased fc_head); `why_not(agent)` adds the agent-side conditions and names the first one that fails;
+`Rollout(agent)` builds the kernels' structs over the agent's flat parameter buffer and the TARGET network's flat buffer of the
+same layout, stages the rollout's exploration draws (support.plan_epsilon_greedy: the reference's draw order) and launches a
+rollout (NStepDQN_agent.py:31-57: one launch instead of T x [forward, download q, 5 environment steps, upload]); `update(...)`
+is NStepDQN_agent.py:58-65 with the whole backward as one more launch.  There is no CPU / eager implementation here: without the
+HIP library every call raises.
+"""
+import ctypes
+
+import numpy as np
+import torch
+
+from . import mlp_rollout
+from ._lib import lib, stream_ptr
+from .device_env import DeviceCartPoleVec
+from .mlp_rollout import GATES, body_params, fc_body, head_out      # noqa: F401  (GATES: this module's public name)
+from .support import Config, StagedUpload, plan_epsilon_greedy
+
+
+class Net(ctypes.Structure):
+    """Mirror of dra_q_mlp_net (include/deeprl_amd.h)."""
+    _fields_ = [("param", ctypes.c_void_p), ("target", ctypes.c_void_p),
+                ("w1", ctypes.c_int32), ("b1", ctypes.c_int32), ("w2", ctypes.c_int32), ("b2", ctypes.c_int32),
+                ("wq", ctypes.c_int32), ("bq", ctypes.c_int32),
+                ("gate", ctypes.c_int32), ("state_dim", ctypes.c_int32), ("n_actions", ctypes.c_int32),
+                ("hidden", ctypes.c_int32)]
+
+
+class RolloutIO(ctypes.Structure):
+    """Mirror of dra_q_mlp_rollout_io."""
+    _fields_ = [("env_state", ctypes.c_void_p), ("env_counter", ctypes.c_void_p), ("ep_steps", ctypes.c_void_p),
+                ("ep_return", ctypes.c_void_p), ("env_seed", ctypes.c_void_p), ("step_counter", ctypes.c_void_p),
+                ("ep_count", ctypes.c_void_p), ("ep_ring", ctypes.c_void_p),
+                ("explore", ctypes.c_void_p), ("random_action", ctypes.c_void_p),
+                ("out_state", ctypes.c_void_p), ("out_q", ctypes.c_void_p), ("out_action", ctypes.c_void_p),
+                ("out_reward", ctypes.c_void_p), ("out_mask", ctypes.c_void_p), ("bootstrap", ctypes.c_void_p),
+                ("horizon", ctypes.c_int64), ("ring_cap", ctypes.c_int64), ("reward_coef", ctypes.c_double),
+                ("t_len", ctypes.c_int32), ("n_env", ctypes.c_int32)]
+
+
+class UpdateIO(ctypes.Structure):
+    """Mirror of dra_q_mlp_update_io."""
+    _fields_ = [("state", ctypes.c_void_p), ("action", ctypes.c_void_p), ("reward", ctypes.c_void_p), ("mask", ctypes.c_void_p),
+                ("bootstrap", ctypes.c_void_p), ("grad", ctypes.c_void_p), ("out_ret", ctypes.c_void_p),
+                ("out_loss", ctypes.c_void_p), ("discount", ctypes.c_double), ("t_len", ctypes.c_int32), ("n_env", ctypes.c_int32)]
+
+
+def shape(network):
+    """(state_dim, n_actions, hidden, gate code) when `network` is a VanillaNet whose body is a two-layer FCBody of one width with
+    a relu or tanh gate and whose fc_head is a plain Linear layer with a bias; else None."""
+    from .nets import VanillaNet
+    if type(network) is not VanillaNet:
+        return None
+    body = fc_body(network.body)
+    if body is None or body[1] != body[2]:
+        return None
+    s_dim, hidden, _, gate = body
+    n_actions = head_out(network.fc_head, hidden)
+    if n_actions is None or network.fc_head.fused_act is not None:
+        return None
+    return s_dim, n_actions, hidden, gate
+
+
+def supported(state_dim, n_actions, hidden, n_env, gate):
+    """dra_q_mlp_supported: the shapes the rollout kernel is built for."""
+    return lib.dra_q_mlp_supported.raw(int(state_dim), int(n_actions), int(hidden), int(n_env), int(gate)) == 0
+
+
+def update_supported(state_dim, n_actions, hidden, rows, gate):
+    """dra_q_mlp_update_supported: the shapes (rows = rollout length x environments) the update kernel is built for."""
+    return lib.dra_q_mlp_update_supported.raw(int(state_dim), int(n_actions), int(hidden), int(rows), int(gate)) == 0
+
+
+def _fields(net):
+    return list(zip(("w1", "b1", "w2", "b2", "wq", "bq"), body_params(net.body) + [net.fc_head.weight, net.fc_head.bias]))
+
+
+def why_not(agent, supported_fn=supported):
+    """None when NStepDQNAgent may run `agent` on the kernels, else the first reason it may not (everything but the task itself,
+    which device_env.DeviceCartPoleVec.eligible decides).  The path is opt-in: config.fused_nstep_feature must be True."""
+    cfg = agent.config
+    if getattr(cfg, Rollout.SWITCH, False) is not True:
+        return "config.%s is not on" % Rollout.SWITCH
+    if agent.grad_hook is not None:
+        return "a grad_hook is installed"
+    shp = shape(agent.network)
+    if shp is None or shape(agent.target_network) != shp:
+        return "the network is not %s" % Rollout.NETWORK
+    flat, target = agent._fused.flat, agent._target_flat
+    if any(all(p is not q for q in flat.params) for _, p in _fields(agent.network)):
+        return "one optimiser does not own every parameter the kernel reads"
+    if ([flat.offset_of(p) for _, p in _fields(agent.network)] != [target.offset_of(p) for _, p in _fields(agent.target_network)]):
+        return "the online and the target parameters are laid out differently in their flat buffers"
+    n, t_len = int(cfg.num_workers), int(cfg.rollout_length)
+    if not supported_fn(shp[0], shp[1], shp[2], n, shp[3]):
+        return "%s is not built for state_dim %d, %d actions, hidden %d, %d environments" % (Rollout.ENTRY, shp[0], shp[1], shp[2], n)
+    if getattr(cfg, 'fused_nstep_update', True) is not False and not update_supported(shp[0], shp[1], shp[2], t_len * n, shp[3]):
+        return "dra_q_mlp_update is not built for %d rows (rollout length %d x %d environments)" % (t_len * n, t_len, n)
+    return None
+
+
+def update(net, state, action, reward, mask, bootstrap, discount, grad, out_ret, out_loss):
+    """dra_q_mlp_update on the current stream: returns, loss and the gradient of 0.5 mean (q_a - ret)^2 with respect to the six
+    tensors `net` (a Net struct) names, written into the flat buffer `grad` at the parameters' offsets.  state [T, N, 4], action
+    int64 [T, N], reward / mask [T, N], bootstrap [N]; out_ret [T, N], out_loss [1]."""
+    io = UpdateIO()
+    io.state, io.action, io.reward, io.mask = state.data_ptr(), action.data_ptr(), reward.data_ptr(), mask.data_ptr()
+    io.bootstrap, io.grad, io.out_ret, io.out_loss = bootstrap.data_ptr(), grad.data_ptr(), out_ret.data_ptr(), out_loss.data_ptr()
+    io.discount, io.t_len, io.n_env = float(discount), int(action.shape[0]), int(action.shape[1])
+    lib.dra_q_mlp_update(ctypes.byref(net), ctypes.byref(io), stream_ptr())
+
+
+class Rollout(mlp_rollout.Rollout):
+    """dra_q_mlp_rollout over a DeviceCartPoleVec, the agent's flat parameter buffer and its target network's."""
+    SWITCH, ENTRY, VEC = 'fused_nstep_feature', 'dra_q_mlp_rollout', DeviceCartPoleVec
+    NETWORK = "VanillaNet over a two-layer relu / tanh FCBody with a plain head"
+    Net, IO, DIMS, ACTION_VIEW = Net, RolloutIO, ("state_dim", "n_actions", "hidden", "gate"), ()
+    network_shape, fields, supported = staticmethod(shape), staticmethod(_fields), staticmethod(supported)
+
+    def __init__(self, agent, shp):
+        mlp_rollout.Rollout.__init__(self, agent, shp)
+        self._bufs, self._up = {}, None
+        self.explore = self.random_action = None
+        # the kernel's own step counter: the ring rows carry it (NStepDQNAgent.drain_episodes turns it into a step number)
+        self.step_dev = torch.zeros(1, dtype=torch.int64, device=Config.DEVICE)
+
+    def attach(self):
+        """The environments move to the device; episode ends come back through the device's episode ring."""
+        self.agent.task = DeviceCartPoleVec(self.agent.task)
+
+    @staticmethod
+    def stays_on_host(agent, why):
+        getattr(agent.logger, 'warning', agent.logger.info)(
+            'the cart-pole environments stay on the host and this agent keeps the module path: %s' % why)
+
+    def net_struct(self):
+        n = mlp_rollout.Rollout.net_struct(self)
+        n.target = self.agent._target_flat.flat.data_ptr()
+        return n
+
+    def buffers(self, t_len):
+        """What a rollout of t_len steps leaves (and the update's two outputs), at fixed addresses."""
+        if t_len not in self._bufs:
+            n, dev = self.agent.task.num_envs, Config.DEVICE
+            f = lambda *s: torch.zeros(s, dtype=torch.float32, device=dev)
+            self._bufs[t_len] = dict(state=f(t_len, n, 4), q=f(t_len, n, 2), action=torch.zeros((t_len, n), dtype=torch.int64, device=dev),
+                                     reward=f(t_len, n), mask=f(t_len, n), bootstrap=f(n), ret=f(t_len, n), loss=f(1))
+        return self._bufs[t_len]
+
+    def prepare(self, t_len):
+        """Draws the rollout's exploration (support.plan_epsilon_greedy: NStepDQN_agent.py:34-35's calls in their order, so that
+        np.random and the schedule end where the step-by-step loop leaves them) and stages it into the persistent device buffers
+        the kernel reads (fixed addresses: graph replays see the new values).  -> (explore, random_action) as drawn."""
+        cfg = self.agent.config
+        n = self.agent.task.num_envs
+        explore, rand = plan_epsilon_greedy(cfg.random_action_prob, t_len, n, self.shape[1], cfg.num_workers)
+        o = t_len * n * 8       # one block, one copy: int64 random actions | uint8 explore flags
+        if self._up is None or self.explore.shape[0] != t_len:
+            self._up = StagedUpload(o + t_len * n, torch.uint8, Config.DEVICE)
+            self.random_action = self._up.dev[:o].view(torch.int64).view(t_len, n)
+            self.explore = self._up.dev[o:].view(t_len, n)
+        raw = self._up.stage().numpy()
+        raw[:o].view(np.int64).reshape(t_len, n)[...] = rand
+        raw[o:].reshape(t_len, n)[...] = explore
+        self._up.send()
+        return explore, rand
+
+    def run(self, t_len):
+        """One rollout launch on the current stream (after prepare(t_len)); returns buffers(t_len)."""
+        vec, cfg = self.agent.task, self.agent.config
+        b = self.buffers(t_len)
+        io = RolloutIO()
+        io.env_state, io.env_counter, io.env_seed = vec.env_state.data_ptr(), vec.env_counter.data_ptr(), vec.env_seed.data_ptr()
+        io.ep_steps, io.ep_return = vec.ep_steps.data_ptr(), vec.ep_return.data_ptr()
+        io.ep_count, io.ep_ring, io.ring_cap = vec.ep_count.data_ptr(), vec.ep_ring.data_ptr(), vec.ring_cap
+        io.step_counter = self.step_dev.data_ptr()
+        io.explore, io.random_action = self.explore.data_ptr(), self.random_action.data_ptr()
+        io.out_state, io.out_q, io.out_action = b['state'].data_ptr(), b['q'].data_ptr(), b['action'].data_ptr()
+        io.out_reward, io.out_mask, io.bootstrap = b['reward'].data_ptr(), b['mask'].data_ptr(), b['bootstrap'].data_ptr()
+        io.horizon, io.reward_coef = vec.horizon, float(cfg.reward_normalizer.coef)
+        io.t_len, io.n_env = int(t_len), vec.num_envs
+        net = self.net_struct()
+        lib.dra_q_mlp_rollout(ctypes.byref(net), ctypes.byref(io), stream_ptr())
+        self.launches += 1
+        return b
+
+    def update(self, b, discount):
+        """dra_q_mlp_update on the buffers run() left: the gradient lands in the optimiser's flat gradient buffer."""
+        net = self.net_struct()
+        update(net, b['state'], b['action'], b['reward'], b['mask'], b['bootstrap'], discount, self.agent._fused.flat.grad,
+               b['ret'], b['loss'])
+        return b['loss']

@@ -108,6 +108,14 @@ ZOO = {
                                                    critic_body=N.FCBody(c.state_dim)),
         fields=dict(discount=0.99, use_gae=True, gae_tau=1.0, entropy_weight=0.01, rollout_length=5, gradient_clip=5,
                     max_steps=int(2e7))),
+    # examples.py:408-424 (fused_nstep_feature=True moves the cart-poles and the update onto the device: csrc/q_mlp.hip)
+    "n_step_dqn_feature": dict(
+        agent="NStepDQNAgent", kw=dict(log_level=0), pre_fields=dict(num_workers=5),
+        task=lambda c: Task(c.game, num_envs=c.num_workers), eval_task=lambda c: Task(c.game),
+        optimizer=_rmsprop(lr=0.001),
+        network=lambda c: N.VanillaNet(c.action_dim, N.FCBody(c.state_dim)),
+        fields=dict(discount=0.99, target_network_update_freq=200, rollout_length=5, gradient_clip=5),
+        eps=(1.0, 0.1, 1e4)),
     # examples.py:427-447
     "n_step_dqn_pixel": dict(
         agent="NStepDQNAgent", kw=dict(log_level=0), pre_fields=dict(num_workers=16),

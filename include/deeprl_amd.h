@@ -1043,6 +1043,67 @@ typedef struct dra_cat_mlp_rollout_io {
 int dra_cat_mlp_supported(int state_dim, int n_actions, int hidden, int n_env, int gate);   /* 0 = yes */
 int dra_cat_mlp_rollout(const dra_cat_mlp_net* net, const dra_cat_mlp_rollout_io* io, void* stream);
 
+/* ---- q_mlp: n_step_dqn_feature (examples.py:408-424, NStepDQN_agent.py:13-67) over device-resident cart-pole environments.
+ * VanillaNet(action_dim, FCBody(state_dim)): a two-layer FCBody of one width (relu or tanh) under a plain biased fc_head.  The
+ * online and the target network live in two flat buffers of EQUAL layout (one set of offsets).  state_dim 4, 2 actions, hidden
+ * in {16, 32, 64}. */
+typedef struct dra_q_mlp_net {
+  const float* param;                /* the optimiser's flat parameter buffer (device): the ONLINE network; read only */
+  const float* target;               /* the TARGET network's flat buffer, same offsets; read only (the update does not read it) */
+  int32_t w1, b1, w2, b2;            /* body.layers[0..1]: float offsets into param / target (and the flat gradient buffer) */
+  int32_t wq, bq;                    /* fc_head [n_actions][hidden], [n_actions] */
+  int32_t gate;                      /* 1 relu, 2 tanh */
+  int32_t state_dim, n_actions, hidden;
+} dra_q_mlp_net;
+/* NStepDQN_agent.py:31-57 in ONE launch of one workgroup: for t < t_len [observation narrowed to float32 and stored, body, q
+ * stored, action = random_action[t][e] where explore[t][e] else the FIRST maximum of q (np.argmax), environment step, reward *
+ * reward_coef, mask = 1 - done, and for every episode that ended one appended row of ep_ring], then bootstrap[e] = max_a of the
+ * TARGET network's q on the last observation.  No parameter is written.  *step_counter advances by t_len; ep_ring row
+ * (*ep_count mod ring_cap) = (*step_counter + t of the end, environment, episodic return), appended in (step, environment)
+ * order with vector stores; *ep_count counts every episode ever ended.  n_env <= 64. */
+typedef struct dra_q_mlp_rollout_io {
+  double* env_state;            /* [n_env][4] (in/out) */
+  int64_t* env_counter;         /* [n_env] (in/out) */
+  int32_t* ep_steps;            /* [n_env] (in/out) */
+  double* ep_return;            /* [n_env] (in/out) */
+  const int64_t* env_seed;      /* [n_env] */
+  int64_t* step_counter;        /* [1] (in/out) */
+  int64_t* ep_count;            /* [1] (in/out) */
+  double* ep_ring;              /* [ring_cap][3] */
+  const uint8_t* explore;       /* [t_len][n_env]: nonzero = take random_action */
+  const int64_t* random_action; /* [t_len][n_env] */
+  float* out_state;             /* [t_len][n_env][4] */
+  float* out_q;                 /* [t_len][n_env][2] */
+  int64_t* out_action;          /* [t_len][n_env] */
+  float* out_reward;            /* [t_len][n_env] */
+  float* out_mask;              /* [t_len][n_env] */
+  float* bootstrap;             /* [n_env] */
+  int64_t horizon, ring_cap;
+  double reward_coef;
+  int32_t t_len, n_env;
+} dra_q_mlp_rollout_io;
+/* NStepDQN_agent.py:58-65 and the whole backward in ONE launch of one workgroup: ret[t][e] = reward + (discount * mask) * ret
+ * backwards from bootstrap (the reference's loop and operation order, fp32), the forward recomputed from the stored states with
+ * the ONLINE parameters, loss = 0.5 * mean_r (q[r][a_r] - ret_r)^2 and its gradient with respect to w1 b1 w2 b2 wq bq, written
+ * (every element, nothing between the tensors) into `grad` at the parameters' offsets.  Fixed summation order, no atomics.
+ * rows = t_len * n_env <= 1024 (dra_q_mlp_update_supported). */
+typedef struct dra_q_mlp_update_io {
+  const float* state;           /* [t_len][n_env][4] */
+  const int64_t* action;        /* [t_len][n_env] (1 = the second action, anything else the first) */
+  const float* reward;          /* [t_len][n_env] */
+  const float* mask;            /* [t_len][n_env] */
+  const float* bootstrap;       /* [n_env] */
+  float* grad;                  /* the flat gradient buffer (device) */
+  float* out_ret;               /* [t_len][n_env] */
+  float* out_loss;              /* [1] */
+  double discount;
+  int32_t t_len, n_env;
+} dra_q_mlp_update_io;
+int dra_q_mlp_supported(int state_dim, int n_actions, int hidden, int n_env, int gate);         /* the rollout; 0 = yes */
+int dra_q_mlp_update_supported(int state_dim, int n_actions, int hidden, int rows, int gate);   /* the update; 0 = yes */
+int dra_q_mlp_rollout(const dra_q_mlp_net* net, const dra_q_mlp_rollout_io* io, void* stream);
+int dra_q_mlp_update(const dra_q_mlp_net* net, const dra_q_mlp_update_io* io, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
