@@ -21,7 +21,6 @@ Differences that are the point of the rewrite (results unchanged):
     the IS-weight / priority kernel and runs the chain eagerly) and one C call per actor forward;
     `config.fused_learner = False` keeps the generic autograd path.
 """
-import collections
 import pickle
 import os
 
@@ -38,7 +37,7 @@ from .envs import LazyFrames
 from .optim import FlatParams, FusedOptimizer, nature_conv_weights
 from .replay import PrioritizedTransition, Storage
 from ._lib import DraError
-from .device_env import DeviceAtariVec
+from .device_env import DeviceAtariVec, EpisodeRing
 from .pixel_rollout import _OCRollout, _PixelRollout, _QRollout, hand_over, k_major     # noqa: F401  (the rollouts: this module's names too)
 from .support import (Config, LinearSchedule, StagedUpload, close_obj, epsilon_greedy, get_logger, random_sample, range_tensor, tensor,
                       to_np)
@@ -1315,28 +1314,13 @@ class A2CAgent(BaseAgent):
         self.network.rollout_fc4_slices = bool(getattr(config, 'rollout_fc4_slices', True))
         # action noise of the device rollout: the rank-invariant stream when one is configured, else a seed of its own
         self._noise_seed = self.dp.noise_seed
-        self._cat_steps, self._ep_anchor, self._ep_log = 0, None, collections.deque(maxlen=16384)
+        self._episodes = EpisodeRing(self, 1, self.dp.global_workers)      # (a sampler step per rollout step and the bootstrap's)
         # one launch per rollout over device-resident environments (_step_device_rollout) -- a2c_continuous, examples.py:384-404:
         # synthetic continuous-control environments under GaussianActorCriticNet over two small MLPs (csrc/a2c_mlp.hip);
         # a2c_feature, examples.py:340-358: cart-poles under CategoricalActorCriticNet over a small FCBody (csrc/cat_mlp.hip)
-        from . import a2c_mlp, cat_mlp
-        self._mlp_rollout = self._adopt_rollout(a2c_mlp.Rollout)
-        self._cat_rollout = self._adopt_rollout(cat_mlp.Rollout)
-
-    def _adopt_rollout(self, kind):
-        """A `kind` rollout with self.task moved to the device when the task, the configuration and this agent allow it; else
-        None (the host path)."""
-        from .mlp_rollout import why_not
-        if not kind.VEC.eligible(self.task, self.config):
-            return None
-        why = why_not(kind, self)
-        if why is not None:
-            kind.stays_on_host(self, why)
-            return None
-        rollout = kind(self, kind.network_shape(self.network))
-        rollout.attach()
-        self.states = None
-        return rollout
+        from . import a2c_mlp, cat_mlp, mlp_rollout
+        self._mlp_rollout = mlp_rollout.adopt(self, a2c_mlp.Rollout)
+        self._cat_rollout = mlp_rollout.adopt(self, cat_mlp.Rollout)
 
     def close(self):
         self.drain_episodes()
@@ -1356,7 +1340,7 @@ class A2CAgent(BaseAgent):
         if self._device_rollout() is not None and self.dp.is_main:
             state = self.dp.sampler_state()
             if self._cat_rollout is not None:
-                state['envs'] = self.task.state_dict()
+                state.update(self._episodes.state_dict())
             with open(filename + '.sampler', 'wb') as f:
                 pickle.dump(state, f)
 
@@ -1368,37 +1352,17 @@ class A2CAgent(BaseAgent):
             self.dp.load_sampler_state(state, Config.DEVICE)
             self._noise_seed = self.dp.noise_seed
             if self._cat_rollout is not None:
-                self.drain_episodes()
-                self._sampler_host, self._ep_anchor = int(state['step']), None
-                if 'envs' in state:
-                    self.task.load_state_dict(state['envs'])
+                self._episodes.load_state_dict(state)
 
-    # -- a2c_feature over device-resident cart-pole environments ------------------------------------------------------------
+    # -- a2c_feature over device-resident cart-pole environments: device_env.EpisodeRing ------------------------------------
+    _cat_steps = property(lambda self: self._episodes.steps)      # (agent steps on the device path)
     def drain_episodes(self):
-        """Fetches the episodes that ended on the device since the last drain (DeviceCartPoleVec.drain: one copy) and emits the
-        reference's 'episodic_return_train' lines for them, with the step numbers the host path logs -- total_steps at the start
-        of the episode's rollout + t * N + environment.  The lines arrive late (up to config.episode_drain_interval agent steps),
-        otherwise unchanged.  Returns the (step, return) pairs of this drain."""
-        if getattr(self, '_cat_rollout', None) is None or self._ep_anchor is None:
-            return []
-        s0, total0, t_len = self._ep_anchor
-        n = self.dp.global_workers
-        out = []
-        for s, i, ret in self.task.drain():
-            k, t = divmod(s - s0, t_len + 1)
-            at = total0 + (k * t_len + t) * n + i
-            self.log_train_return(ret, at)
-            out.append((at, ret))
-        self._ep_log.extend(out)
-        return out
+        """EpisodeRing.drain: logs the episodes that ended on the device since the last drain -> their (step, return) pairs."""
+        return self._episodes.drain()
 
     def episodes(self):
-        """(step, episodic return) of the training episodes that ended since the previous call (the newest 16384 at most), after
-        a drain.  Empty on the host-stepped paths, whose episodes are only logged."""
-        self.drain_episodes()
-        out = list(self._ep_log)
-        self._ep_log.clear()
-        return out
+        """EpisodeRing.episodes: (step, episodic return) of the training episodes that ended since the previous call."""
+        return self._episodes.episodes()
 
     def _device_rollout(self):
         return self._mlp_rollout or self._cat_rollout
@@ -1617,29 +1581,13 @@ class NStepDQNAgent(_TargetRolloutAgent):
         self._adopt_device(self._q_rollout)     # synthetic Atari emulators + VanillaNet(NatureConvBody): the rollout lives on the device
         # n_step_dqn_feature, examples.py:408-424 (opt-in, config.fused_nstep_feature): cart-poles under VanillaNet over a small
         # FCBody live on the device, one launch per rollout and one per update (csrc/q_mlp.hip)
-        self._dev_steps, self._step_host, self._ep_anchor, self._ep_log = 0, 0, None, collections.deque(maxlen=16384)
+        self._episodes = EpisodeRing(self, 0, config.num_workers)     # (the kernel's step counter: one stamp per rollout step)
         self.states = self.task.reset()
         self._feature = self._adopt_feature()       # (the environments move as reset() left them)
-        if self._feature is not None:
-            self.states = None
 
     def _adopt_feature(self):
-        """A q_mlp.Rollout with self.task moved to the device when config.fused_nstep_feature is True and the task, the
-        configuration and this agent allow it; else None (the host path; the first reason is logged when the switch was on)."""
-        if getattr(self.config, 'fused_nstep_feature', False) is not True:
-            return None
-        from . import q_mlp
-        kind = q_mlp.Rollout
-        if not kind.VEC.eligible(self.task, self.config):
-            why = "the task is not a vector of at most 64 envs.CartPole environments under RescaleNormalizer(1.0), or there is no device"
-        else:
-            why = q_mlp.why_not(self)
-        if why is not None:
-            kind.stays_on_host(self, why)
-            return None
-        rollout = kind(self, kind.network_shape(self.network))
-        rollout.attach()
-        return rollout
+        from . import mlp_rollout, q_mlp
+        return mlp_rollout.adopt(self, q_mlp.Rollout)
 
     def close(self):
         self.drain_episodes()
@@ -1658,43 +1606,26 @@ class NStepDQNAgent(_TargetRolloutAgent):
         if self._feature is not None:
             torch.cuda.current_stream().synchronize()
             with open(filename + '.envs', 'wb') as f:
-                pickle.dump(dict(envs=self.task.state_dict(), step=int(self._feature.step_dev.item())), f)
+                pickle.dump(dict(self._episodes.state_dict(), step=int(self._feature.step_dev.item())), f)
 
     def load(self, filename):
         BaseAgent.load(self, filename)
         if self._feature is not None and os.path.isfile(filename + '.envs'):
             with open(filename + '.envs', 'rb') as f:
                 state = pickle.load(f)
-            self.drain_episodes()
-            self.task.load_state_dict(state['envs'])
+            self._episodes.load_state_dict(state)
             self._feature.step_dev.fill_(int(state['step']))
-            self._step_host, self._ep_anchor = int(state['step']), None
 
-    # -- n_step_dqn_feature over device-resident cart-pole environments --------------------------------------------------------
+    # -- n_step_dqn_feature over device-resident cart-pole environments: device_env.EpisodeRing ------------------------------
+    _dev_steps = property(lambda self: self._episodes.steps)      # (agent steps on the device path)
+    _step_host = property(lambda self: self._episodes.stamp)      # (the host's copy of the kernel's step counter)
     def drain_episodes(self):
-        """A2CAgent.drain_episodes' meaning: fetches the episodes that ended on the device since the last drain and emits the
-        reference's 'episodic_return_train' lines for them with the step numbers the host path logs -- total_steps at the start of
-        the episode's rollout + t * N + environment.  The lines arrive late (up to config.episode_drain_interval agent steps),
-        otherwise unchanged.  Returns the (step, return) pairs of this drain."""
-        if getattr(self, '_feature', None) is None or self._ep_anchor is None:
-            return []
-        s0, total0, t_len = self._ep_anchor
-        n = self.task.num_envs
-        out = []
-        for s, i, ret in self.task.drain():
-            at = total0 + (s - s0) * n + i
-            self.log_train_return(ret, at)
-            out.append((at, ret))
-        self._ep_log.extend(out)
-        return out
+        """EpisodeRing.drain: logs the episodes that ended on the device since the last drain -> their (step, return) pairs."""
+        return self._episodes.drain()
 
     def episodes(self):
-        """(step, episodic return) of the training episodes that ended since the previous call (the newest 16384 at most), after
-        a drain.  Empty on the host-stepped paths, whose episodes are only logged."""
-        self.drain_episodes()
-        out = list(self._ep_log)
-        self._ep_log.clear()
-        return out
+        """EpisodeRing.episodes: (step, episodic return) of the training episodes that ended since the previous call."""
+        return self._episodes.episodes()
 
     def _step_feature(self):
         """step() over device_env.DeviceCartPoleVec: the host makes the rollout's exploration draws in the reference's order and
@@ -1707,10 +1638,7 @@ class NStepDQNAgent(_TargetRolloutAgent):
         config = self.config
         t_len, n = int(config.rollout_length), config.num_workers
         self._feature.prepare(t_len)
-        if self._ep_anchor is None or self._ep_anchor[2] != t_len:
-            self.drain_episodes()
-            self._ep_anchor = (self._step_host, self.total_steps, t_len)
-        self._step_host += t_len
+        self._episodes.begin(t_len)
         freq, sync = config.target_network_update_freq, False
         for _ in range(t_len):
             self.total_steps += n
@@ -1719,9 +1647,7 @@ class NStepDQNAgent(_TargetRolloutAgent):
         if sync:
             self._sync_target()
         self.last_loss = self._dev_graph.run(Plan(self.task.env_counter, t_len), self._feature_learn)
-        self._dev_steps += 1
-        if self._dev_steps % max(1, int(getattr(config, 'episode_drain_interval', 64))) == 0:
-            self.drain_episodes()
+        self._episodes.end()
 
     def _feature_learn(self, plan):
         config = self.config

@@ -89,33 +89,19 @@ class Rollout(mlp_rollout.Rollout):
 
     def attach(self):
         """The environments move to the device; episode ends come back through the device's episode ring."""
+        mlp_rollout.Rollout.attach(self)
         a = self.agent
-        a.task = DeviceCartPoleVec(a.task)
         if a.dp.step_dev is None:      # the rank-invariant sampler's position: the kernel reads and advances it
             a.dp.step_dev = torch.zeros(1, dtype=torch.int64, device=Config.DEVICE)
-        a._sampler_host = int(a.dp.step_dev.item())
-
-    @staticmethod
-    def stays_on_host(agent, why):
-        if getattr(agent.config, 'fused_a2c_cat', True) is not False:
-            getattr(agent.logger, 'warning', agent.logger.info)(
-                'the cart-pole environments stay on the host and this agent keeps the module path: %s' % why)
+        a._episodes.stamp = int(a.dp.step_dev.item())
 
     def begin_step(self, t_len):
-        """Episode reporting: the terminals depend on the actions, so the episodes that end come back through the device's ring
-        (A2CAgent.drain_episodes); what the host keeps is the anchor that turns a ring row's sampler step into a step number."""
-        a = self.agent
-        if a._ep_anchor is None or a._ep_anchor[2] != t_len:
-            a.drain_episodes()       # (what is pending was appended under the old rollout length)
-            a._ep_anchor = (a._sampler_host, a.total_steps, t_len)
-        a._sampler_host += t_len + 1
+        """Episode reporting: the terminals depend on the actions, so episode ends come back through the device's ring (EpisodeRing)."""
+        self.agent._episodes.begin(t_len)
 
     def signature(self):
         """What the captured launch has baked in besides the optimizer's hyper-parameters: the seed of the noise stream."""
         return (int(self.agent._noise_seed),)
 
     def end_step(self):
-        a = self.agent
-        a._cat_steps += 1
-        if a._cat_steps % max(1, int(getattr(a.config, 'episode_drain_interval', 64))) == 0:
-            a.drain_episodes()
+        self.agent._episodes.end()

@@ -17,21 +17,19 @@
 // activations are kept TRANSPOSED ([unit][row]) so that a thread's 8 rows of one input unit are two 16-byte LDS reads, and every
 // dot product is one fp32 FMA chain in ascending k.  The environments live in the registers of wave 0 (lane e = environment e:
 // four fp64 state components, counters, the running return) for the whole launch; the ring position of an ending episode is the
-// rank of its lane in the wave's ballot, so rows land in (step, environment) order without a serial pass.
+// rank of its lane in the wave's ballot, so rows land in (step, environment) order without a serial pass (cartpole_rollout.h).
 #include "common.h"
-#include "cartpole_env.h"
+#include "cartpole_rollout.h"
 #include "gumbel_noise.h"
-#include "mlp_rollout.h"
 #include <math.h>
 
 namespace {
 
-constexpr int kS = kCartPoleS, kA = kCartPoleA, kMaxN = 64;
 constexpr int kOut = kA + 1;                  // logits and the value
 
 // LDS of the rollout kernel, in floats; every region starts at a multiple of 4 floats (16 bytes)
 __host__ __device__ constexpr size_t rollout_lds_floats(int H, int N) {
-  return (size_t)kS * H + (size_t)H * H + 2 * (size_t)H       // W1^T [S][H], W2^T [H][H], b1, b2
+  return body_weight_floats(H)                                // W1^T [S][H], W2^T [H][H], b1, b2
          + round_up4(kOut * (H + 1)) + 4                      // heads [3][H + 1], their biases
          + round_up4(kA * kMaxN)                              // logits [N][A]
          + (size_t)kS * round_up8(N) + 2 * (size_t)H * round_up8(N);   // x^T [S][NP], h1^T, h2^T [H][NP]
@@ -45,11 +43,8 @@ cat_mlp_rollout_kernel(dra_cat_mlp_net net, dra_cat_mlp_rollout_io io) {
   const int N = io.n_env, T = io.t_len, NP = round_up8(N);
   const float* __restrict__ P = net.param;
 
-  float* sW1 = lds;                                   // [S][H]  (transposed: [k][unit])
-  float* sW2 = sW1 + kS * H;                          // [H][H]
-  float* sB1 = sW2 + H * H;                           // [H]
-  float* sB2 = sB1 + H;                               // [H]
-  float* sWh = sB2 + H;                               // [3][H + 1]: fc_action's two rows, fc_critic's one
+  const BodyWeights<H> body(lds);
+  float* sWh = lds + body_weight_floats(H);           // [3][H + 1]: fc_action's two rows, fc_critic's one
   float* sBh = sWh + round_up4(kOut * (H + 1));       // [3] (+ pad)
   float* sLogit = sBh + 4;                            // [N][A]
   float* sXT = sLogit + round_up4(kA * kMaxN);        // [S][NP]
@@ -61,18 +56,7 @@ cat_mlp_rollout_kernel(dra_cat_mlp_net net, dra_cat_mlp_rollout_io io) {
   __syncthreads();
 
   // ---- weights, once per launch
-  for (int i = tid; i < kS * H; i += 256) {
-    const int k = i / H, u = i - k * H;
-    sW1[i] = P[net.w1 + u * kS + k];
-  }
-  for (int i = tid; i < H * H; i += 256) {
-    const int k = i / H, u = i - k * H;
-    sW2[i] = P[net.w2 + u * H + k];
-  }
-  for (int i = tid; i < H; i += 256) {
-    sB1[i] = P[net.b1 + i];
-    sB2[i] = P[net.b2 + i];
-  }
+  body.stage(P, net, tid);
   for (int i = tid; i < kOut * H; i += 256) {
     const int c = i / H, k = i - c * H;
     sWh[c * (H + 1) + k] = c < kA ? P[net.wa + c * H + k] : P[net.wc + k];
@@ -81,39 +65,16 @@ cat_mlp_rollout_kernel(dra_cat_mlp_net net, dra_cat_mlp_rollout_io io) {
 
   // ---- the environments: lane e of wave 0 carries environment e
   const bool env_lane = tid < N;
-  CartPoleState st = {0.0, 0.0, 0.0, 0.0};
-  int64_t counter = 0;
-  int32_t ep_steps = 0;
-  double ep_return = 0.0;
-  uint64_t seed = 0;
-  int64_t ring_count = 0;
-  if (env_lane) {
-    st.x = io.env_state[tid * kS + 0];
-    st.xd = io.env_state[tid * kS + 1];
-    st.th = io.env_state[tid * kS + 2];
-    st.thd = io.env_state[tid * kS + 3];
-    counter = io.env_counter[tid];
-    ep_steps = io.ep_steps[tid];
-    ep_return = io.ep_return[tid];
-    seed = (uint64_t)io.env_seed[tid];
-  }
-  if (tid < 64) ring_count = *io.ep_count;
-  const float reward = (float)(1.0 * io.reward_coef);       // what tensor(reward_normalizer(rewards)) uploads
+  CartPoleLanes lanes;
+  lanes.load(io, tid);
+  const float reward = (float)(1.0 * io.reward_coef);
 
   for (int t = 0; t <= T; ++t) {
-    // ---- the observation: float32 of the fp64 state (torch_utils.py:23)
-    if (env_lane) {
-      const float x[kS] = {(float)st.x, (float)st.xd, (float)st.th, (float)st.thd};
-#pragma unroll
-      for (int j = 0; j < kS; ++j) {
-        sXT[j * NP + tid] = x[j];
-        if (t < T) io.out_state[((int64_t)t * N + tid) * kS + j] = x[j];
-      }
-    }
+    if (env_lane) lanes.observe(sXT, NP, io.out_state, N, T, t, tid);
     __syncthreads();
-    hidden_layer<H, GATE, 256>(sXT, sW1, sB1, sH1T, kS, NP, tid);
+    hidden_layer<H, GATE, 256>(sXT, body.w1, body.b1, sH1T, kS, NP, tid);
     __syncthreads();
-    hidden_layer<H, GATE, 256>(sH1T, sW2, sB2, sH2T, H, NP, tid);
+    hidden_layer<H, GATE, 256>(sH1T, body.w2, body.b2, sH2T, H, NP, tid);
     __syncthreads();
     // ---- heads: one output per thread -- (environment e, logit c) or (e, the value); the bootstrap step needs the value alone
     if (tid < N * kOut) {
@@ -133,6 +94,7 @@ cat_mlp_rollout_kernel(dra_cat_mlp_net net, dra_cat_mlp_rollout_io io) {
     __syncthreads();
     // ---- action (gumbel_sample_kernel's loop, bit for bit), environment step, ring append: wave 0
     if (tid < 64) {
+      const CartPoleRow row(io);
       bool done = false;
       double ended = 0.0;
       if (env_lane) {
@@ -144,38 +106,15 @@ cat_mlp_rollout_kernel(dra_cat_mlp_net net, dra_cat_mlp_rollout_io io) {
           const float v = gs_perturbed(base, io.env0 + tid, a, sLogit[tid * kA + a]);
           if (v > best) { best = v; arg = a; }
         }
-        done = cartpole_step(st, counter, ep_steps, ep_return, seed, arg, io.horizon, ended);
-        const int64_t o = (int64_t)t * N + tid;
-        io.out_action[o] = arg;
-        io.out_reward[o] = reward;
-        io.out_mask[o] = done ? 0.f : 1.f;
+        done = lanes.advance(row, t, arg, reward, tid, ended);
       }
-      const unsigned long long ends = __ballot(done ? 1 : 0);
-      if (done) {
-        const int before = __popcll(ends & ((1ull << tid) - 1ull));
-        double* row = io.ep_ring + ((ring_count + before) % io.ring_cap) * 3;
-        row[0] = (double)(t0 + t);
-        row[1] = (double)(io.env0 + tid);
-        row[2] = ended;
-      }
-      ring_count += __popcll(ends);
+      lanes.append(row, done, ended, t0 + t, io.env0 + tid, tid);
     }
     // (wave 0 writes the next observation into x^T next: layer 1 of this step, its only reader, is three barriers back)
   }
   __syncthreads();
-  if (env_lane) {
-    io.env_state[tid * kS + 0] = st.x;
-    io.env_state[tid * kS + 1] = st.xd;
-    io.env_state[tid * kS + 2] = st.th;
-    io.env_state[tid * kS + 3] = st.thd;
-    io.env_counter[tid] = counter;
-    io.ep_steps[tid] = ep_steps;
-    io.ep_return[tid] = ep_return;
-  }
-  if (tid == 0) {
-    *io.sampler_step = t0 + T + 1;
-    *io.ep_count = ring_count;
-  }
+  lanes.store(io, tid);
+  if (tid == 0) *io.sampler_step = t0 + T + 1;
 }
 
 __global__ void __launch_bounds__(64)
@@ -200,41 +139,22 @@ cartpole_step_kernel(double* __restrict__ state, int64_t* __restrict__ counter, 
   out_done[i] = done ? 1 : 0;
 }
 
-template <int H, int GATE>
-int launch_rollout(const dra_cat_mlp_net* net, const dra_cat_mlp_rollout_io* io, void* stream) {
-  return launch_one_workgroup<&cat_mlp_rollout_kernel<H, GATE>>(rollout_lds_floats(H, io->n_env) * sizeof(float), net, io, stream);
-}
-
-template <int H>
-int launch_gate(const dra_cat_mlp_net* net, const dra_cat_mlp_rollout_io* io, void* stream) {
-  return net->gate == kGateRelu ? launch_rollout<H, kGateRelu>(net, io, stream) : launch_rollout<H, kGateTanh>(net, io, stream);
-}
-
 }  // namespace
 
 DRA_API int dra_cat_mlp_supported(int state_dim, int n_actions, int hidden, int n_env, int gate) {
-  if (state_dim != kS || n_actions != kA) return DRA_EINVAL;
-  if (hidden != 16 && hidden != 32 && hidden != 64) return DRA_EINVAL;
-  if (n_env < 1 || n_env > kMaxN || (gate != kGateRelu && gate != kGateTanh)) return DRA_EINVAL;
-  return DRA_OK;
+  return cartpole_mlp_supported(state_dim, n_actions, hidden, n_env, gate);
 }
 
 DRA_API int dra_cat_mlp_rollout(const dra_cat_mlp_net* net, const dra_cat_mlp_rollout_io* io, void* stream) {
   if (!net || !io || !net->param) return DRA_EINVAL;
-  if (dra_cat_mlp_supported(net->state_dim, net->n_actions, net->hidden, io->n_env, net->gate)) return DRA_EINVAL;
-  const int32_t offs[8] = {net->w1, net->b1, net->w2, net->b2, net->wa, net->ba, net->wc, net->bc};
-  for (int i = 0; i < 8; ++i)
-    if (offs[i] < 0) return DRA_EINVAL;
-  if (io->t_len < 1 || io->horizon < 1 || io->ring_cap < 1 || io->n_global < io->n_env || io->env0 < 0 ||
-      io->env0 + io->n_env > io->n_global)
-    return DRA_EINVAL;
-  if ((int64_t)(io->t_len + 1) * io->n_env * kS > 0x7fffffff) return DRA_EINVAL;
-  if (!io->env_state || !io->env_counter || !io->ep_steps || !io->ep_return || !io->env_seed || !io->sampler_step || !io->ep_count ||
-      !io->ep_ring || !io->out_state || !io->out_action || !io->out_v || !io->out_reward || !io->out_mask)
-    return DRA_EINVAL;
-  if (net->hidden == 16) return launch_gate<16>(net, io, stream);
-  if (net->hidden == 32) return launch_gate<32>(net, io, stream);
-  return launch_gate<64>(net, io, stream);
+  if (cartpole_mlp_supported(net->state_dim, net->n_actions, net->hidden, io->n_env, net->gate)) return DRA_EINVAL;
+  if (!offsets_nonnegative({net->w1, net->b1, net->w2, net->b2, net->wa, net->ba, net->wc, net->bc})) return DRA_EINVAL;
+  if (!cartpole_io_ok(io) || !io->sampler_step || !io->out_v) return DRA_EINVAL;
+  if (io->n_global < io->n_env || io->env0 < 0 || io->env0 + io->n_env > io->n_global) return DRA_EINVAL;
+  return dispatch_hidden_gate(net->hidden, net->gate, [&](auto h, auto g) {
+    constexpr int H = decltype(h)::value, GATE = decltype(g)::value;
+    return launch_one_workgroup<&cat_mlp_rollout_kernel<H, GATE>>(rollout_lds_floats(H, io->n_env) * sizeof(float), net, io, stream);
+  });
 }
 
 DRA_API int dra_cartpole_step(double* state, int64_t* counter, int32_t* ep_steps, double* ep_return, const int64_t* seed,

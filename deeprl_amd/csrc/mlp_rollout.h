@@ -1,7 +1,15 @@
-// What the one-workgroup rollout kernels over small MLPs share (a2c_mlp.hip, cat_mlp.hip): gate codes, row rounding, one hidden
-// layer over TRANSPOSED activations and the launch; ppo_mlp.hip and dpg_mlp.hip take the vector type, the gate codes and softplus_f.
-// The device functions are __forceinline__ and compile to the instructions the kernels had with the text in place.  The weight
-// staging and the heads' dot products do NOT (as functions they perturb these latency-bound chains): each kernel keeps its own.
+// What the one-workgroup rollout kernels over small MLPs share (a2c_mlp.hip, cat_mlp.hip, q_mlp.hip): gate codes, row rounding,
+// one hidden layer over TRANSPOSED activations and the launch; ppo_mlp.hip and dpg_mlp.hip take the vector type, the gate codes
+// and softplus_f.  The two cart-pole kernels (cat_mlp.hip, q_mlp.hip) share more in cartpole_rollout.h: the environment lanes
+// (load, observe, step with the episode-ring append, store), the staging of a two-layer body's weights (BodyWeights<H>), the
+// shape / offset / io checks and the hidden x gate dispatch.
+//
+// Shared or not is decided by the generated code and the kernel trace, not by taste: a __forceinline__ function is optimised on
+// its own before it is inlined, and these kernels sit at the edge of the SGPR file (DESIGN.md 4.13 has every figure).  Shared:
+// the cart-pole pair above, at equal VGPRs / scratch / occupancy and SGPR spills at or below the text in place.  NOT shared:
+//   q_mlp_update_kernel's weight staging (through BodyWeights<H> its VGPRs go 71 -> 78 at H 16 tanh, occupancy 7 -> 6);
+//   q_mlp.hip's block_layer (folded into hidden_layer, q_mlp_update_kernel<16, tanh> goes from 71 to 77 VGPRs, 7 -> 6 waves);
+//   the heads' dot products: each kernel has its own outputs per thread.
 #pragma once
 #include "common.h"
 #include <math.h>

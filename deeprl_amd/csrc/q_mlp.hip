@@ -12,22 +12,19 @@
 //                          optimiser's flat gradient buffer at the parameters' own offsets.
 //
 // Both are chains of dependent layers over a few rows: latency-bound, nothing to spread over 256 CUs.  Plain fp32 VALU code as in
-// cat_mlp.hip: weights are copied to LDS once per launch, activations are kept TRANSPOSED ([unit][row]) and read 16 bytes at a
+// cat_mlp.hip (the rollout's environment lanes and body staging ARE cat_mlp.hip's: cartpole_rollout.h): weights are copied to LDS once per launch, activations are kept TRANSPOSED ([unit][row]) and read 16 bytes at a
 // time, every dot product is one FMA chain in ascending k.  The update walks the rows in blocks of 64; every gradient element is
 // owned by ONE thread that adds its rows in ascending order, block after block: no atomics, the same bits on every launch.
 #include "common.h"
-#include "cartpole_env.h"
-#include "mlp_rollout.h"
+#include "cartpole_rollout.h"
 #include <math.h>
 
 namespace {
 
-constexpr int kS = kCartPoleS, kA = kCartPoleA, kMaxN = 64;
-
 // ---------------------------------------------------------------------------------------------------- the rollout
 // one network's weights in LDS, in floats; every region starts at a multiple of 4 floats (16 bytes)
 __host__ __device__ constexpr size_t weight_floats(int H) {
-  return (size_t)kS * H + (size_t)H * H + 2 * (size_t)H + round_up4(kA * (H + 1)) + 4;
+  return body_weight_floats(H) + round_up4(kA * (H + 1)) + 4;
 }
 __host__ __device__ constexpr size_t rollout_lds_floats(int H, int N) {
   return 2 * weight_floats(H)                                            // online, target
@@ -37,22 +34,11 @@ __host__ __device__ constexpr size_t rollout_lds_floats(int H, int N) {
 
 template <int H>
 struct Weights {
-  float *w1, *w2, *b1, *b2, *wq, *bq;       // W1^T [S][H], W2^T [H][H] (transposed: [k][unit]), b1, b2, head [A][H + 1], its bias
-  __device__ explicit Weights(float* base)
-      : w1(base), w2(w1 + kS * H), b1(w2 + H * H), b2(b1 + H), wq(b2 + H), bq(wq + round_up4(kA * (H + 1))) {}
-  __device__ void stage(const float* __restrict__ P, const dra_q_mlp_net& net, int tid) const {
-    for (int i = tid; i < kS * H; i += 256) {
-      const int k = i / H, u = i - k * H;
-      w1[i] = P[net.w1 + u * kS + k];
-    }
-    for (int i = tid; i < H * H; i += 256) {
-      const int k = i / H, u = i - k * H;
-      w2[i] = P[net.w2 + u * H + k];
-    }
-    for (int i = tid; i < H; i += 256) {
-      b1[i] = P[net.b1 + i];
-      b2[i] = P[net.b2 + i];
-    }
+  BodyWeights<H> body;
+  float *wq, *bq;                           // the head [A][H + 1], its bias
+  __device__ explicit Weights(float* base) : body(base), wq(base + body_weight_floats(H)), bq(wq + round_up4(kA * (H + 1))) {}
+  __device__ __forceinline__ void stage(const float* __restrict__ P, const dra_q_mlp_net& net, int tid) const {
+    body.stage(P, net, tid);
     for (int i = tid; i < kA * H; i += 256) {
       const int c = i / H, k = i - c * H;
       wq[c * (H + 1) + k] = P[net.wq + c * H + k];
@@ -84,40 +70,17 @@ q_mlp_rollout_kernel(dra_q_mlp_net net, dra_q_mlp_rollout_io io) {
 
   // ---- the environments: lane e of wave 0 carries environment e
   const bool env_lane = tid < N;
-  CartPoleState st = {0.0, 0.0, 0.0, 0.0};
-  int64_t counter = 0;
-  int32_t ep_steps = 0;
-  double ep_return = 0.0;
-  uint64_t seed = 0;
-  int64_t ring_count = 0;
-  if (env_lane) {
-    st.x = io.env_state[tid * kS + 0];
-    st.xd = io.env_state[tid * kS + 1];
-    st.th = io.env_state[tid * kS + 2];
-    st.thd = io.env_state[tid * kS + 3];
-    counter = io.env_counter[tid];
-    ep_steps = io.ep_steps[tid];
-    ep_return = io.ep_return[tid];
-    seed = (uint64_t)io.env_seed[tid];
-  }
-  if (tid < 64) ring_count = *io.ep_count;
-  const float reward = (float)(1.0 * io.reward_coef);       // what tensor(reward_normalizer(rewards)) uploads
+  CartPoleLanes lanes;
+  lanes.load(io, tid);
+  const float reward = (float)(1.0 * io.reward_coef);
 
   for (int t = 0; t <= T; ++t) {
     const Weights<H>& w = t < T ? online : target;          // NStepDQN_agent.py:56: the bootstrap is the TARGET network's
-    // ---- the observation: float32 of the fp64 state (torch_utils.py:23)
-    if (env_lane) {
-      const float x[kS] = {(float)st.x, (float)st.xd, (float)st.th, (float)st.thd};
-#pragma unroll
-      for (int j = 0; j < kS; ++j) {
-        sXT[j * NP + tid] = x[j];
-        if (t < T) io.out_state[((int64_t)t * N + tid) * kS + j] = x[j];
-      }
-    }
+    if (env_lane) lanes.observe(sXT, NP, io.out_state, N, T, t, tid);
     __syncthreads();
-    hidden_layer<H, GATE, 256>(sXT, w.w1, w.b1, sH1T, kS, NP, tid);
+    hidden_layer<H, GATE, 256>(sXT, w.body.w1, w.body.b1, sH1T, kS, NP, tid);
     __syncthreads();
-    hidden_layer<H, GATE, 256>(sH1T, w.w2, w.b2, sH2T, H, NP, tid);
+    hidden_layer<H, GATE, 256>(sH1T, w.body.w2, w.body.b2, sH2T, H, NP, tid);
     __syncthreads();
     // ---- the head: one output per thread, (environment e, action c)
     if (tid < N * kA) {
@@ -138,44 +101,20 @@ q_mlp_rollout_kernel(dra_q_mlp_net net, dra_q_mlp_rollout_io io) {
     }
     // ---- epsilon-greedy action (torch_utils.py:51-58 with the draws made ahead), environment step, ring append: wave 0
     if (tid < 64) {
-      bool done = false;
-      double ended = 0.0;
+      int arg = 0;
       if (env_lane) {
         const int64_t o = (int64_t)t * N + tid;
-        int arg = sQ[tid * kA + 1] > sQ[tid * kA] ? 1 : 0;          // np.argmax: the first maximum
+        arg = sQ[tid * kA + 1] > sQ[tid * kA] ? 1 : 0;              // np.argmax: the first maximum
         if (io.explore[o]) arg = io.random_action[o] == 1 ? 1 : 0;
-        done = cartpole_step(st, counter, ep_steps, ep_return, seed, arg, io.horizon, ended);
-        io.out_action[o] = arg;
-        io.out_reward[o] = reward;
-        io.out_mask[o] = done ? 0.f : 1.f;
       }
-      const unsigned long long ends = __ballot(done ? 1 : 0);
-      if (done) {
-        const int before = __popcll(ends & ((1ull << tid) - 1ull));
-        double* row = io.ep_ring + ((ring_count + before) % io.ring_cap) * 3;
-        row[0] = (double)(t0 + t);
-        row[1] = (double)tid;
-        row[2] = ended;
-      }
-      ring_count += __popcll(ends);
+      lanes.step(io, t, arg, reward, t0 + t, tid, tid);
     }
     // (wave 0 writes the next observation into x^T next: layer 1 of this step, its only reader, is three barriers back; q is
     // rewritten behind the three barriers of the next step)
   }
   __syncthreads();
-  if (env_lane) {
-    io.env_state[tid * kS + 0] = st.x;
-    io.env_state[tid * kS + 1] = st.xd;
-    io.env_state[tid * kS + 2] = st.th;
-    io.env_state[tid * kS + 3] = st.thd;
-    io.env_counter[tid] = counter;
-    io.ep_steps[tid] = ep_steps;
-    io.ep_return[tid] = ep_return;
-  }
-  if (tid == 0) {
-    *io.step_counter = t0 + T;
-    *io.ep_count = ring_count;
-  }
+  lanes.store(io, tid);
+  if (tid == 0) *io.step_counter = t0 + T;
 }
 
 // ---------------------------------------------------------------------------------------------------- the update
@@ -196,7 +135,7 @@ __device__ __forceinline__ float gate_back(float g, float h) {       // g * gate
 }
 
 // hidden_layer (mlp_rollout.h) over one block of kUB rows with the row stride kLD.  BACK false: out = gate(b + in W); BACK true
-// (b unused): out = (in W) * gate'(post), post^T the stored post-activations of this layer's units.
+// (b unused): out = (in W) * gate'(post), post^T the stored post-activations.  Not folded into hidden_layer: mlp_rollout.h's banner.
 template <int H, int GATE, bool BACK>
 __device__ __forceinline__ void block_layer(const float* __restrict__ inT, const float* __restrict__ wT, const float* __restrict__ b,
                                             const float* __restrict__ postT, float* __restrict__ outT, int K, int tid) {
@@ -406,56 +345,28 @@ q_mlp_update_kernel(dra_q_mlp_net net, dra_q_mlp_update_io io) {
   }
 }
 
-template <int H>
-int launch_rollout(const dra_q_mlp_net* net, const dra_q_mlp_rollout_io* io, void* stream) {
-  const size_t bytes = rollout_lds_floats(H, io->n_env) * sizeof(float);
-  return net->gate == kGateRelu ? launch_one_workgroup<&q_mlp_rollout_kernel<H, kGateRelu>>(bytes, net, io, stream)
-                                : launch_one_workgroup<&q_mlp_rollout_kernel<H, kGateTanh>>(bytes, net, io, stream);
-}
-
-template <int H>
-int launch_update(const dra_q_mlp_net* net, const dra_q_mlp_update_io* io, void* stream) {
-  const size_t bytes = update_lds_floats(H) * sizeof(float);
-  return net->gate == kGateRelu ? launch_one_workgroup<&q_mlp_update_kernel<H, kGateRelu>>(bytes, net, io, stream)
-                                : launch_one_workgroup<&q_mlp_update_kernel<H, kGateTanh>>(bytes, net, io, stream);
-}
-
-bool offsets_ok(const dra_q_mlp_net* net) {
-  const int32_t offs[6] = {net->w1, net->b1, net->w2, net->b2, net->wq, net->bq};
-  for (int i = 0; i < 6; ++i)
-    if (offs[i] < 0) return false;
-  return true;
-}
+bool offsets_ok(const dra_q_mlp_net* net) { return offsets_nonnegative({net->w1, net->b1, net->w2, net->b2, net->wq, net->bq}); }
 
 }  // namespace
 
 DRA_API int dra_q_mlp_supported(int state_dim, int n_actions, int hidden, int n_env, int gate) {
-  if (state_dim != kS || n_actions != kA) return DRA_EINVAL;
-  if (hidden != 16 && hidden != 32 && hidden != 64) return DRA_EINVAL;
-  if (n_env < 1 || n_env > kMaxN || (gate != kGateRelu && gate != kGateTanh)) return DRA_EINVAL;
-  return DRA_OK;
+  return cartpole_mlp_supported(state_dim, n_actions, hidden, n_env, gate);
 }
 
 DRA_API int dra_q_mlp_update_supported(int state_dim, int n_actions, int hidden, int rows, int gate) {
-  if (state_dim != kS || n_actions != kA) return DRA_EINVAL;
-  if (hidden != 16 && hidden != 32 && hidden != 64) return DRA_EINVAL;
-  if (rows < 1 || rows > kMaxRows || (gate != kGateRelu && gate != kGateTanh)) return DRA_EINVAL;
-  return DRA_OK;
+  if (cartpole_mlp_supported(state_dim, n_actions, hidden, 1, gate)) return DRA_EINVAL;
+  return rows < 1 || rows > kMaxRows ? DRA_EINVAL : DRA_OK;
 }
 
 DRA_API int dra_q_mlp_rollout(const dra_q_mlp_net* net, const dra_q_mlp_rollout_io* io, void* stream) {
   if (!net || !io || !net->param || !net->target) return DRA_EINVAL;
-  if (dra_q_mlp_supported(net->state_dim, net->n_actions, net->hidden, io->n_env, net->gate)) return DRA_EINVAL;
-  if (!offsets_ok(net)) return DRA_EINVAL;
-  if (io->t_len < 1 || io->horizon < 1 || io->ring_cap < 1) return DRA_EINVAL;
-  if ((int64_t)(io->t_len + 1) * io->n_env * kS > 0x7fffffff) return DRA_EINVAL;
-  if (!io->env_state || !io->env_counter || !io->ep_steps || !io->ep_return || !io->env_seed || !io->step_counter || !io->ep_count ||
-      !io->ep_ring || !io->explore || !io->random_action || !io->out_state || !io->out_q || !io->out_action || !io->out_reward ||
-      !io->out_mask || !io->bootstrap)
-    return DRA_EINVAL;
-  if (net->hidden == 16) return launch_rollout<16>(net, io, stream);
-  if (net->hidden == 32) return launch_rollout<32>(net, io, stream);
-  return launch_rollout<64>(net, io, stream);
+  if (cartpole_mlp_supported(net->state_dim, net->n_actions, net->hidden, io->n_env, net->gate)) return DRA_EINVAL;
+  if (!offsets_ok(net) || !cartpole_io_ok(io)) return DRA_EINVAL;
+  if (!io->step_counter || !io->explore || !io->random_action || !io->out_q || !io->bootstrap) return DRA_EINVAL;
+  return dispatch_hidden_gate(net->hidden, net->gate, [&](auto h, auto g) {
+    constexpr int H = decltype(h)::value, GATE = decltype(g)::value;
+    return launch_one_workgroup<&q_mlp_rollout_kernel<H, GATE>>(rollout_lds_floats(H, io->n_env) * sizeof(float), net, io, stream);
+  });
 }
 
 DRA_API int dra_q_mlp_update(const dra_q_mlp_net* net, const dra_q_mlp_update_io* io, void* stream) {
@@ -465,7 +376,8 @@ DRA_API int dra_q_mlp_update(const dra_q_mlp_net* net, const dra_q_mlp_update_io
   if (!offsets_ok(net)) return DRA_EINVAL;
   if (!io->state || !io->action || !io->reward || !io->mask || !io->bootstrap || !io->grad || !io->out_ret || !io->out_loss)
     return DRA_EINVAL;
-  if (net->hidden == 16) return launch_update<16>(net, io, stream);
-  if (net->hidden == 32) return launch_update<32>(net, io, stream);
-  return launch_update<64>(net, io, stream);
+  return dispatch_hidden_gate(net->hidden, net->gate, [&](auto h, auto g) {
+    constexpr int H = decltype(h)::value, GATE = decltype(g)::value;
+    return launch_one_workgroup<&q_mlp_update_kernel<H, GATE>>(update_lds_floats(H) * sizeof(float), net, io, stream);
+  });
 }

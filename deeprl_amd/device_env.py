@@ -9,6 +9,7 @@ one copy, and `states(plan, t)` produces the uint8 [N,4,84,84] observations of s
 observations go through the same image normaliser table (f32(f64(v) / 255)) as host frames, so the arithmetic an agent
 performs is bit-identical to the host-emulator path.
 """
+import collections
 import ctypes
 from collections import namedtuple
 
@@ -190,16 +191,19 @@ class _RolloutVec:
         return self._bufs[t_len]
 
     def fill_io(self, io, agent, t_len):
-        """The fields every rollout_io struct over these environments has (an out_* pointer per buffer it takes); returns the buffers."""
-        dp = agent.dp
+        """The fields every rollout_io struct over these environments has, an out_* pointer per buffer it takes and, where the
+        struct has them, the rank-invariant sampler's fields (an io struct without sampler_step brings a counter of its own);
+        returns the buffers."""
         b = self.buffers(t_len)
         io.env_state, io.env_counter, io.env_seed = self.env_state.data_ptr(), self.env_counter.data_ptr(), self.env_seed.data_ptr()
-        io.sampler_step = dp.step_dev.data_ptr()
         for k, v in b.items():
             if hasattr(io, 'out_' + k):
                 setattr(io, 'out_' + k, v.data_ptr())
-        io.env0, io.n_global, io.noise_seed, io.horizon = dp.lo, dp.global_workers, agent._noise_seed, self.horizon
-        io.reward_coef = float(agent.config.reward_normalizer.coef)
+        if hasattr(io, 'sampler_step'):
+            dp = agent.dp
+            io.sampler_step = dp.step_dev.data_ptr()
+            io.env0, io.n_global, io.noise_seed = dp.lo, dp.global_workers, agent._noise_seed
+        io.horizon, io.reward_coef = self.horizon, float(agent.config.reward_normalizer.coef)
         io.t_len, io.n_env = int(t_len), self.num_envs
         return b
 
@@ -306,20 +310,23 @@ class DeviceContinuousVec(_RolloutVec):
 
 
 class DeviceCartPoleVec(_RolloutVec):
-    """The envs.CartPole environments of a Task, resident on the device (a2c_feature, examples.py:340-358): fp64 state, total
-    step counters, episode steps and running returns live in HBM and one launch (dra_cat_mlp_rollout) walks a whole rollout --
-    forward, action, environment step -- without a host round trip.  Same arithmetic as envs.CartPole stepped from python
-    (csrc/cartpole_env.h; tests/test_gpu_a2c_feature.py compares the two).
+    """The envs.CartPole environments of a Task, resident on the device (a2c_feature, examples.py:340-358, under A2CAgent;
+    n_step_dqn_feature, examples.py:408-424, under NStepDQNAgent): fp64 state, total step counters, episode steps and running
+    returns live in HBM and one launch (dra_cat_mlp_rollout / dra_q_mlp_rollout) walks a whole rollout -- forward, action,
+    environment step -- without a host round trip.  Same arithmetic as envs.CartPole stepped from python (csrc/cartpole_env.h;
+    the two agents' GPU tests compare the two).  `buffers(t_len, n, zeros)`: what the kernel leaves besides state and action.
 
     The terminals depend on the actions, so the host cannot shadow them (DeviceContinuousVec.shadow has no counterpart here).
-    Episode ends are REPORTED by the device instead: the rollout kernel appends one row (sampler step of the end, global
-    environment, episodic return) per finished episode to `ep_ring` [RING_CAP][3] and counts them in `ep_count`; `drain()`
-    fetches what is new with one device-to-host copy."""
-    DRIVER = "A2CAgent"
+    Episode ends are REPORTED by the device instead: the rollout kernel (csrc/cartpole_rollout.h) appends one row (its stamp
+    of the end -- A2C: the sampler step, n-step DQN: its step counter --, global environment, episodic return) per finished
+    episode to `ep_ring` [RING_CAP][3] and counts them in `ep_count`; `drain()` is one device-to-host copy (EpisodeRing)."""
+    DRIVER = "A2CAgent / NStepDQNAgent"
     RING_CAP = 4096
+    HOST_NOTE = 'the cart-pole environments stay on the host and this agent keeps the module path: %s'
 
-    def __init__(self, task):
+    def __init__(self, task, buffers=None):
         _RolloutVec.__init__(self, task)
+        self._more_buffers = buffers or (lambda t_len, n, f: dict(v=f(t_len + 1, n, 1), reward=f(t_len, n, 1), mask=f(t_len, n, 1)))
         envs = task.env.envs
         dev = Config.DEVICE
         self.ring_cap = int(self.RING_CAP)
@@ -349,17 +356,17 @@ class DeviceCartPoleVec(_RolloutVec):
     def _new_buffers(self, t_len, f):
         n = self.num_envs
         return dict(state=f(t_len, n, self.state_dim), action=torch.zeros((t_len, n), dtype=torch.int64, device=Config.DEVICE),
-                    v=f(t_len + 1, n, 1), reward=f(t_len, n, 1), mask=f(t_len, n, 1))
+                    **self._more_buffers(t_len, n, f))
 
     def fill_io(self, io, agent, t_len):
-        """_RolloutVec.fill_io and the episode bookkeeping's fields (cat_mlp.RolloutIO)."""
+        """_RolloutVec.fill_io and the episode bookkeeping's fields (cat_mlp.RolloutIO, q_mlp.RolloutIO)."""
         b = _RolloutVec.fill_io(self, io, agent, t_len)
         io.ep_steps, io.ep_return = self.ep_steps.data_ptr(), self.ep_return.data_ptr()
         io.ep_count, io.ep_ring, io.ring_cap = self.ep_count.data_ptr(), self.ep_ring.data_ptr(), self.ring_cap
         return b
 
     def drain(self):
-        """The episodes that ended since the last drain -> list of (sampler step, global environment, episodic return) in the
+        """The episodes that ended since the last drain -> list of (the kernel's stamp, global environment, episodic return) in the
         order they were appended ((step, environment) order).  One device-to-host copy; raises when more than RING_CAP rows were
         pending (the oldest have been overwritten)."""
         self._ring_host.copy_(self._ring_buf, non_blocking=True)
@@ -387,3 +394,62 @@ class DeviceCartPoleVec(_RolloutVec):
         for k in ("env_state", "env_counter", "ep_steps", "ep_return", "env_seed", "_ring_buf"):
             getattr(self, k).copy_(torch.from_numpy(np.asarray(d[k])))
         self.drained = int(d["drained"])
+
+
+class EpisodeRing:
+    """The host's reader of DeviceCartPoleVec's episode ring, owned by the agent that drives the rollouts.  The kernel stamps a row
+    with its own counter: t_len + `bootstrap_stamps` per rollout (A2C: 1, the sampler's bootstrap slot; n-step DQN: 0).  `stamp`
+    follows it on the host; the anchor (stamp, agent.total_steps, t_len) taken at the first rollout of a rollout length turns a row
+    into the step number the host path logs -- total_steps at the start of the episode's rollout + t * n_global + environment."""
+    LOG = 16384
+
+    def __init__(self, agent, bootstrap_stamps, n_global):
+        self.agent, self.extra, self.n_global = agent, int(bootstrap_stamps), int(n_global)
+        self.stamp, self.anchor, self.steps = 0, None, 0
+        self.log = collections.deque(maxlen=self.LOG)
+
+    def begin(self, t_len):
+        # ahead of a rollout of t_len steps (and of the agent's total_steps advancing)
+        if self.anchor is None or self.anchor[2] != t_len:
+            self.drain()       # (what is pending was appended under the old rollout length)
+            self.anchor = (self.stamp, self.agent.total_steps, t_len)
+        self.stamp += t_len + self.extra
+
+    def end(self):
+        # behind an agent step: drains every config.episode_drain_interval of them
+        self.steps += 1
+        if self.steps % max(1, int(getattr(self.agent.config, 'episode_drain_interval', 64))) == 0:
+            self.drain()
+
+    def drain(self):
+        """Fetches the episodes that ended on the device since the last drain (one copy) and emits the reference's
+        'episodic_return_train' lines for them, late (up to config.episode_drain_interval agent steps) but with the host path's
+        step numbers.  Returns the (step, return) pairs of this drain; nothing before the first device rollout."""
+        if self.anchor is None:
+            return []
+        s0, total0, t_len = self.anchor
+        out = []
+        for s, i, ret in self.agent.task.drain():
+            k, t = divmod(s - s0, t_len + self.extra)
+            at = total0 + (k * t_len + t) * self.n_global + i
+            self.agent.log_train_return(ret, at)
+            out.append((at, ret))
+        self.log.extend(out)
+        return out
+
+    def episodes(self):
+        """(step, return) of the training episodes since the previous call (the newest LOG), after a drain; empty on host paths."""
+        self.drain()
+        out = list(self.log)
+        self.log.clear()
+        return out
+
+    def state_dict(self):
+        return dict(envs=self.agent.task.state_dict())
+
+    def load_state_dict(self, state):
+        """From a side file's dict: `step` is the kernel's counter, `envs` (absent in files older than the ring) the arrays."""
+        self.drain()
+        self.stamp, self.anchor = int(state['step']), None
+        if 'envs' in state:
+            self.agent.task.load_state_dict(state['envs'])

@@ -1,7 +1,8 @@
 """What the host sides of the small-MLP kernels share (a2c_mlp.py, cat_mlp.py, ppo_mlp.py, dpg_mlp.py): the gate codes, the ONE
 check that a body is a two-layer FCBody the kernels walk and that a head is a plain Linear, the agent-side conditions of a
-device rollout (`why_not`) and the `Rollout` base of a2c_mlp.Rollout / cat_mlp.Rollout: the kernel's two structs over the agent's
-ONE flat parameter buffer and its device-resident environments, one launch per rollout.
+device rollout (`why_not`), the ONE way an agent takes such a rollout up (`adopt`) and the `Rollout` base of a2c_mlp.Rollout /
+cat_mlp.Rollout / q_mlp.Rollout: the kernel's two structs over the agent's ONE flat parameter buffer and its device-resident
+environments, one launch per rollout.
 There is no CPU / eager implementation here: without the HIP library every call raises.
 """
 import ctypes
@@ -45,12 +46,12 @@ def body_params(body):
 
 
 def why_not(kind, agent, supported_fn=None):
-    """None when A2CAgent may run `agent` on the rollout kernel of `kind` (a Rollout subclass), else the first reason it may not
-    (everything but the task itself, which the device_env class decides)."""
+    """None when `agent` may run on the rollout kernel of `kind` (a Rollout subclass), else the first reason it may not
+    (everything but the task itself, which the device_env class decides).  An agent without a `dp` is not data parallel."""
     cfg = agent.config
-    if getattr(cfg, kind.SWITCH, True) is False:
-        return "config.%s is off" % kind.SWITCH
-    if agent.dp.active:
+    if not kind.switched_on(cfg):
+        return "config.%s is %s" % (kind.SWITCH, "not on" if kind.OPT_IN else "off")
+    if getattr(agent, 'dp', None) is not None and agent.dp.active:
         return "the agent is data parallel"
     if agent.grad_hook is not None:
         return "a grad_hook is installed"
@@ -66,15 +67,31 @@ def why_not(kind, agent, supported_fn=None):
     return None
 
 
+def adopt(agent, kind):
+    """A `kind` rollout with agent.task on the device when task, configuration and agent allow it; else None (the host path)."""
+    able = kind.VEC.eligible(agent.task, agent.config)
+    why = kind.why_not(agent) if able else kind.NOT_TASK
+    if why is not None:
+        kind.stays_on_host(agent, why)
+    if why is not None or not able:
+        return None
+    rollout = kind(agent, kind.network_shape(agent.network))
+    rollout.attach()
+    agent.states = None
+    return rollout
+
+
 class Rollout:
     """One launch per rollout over the agent's device-resident environments (agent.task: a device_env class with fill_io) and its
     flat parameter buffer.  A subclass names its kernel: the config switch, the library entry, the two struct mirrors, the
     struct's four shape fields, `network_shape(network)`, `fields(network)` -- the (offset field, parameter) pairs -- and
-    `supported(...)`; how the task moves to the device (`VEC`, `attach`, `stays_on_host`); and where A2CAgent's device step
+    `supported(...)`; whether the switch must be set to turn the path on (`OPT_IN`) and what is said of a task that cannot move
+    (`NOT_TASK`, None: nothing); how the task moves to the device (`VEC`, `attach`); and where A2CAgent's device step
     differs between them: `begin_step` / `end_step` (episode reporting), `signature()` (what a captured launch has baked in: the
     arguments fill_io takes behind t_len, then the noise seed; kept in `sig`) and `ACTION_VIEW` (the stored actions' shape
     behind the row axis)."""
-    SWITCH = ENTRY = VEC = NETWORK = Net = IO = DIMS = ACTION_VIEW = None
+    SWITCH = ENTRY = VEC = NETWORK = Net = IO = DIMS = ACTION_VIEW = NOT_TASK = None
+    OPT_IN = False
 
     def __init__(self, agent, shp):
         self.agent = agent
@@ -101,9 +118,21 @@ class Rollout:
         self.launches += 1
         return b
 
-    @staticmethod
-    def stays_on_host(agent, why):
-        return
+    @classmethod
+    def switched_on(cls, cfg):
+        return getattr(cfg, cls.SWITCH, False) is True if cls.OPT_IN else getattr(cfg, cls.SWITCH, True) is not False
+
+    why_not = classmethod(lambda cls, agent: why_not(cls, agent))      # (a kind with conditions of its own adds them)
+
+    def attach(self):
+        self.agent.task = self.VEC(self.agent.task)
+
+    @classmethod
+    def stays_on_host(cls, agent, why):
+        # (logged where the VEC has a line for it, HOST_NOTE, unless the switch itself is off)
+        note = getattr(cls.VEC, 'HOST_NOTE', None)
+        if note and cls.switched_on(agent.config):
+            getattr(agent.logger, 'warning', agent.logger.info)(note % why)
 
     def end_step(self):
         return

@@ -79,24 +79,18 @@ def _fields(net):
 
 
 def why_not(agent, supported_fn=supported):
-    """None when NStepDQNAgent may run `agent` on the kernels, else the first reason it may not (everything but the task itself,
-    which device_env.DeviceCartPoleVec.eligible decides).  The path is opt-in: config.fused_nstep_feature must be True."""
-    cfg = agent.config
-    if getattr(cfg, Rollout.SWITCH, False) is not True:
-        return "config.%s is not on" % Rollout.SWITCH
-    if agent.grad_hook is not None:
-        return "a grad_hook is installed"
-    shp = shape(agent.network)
-    if shp is None or shape(agent.target_network) != shp:
+    """None when NStepDQNAgent may run `agent` on the kernels, else the first reason it may not (all but the task itself, which
+    DeviceCartPoleVec.eligible decides): mlp_rollout.why_not's -- opt-in: config.fused_nstep_feature must be True --, then the target's."""
+    why = mlp_rollout.why_not(Rollout, agent, supported_fn)
+    if why is not None:
+        return why
+    cfg, shp = agent.config, shape(agent.network)
+    if shape(agent.target_network) != shp:
         return "the network is not %s" % Rollout.NETWORK
     flat, target = agent._fused.flat, agent._target_flat
-    if any(all(p is not q for q in flat.params) for _, p in _fields(agent.network)):
-        return "one optimiser does not own every parameter the kernel reads"
     if ([flat.offset_of(p) for _, p in _fields(agent.network)] != [target.offset_of(p) for _, p in _fields(agent.target_network)]):
         return "the online and the target parameters are laid out differently in their flat buffers"
     n, t_len = int(cfg.num_workers), int(cfg.rollout_length)
-    if not supported_fn(shp[0], shp[1], shp[2], n, shp[3]):
-        return "%s is not built for state_dim %d, %d actions, hidden %d, %d environments" % (Rollout.ENTRY, shp[0], shp[1], shp[2], n)
     if getattr(cfg, 'fused_nstep_update', True) is not False and not update_supported(shp[0], shp[1], shp[2], t_len * n, shp[3]):
         return "dra_q_mlp_update is not built for %d rows (rollout length %d x %d environments)" % (t_len * n, t_len, n)
     return None
@@ -115,26 +109,23 @@ def update(net, state, action, reward, mask, bootstrap, discount, grad, out_ret,
 
 class Rollout(mlp_rollout.Rollout):
     """dra_q_mlp_rollout over a DeviceCartPoleVec, the agent's flat parameter buffer and its target network's."""
-    SWITCH, ENTRY, VEC = 'fused_nstep_feature', 'dra_q_mlp_rollout', DeviceCartPoleVec
+    SWITCH, ENTRY, VEC, OPT_IN = 'fused_nstep_feature', 'dra_q_mlp_rollout', DeviceCartPoleVec, True
     NETWORK = "VanillaNet over a two-layer relu / tanh FCBody with a plain head"
+    NOT_TASK = "the task is not a vector of at most 64 envs.CartPole environments under RescaleNormalizer(1.0), or there is no device"
     Net, IO, DIMS, ACTION_VIEW = Net, RolloutIO, ("state_dim", "n_actions", "hidden", "gate"), ()
-    network_shape, fields, supported = staticmethod(shape), staticmethod(_fields), staticmethod(supported)
+    network_shape, fields, supported, why_not = staticmethod(shape), staticmethod(_fields), staticmethod(supported), staticmethod(why_not)
 
     def __init__(self, agent, shp):
         mlp_rollout.Rollout.__init__(self, agent, shp)
-        self._bufs, self._up = {}, None
+        self._up = None
         self.explore = self.random_action = None
-        # the kernel's own step counter: the ring rows carry it (NStepDQNAgent.drain_episodes turns it into a step number)
+        # the kernel's own step counter: the ring rows carry it (device_env.EpisodeRing turns it into a step number)
         self.step_dev = torch.zeros(1, dtype=torch.int64, device=Config.DEVICE)
 
     def attach(self):
-        """The environments move to the device; episode ends come back through the device's episode ring."""
-        self.agent.task = DeviceCartPoleVec(self.agent.task)
-
-    @staticmethod
-    def stays_on_host(agent, why):
-        getattr(agent.logger, 'warning', agent.logger.info)(
-            'the cart-pole environments stay on the host and this agent keeps the module path: %s' % why)
+        """The environments move to the device with the buffers these kernels leave (and the update's two outputs)."""
+        self.agent.task = DeviceCartPoleVec(self.agent.task, buffers=lambda t_len, n, f: dict(
+            q=f(t_len, n, 2), reward=f(t_len, n), mask=f(t_len, n), bootstrap=f(n), ret=f(t_len, n), loss=f(1)))
 
     def net_struct(self):
         n = mlp_rollout.Rollout.net_struct(self)
@@ -142,13 +133,7 @@ class Rollout(mlp_rollout.Rollout):
         return n
 
     def buffers(self, t_len):
-        """What a rollout of t_len steps leaves (and the update's two outputs), at fixed addresses."""
-        if t_len not in self._bufs:
-            n, dev = self.agent.task.num_envs, Config.DEVICE
-            f = lambda *s: torch.zeros(s, dtype=torch.float32, device=dev)
-            self._bufs[t_len] = dict(state=f(t_len, n, 4), q=f(t_len, n, 2), action=torch.zeros((t_len, n), dtype=torch.int64, device=dev),
-                                     reward=f(t_len, n), mask=f(t_len, n), bootstrap=f(n), ret=f(t_len, n), loss=f(1))
-        return self._bufs[t_len]
+        return self.agent.task.buffers(t_len)
 
     def prepare(self, t_len):
         """Draws the rollout's exploration (support.plan_epsilon_greedy: NStepDQN_agent.py:34-35's calls in their order, so that
@@ -169,19 +154,11 @@ class Rollout(mlp_rollout.Rollout):
         return explore, rand
 
     def run(self, t_len):
-        """One rollout launch on the current stream (after prepare(t_len)); returns buffers(t_len)."""
-        vec, cfg = self.agent.task, self.agent.config
-        b = self.buffers(t_len)
+        """One rollout launch on the current stream (after prepare(t_len)); returns the task's buffers of t_len."""
         io = RolloutIO()
-        io.env_state, io.env_counter, io.env_seed = vec.env_state.data_ptr(), vec.env_counter.data_ptr(), vec.env_seed.data_ptr()
-        io.ep_steps, io.ep_return = vec.ep_steps.data_ptr(), vec.ep_return.data_ptr()
-        io.ep_count, io.ep_ring, io.ring_cap = vec.ep_count.data_ptr(), vec.ep_ring.data_ptr(), vec.ring_cap
-        io.step_counter = self.step_dev.data_ptr()
+        b = self.agent.task.fill_io(io, self.agent, t_len)
+        io.step_counter, io.bootstrap = self.step_dev.data_ptr(), b['bootstrap'].data_ptr()
         io.explore, io.random_action = self.explore.data_ptr(), self.random_action.data_ptr()
-        io.out_state, io.out_q, io.out_action = b['state'].data_ptr(), b['q'].data_ptr(), b['action'].data_ptr()
-        io.out_reward, io.out_mask, io.bootstrap = b['reward'].data_ptr(), b['mask'].data_ptr(), b['bootstrap'].data_ptr()
-        io.horizon, io.reward_coef = vec.horizon, float(cfg.reward_normalizer.coef)
-        io.t_len, io.n_env = int(t_len), vec.num_envs
         net = self.net_struct()
         lib.dra_q_mlp_rollout(ctypes.byref(net), ctypes.byref(io), stream_ptr())
         self.launches += 1

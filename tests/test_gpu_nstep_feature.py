@@ -221,6 +221,88 @@ def test_rollout_refuses_unsupported_shapes_and_launches_nothing(dra):
     assert refused(out_q=None) and refused(bootstrap=None) and refused(explore=None) and refused(target=None)
 
 
+CORE_CASES = [      # (n_env, t_len, horizon, ring_cap)
+    (1, 1, 200, 64),        # one lane, no episode end
+    (64, 3, 2, 4096),       # every lane of the wave, 64 ends in one step: the ballot rank at lane 63
+    (5, 6, 2, 8),           # 15 rows through an 8-row ring (5 a step: never more ends in one step than the ring has rows)
+]
+
+
+@pytest.mark.parametrize("gate", ["relu", "tanh"])
+@pytest.mark.parametrize("n,t_len,horizon,ring_cap", CORE_CASES, ids=lambda v: str(v))
+def test_rollout_cores_agree(dra, n, t_len, horizon, ring_cap, gate):
+    """dra_cat_mlp_rollout and dra_q_mlp_rollout share csrc/cartpole_rollout.h: from the same environments, with the second
+    launch made to take the actions the first one stored (explore all ones), everything the shared text computes is the same
+    bits -- the environments' arrays, the stored observations, rewards and masks, the ring's count and columns 1 and 2 of every
+    row; column 0 differs by the two starting stamps alone.  Hidden 16, both gates."""
+    from deeprl_amd import cat_mlp, q_mlp
+    from deeprl_amd._lib import lib, stream_ptr
+    dev, hidden = dra.Config.DEVICE, 16
+    rng = np.random.RandomState(1000 * n + t_len)
+    shapes = dict(w1=(hidden, 4), b1=(hidden,), w2=(hidden, hidden), b2=(hidden,))
+    cat_keys, q_keys = dict(shapes, wa=(2, hidden), ba=(2,), wc=(1, hidden), bc=(1,)), dict(shapes, wq=(2, hidden), bq=(2,))
+    stamp_cat, stamp_q, count0 = 1000, 70, 3
+
+    def flat_net(struct, keys):
+        off, chunks = 0, []
+        for k, shape in keys.items():
+            setattr(struct, k, off)
+            chunks.append(rng.uniform(-0.5, 0.5, size=shape).astype(np.float32).reshape(-1))
+            off += chunks[-1].size
+        struct.state_dim, struct.n_actions, struct.hidden, struct.gate = 4, 2, hidden, GATE[gate]
+        return torch.from_numpy(np.concatenate(chunks)).to(dev)
+
+    start = dict(env_state=torch.from_numpy(rng.uniform(-0.05, 0.05, size=(n, 4))), env_counter=torch.arange(n, dtype=torch.int64) * 3,
+                 ep_steps=torch.zeros(n, dtype=torch.int32), ep_return=torch.zeros(n, dtype=torch.float64),
+                 env_seed=torch.arange(n, dtype=torch.int64) + 11, ep_count=torch.full((1,), count0, dtype=torch.int64),
+                 ep_ring=torch.full((ring_cap, 3), float("nan"), dtype=torch.float64))
+    f32 = lambda *s: torch.full(s, float("nan"), dtype=torch.float32, device=dev)
+
+    def side(io, stamp):
+        t = {k: v.clone().to(dev) for k, v in start.items()}
+        t.update(state=f32(t_len, n, 4), action=torch.full((t_len, n), -7, dtype=torch.int64, device=dev), reward=f32(t_len, n),
+                 mask=f32(t_len, n), stamp=torch.full((1,), stamp, dtype=torch.int64, device=dev))
+        for k in start:
+            setattr(io, k, t[k].data_ptr())
+        for k in ("state", "action", "reward", "mask"):
+            setattr(io, "out_" + k, t[k].data_ptr())
+        io.horizon, io.ring_cap, io.reward_coef, io.t_len, io.n_env = horizon, ring_cap, 1.0, t_len, n
+        return t
+
+    cnet, cio = cat_mlp.Net(), cat_mlp.RolloutIO()
+    cflat = flat_net(cnet, cat_keys)
+    cnet.param = cflat.data_ptr()
+    c = side(cio, stamp_cat)
+    c["v"] = f32(t_len + 1, n)
+    cio.sampler_step, cio.out_v, cio.env0, cio.n_global, cio.noise_seed = c["stamp"].data_ptr(), c["v"].data_ptr(), 0, n, 12345
+    assert lib.dra_cat_mlp_rollout.raw(ctypes.byref(cnet), ctypes.byref(cio), stream_ptr()) == 0
+    torch.cuda.synchronize()
+    assert bool(((c["action"] == 0) | (c["action"] == 1)).all())
+
+    qnet, qio = q_mlp.Net(), q_mlp.RolloutIO()
+    qflat = flat_net(qnet, q_keys)
+    qnet.param = qnet.target = qflat.data_ptr()
+    q = side(qio, stamp_q)
+    q.update(q=f32(t_len, n, 2), bootstrap=f32(n), explore=torch.ones((t_len, n), dtype=torch.uint8, device=dev),
+             random_action=c["action"].clone())
+    qio.step_counter, qio.out_q, qio.bootstrap = q["stamp"].data_ptr(), q["q"].data_ptr(), q["bootstrap"].data_ptr()
+    qio.explore, qio.random_action = q["explore"].data_ptr(), q["random_action"].data_ptr()
+    assert lib.dra_q_mlp_rollout.raw(ctypes.byref(qnet), ctypes.byref(qio), stream_ptr()) == 0
+    torch.cuda.synchronize()
+
+    for k in ("env_state", "env_counter", "ep_steps", "ep_return", "state", "action", "reward", "mask", "ep_count"):
+        assert torch.equal(_as_int(c[k]), _as_int(q[k])), k
+    assert int(c["stamp"].item()) == stamp_cat + t_len + 1 and int(q["stamp"].item()) == stamp_q + t_len
+    ends = sum(1 for t in range(t_len) if (t + 1) % horizon == 0) * n         # (no pole falls within `horizon` steps of such a start)
+    assert int(c["ep_count"].item()) == count0 + ends and float((1 - c["mask"]).sum().item()) == ends
+    cr, qr = c["ep_ring"].cpu().numpy(), q["ep_ring"].cpu().numpy()
+    assert np.array_equal(_bits(cr[:, 1:]), _bits(qr[:, 1:]))
+    written = ~np.isnan(cr[:, 0])
+    assert written.sum() == min(ends, ring_cap) and np.array_equal(written, ~np.isnan(qr[:, 0]))
+    assert np.array_equal(cr[written, 0] - stamp_cat, qr[written, 0] - stamp_q)
+    assert np.array_equal(np.isnan(cr[:, 1]), ~written) and (cr[written, 2] == horizon).all()
+
+
 # ------------------------------------------------------------------------------------------ update kernel
 SENTINEL = 123.25       # what the gaps of the gradient buffer hold before a launch
 
