@@ -100,6 +100,6 @@ class Rollout(mlp_rollout.Rollout):
             a.log_train_return(ret, a.total_steps + t * a.dp.global_workers + i)
 
     def signature(self):
-        """What the captured launch has baked in besides the optimizer's hyper-parameters (_OnPolicyGraph's own key): whether the
+        """What the captured launch has baked in besides the optimizer's hyper-parameters (graphs._OnPolicyGraph's own key): whether the
         normaliser's statistics are left alone (fill_io's read_only), and the seed of the noise stream."""
         return bool(getattr(self.agent.config.state_normalizer, 'read_only', False)), int(self.agent._noise_seed)

@@ -24,9 +24,6 @@ Differences that are the point of the rewrite (results unchanged):
 import pickle
 import os
 
-import contextlib
-import gc
-
 import numpy as np
 import torch
 import torch.nn as nn
@@ -39,27 +36,9 @@ from .replay import PrioritizedTransition, Storage
 from ._lib import DraError
 from .device_env import DeviceAtariVec, EpisodeRing
 from .pixel_rollout import _OCRollout, _PixelRollout, _QRollout, hand_over, k_major     # noqa: F401  (the rollouts: this module's names too)
-from .support import (Config, LinearSchedule, StagedUpload, close_obj, epsilon_greedy, get_logger, random_sample, range_tensor, tensor,
-                      to_np)
-
-
-
-@contextlib.contextmanager
-def _capture(graph):
-    """torch.cuda.graph(graph) with the cyclic garbage collector held off for the duration of the capture.  A collection that
-    runs INSIDE a capture may finalise objects of an earlier agent that own HIP resources (pinned host tensors, the fused
-    learner's library handle): their frees / device synchronisation are illegal while a stream captures and end the process
-    (std::terminate out of a deleter) -- seen as a sporadic abort of the test suite at the first captured update that followed a
-    closed device-pipeline agent.  Collect first, then capture without the collector."""
-    gc.collect()
-    was = gc.isenabled()
-    gc.disable()
-    try:
-        with torch.cuda.graph(graph):
-            yield
-    finally:
-        if was:
-            gc.enable()
+from .graphs import (_capture, _capture_failed, _fused_noisy, _GraphedAct, _GraphedPPO, _GraphedQ,   # noqa: F401  (the captured regions:
+                     _GraphedUpdate, _OnPolicyGraph)                                               # this module's names too)
+from .support import Config, LinearSchedule, close_obj, epsilon_greedy, get_logger, random_sample, range_tensor, tensor, to_np
 
 
 class _NullLock:
@@ -254,191 +233,6 @@ class DQNActor(BaseActor):
         self._total_steps += 1
         self._state = next_state
         return entry
-
-
-def _fused_noisy(config, net):
-    """Noisy layers on csrc/noisy.hip: config.fused_noisy (default on) over a network that stages its noise in one block
-    (nets.RainbowNet), on the device.  Only then may the actor forward / the update of a noisy agent be captured."""
-    return (getattr(config, 'fused_noisy', True) is not False and Config.DEVICE.type == 'cuda' and net is not None
-            and hasattr(net, 'noise_block') and getattr(net, 'fused_noisy', False))
-
-
-def _capture_failed(config, what, error):
-    """A hipGraph capture failed.  Falling back to the eager kernels silently would turn a broken capture into nothing but a
-    slower number, so it is an error unless the configuration opts into the fallback (config.allow_eager_fallback = True:
-    e.g. a user network with host-side control flow)."""
-    if not getattr(config, 'allow_eager_fallback', False):
-        raise RuntimeError("%s could not be captured as a hipGraph (%r); set config.allow_eager_fallback = True to run it "
-                           "eagerly, or config.graph_update = False to skip capturing" % (what, error)) from error
-    import warnings
-    warnings.warn("%s could not be captured as a graph (%r); using the eager path" % (what, error))
-
-
-class _GraphedQ:
-    """DQNActor's forward (DQN_agent.py:29-33) as ONE hipGraph replay for image observations: the uint8
-    [1,C,H,W] observation goes through pinned staging into a static device buffer; normaliser table kernel,
-    network forward and the action-value reduction replay from a graph captured (torch.cuda.graphs) after four
-    eager calls (one agent step: by then a DQNAgent that qualifies for the fused learner has switched to it).
-    Same kernels, same arguments as the eager path -> bit-identical action values."""
-    WARMUP = 4
-
-    def __init__(self, actor):
-        self.actor = actor
-        self.calls = 0
-        self.graph = None
-        self.static_in = self.static_out = None
-        self.upload = None
-        self.failed = False
-
-    def usable(self, state):
-        from .normalizers import RescaleNormalizer
-        cfg = self.actor.config
-        if self.failed or getattr(cfg, 'graph_update', True) is False:
-            return False
-        if cfg.noisy_linear and not _fused_noisy(cfg, self.actor._network):
-            return False        # the module path materialises the mixed weights with ATen kernels: eager
-        if not isinstance(cfg.state_normalizer, RescaleNormalizer):
-            return False
-        first = state[0] if isinstance(state, (list, tuple)) else state
-        return isinstance(first, LazyFrames) or (isinstance(first, np.ndarray) and first.dtype == np.uint8)
-
-    def __call__(self, state):
-        a = self.actor
-        cfg = a.config
-        self.calls += 1
-        if self.calls <= self.WARMUP:
-            return None
-        x = np.ascontiguousarray(np.asarray(state, dtype=np.uint8))
-        dev = next(a._network.parameters()).device
-        if self.graph is None:
-            try:
-                self.upload = StagedUpload(x.shape, torch.uint8, dev)
-                self.static_in = self.upload.dev
-                with torch.no_grad():   # eager dry run of exactly what is captured: creates every lazily built
-                    a.q_device(a._network(cfg.state_normalizer(self.static_in)))   # object (normaliser table, ...)
-                g = torch.cuda.CUDAGraph()
-                torch.cuda.synchronize()
-                with _capture(g):
-                    with torch.no_grad():
-                        self.static_out = a.q_device(a._network(cfg.state_normalizer(self.static_in)))
-                self.graph = g
-            except Exception as e:      # e.g. a network with host-side control flow: stay on the eager path
-                _capture_failed(cfg, "the actor forward", e)
-                self.failed = True
-                self.graph = None
-                return None
-        self.upload.put(x)
-        self.graph.replay()
-        return to_np(self.static_out)
-
-
-class _GraphedUpdate:
-    """One DQN-family update (DQN_agent.py:114-134: normalise, target / online forwards, fused loss kernel,
-    backward, clip, optimizer) as ONE hipGraph replay over static minibatch buffers that the ring gather refills
-    in place.  Captured with torch.cuda.graphs after two eager updates (which also run every lazy one-time
-    initialisation); same kernels and arguments as the eager path -> bit-identical parameters.
-
-    Agents without noisy layers: uniform replay only.  Noisy layers on csrc/noisy.hip (_fused_noisy): uniform replay and the
-    PER form -- rp.draw() -> gather into the static buffers -> sampling probabilities and the importance exponent in one
-    small upload (the captured launches read beta from a device word) -> replay -> rp.commit_device(tree_idx, prio): the
-    priorities never visit the host.  reset_noise() (target, then online: DQN_agent.py:116-118) runs outside the captured
-    region; the graph reads the noise through static addresses."""
-    WARMUP = 2
-
-    def __init__(self, agent):
-        self.agent = agent
-        self.updates = 0
-        self.graph = None
-        self.static = None
-        self.out = None
-        self.signature = None
-        self.failed = False
-        self.per_words = None       # [batch sampling probabilities | beta] f32, device
-        self._per_up = None
-
-    def usable(self, rp):
-        cfg = self.agent.config
-        if self.failed or getattr(cfg, 'graph_update', True) is False or self.agent._fused is None:
-            return False
-        if cfg.noisy_linear:
-            return _fused_noisy(cfg, self.agent.network) and _fused_noisy(cfg, self.agent.target_network)
-        return not hasattr(rp, 'draw')
-
-    def _upload_per(self, prob, beta):
-        from .replay import _PinnedUploader
-        b = len(prob)
-        if self.per_words is None:
-            dev = next(self.agent.network.parameters()).device
-            self.per_words = torch.zeros(b + 1, dtype=torch.float32, device=dev)
-            self._per_up = _PinnedUploader(torch.float32, b + 1, dev)
-        words = np.empty(b + 1, dtype=np.float32)
-        words[:b] = prob            # (f64 -> f32: the rounding the eager path's .float() applies)
-        words[b] = beta
-        self._per_up.upload_into(self.per_words, words)
-
-    def run(self, rp):
-        """Returns the loss-kernel outputs of the update it performed, or None (caller runs the eager update)."""
-        agent = self.agent
-        cfg = agent.config
-        self.updates += 1
-        if self.updates <= self.WARMUP:
-            return None
-        opt = agent._fused
-        if self.graph is not None and self.signature != opt.hyper_signature():
-            self.graph = None       # a hyper-parameter baked into the graph changed (lr schedule): re-capture
-        per = hasattr(rp, 'draw')
-        tree_idx = None
-        if per:
-            tree_idx, prob, idx = rp.draw()
-            self._upload_per(prob, cfg.replay_beta())
-        else:
-            idx = rp.draw_indices()
-        if cfg.noisy_linear:
-            agent.target_network.reset_noise()
-            agent.network.reset_noise()
-        if self.graph is None:
-            try:
-                self.static = rp.gather(idx)
-                fields = dict(state=self.static['state'], action=self.static['action'], reward=self.static['reward'],
-                              next_state=self.static['next_state'], mask=self.static['mask'])
-                per_args = None
-                if per:
-                    b = len(idx)
-                    fields.update(sampling_prob=self.per_words[:b], idx=None)
-                    # beta < 0: dra_td_loss reads the exponent behind the probabilities; beta_dev: dra_per_weights_dev
-                    per_args = dict(sampling_prob=self.per_words[:b], beta=-1.0, beta_dev=self.per_words[b:b + 1],
-                                    replay_eps=cfg.replay_eps, replay_alpha=cfg.replay_alpha)
-                tr = rp.TransitionCLS(**fields)
-                opt.enable_graph_mode()
-                g = torch.cuda.CUDAGraph()
-                torch.cuda.synchronize()
-                with _capture(g):
-                    out, (net_out, grad) = agent._loss_grad(tr, per_args)
-                    opt.zero_grad()
-                    agent._backward(net_out, grad)
-                    opt.step(cfg.gradient_clip)
-                self.out = out
-                self.graph = g
-                self.signature = opt.hyper_signature()
-            except Exception as e:
-                _capture_failed(cfg, "the update", e)
-                self.failed = True
-                self.graph = None
-                opt.graph_mode = False
-                g = rp.gather(idx)
-                if per:
-                    dev = g['state'].device
-                    g.update(sampling_prob=torch.from_numpy(prob).to(dev), idx=torch.from_numpy(tree_idx).to(dev))
-                    return agent._learn(rp.TransitionCLS(**{k: v for k, v in g.items() if k in rp.TransitionCLS._fields}),
-                                        beta=float(self.per_words[-1].item()))
-                return agent._learn(rp.TransitionCLS(**{k: v for k, v in g.items() if k in rp.TransitionCLS._fields}))
-        else:
-            rp.gather(idx, out=self.static)
-        opt.prepare_step()
-        self.graph.replay()
-        if per:
-            rp.commit_device(tree_idx, self.out['prio'])      # replay.py:193-196, the priorities stay on the device
-        return self.out
 
 
 class DQNAgent(BaseAgent):
@@ -1160,73 +954,6 @@ def _install_sampler(agent):
     net.sampler = lambda logits: dp.sample(logits.detach())
 
 
-class _OnPolicyGraph:
-    """Replays an on-policy agent's device-side work of one rollout (A2CAgent._rollout_compute: T forwards with action
-    sampling, the return scan, loss, backward, clip, optimizer) from ONE captured hipGraph after two eager rollouts.  The
-    rollout plan lives in persistent device buffers (DeviceAtariVec.plan), so every kernel argument is constant across
-    rollouts; torch's graph-safe Philox bookkeeping continues the sampling generator exactly as the eager kernels would.
-    Data parallel (dist.DataParallel): the captured region ends BEFORE the gradient exchange -- run(plan, compute, tail)
-    replays [rollout + loss + backward] and then calls tail() eagerly (all-reduce of the flat gradient over RCCL / gloo,
-    clip + optimizer step: three launches), so that ranks x environments-per-rank runs at the single-process graph speed.
-    Not used with grad hooks or config.graph_update off."""
-    WARMUP = 2
-
-    def __init__(self, agent, optimizer_inside=True):
-        self.agent = agent
-        self.optimizer_inside = optimizer_inside      # the captured region ends with agent._fused.step()
-        self.calls = 0
-        self.graph = None
-        self.out = None
-        self.key = None
-        self.failed = False
-
-    def usable(self):
-        a = self.agent
-        cfg = a.config
-        return not (self.failed or getattr(cfg, 'graph_update', True) is False or a.grad_hook is not None)
-
-    def run(self, plan, compute, tail=None):
-        """compute(plan): the capturable device work; tail(out) (optional): what must stay eager after it (the data-parallel
-        exchange and the optimizer step behind it) -- called after the eager compute as well as after a replay."""
-        a = self.agent
-        self.calls += 1
-        if not self.usable() or self.calls <= self.WARMUP:
-            out = compute(plan)
-            return out if tail is None else tail(out)
-        opt = a._fused if (self.optimizer_inside and tail is None) else None
-        key = (plan.counters.data_ptr(), plan.t_len, opt.hyper_signature() if opt is not None else None)
-        if self.graph is not None and key != self.key:
-            self.graph = None
-        if self.graph is None:
-            validate = torch.distributions.Distribution._validate_args
-            try:
-                torch.distributions.Distribution.set_default_validate_args(False)   # its checks synchronise with the host
-                if opt is not None:
-                    opt.enable_graph_mode()
-                g = torch.cuda.CUDAGraph()
-                torch.cuda.synchronize()
-                steps = a._rollout_step
-                with _capture(g):
-                    self.out = compute(plan)
-                a._rollout_step = steps       # the capture pass only recorded the work
-                self.graph, self.key = g, key
-            except Exception as e:
-                _capture_failed(a.config, "the rollout", e)
-                self.failed = True
-                self.graph = None
-                if opt is not None:
-                    opt.graph_mode = False
-                out = compute(plan)
-                return out if tail is None else tail(out)
-            finally:
-                torch.distributions.Distribution.set_default_validate_args(validate)
-        if opt is not None:
-            opt.prepare_step()
-        self.graph.replay()
-        a._rollout_step += plan.t_len + (1 if hasattr(a, '_act') else 0)
-        return self.out if tail is None else tail(self.out)
-
-
 def _dp_sync_start(dp, network, *fused):
     """Data parallel: every rank starts from rank 0's parameters, module buffers and optimizer state (only gradients are
     exchanged afterwards, so equal starts stay equal)."""
@@ -1762,7 +1489,7 @@ class PPOAgent(BaseAgent):
         if config.shared_repr:
             self.lr_scheduler = torch.optim.lr_scheduler.LambdaLR(self.opt, lambda step: 1 - step / config.max_steps)
         self._graphed = _GraphedPPO(self)
-        self._rollout_graph = dict(calls=0, graph=None, failed=False)
+        self._rollout_graph = _GraphedAct(self)
         self._rollout_step = 0
         _install_sampler(self)
         self._pixel_rollout = _PixelRollout(self)
@@ -1936,53 +1663,11 @@ class PPOAgent(BaseAgent):
 
     def _act(self, states):
         """The rollout's no-grad forward (PPO_agent.py:35-36, incl. the action sample) -> (prediction dict, the
-        f32 device copy of `states` that PPO_agent.py:41 stores).  After two eager calls it is replayed from a
-        captured hipGraph over a static input buffer: same kernels, same arguments, and torch's graph-safe Philox
-        bookkeeping continues the generator's sequence exactly as the eager sampling kernels would."""
-        g = self._rollout_graph
-        cfg = self.config
-        usable = (g is not None and not g['failed'] and getattr(cfg, 'graph_rollout', getattr(cfg, 'graph_update', True))
-                  and Config.DEVICE.type == 'cuda' and not isinstance(states, torch.Tensor))
-        if usable:
-            x = np.ascontiguousarray(np.asarray(states, dtype=np.float32))    # what tensor() uploads (torch_utils.py:23)
-            g['calls'] += 1
-            if g['calls'] > 2:
-                if g['graph'] is None or g['in'].shape != x.shape:
-                    validate = torch.distributions.Distribution._validate_args
-                    try:
-                        g['upload'] = StagedUpload(x.shape, torch.float32, Config.DEVICE)
-                        g['in'] = g['upload'].dev
-                        torch.distributions.Distribution.set_default_validate_args(False)
-                        graph = torch.cuda.CUDAGraph()
-                        # (a categorical net reads its uniforms from the rollout's one draw: the captured forward reads a static
-                        # row that every replay fills from that draw first)
-                        slots = getattr(self.network, 'rollout_slots', None)
-                        g['u'] = None
-                        if slots is not None and getattr(self.network, 'sampler', None) is None:
-                            g['u'] = torch.zeros(x.shape[0], dtype=torch.float32, device=Config.DEVICE)
-                            slots.pin(g['u'])
-                        torch.cuda.synchronize()
-                        with _capture(graph):
-                            with torch.no_grad():
-                                g['out'] = self.network(g['in'])
-                        g['graph'] = graph
-                    except Exception as e:
-                        _capture_failed(cfg, "the rollout forward", e)
-                        g['failed'] = True
-                    finally:
-                        torch.distributions.Distribution.set_default_validate_args(validate)
-                        if getattr(self.network, 'rollout_slots', None) is not None:
-                            self.network.rollout_slots.pin(None)
-                if not g['failed']:
-                    g['upload'].put(x)
-                    if g['u'] is not None:
-                        u = self.network.rollout_slots.next_uniform()
-                        if u is not None and u.numel() == g['u'].numel():
-                            g['u'].copy_(u)
-                        else:
-                            g['u'].uniform_()
-                    g['graph'].replay()
-                    return {key: v.clone() for key, v in g['out'].items()}, g['in'].clone()
+        f32 device copy of `states` that PPO_agent.py:41 stores): replayed from a captured hipGraph over a static input
+        buffer (graphs._GraphedAct) once that is past its warm-up, eager until then and for device tensors."""
+        graphed = self._rollout_graph(states)
+        if graphed is not None:
+            return graphed
         with torch.no_grad():
             prediction = self.network(states)
         return prediction, tensor(states)
@@ -2075,206 +1760,6 @@ class PPOAgent(BaseAgent):
                 entry = entry_cls(*[x[rows] for x in entries])
                 out3 = self._minibatch(entry, weight=float(len(local)) / float(len(g_idx)))
         self.last_loss = out3
-
-
-class _GraphedPPO:
-    """PPO's optimisation phase (PPO_agent.py:71-99: epochs x minibatches, each a forward, the clip loss, a
-    backward and one or two Adam steps -- 320 tiny updates per rollout at ppo_continuous's sizes) with every
-    full-size minibatch replayed from captured hipGraphs: the rollout's rows live in static buffers, a static
-    index tensor selects the minibatch inside the graph, Adam's step-dependent scalars (and a scheduled lr) reach
-    the kernels through device memory (FusedOptimizer.prepare_step).  shared_repr: one graph (forward, loss,
-    backward, clip, step).  Separate actor / critic optimisers: the KL gate of PPO_agent.py:88-93 needs the
-    forward's result on the host first, so a forward+loss graph runs, the host decides, and one of two update
-    graphs (actor+critic, critic only) -- each recomputing the same forward -- runs.  Same kernels and arguments
-    as the eager path: bit-identical parameters.  First rollout and odd-sized remainder minibatches run eagerly."""
-    WARMUP = 1
-
-    def __init__(self, agent):
-        self.agent = agent
-        self.rollouts = 0
-        self.static = None
-        self.idx = None
-        self.graphs = None
-        self.out3 = None
-        self.failed = False
-        self._up = None
-
-    def usable(self):
-        a = self.agent
-        cfg = a.config
-        if self.failed or getattr(cfg, 'graph_update', True) is False or a.grad_hook is not None or a.dp.active:
-            return False
-        if Config.DEVICE.type != 'cuda':
-            return False
-        opts = [a._fused] if cfg.shared_repr else [a._fused_actor, a._fused_critic]
-        return all(o.kind == 'adam' for o in opts)      # scheduled / stepped scalars travel through device memory
-
-    def _capture(self, entry_cls):
-        a = self.agent
-        cfg = a.config
-        rows = lambda: entry_cls(*ops.gather_rows(list(self.static), self.idx))     # all five fields, one launch
-        opts = [a._fused] if cfg.shared_repr else [a._fused_actor, a._fused_critic]
-        for o in opts:
-            o.enable_graph_mode()
-        validate = torch.distributions.Distribution._validate_args
-        torch.distributions.Distribution.set_default_validate_args(False)   # argument checks synchronise with the host
-        try:
-            torch.cuda.synchronize()
-            if cfg.shared_repr:
-                g = torch.cuda.CUDAGraph()
-                with _capture(g):
-                    self.out3 = a._minibatch(rows(), prepared=True)
-                self.graphs = dict(all=g)
-            else:
-                net = a.network
-                g_fwd, g_both, g_critic = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
-
-                def forward_loss():
-                    e = rows()
-                    p = net(e.state, e.action)
-                    out3, grads = ops.ppo_loss(p['log_pi_a'].detach(), p['entropy'].detach(), p['v'].detach(), e.log_pi_a,
-                                               e.advantage, e.ret, cfg.ppo_ratio_clip, cfg.entropy_weight)
-                    return p, out3, grads
-
-                with _capture(g_fwd):
-                    with torch.no_grad():
-                        _, self.out3, _ = forward_loss()
-                with _capture(g_both):
-                    p, _, (g_lp, g_ent, g_v) = forward_loss()
-                    a._fused_actor.zero_grad()
-                    torch.autograd.backward([p['log_pi_a'], p['entropy']], [g_lp, g_ent])
-                    a._fused_actor.step(None)
-                    a._fused_critic.zero_grad()
-                    p['v'].backward(g_v)
-                    a._fused_critic.step(None)
-                with _capture(g_critic):
-                    p, _, (g_lp, g_ent, g_v) = forward_loss()
-                    a._fused_critic.zero_grad()
-                    p['v'].backward(g_v)
-                    a._fused_critic.step(None)
-                self.graphs = dict(fwd=g_fwd, both=g_both, critic=g_critic)
-        finally:
-            torch.distributions.Distribution.set_default_validate_args(validate)
-
-    def optimize(self, entries):
-        a = self.agent
-        cfg = a.config
-        self.rollouts += 1
-        if self.rollouts <= self.WARMUP:
-            return False
-        entry_cls = entries.__class__
-        mb = cfg.mini_batch_size
-        n = entries.state.size(0)
-        try:
-            if self.static is None or any(s.shape != x.shape for s, x in zip(self.static, entries)):
-                self.static = entry_cls(*[x.clone() for x in entries])
-                self.idx = torch.zeros(mb, dtype=torch.int64, device=entries.state.device)
-                self.graphs = None
-                from .replay import _PinnedUploader
-                self._up = _PinnedUploader(torch.int64, mb, entries.state.device)
-            else:
-                for st, x in zip(self.static, entries):
-                    st.copy_(x)
-            if self.graphs is None:
-                self._capture(entry_cls)
-        except Exception as e:
-            _capture_failed(cfg, "the PPO minibatch update", e)
-            self.failed = True
-            for o in ([a._fused] if cfg.shared_repr else [a._fused_actor, a._fused_critic]):
-                o.graph_mode = False
-            return False
-        if cfg.shared_repr and n % mb == 0 and getattr(cfg, 'graph_ppo_block', True):
-            return self._optimize_block(entry_cls, n, mb)
-        opts = [a._fused] if cfg.shared_repr else None
-        for _ in range(cfg.optimization_epochs):
-            for batch_indices in random_sample(np.arange(n), mb):
-                if len(batch_indices) != mb:          # remainder minibatch: eager, optimisers stay in graph mode
-                    bi = tensor(batch_indices).long()
-                    if cfg.shared_repr:
-                        a._fused.prepare_step()
-                        out3 = a._minibatch(entry_cls(*[x[bi] for x in self.static]), prepared=True)
-                    else:
-                        out3 = self._eager_split(entry_cls(*[x[bi] for x in self.static]))
-                    continue
-                self._up.upload_into(self.idx, np.asarray(batch_indices, dtype=np.int64))
-                if cfg.shared_repr:
-                    a._fused.prepare_step()
-                    self.graphs['all'].replay()
-                else:
-                    self.graphs['fwd'].replay()
-                    if self.out3[2].item() <= 1.5 * cfg.target_kl:
-                        a._fused_actor.prepare_step()
-                        a._fused_critic.prepare_step()
-                        self.graphs['both'].replay()
-                    else:
-                        a._fused_critic.prepare_step()
-                        self.graphs['critic'].replay()
-                out3 = self.out3
-        a.last_loss = out3
-        return True
-
-    def _optimize_block(self, entry_cls, n, mb):
-        """shared_repr with full minibatches only (ppo_pixel: 4 epochs x 4 minibatches of 256): the WHOLE optimisation phase is one
-        captured graph -- minibatch j gathers its rows by row j of one [epochs x n / mb, mb] index block and reads its Adam scalars
-        from row j of one [., 2] block, both uploaded once per rollout -- instead of a graph launch and two uploads per minibatch
-        (32 copies of ~4 us in the stream + 15 launch gaps per agent step: profiles/r05t_kernel_stats_ppo_pixel_8.txt).  The
-        permutations are drawn exactly as the per-minibatch loop draws them; same kernels, same arguments: same parameters."""
-        a = self.agent
-        cfg = a.config
-        k = cfg.optimization_epochs * (n // mb)
-        opt = a._fused
-        try:
-            if getattr(self, 'block', None) is None or self.block['k'] != k or self.block['static'] is not self.static:
-                from .replay import _PinnedUploader
-                idx_all = torch.zeros((k, mb), dtype=torch.int64, device=self.static.state.device)
-                block = opt.enable_block_mode(k)
-                validate = torch.distributions.Distribution._validate_args
-                torch.distributions.Distribution.set_default_validate_args(False)
-                keep = opt._hyper_dev
-                try:
-                    torch.cuda.synchronize()
-                    g = torch.cuda.CUDAGraph()
-                    with _capture(g):
-                        for j in range(k):
-                            opt._hyper_dev = block[j]
-                            out3 = a._minibatch(entry_cls(*ops.gather_rows(list(self.static), idx_all[j])), prepared=True)
-                finally:
-                    opt._hyper_dev = keep
-                    torch.distributions.Distribution.set_default_validate_args(validate)
-                self.block = dict(k=k, static=self.static, idx=idx_all, graph=g, out3=out3,
-                                  up=_PinnedUploader(torch.int64, k * mb, idx_all.device))
-        except Exception as e:
-            _capture_failed(cfg, "the PPO optimisation phase", e)
-            self.failed = True
-            opt.graph_mode = False
-            return False
-        b = self.block
-        batches = []
-        for _ in range(cfg.optimization_epochs):
-            batches += [np.asarray(bi, dtype=np.int64) for bi in random_sample(np.arange(n), mb)]
-        b['up'].upload_into(b['idx'].view(-1), np.concatenate(batches))
-        opt.prepare_steps(k)
-        b['graph'].replay()
-        a.last_loss = b['out3']
-        return True
-
-    def _eager_split(self, entry):
-        """remainder minibatch with separate optimisers in graph mode: same arithmetic as PPOAgent._minibatch."""
-        a = self.agent
-        cfg = a.config
-        p = a.network(entry.state, entry.action)
-        out3, (g_lp, g_ent, g_v) = ops.ppo_loss(p['log_pi_a'].detach(), p['entropy'].detach(), p['v'].detach(), entry.log_pi_a,
-                                                entry.advantage, entry.ret, cfg.ppo_ratio_clip, cfg.entropy_weight)
-        if out3[2].item() <= 1.5 * cfg.target_kl:
-            a._fused_actor.prepare_step()
-            a._fused_actor.zero_grad()
-            torch.autograd.backward([p['log_pi_a'], p['entropy']], [g_lp, g_ent])
-            a._fused_actor.step(None)
-        a._fused_critic.prepare_step()
-        a._fused_critic.zero_grad()
-        p['v'].backward(g_v)
-        a._fused_critic.step(None)
-        return out3
 
 
 # ==================================================================================================== replay-based actor-critic

@@ -15,7 +15,7 @@ from ._lib import lib, stream_ptr
 
 GATES = {F.relu: 1, torch.relu: 1, torch.tanh: 2, F.tanh: 2}      # ops.ACT codes
 
-Plan = namedtuple('Plan', ['counters', 't_len'])      # what _OnPolicyGraph.run reads of a rollout plan
+Plan = namedtuple('Plan', ['counters', 't_len'])      # what graphs._OnPolicyGraph.run reads of a rollout plan
 
 
 def fc_body(body):

@@ -742,7 +742,7 @@ class NoisyLinear(nn.Module):
 
 class _NoiseBlock:
     """The noise vectors of several NoisyLinear layers as views of ONE flat device buffer, refilled by one asynchronous copy from a
-    rotating pinned staging block (an event per slot guards its reuse, as agents._GraphedQ stages observations).  The draws stay
+    rotating pinned staging block (an event per slot guards its reuse, as graphs._GraphedQ stages observations).  The draws stay
     on the host: one normal_ per vector from torch's CPU generator, in the reference's order -- a single draw of the concatenated
     length would not give the same stream.  Static addresses: a captured graph reads whatever the last reset_noise() uploaded."""
     SLOTS = 4

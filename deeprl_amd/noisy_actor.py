@@ -14,7 +14,7 @@ Per agent step the host draws the R x 9 noise vectors (torch's CPU generator, th
 advances the shadow by R transitions, consumes np.random as epsilon_greedy(0, q[1, A]) does, and uploads one small plan; the
 device runs synth_stacks -> normaliser table -> conv1-3 at batch R -> fc4 / value / advantage with per-row noise ->
 dra_rainbow_act_rows -> dra_ring_put_rows, eagerly for the first two agent steps and as one captured graph afterwards.  No D2H
-copy and no synchronisation inside the block.  The update is the agent's own (_GraphedUpdate or the eager _learn).
+copy and no synchronisation inside the block.  The update is the agent's own (graphs._GraphedUpdate or the eager _learn).
 """
 import ctypes
 from collections import namedtuple
@@ -24,6 +24,7 @@ import torch
 
 from . import ops
 from ._lib import lib, stream_ptr
+from .graphs import Region, _fused_noisy
 from .support import Config
 
 MAX_ROWS = 8
@@ -39,7 +40,7 @@ def _env_of(agent):
 
 def why_not(agent):
     """None when `agent` may run its actor and environment on the device, else the first condition that fails, in words."""
-    from .agents import CategoricalDQNAgent, _fused_noisy
+    from .agents import CategoricalDQNAgent
     from .envs import SyntheticAtari
     from .nets import NatureConvBody, NoisyLinear, RainbowNet
     from .normalizers import ImageNormalizer, RescaleNormalizer, SignNormalizer
@@ -135,6 +136,7 @@ class ActorPlan:
 class NoisyActor:
     """The actor block of a Rainbow agent whose environment lives on the device (see the module docstring)."""
     WARMUP = 2
+    graph = property(lambda self: self.region.graph)
 
     def __init__(self, agent, env):
         from .learner import SyntheticEpisodeStream
@@ -164,9 +166,7 @@ class NoisyActor:
         self.stacks = torch.zeros((r, env.history, 84, 84), dtype=torch.uint8, device=dev)
         self.actions = torch.zeros(r, dtype=torch.int64, device=dev)
         self.atoms = agent.atoms.float().contiguous()
-        self.steps = 0
-        self.graph = None
-        self.failed = False
+        self.region = Region("the device-resident noisy actor", cfg, self.WARMUP)
         self.noise = None               # the [R][numel] device block of the last draw_rows()
 
     def _layer(self, x, layer, name, act=None):
@@ -196,32 +196,16 @@ class NoisyActor:
 
     def step(self):
         """One agent step's transitions -> their infos (episodic returns), the ring and the replay's cursor advanced."""
-        from .agents import _capture, _capture_failed
         agent = self.agent
-        cfg = agent.config
         nb = agent.network.noise_block()
         block = self.plan.next()
+        region = self.region
         with torch.no_grad():
-            noise = nb.draw_rows(self.rows)
-            if self.noise is not None and noise.data_ptr() != self.noise.data_ptr():
-                self.graph = None       # (the noise block was rebuilt: Module.to())
-            self.noise = noise
+            self.noise = nb.draw_rows(self.rows)
+            key = self.noise.data_ptr()         # (the noise block moves when it is rebuilt: Module.to())
             self._up.upload_into(self.words, self.plan.pack(block, self._host))
-            self.steps += 1
-            want_graph = getattr(cfg, 'graph_update', True) is not False and not self.failed and self.steps > self.WARMUP
-            if want_graph and self.graph is None:
-                try:
-                    g = torch.cuda.CUDAGraph()
-                    torch.cuda.synchronize()
-                    with _capture(g):
-                        self._device_block()
-                    self.graph = g
-                except Exception as e:
-                    _capture_failed(cfg, "the device-resident noisy actor", e)
-                    self.failed = True
-                    self.graph = None
-            if self.graph is not None:
-                self.graph.replay()
+            if region.due(key) and (region.graph is not None or region.capture(self._device_block, key)):
+                region.replay()
             else:
                 self._device_block()
         self.rp.advance(self.rows)
