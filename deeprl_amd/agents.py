@@ -1251,8 +1251,9 @@ class A2CAgent(BaseAgent):
 
 
 class _TargetRolloutAgent(BaseAgent):
-    """What NStepDQNAgent and OptionCriticAgent share: a target network in a flat buffer of its own and, over synthetic Atari
-    emulators, the device path of a pixel_rollout._TargetRollout."""
+    """What NStepDQNAgent and OptionCriticAgent share: a target network in a flat buffer of its own, over synthetic Atari
+    emulators the device path of a pixel_rollout._TargetRollout, and over device-resident cart-poles the step, episode ring and
+    save / load of their feature entries (each agent brings its mlp_rollout.Rollout and its _feature_learn)."""
 
     def _sync_target(self):
         ops.copy_f32(self._target_flat.flat, self._fused.flat.flat)
@@ -1286,6 +1287,78 @@ class _TargetRolloutAgent(BaseAgent):
         self.last_loss = out['loss']
         self.last_rollout = out
 
+    # -- the feature entries (n_step_dqn_feature, option_critic_feature) over device-resident cart-pole environments: one
+    # mlp_rollout.Rollout (`_feature`, None on every other path) and device_env.EpisodeRing (`_episodes`) --------------------
+    _feature = None
+
+    def close(self):
+        self.drain_episodes()
+        BaseAgent.close(self)
+
+    def eval_episodes(self):
+        self.drain_episodes()
+        return BaseAgent.eval_episodes(self)
+
+    def _feature_state(self):
+        """What `<filename>.envs` holds besides the environments' arrays and the device step counter."""
+        return {}
+
+    def _load_feature_state(self, state):
+        return
+
+    def save(self, filename):
+        """The reference's two files (BaseAgent.py:24-27); on the cart-pole device path also `<filename>.envs`: the environments'
+        arrays (state, counters, episode steps, returns, the episode ring), the device step counter and what the agent carries
+        from rollout to rollout (_feature_state), so that a loaded run continues bit for bit."""
+        self.drain_episodes()
+        BaseAgent.save(self, filename)
+        if self._feature is not None:
+            torch.cuda.current_stream().synchronize()
+            with open(filename + '.envs', 'wb') as f:
+                pickle.dump(dict(self._episodes.state_dict(), step=int(self._feature.step_dev.item()), **self._feature_state()), f)
+
+    def load(self, filename):
+        BaseAgent.load(self, filename)
+        if self._feature is not None and os.path.isfile(filename + '.envs'):
+            with open(filename + '.envs', 'rb') as f:
+                state = pickle.load(f)
+            self._episodes.load_state_dict(state)
+            self._feature.step_dev.fill_(int(state['step']))
+            self._load_feature_state(state)
+
+    _dev_steps = property(lambda self: self._episodes.steps)      # (agent steps on the device path)
+    _step_host = property(lambda self: self._episodes.stamp)      # (the host's copy of the kernel's step counter)
+    def drain_episodes(self):
+        """EpisodeRing.drain: logs the episodes that ended on the device since the last drain -> their (step, return) pairs."""
+        return self._episodes.drain()
+
+    def episodes(self):
+        """EpisodeRing.episodes: (step, episodic return) of the training episodes that ended since the previous call."""
+        return self._episodes.episodes()
+
+    def _step_feature(self):
+        """step() over device_env.DeviceCartPoleVec: the host makes the rollout's draws in the reference's order and stages them
+        (the rollout's prepare()); the rollout is ONE launch (dra_q_mlp_rollout / dra_oc_mlp_rollout), the update with its
+        backward a second one (config.fused_nstep_update / fused_oc_update False: the module path on the same buffers), then the
+        fused clip + optimizer step -- after _OnPolicyGraph.WARMUP eager steps all replayed from one captured graph (a single
+        stream, no parallel branches).  The target copy of NStepDQN_agent.py:48-50 / OptionCritic_agent.py:83-85 runs before the
+        launch when a step of this rollout reaches target_network_update_freq: the parameters do not change inside a rollout
+        (_step_device)."""
+        from .mlp_rollout import Plan
+        config = self.config
+        t_len, n = int(config.rollout_length), config.num_workers
+        self._feature.prepare(t_len)
+        self._episodes.begin(t_len)
+        freq, sync = config.target_network_update_freq, False
+        for _ in range(t_len):
+            self.total_steps += n
+            if freq is not None and self.total_steps // n % freq == 0:
+                sync = True
+        if sync:
+            self._sync_target()
+        self.last_loss = self._dev_graph.run(Plan(self.task.env_counter, t_len), self._feature_learn)
+        self._episodes.end()
+
 
 class NStepDQNAgent(_TargetRolloutAgent):
     """NStepDQN_agent.py:12-67: on-policy n-step Q-learning; returns via the scan kernel (use_gae off)."""
@@ -1315,66 +1388,6 @@ class NStepDQNAgent(_TargetRolloutAgent):
     def _adopt_feature(self):
         from . import mlp_rollout, q_mlp
         return mlp_rollout.adopt(self, q_mlp.Rollout)
-
-    def close(self):
-        self.drain_episodes()
-        BaseAgent.close(self)
-
-    def eval_episodes(self):
-        self.drain_episodes()
-        return BaseAgent.eval_episodes(self)
-
-    def save(self, filename):
-        """The reference's two files (BaseAgent.py:24-27); on the cart-pole device path also `<filename>.envs`: the environments'
-        arrays (state, counters, episode steps, returns, the episode ring) and the device step counter, so that a loaded run
-        continues bit for bit."""
-        self.drain_episodes()
-        BaseAgent.save(self, filename)
-        if self._feature is not None:
-            torch.cuda.current_stream().synchronize()
-            with open(filename + '.envs', 'wb') as f:
-                pickle.dump(dict(self._episodes.state_dict(), step=int(self._feature.step_dev.item())), f)
-
-    def load(self, filename):
-        BaseAgent.load(self, filename)
-        if self._feature is not None and os.path.isfile(filename + '.envs'):
-            with open(filename + '.envs', 'rb') as f:
-                state = pickle.load(f)
-            self._episodes.load_state_dict(state)
-            self._feature.step_dev.fill_(int(state['step']))
-
-    # -- n_step_dqn_feature over device-resident cart-pole environments: device_env.EpisodeRing ------------------------------
-    _dev_steps = property(lambda self: self._episodes.steps)      # (agent steps on the device path)
-    _step_host = property(lambda self: self._episodes.stamp)      # (the host's copy of the kernel's step counter)
-    def drain_episodes(self):
-        """EpisodeRing.drain: logs the episodes that ended on the device since the last drain -> their (step, return) pairs."""
-        return self._episodes.drain()
-
-    def episodes(self):
-        """EpisodeRing.episodes: (step, episodic return) of the training episodes that ended since the previous call."""
-        return self._episodes.episodes()
-
-    def _step_feature(self):
-        """step() over device_env.DeviceCartPoleVec: the host makes the rollout's exploration draws in the reference's order and
-        stages them; NStepDQN_agent.py:31-57 is ONE launch (dra_q_mlp_rollout), :58-65 with the backward a second one
-        (dra_q_mlp_update; config.fused_nstep_update False: the module path on the same buffers), then the fused clip + optimizer
-        step -- after _OnPolicyGraph.WARMUP eager steps all replayed from one captured graph (a single stream, no parallel
-        branches).  The target copy of NStepDQN_agent.py:48-50 runs before the launch when a step of this rollout reaches
-        target_network_update_freq: the parameters do not change inside a rollout (_TargetRolloutAgent._step_device)."""
-        from .mlp_rollout import Plan
-        config = self.config
-        t_len, n = int(config.rollout_length), config.num_workers
-        self._feature.prepare(t_len)
-        self._episodes.begin(t_len)
-        freq, sync = config.target_network_update_freq, False
-        for _ in range(t_len):
-            self.total_steps += n
-            if freq is not None and self.total_steps // n % freq == 0:
-                sync = True
-        if sync:
-            self._sync_target()
-        self.last_loss = self._dev_graph.run(Plan(self.task.env_counter, t_len), self._feature_learn)
-        self._episodes.end()
 
     def _feature_learn(self, plan):
         config = self.config
@@ -1945,7 +1958,10 @@ class OptionCriticAgent(_TargetRolloutAgent):
     (q over options, termination beta, intra-option policies), an epsilon-soft option choice that keeps the previous
     option unless it terminates, an action from the chosen option's policy; per rollout: returns bootstrapped from the
     target network, three losses (option values, intra-option policy, termination) through ONE backward and the fused
-    clip + optimizer step.  Draw order of the three Categorical samples per step is the reference's."""
+    clip + optimizer step.  Draw order of the three Categorical samples per step is the reference's.
+    option_critic_feature (examples.py:450-468) with config.fused_oc_feature = True runs on device-resident cart-poles instead
+    (_step_feature over oc_mlp.Rollout: one rollout launch, one update launch); options and actions then come from uniforms
+    staged per rollout by inverse CDF, not from Categorical.sample()'s own stream (oc_mlp's docstring)."""
 
     def __init__(self, config):
         BaseAgent.__init__(self, config)
@@ -1963,13 +1979,73 @@ class OptionCriticAgent(_TargetRolloutAgent):
         self.grad_hook = None
         self._rollout_step = 0
         self._oc_rollout = _OCRollout(self)
+        self._episodes = EpisodeRing(self, 0, config.num_workers)     # (the feature kernel's step counter: one stamp per rollout step)
         if self._adopt_device(self._oc_rollout):    # synthetic Atari emulators + OptionCriticNet(NatureConvBody): the rollout lives on the device
             self.states = self.task.reset()
             self.prev_options, self.is_initial_states = self._oc_rollout.state(config.num_workers)
             return
         self.states = config.state_normalizer(self.task.reset())
+        # option_critic_feature, examples.py:450-468 (opt-in, config.fused_oc_feature): cart-poles under OptionCriticNet over a small
+        # FCBody live on the device, one launch per rollout and one per update (csrc/oc_mlp.hip)
+        self._feature = self._adopt_feature()       # (the environments move as reset() left them)
+        if self._feature is not None:
+            self.prev_options, self.is_initial_states = self._feature.state(config.num_workers)
+            return
         self.is_initial_states = torch.ones(config.num_workers, dtype=torch.bool, device=Config.DEVICE)
         self.prev_options = torch.ones(config.num_workers, dtype=torch.int64, device=Config.DEVICE)
+
+    def _adopt_feature(self):
+        from . import mlp_rollout, oc_mlp
+        return mlp_rollout.adopt(self, oc_mlp.Rollout)
+
+    def _feature_state(self):
+        return dict(prev_option=self.prev_options.cpu().numpy().copy(), is_initial=self.is_initial_states.cpu().numpy().copy())
+
+    def _load_feature_state(self, state):
+        self.prev_options.copy_(torch.from_numpy(np.asarray(state['prev_option'])))
+        self.is_initial_states.copy_(torch.from_numpy(np.asarray(state['is_initial'])))
+
+    def _feature_learn(self, plan):
+        """OptionCritic_agent.py:55-116 on the device: the rollout launch, then the update launch (config.fused_oc_update False:
+        the module path on the rollout's buffers -- returns by the scan kernel, the detached terms from the stored q, one batched
+        forward, the three losses in torch, autograd), then the fused clip + optimizer step.  -> the total loss [1];
+        `last_losses` [4] = (total, q_loss, pi_loss, beta_loss)."""
+        config = self.config
+        rollout = self._feature
+        b = rollout.run(plan.t_len)
+        self._rollout_step += plan.t_len
+        if getattr(config, 'fused_oc_update', True) is not False:
+            losses = rollout.update(b, config)
+        else:
+            t_len, n = b['action'].shape
+            rows = t_len * n
+            value = torch.zeros((t_len + 1, n, 1), device=b['reward'].device)
+            value[t_len] = b['bootstrap'].view(n, 1)
+            _, rets = ops.gae(b['reward'].view(t_len, n, 1), b['mask'].view(t_len, n, 1), value, config.discount, 1.0, False)
+            ret = rets.view(rows, 1)
+            q_s = b['q'].view(rows, -1)
+            option, prev, action = b['option'].view(rows, 1), b['prev_option'].view(rows, 1), b['action'].view(rows, 1)
+            eps = rollout.eps.view(t_len, 1).expand(t_len, n).reshape(rows, 1)
+            adv = ret - q_s.gather(1, option)
+            v = q_s.max(dim=-1, keepdim=True)[0] * (1 - eps) + q_s.mean(-1).unsqueeze(-1) * eps
+            beta_adv = q_s.gather(1, prev) - v + config.termination_regularizer
+            b['ret'].copy_(ret.view(t_len, n))
+            b['adv'].copy_(adv.view(t_len, n))
+            b['beta_adv'].copy_(beta_adv.view(t_len, n))
+            pred = self.network(b['state'].view(rows, -1))
+            rows_i = torch.arange(rows, device=option.device)
+            log_pi, pi = pred['log_pi'][rows_i, option.view(-1)], pred['pi'][rows_i, option.view(-1)]
+            entropy = -(pi * log_pi).sum(-1, keepdim=True)      # (Categorical.entropy without its argument checks: no sync)
+            q_loss = (pred['q'].gather(1, option) - ret).pow(2).mul(0.5).mean()
+            pi_loss = (-(log_pi.gather(1, action) * adv) - config.entropy_weight * entropy).mean()
+            beta_loss = (pred['beta'].gather(1, prev) * beta_adv * (1 - b['init'].view(rows, 1))).mean()
+            total = pi_loss + q_loss + beta_loss
+            self._fused.zero_grad()
+            total.backward()
+            losses = torch.stack([total.detach(), q_loss.detach(), pi_loss.detach(), beta_loss.detach()])
+        self._fused.step(config.gradient_clip)
+        self.last_losses = losses
+        return losses[:1]
 
     def sample_option(self, prediction, epsilon, prev_option, is_initial):
         with torch.no_grad():
@@ -1986,6 +2062,8 @@ class OptionCriticAgent(_TargetRolloutAgent):
             return torch.where(is_initial, fresh, continued)
 
     def step(self):
+        if self._feature is not None:
+            return self._step_feature()
         if getattr(self.task, 'on_device', False):
             return self._step_device()
         config = self.config

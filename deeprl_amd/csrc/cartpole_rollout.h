@@ -1,18 +1,20 @@
 // What the one-workgroup rollout kernels over device-resident cart-poles share (cat_mlp.hip: a2c_feature, q_mlp.hip:
-// n_step_dqn_feature), stated ONCE:
+// n_step_dqn_feature, oc_mlp.hip: option_critic_feature), stated ONCE:
 //
 //   CartPoleLanes    the environments in the registers of wave 0 (lane e = environment e) for the whole launch: load, observe,
 //                    advance (cartpole_step, the action / reward / mask row), append (the episode ring: an ending episode's
 //                    position is the rank of its lane in the wave's ballot, so rows land in (step, environment) order) and
 //                    store.  A ring row is (stamp, environment id, episodic return): the kernel says what the stamp counts
-//                    (cat_mlp: sampler steps, T + 1 per rollout; q_mlp: its step counter, T per rollout) and how its lanes
-//                    are numbered (cat_mlp: env0 + lane, q_mlp: lane).
+//                    (cat_mlp: sampler steps, T + 1 per rollout; q_mlp and oc_mlp: their step counter, T per rollout) and how
+//                    its lanes are numbered (cat_mlp: env0 + lane, q_mlp and oc_mlp: lane).
 //   BodyWeights<H>   the two-layer body's W1^T, W2^T, b1, b2 in LDS and their staging from a flat parameter buffer.
 //   the host checks  cartpole_mlp_supported, offsets_nonnegative, cartpole_io_ok, and the hidden x gate dispatch.
 //
-// Each kernel keeps its action choice (Gumbel-max / staged epsilon-greedy), its heads and which counter it advances.  What runs
-// inside the step loop is written for the register allocator (the figures): observe() takes plain pointers and
-// scalars; cat_mlp calls advance inside the block of its choice, q_mlp step() with the choice made in a block of its own.
+// Each kernel keeps its action choice (Gumbel-max / staged epsilon-greedy / option-critic's two inverse-CDF draws with the carried
+// prev_option and is_initial), its heads and which counter it advances.  What runs inside the step loop is written for the
+// register allocator (the figures): observe() takes plain pointers and scalars; cat_mlp calls advance inside the
+// block of its choice, q_mlp step() with the choice made in a block of its own, oc_mlp advance and append behind its decision
+// block (the next step's is_initial is the `done` advance returns).
 #pragma once
 #include "cartpole_env.h"
 #include "mlp_rollout.h"

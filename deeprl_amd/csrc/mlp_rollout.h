@@ -1,6 +1,6 @@
-// What the one-workgroup rollout kernels over small MLPs share (a2c_mlp.hip, cat_mlp.hip, q_mlp.hip): gate codes, row rounding,
-// one hidden layer over TRANSPOSED activations and the launch; ppo_mlp.hip and dpg_mlp.hip take the vector type, the gate codes
-// and softplus_f.  The two cart-pole kernels (cat_mlp.hip, q_mlp.hip) share more in cartpole_rollout.h: the environment lanes
+// What the one-workgroup rollout kernels over small MLPs share (a2c_mlp.hip, cat_mlp.hip, q_mlp.hip, oc_mlp.hip): gate codes, row
+// rounding, one hidden layer over TRANSPOSED activations and the launch; ppo_mlp.hip and dpg_mlp.hip take the vector type, the gate
+// codes and softplus_f.  The three cart-pole kernels (cat_mlp.hip, q_mlp.hip, oc_mlp.hip) share more in cartpole_rollout.h: the environment lanes
 // (load, observe, step with the episode-ring append, store), the staging of a two-layer body's weights (BodyWeights<H>), the
 // shape / offset / io checks and the hidden x gate dispatch.
 //
@@ -9,6 +9,7 @@
 // the cart-pole pair above, at equal VGPRs / scratch / occupancy and SGPR spills at or below the text in place.  NOT shared:
 //   q_mlp_update_kernel's weight staging (through BodyWeights<H> its VGPRs go 71 -> 78 at H 16 tanh, occupancy 7 -> 6);
 //   q_mlp.hip's block_layer (folded into hidden_layer, q_mlp_update_kernel<16, tanh> goes from 71 to 77 VGPRs, 7 -> 6 waves);
+//   oc_mlp.hip's update restates that staging and block_layer for the same reason (its figures: DESIGN.md 4.14);
 //   the heads' dot products: each kernel has its own outputs per thread.
 #pragma once
 #include "common.h"

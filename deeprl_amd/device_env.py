@@ -311,16 +311,17 @@ class DeviceContinuousVec(_RolloutVec):
 
 class DeviceCartPoleVec(_RolloutVec):
     """The envs.CartPole environments of a Task, resident on the device (a2c_feature, examples.py:340-358, under A2CAgent;
-    n_step_dqn_feature, examples.py:408-424, under NStepDQNAgent): fp64 state, total step counters, episode steps and running
-    returns live in HBM and one launch (dra_cat_mlp_rollout / dra_q_mlp_rollout) walks a whole rollout -- forward, action,
+    n_step_dqn_feature, examples.py:408-424, under NStepDQNAgent; option_critic_feature, examples.py:450-468, under
+    OptionCriticAgent): fp64 state, total step counters, episode steps and running returns live in HBM and one launch
+    (dra_cat_mlp_rollout / dra_q_mlp_rollout / dra_oc_mlp_rollout) walks a whole rollout -- forward, action,
     environment step -- without a host round trip.  Same arithmetic as envs.CartPole stepped from python (csrc/cartpole_env.h;
     the two agents' GPU tests compare the two).  `buffers(t_len, n, zeros)`: what the kernel leaves besides state and action.
 
     The terminals depend on the actions, so the host cannot shadow them (DeviceContinuousVec.shadow has no counterpart here).
     Episode ends are REPORTED by the device instead: the rollout kernel (csrc/cartpole_rollout.h) appends one row (its stamp
-    of the end -- A2C: the sampler step, n-step DQN: its step counter --, global environment, episodic return) per finished
+    of the end -- A2C: the sampler step, n-step DQN and option-critic: their step counter --, global environment, episodic return) per finished
     episode to `ep_ring` [RING_CAP][3] and counts them in `ep_count`; `drain()` is one device-to-host copy (EpisodeRing)."""
-    DRIVER = "A2CAgent / NStepDQNAgent"
+    DRIVER = "A2CAgent / NStepDQNAgent / OptionCriticAgent"
     RING_CAP = 4096
     HOST_NOTE = 'the cart-pole environments stay on the host and this agent keeps the module path: %s'
 
@@ -359,7 +360,7 @@ class DeviceCartPoleVec(_RolloutVec):
                     **self._more_buffers(t_len, n, f))
 
     def fill_io(self, io, agent, t_len):
-        """_RolloutVec.fill_io and the episode bookkeeping's fields (cat_mlp.RolloutIO, q_mlp.RolloutIO)."""
+        """_RolloutVec.fill_io and the episode bookkeeping's fields (cat_mlp.RolloutIO, q_mlp.RolloutIO, oc_mlp.RolloutIO)."""
         b = _RolloutVec.fill_io(self, io, agent, t_len)
         io.ep_steps, io.ep_return = self.ep_steps.data_ptr(), self.ep_return.data_ptr()
         io.ep_count, io.ep_ring, io.ring_cap = self.ep_count.data_ptr(), self.ep_ring.data_ptr(), self.ring_cap

@@ -1,7 +1,7 @@
 """What the host sides of the small-MLP kernels share (a2c_mlp.py, cat_mlp.py, ppo_mlp.py, dpg_mlp.py): the gate codes, the ONE
 check that a body is a two-layer FCBody the kernels walk and that a head is a plain Linear, the agent-side conditions of a
 device rollout (`why_not`), the ONE way an agent takes such a rollout up (`adopt`) and the `Rollout` base of a2c_mlp.Rollout /
-cat_mlp.Rollout / q_mlp.Rollout: the kernel's two structs over the agent's ONE flat parameter buffer and its device-resident
+cat_mlp.Rollout / q_mlp.Rollout / oc_mlp.Rollout: the kernel's two structs over the agent's ONE flat parameter buffer and its device-resident
 environments, one launch per rollout.
 There is no CPU / eager implementation here: without the HIP library every call raises.
 """

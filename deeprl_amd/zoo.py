@@ -124,6 +124,15 @@ ZOO = {
         network=lambda c: N.VanillaNet(c.action_dim, N.NatureConvBody()),
         fields=dict(discount=0.99, target_network_update_freq=10000, rollout_length=5, gradient_clip=5, max_steps=int(2e7)),
         eps=(1.0, 0.05, 1e6), normalizers=(ImageNormalizer, SignNormalizer)),
+    # examples.py:450-468 (fused_oc_feature=True moves the cart-poles, the option choice and the update onto the device: csrc/oc_mlp.hip)
+    "option_critic_feature": dict(
+        agent="OptionCriticAgent", kw=dict(log_level=0), pre_fields=dict(num_workers=5),
+        task=lambda c: Task(c.game, num_envs=c.num_workers), eval_task=lambda c: Task(c.game),
+        optimizer=_rmsprop(lr=0.001),
+        network=lambda c: N.OptionCriticNet(N.FCBody(c.state_dim), c.action_dim, num_options=2),
+        fields=dict(discount=0.99, target_network_update_freq=200, rollout_length=5, termination_regularizer=0.01,
+                    entropy_weight=0.01, gradient_clip=5),
+        option_eps=(1.0, 0.1, 1e4)),
     # examples.py:471-492
     "option_critic_pixel": dict(
         agent="OptionCriticAgent", kw=dict(log_level=0), pre_fields=dict(num_workers=16),

@@ -1104,6 +1104,98 @@ int dra_q_mlp_update_supported(int state_dim, int n_actions, int hidden, int row
 int dra_q_mlp_rollout(const dra_q_mlp_net* net, const dra_q_mlp_rollout_io* io, void* stream);
 int dra_q_mlp_update(const dra_q_mlp_net* net, const dra_q_mlp_update_io* io, void* stream);
 
+/* ---- oc_mlp: option_critic_feature (examples.py:450-468, OptionCritic_agent.py:11-119) over device-resident cart-pole
+ * environments.  OptionCriticNet(FCBody(state_dim), action_dim, num_options): a two-layer FCBody of one width (relu or tanh)
+ * under three plain biased heads, fc_q [O][hidden], fc_pi [O * A][hidden] (row o * A + a: action a of option o) and fc_beta
+ * [O][hidden] (network_heads.py:105-127).  The online and the target network live in two flat buffers of EQUAL layout.
+ * state_dim 4, 2 actions, hidden in {16, 32, 64}, 2 <= n_options <= 8 (one option is refused: the reference's initial
+ * prev_options = ones, OptionCritic_agent.py:26, is out of range there). */
+typedef struct dra_oc_mlp_net {
+  const float* param;                /* the optimiser's flat parameter buffer (device): the ONLINE network; read only */
+  const float* target;               /* the TARGET network's flat buffer, same offsets; read only (the update does not read it) */
+  int32_t w1, b1, w2, b2;            /* body.layers[0..1]: float offsets into param / target (and the flat gradient buffer) */
+  int32_t wq, bq;                    /* fc_q [n_options][hidden], [n_options] */
+  int32_t wp, bp;                    /* fc_pi [n_options * n_actions][hidden], [n_options * n_actions] */
+  int32_t wb, bb;                    /* fc_beta [n_options][hidden], [n_options] */
+  int32_t gate;                      /* 1 relu, 2 tanh */
+  int32_t state_dim, n_actions, hidden, n_options;
+} dra_oc_mlp_net;
+/* OptionCritic_agent.py:55-93 in ONE launch of one workgroup: for t < t_len [observation narrowed to float32 and stored, body,
+ * q, beta = sigmoid(.) and the intra-option logits of the ONLINE network, sample_option (OptionCritic_agent.py:29-49) with
+ * eps[t]: g = the FIRST maximum of q, pi_opt = eps / O with 1 - eps + eps / O at g, pi_hat = (1 - beta) 1[o == prev] + beta
+ * pi_opt, option = is_initial ? invCDF(pi_opt, uniform[t][e][0]) : invCDF(pi_hat, uniform[t][e][1]) (each row divided by its sum
+ * first, as Categorical(probs=) does), action / log pi(a) / entropy from the chosen option's logits by inverse CDF at
+ * uniform[t][e][2], environment step, reward * reward_coef, mask = 1 - done, prev_option <- option, is_initial <- done, and for
+ * every episode that ended one appended row of ep_ring], then from the TARGET network's q and beta on the last observation
+ * bootstrap[e] = (1 - beta[prev]) q[prev] + beta[prev] max q with prev the option of step t_len - 1.  No parameter is written.
+ * prev_option / is_initial are read at the start (values outside [0, n_options) are clamped) and replaced at the end;
+ * *step_counter advances by t_len; ep_ring as in dra_q_mlp_rollout.  n_env <= 64. */
+typedef struct dra_oc_mlp_rollout_io {
+  double* env_state;            /* [n_env][4] (in/out) */
+  int64_t* env_counter;         /* [n_env] (in/out) */
+  int32_t* ep_steps;            /* [n_env] (in/out) */
+  double* ep_return;            /* [n_env] (in/out) */
+  const int64_t* env_seed;      /* [n_env] */
+  int64_t* step_counter;        /* [1] (in/out) */
+  int64_t* ep_count;            /* [1] (in/out) */
+  double* ep_ring;              /* [ring_cap][3] */
+  const float* eps;             /* [t_len]: random_option_prob of each step */
+  const float* uniform;         /* [t_len][n_env][3]: fresh option, continued option, action */
+  int64_t* prev_option;         /* [n_env] (in/out) */
+  uint8_t* is_initial;          /* [n_env] (in/out) */
+  float* out_state;             /* [t_len][n_env][4] */
+  float* out_q;                 /* [t_len][n_env][n_options] */
+  float* out_beta;              /* [t_len][n_env][n_options] */
+  float* out_logits;            /* [t_len][n_env][2]: the chosen option's */
+  int64_t* out_option;          /* [t_len][n_env] */
+  int64_t* out_prev_option;     /* [t_len][n_env]: what the step read */
+  int64_t* out_action;          /* [t_len][n_env] */
+  float* out_init;              /* [t_len][n_env]: what the step read, 0 / 1 */
+  float* out_log_pi_a;          /* [t_len][n_env] */
+  float* out_entropy;           /* [t_len][n_env] */
+  float* out_reward;            /* [t_len][n_env] */
+  float* out_mask;              /* [t_len][n_env] */
+  float* bootstrap;             /* [n_env] */
+  int64_t horizon, ring_cap;
+  double reward_coef;
+  int32_t t_len, n_env;
+} dra_oc_mlp_rollout_io;
+/* OptionCritic_agent.py:95-116 and the whole backward in ONE launch of one workgroup: ret[t][e] = reward + (discount * mask) *
+ * ret backwards from bootstrap (fp32, the reference's operation order), adv = ret - q[option], v = max q (1 - eps_t) + mean q
+ * eps_t, beta_adv = q[prev_option] - v + termination_regularizer -- all from the rollout's STORED q / beta / logits --, the body
+ * recomputed from the stored states with the ONLINE parameters, and the gradient of pi_loss + q_loss + beta_loss (q_loss = mean
+ * 0.5 (q[option] - ret)^2, pi_loss = mean (-log pi(a) adv - entropy_weight entropy), beta_loss = mean beta[prev_option] beta_adv
+ * (1 - init)) with respect to w1 b1 w2 b2 wq bq wp bp wb bb, written (every element, nothing between the tensors) into `grad`
+ * at the parameters' offsets.  Fixed summation order, no atomics.  loss [4] = (total, q_loss, pi_loss, beta_loss).
+ * rows = t_len * n_env <= 1024 (dra_oc_mlp_update_supported). */
+typedef struct dra_oc_mlp_update_io {
+  const float* state;           /* [t_len][n_env][4] */
+  const float* q;               /* [t_len][n_env][n_options] */
+  const float* beta;            /* [t_len][n_env][n_options] */
+  const float* logits;          /* [t_len][n_env][2] */
+  const int64_t* option;        /* [t_len][n_env] */
+  const int64_t* prev_option;   /* [t_len][n_env] */
+  const int64_t* action;        /* [t_len][n_env] */
+  const float* init;            /* [t_len][n_env] */
+  const float* log_pi_a;        /* [t_len][n_env] */
+  const float* entropy;         /* [t_len][n_env] */
+  const float* reward;          /* [t_len][n_env] */
+  const float* mask;            /* [t_len][n_env] */
+  const float* bootstrap;       /* [n_env] */
+  const float* eps;             /* [t_len] */
+  float* grad;                  /* the flat gradient buffer (device) */
+  float* out_ret;               /* [t_len][n_env] */
+  float* out_adv;               /* [t_len][n_env] */
+  float* out_beta_adv;          /* [t_len][n_env] */
+  float* out_loss;              /* [4] */
+  double discount, termination_regularizer, entropy_weight;
+  int32_t t_len, n_env;
+} dra_oc_mlp_update_io;
+int dra_oc_mlp_supported(int state_dim, int n_actions, int hidden, int n_env, int gate, int n_options);         /* the rollout; 0 = yes */
+int dra_oc_mlp_update_supported(int state_dim, int n_actions, int hidden, int rows, int gate, int n_options);   /* the update; 0 = yes */
+int dra_oc_mlp_rollout(const dra_oc_mlp_net* net, const dra_oc_mlp_rollout_io* io, void* stream);
+int dra_oc_mlp_update(const dra_oc_mlp_net* net, const dra_oc_mlp_update_io* io, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -18,6 +18,8 @@ after a warm-up.  Prints one JSON object per line: agent steps/s, env steps/s, g
             n_step_dqn_pixel examples.py:427-447 (16 workers), option_critic_pixel examples.py:471-492 (16 workers)
             n_step_dqn_feature examples.py:408-424 (5 workers, classic-CartPole-v0, config.fused_nstep_feature True;
             `_module_update` = config.fused_nstep_update False; `_host` = the switch off: python environments)
+            option_critic_feature examples.py:450-468 (5 workers, classic-CartPole-v0, config.fused_oc_feature True;
+            `_module_update` = config.fused_oc_update False; `_host` = the switch off: python environments)
   ddpg_continuous examples.py:554-583, td3_continuous examples.py:587-617 (one host environment, (400, 300) relu MLPs, Adam 1e-3,
             minibatch 100, a 1M ring; warm_up shortened to 1000 so that the timed window is all updates; the default is
             config.fused_dpg_update True: csrc/dpg_mlp.hip; `_modules` = the switch off: torch modules and optimisers)
@@ -210,6 +212,20 @@ def option_critic_pixel(workers=16, device=True, **switches):
     return d.OptionCriticAgent(c), dict(env_per_step=5 * workers, updates_per_step=1)
 
 
+def option_critic_feature(workers=5, **switches):
+    c = d.Config()
+    c.merge(dict(game="classic-CartPole-v0", log_level=0, tag="bench", **switches))
+    c.num_workers = workers
+    c.task_fn = lambda: d.Task(c.game, num_envs=c.num_workers, seed=1)
+    c.eval_env = d.Task(c.game, seed=2)
+    c.optimizer_fn = lambda p: torch.optim.RMSprop(p, 0.001)
+    c.network_fn = lambda: d.OptionCriticNet(d.FCBody(c.state_dim), c.action_dim, num_options=2)
+    c.random_option_prob = d.LinearSchedule(1.0, 0.1, 1e4)
+    c.discount, c.target_network_update_freq, c.rollout_length, c.gradient_clip = 0.99, 200, 5, 5
+    c.termination_regularizer, c.entropy_weight = 0.01, 0.01
+    return d.OptionCriticAgent(c), dict(env_per_step=5 * workers, updates_per_step=1)
+
+
 def ppo_continuous(workers=1, device=True, fused=True):
     c = d.Config()
     c.merge(dict(game="synthetic-continuous-HalfCheetah", log_level=0, tag="bench", device_env=device, fused_ppo_mlp=fused))
@@ -287,6 +303,10 @@ CASES = {
     "n_step_dqn_feature": lambda: n_step_dqn_feature(5, fused_nstep_feature=True),
     "n_step_dqn_feature_module_update": lambda: n_step_dqn_feature(5, fused_nstep_feature=True, fused_nstep_update=False),
     "n_step_dqn_feature_host": lambda: n_step_dqn_feature(5),   # 5 python cart-poles stepped one by one, one module forward per step
+    # device-resident cart-poles, one rollout and one update launch (csrc/oc_mlp.hip) + one captured graph
+    "option_critic_feature": lambda: option_critic_feature(5, fused_oc_feature=True),
+    "option_critic_feature_module_update": lambda: option_critic_feature(5, fused_oc_feature=True, fused_oc_update=False),
+    "option_critic_feature_host": lambda: option_critic_feature(5),   # 5 python cart-poles, one module forward and three draws per step
     "ppo_continuous_1": lambda: ppo_continuous(1),
     "ppo_continuous_16": lambda: ppo_continuous(16),                                  # device environments + persistent kernels
     "ppo_continuous_16_host": lambda: ppo_continuous(16, device=False),               # host environments, persistent update kernel
