@@ -238,6 +238,7 @@ class DQNActor(BaseActor):
 class DQNAgent(BaseAgent):
     """DQN_agent.py:48-138."""
     ActorCLS = DQNActor
+    _feature = None     # dqn_mlp.Step on the cart-pole device path (config.fused_dqn_feature), None on every other path
 
     def __init__(self, config):
         BaseAgent.__init__(self, config)
@@ -270,6 +271,12 @@ class DQNAgent(BaseAgent):
         if env is not None:
             self._attach_device_pipeline(env)
         self._noisy_actor = self._device_noisy_actor()
+        # dqn_feature, examples.py:11-52 (opt-in, config.fused_dqn_feature): the cart-pole and the replay's feed live on the device,
+        # one launch per agent step's transitions and one per update (csrc/dqn_mlp.hip); dqn_mlp.Step, None on every other path
+        self._feature = None
+        if getattr(config, 'fused_dqn_feature', False) is True:
+            from . import dqn_mlp
+            self._feature = dqn_mlp.adopt(self)
 
     def _device_noisy_actor(self):
         """noisy_actor.NoisyActor when `config.device_noisy_actor` is on and the agent is eligible (Rainbow over one synthetic
@@ -464,14 +471,25 @@ class DQNAgent(BaseAgent):
         pass
 
     def save(self, filename):
+        """The reference's two files (BaseAgent.py:24-27); on the cart-pole device path (config.fused_dqn_feature) also
+        `<filename>.envs`: the environment's arrays, the episode ring and the device step counter, so that a loaded run -- together
+        with the replay's own save_full / load_full -- continues bit for bit."""
         if self._learner is not None:     # updates run asynchronously on the learner's streams
             self._learner.synchronize()
+        if self._feature is not None:
+            self._feature.drain()
         BaseAgent.save(self, filename)
+        if self._feature is not None:
+            with open(filename + '.envs', 'wb') as f:
+                pickle.dump(self._feature.state_dict(), f)
 
     def load(self, filename):
         if self._learner is not None:
             self._learner.synchronize()
         BaseAgent.load(self, filename)
+        if self._feature is not None and os.path.isfile(filename + '.envs'):
+            with open(filename + '.envs', 'rb') as f:
+                self._feature.load_state_dict(pickle.load(f))
         if self._learner is not None:     # parameters changed behind the learner: actor copies are stale
             torch.cuda.synchronize()
             self._learner.invalidate_actor_copy()
@@ -557,9 +575,23 @@ class DQNAgent(BaseAgent):
 
     def eval_episodes(self):
         self.sync_host()
+        self.drain_episodes()
         return super().eval_episodes()
 
+    def drain_episodes(self):
+        """EpisodeRing.drain on the cart-pole device path: logs the episodes that ended on the device since the last drain -> their
+        (step, return) pairs; nothing on every other path."""
+        return self._feature.drain() if getattr(self, '_feature', None) is not None else []
+
+    def episodes(self):
+        """EpisodeRing.episodes: (step, episodic return) of the training episodes that ended since the previous call."""
+        if getattr(self, '_feature', None) is None:
+            return []
+        self._feature.check()
+        return self._feature.episodes.episodes()
+
     def close(self):
+        self.drain_episodes()
         if getattr(self, '_learner', None) is not None:
             self.sync_host()
             self._learner.synchronize()
@@ -671,6 +703,8 @@ class DQNAgent(BaseAgent):
                                       "lr needs config.fused_learner = False (generic path)")
         if self._pipe is not None:
             return self._step_device()
+        if self._feature is not None:   # dqn_mlp.Step: the transitions, the feed and the update without a host round trip
+            return self._feature.step()
         if self._noisy_actor is not None:
             return self._step_noisy_device()
         if self._learner is not None:   # ring feeds, actor forwards and updates share the learner's stream

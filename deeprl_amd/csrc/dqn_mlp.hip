@@ -1,0 +1,495 @@
+// dqn_mlp: dqn_feature (examples.py:11-52: DQNAgent over one cart-pole, VanillaNet over FCBody(state_dim), RMSprop, a uniform replay
+// of 10^4 transitions, minibatches of 10, four transitions per update, a target network copied every 200 updates) with the
+// environment (cartpole_env.h) and the replay ring (ring.hip's four arrays) resident on the device.
+//
+//   dqn_mlp_act_kernel      DQN_agent.py:23-45, sgd_update_frequency times, as ONE launch of one workgroup: the observation narrowed
+//                           to float32 (what tensor() uploads), the body (4 -> H -> H, relu or tanh), q, the epsilon-greedy action
+//                           -- the draws are made by the host ahead of the launch, in the reference's order, and read from fixed
+//                           addresses --, the environment step, and the transition written straight into the ring at
+//                           (*slot0 + k) % capacity; one appended row of the episode ring per episode that ended.
+//   dqn_mlp_update_kernel   DQN_agent.py:81-99, 128-133 and the whole backward as ONE launch of one workgroup: the minibatch gathered
+//                           from the ring by the staged indices (state = frame idx, next state = frame idx + 1), the TARGET
+//                           network's (double_q: and the online network's) forward of the next states, q_target, the online
+//                           forward of the states, 0.5 mean (q_target - q_a)^2 and its gradient with respect to all six tensors,
+//                           written into the optimiser's flat gradient buffer at the parameters' own offsets.
+//
+// Both are q_mlp.hip's kernels with the replay between them: latency-bound chains over a few rows, plain fp32 VALU code, weights in
+// LDS once per launch, activations TRANSPOSED and read 16 bytes at a time, every dot product one FMA chain in ascending k.  The
+// update walks the rows in blocks of 64; every gradient element is owned by ONE thread that adds its rows in ascending order:
+// no atomics, the same bits on every launch.  Weights<H>, gate_back and block_layer are q_mlp.hip's, COPIED (DESIGN.md 4.15:
+// lifting them into a header is a change of its own; mlp_rollout.h's banner says what sharing them has cost before).
+#include "common.h"
+#include "cartpole_rollout.h"
+#include <math.h>
+
+namespace {
+
+// ---------------------------------------------------------------------------------------------------- acting
+constexpr int kMaxK = 8;         // transitions of one launch
+constexpr int kNP = 8;           // row stride of the single environment's transposed activations (hidden_layer's row block)
+
+// one network's weights in LDS, in floats; every region starts at a multiple of 4 floats (16 bytes)
+__host__ __device__ constexpr size_t weight_floats(int H) {
+  return body_weight_floats(H) + round_up4(kA * (H + 1)) + 4;
+}
+__host__ __device__ constexpr size_t act_lds_floats(int H) {
+  return weight_floats(H) + 4 + (size_t)kS * kNP + 2 * (size_t)H * kNP;      // the weights, q [A], x^T [S][NP], h1^T, h2^T [H][NP]
+}
+
+template <int H>
+struct Weights {
+  BodyWeights<H> body;
+  float *wq, *bq;                           // the head [A][H + 1], its bias
+  __device__ explicit Weights(float* base) : body(base), wq(base + body_weight_floats(H)), bq(wq + round_up4(kA * (H + 1))) {}
+  __device__ __forceinline__ void stage(const float* __restrict__ P, const dra_q_mlp_net& net, int tid) const {
+    body.stage(P, net, tid);
+    for (int i = tid; i < kA * H; i += 256) {
+      const int c = i / H, k = i - c * H;
+      wq[c * (H + 1) + k] = P[net.wq + c * H + k];
+    }
+    if (tid < kA) bq[tid] = P[net.bq + tid];
+  }
+};
+
+// what CartPoleLanes::append reads of a row: the episode ring alone (the transition itself goes to the replay ring)
+struct EpisodeRow {
+  int64_t* out_action = nullptr;
+  float *out_reward = nullptr, *out_mask = nullptr;
+  double* ep_ring;
+  int64_t horizon, ring_cap;
+  int n_env = 1;
+};
+
+template <int H, int GATE>
+__global__ void __launch_bounds__(256)
+dqn_mlp_act_kernel(dra_q_mlp_net net, dra_dqn_mlp_act_io io) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  const int tid = threadIdx.x;
+  const int K = io.t_len;
+
+  const Weights<H> online(lds);
+  float* sQ = lds + weight_floats(H);                 // [A] (+ pad)
+  float* sXT = sQ + 4;                                // [S][NP]
+  float* sH1T = sXT + kS * kNP;                       // [H][NP]
+  float* sH2T = sH1T + H * kNP;                       // [H][NP]
+  const int act_floats = 4 + kS * kNP + 2 * H * kNP;
+  for (int i = tid; i < act_floats; i += 256) sQ[i] = 0.f;      // (rows 1..7 of x^T stay zero: one environment)
+  const int64_t t0 = *io.step_counter;                // (rewritten by thread 0 behind the last barrier)
+  const int64_t cap = io.capacity;
+  int64_t slot0 = *io.slot0;
+  const bool bad_slot = slot0 < 0 || slot0 >= cap;
+  if (bad_slot) slot0 = 0;
+  online.stage(net.param, net, tid);
+  __syncthreads();                                    // (thread 0 writes x^T next, over what other threads zeroed)
+
+  CartPoleLanes lanes;                               // lane 0 of wave 0 carries the environment
+  lanes.load(io, tid);
+  EpisodeRow ep;
+  ep.ep_ring = io.ep_ring;
+  ep.horizon = io.horizon;
+  ep.ring_cap = io.ring_cap;
+  const CartPoleRow row(ep);
+  const double reward = 1.0 * io.reward_coef;         // what config.reward_normalizer(1.0) feeds
+
+  for (int k = 0; k < K; ++k) {
+    if (tid == 0) {
+      sXT[0 * kNP] = (float)lanes.st.x;
+      sXT[1 * kNP] = (float)lanes.st.xd;
+      sXT[2 * kNP] = (float)lanes.st.th;
+      sXT[3 * kNP] = (float)lanes.st.thd;
+    }
+    __syncthreads();
+    hidden_layer<H, GATE, 256>(sXT, online.body.w1, online.body.b1, sH1T, kS, kNP, tid);
+    __syncthreads();
+    hidden_layer<H, GATE, 256>(sH1T, online.body.w2, online.body.b2, sH2T, H, kNP, tid);
+    __syncthreads();
+    if (tid < kA) {
+      const float* wr = online.wq + tid * (H + 1);
+      float acc = 0.f;
+#pragma unroll 8
+      for (int j = 0; j < H; ++j) acc = fmaf(sH2T[j * kNP], wr[j], acc);
+      acc += online.bq[tid];
+      sQ[tid] = acc;
+      io.out_q[k * kA + tid] = acc;
+    }
+    __syncthreads();
+    // ---- epsilon-greedy action (torch_utils.py:51-58 with the draws made ahead), the ring row, environment step: wave 0
+    if (tid < 64) {
+      bool done = false;
+      double ended = 0.0;
+      if (tid == 0) {
+        int arg = sQ[1] > sQ[0] ? 1 : 0;                          // np.argmax: the first maximum
+        if (io.explore[k]) arg = io.random_action[k] == 1 ? 1 : 0;
+        const int64_t slot = (slot0 + k) % cap;
+        double* frame = io.ring_frames + slot * kS;               // the observation the action was chosen on
+        frame[0] = lanes.st.x;
+        frame[1] = lanes.st.xd;
+        frame[2] = lanes.st.th;
+        frame[3] = lanes.st.thd;
+        done = cartpole_step(lanes.st, lanes.counter, lanes.ep_steps, lanes.ep_return, lanes.seed, arg, io.horizon, ended);
+        io.ring_actions[slot] = arg;
+        io.ring_rewards[slot] = reward;
+        io.ring_masks[slot] = done ? 0 : 1;
+        io.out_action[k] = arg;
+      }
+      lanes.append(row, done, ended, t0 + k, 0, tid);
+    }
+    // (thread 0 writes the next observation into x^T next: layer 1 of this step, its only reader, is three barriers back; q is
+    // rewritten behind the three barriers of the next step)
+  }
+  __syncthreads();
+  lanes.store(io, tid);
+  if (tid == 0) {
+    *io.step_counter = t0 + K;
+    if (bad_slot) *io.err = *io.err + 1;
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------- the update
+constexpr int kUB = 64;          // rows of one block
+constexpr int kLD = kUB + 4;     // row stride of the transposed activations: 16-byte aligned, consecutive units 4 banks apart
+constexpr int kMaxB = 256;       // rows of one minibatch
+
+__host__ __device__ constexpr size_t update_lds_floats(int H) {
+  return (size_t)kS * H + 2 * (size_t)H * H + 2 * (size_t)H + (size_t)kA * H + 4      // online: W1^T, W2^T, W2, b1, b2, head, its bias
+         + (size_t)kS * H + (size_t)H * H + 2 * (size_t)H + (size_t)kA * H + 4        // target: W1^T, W2^T, b1, b2, head, its bias
+         + 6 * kUB + 4 * kUB                                                          // idx, reward, mask, d, action, loss; the two q_next
+         + (size_t)kS * kLD + 3 * (size_t)H * kLD;                                    // x^T, h1^T, h2^T (later dz1^T), dz2^T
+}
+
+template <int GATE>
+__device__ __forceinline__ float gate_back(float g, float h) {       // g * gate'(pre-activation), from the stored post-activation h
+  if constexpr (GATE == kGateRelu) return h > 0.f ? g : 0.f;
+  else return g * (1.f - h * h);
+}
+
+// hidden_layer (mlp_rollout.h) over one block of kUB rows with the row stride kLD.  BACK false: out = gate(b + in W); BACK true
+// (b unused): out = (in W) * gate'(post), post^T the stored post-activations.
+template <int H, int GATE, bool BACK>
+__device__ __forceinline__ void block_layer(const float* __restrict__ inT, const float* __restrict__ wT, const float* __restrict__ b,
+                                            const float* __restrict__ postT, float* __restrict__ outT, int K, int tid) {
+  constexpr int G = 256 / H;
+  const int u = tid & (H - 1), rg = tid / H;
+  const float bias = BACK ? 0.f : b[u];
+  for (int e0 = rg * kRB; e0 < kUB; e0 += G * kRB) {
+    float acc[kRB];
+#pragma unroll
+    for (int r = 0; r < kRB; ++r) acc[r] = 0.f;
+#pragma unroll 4
+    for (int k = 0; k < K; ++k) {
+      const float w = wT[k * H + u];
+      const f32x4 x0 = *reinterpret_cast<const f32x4*>(&inT[k * kLD + e0]);
+      const f32x4 x1 = *reinterpret_cast<const f32x4*>(&inT[k * kLD + e0 + 4]);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        acc[r] = fmaf(x0[r], w, acc[r]);
+        acc[4 + r] = fmaf(x1[r], w, acc[4 + r]);
+      }
+    }
+    f32x4 y0, y1;
+    if constexpr (BACK) {
+      const f32x4 p0 = *reinterpret_cast<const f32x4*>(&postT[u * kLD + e0]);
+      const f32x4 p1 = *reinterpret_cast<const f32x4*>(&postT[u * kLD + e0 + 4]);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        y0[r] = gate_back<GATE>(acc[r], p0[r]);
+        y1[r] = gate_back<GATE>(acc[4 + r], p1[r]);
+      }
+    } else {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        y0[r] = gate_f<GATE>(acc[r] + bias);
+        y1[r] = gate_f<GATE>(acc[4 + r] + bias);
+      }
+    }
+    *reinterpret_cast<f32x4*>(&outT[u * kLD + e0]) = y0;
+    *reinterpret_cast<f32x4*>(&outT[u * kLD + e0 + 4]) = y1;
+  }
+}
+
+// x^T of a block from the ring's fp64 frames at sIdx[row] + shift (256 threads: 64 rows x 4), zero behind the last row
+__device__ __forceinline__ void gather_states(const double* __restrict__ frames, const int* __restrict__ sIdx, int shift, int rows,
+                                              float* __restrict__ sXT, int tid) {
+  const int row = tid / kS, j = tid % kS;
+  sXT[j * kLD + row] = row < rows ? (float)frames[((int64_t)sIdx[row] + shift) * kS + j] : 0.f;
+}
+
+// q [A][kUB] of one block from h2^T: one output per thread, tid < A * kUB
+template <int H>
+__device__ __forceinline__ void block_head(const float* __restrict__ sH2T, const float* __restrict__ wq, const float* __restrict__ bq,
+                                           float* __restrict__ out, int tid) {
+  if (tid < kA * kUB) {
+    const int a = tid / kUB, r = tid % kUB;
+    const float* wr = wq + a * H;
+    float acc = 0.f;
+#pragma unroll 8
+    for (int k = 0; k < H; ++k) acc = fmaf(sH2T[k * kLD + r], wr[k], acc);
+    out[tid] = acc + bq[a];
+  }
+}
+
+template <int H, int GATE>
+__global__ void __launch_bounds__(256)
+dqn_mlp_update_kernel(dra_q_mlp_net net, dra_dqn_mlp_update_io io) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  constexpr int TPU = 256 / H;       // threads that share one unit's row of dW2
+  constexpr int KPT = H / TPU;       // columns of it each carries
+  const int tid = threadIdx.x;
+  const int B = io.batch;
+  const float* __restrict__ P = net.param;
+  const float* __restrict__ PT = net.target;
+
+  float* sW1 = lds;                       // [S][H]  (transposed: [k][unit])
+  float* sW2 = sW1 + kS * H;              // [H][H]  (transposed)
+  float* sW2N = sW2 + H * H;              // [H][H]  (as stored, [unit][k]: the backward's "transposed" operand)
+  float* sB1 = sW2N + H * H;              // [H]
+  float* sB2 = sB1 + H;                   // [H]
+  float* sWq = sB2 + H;                   // [A][H]
+  float* sBq = sWq + kA * H;              // [A] (+ pad)
+  float* tW1 = sBq + 4;                   // the target network's, as above without the untransposed W2
+  float* tW2 = tW1 + kS * H;
+  float* tB1 = tW2 + H * H;
+  float* tB2 = tB1 + H;
+  float* tWq = tB2 + H;
+  float* tBq = tWq + kA * H;
+  int* sIdx = reinterpret_cast<int*>(tBq + 4);       // [kUB]: the block's ring slots, clamped
+  float* sRew = reinterpret_cast<float*>(sIdx + kUB);      // [kUB]
+  float* sMsk = sRew + kUB;               // [kUB]
+  float* sD = sMsk + kUB;                 // [kUB]: (q_a - q_target) / B of the block's rows, 0 behind the last row
+  int* sAct = reinterpret_cast<int*>(sD + kUB);      // [kUB]
+  float* sRed = sD + 2 * kUB;             // [kUB]: the loss partials
+  float* sQN = sRed + kUB;                // [A][kUB]: the target network's q of the next states
+  float* sQO = sQN + kA * kUB;            // [A][kUB]: the online network's (double_q)
+  float* sXT = sQO + kA * kUB;            // [S][kLD]
+  float* sH1T = sXT + kS * kLD;           // [H][kLD]
+  float* sH2T = sH1T + H * kLD;           // [H][kLD]: h2^T, then dz1^T
+  float* sG2T = sH2T + H * kLD;           // [H][kLD]: dz2^T
+
+  for (int i = tid; i < kS * H; i += 256) {
+    const int k = i / H, u = i - k * H;
+    sW1[i] = P[net.w1 + u * kS + k];
+    tW1[i] = PT[net.w1 + u * kS + k];
+  }
+  for (int i = tid; i < H * H; i += 256) {
+    const int k = i / H, u = i - k * H;
+    sW2[i] = P[net.w2 + u * H + k];
+    sW2N[i] = P[net.w2 + i];
+    tW2[i] = PT[net.w2 + u * H + k];
+  }
+  for (int i = tid; i < H; i += 256) {
+    sB1[i] = P[net.b1 + i];
+    sB2[i] = P[net.b2 + i];
+    tB1[i] = PT[net.b1 + i];
+    tB2[i] = PT[net.b2 + i];
+  }
+  for (int i = tid; i < kA * H; i += 256) {
+    sWq[i] = P[net.wq + i];
+    tWq[i] = PT[net.wq + i];
+  }
+  if (tid < kA) {
+    sBq[tid] = P[net.bq + tid];
+    tBq[tid] = PT[net.bq + tid];
+  }
+  const float gamma = (float)io.discount;
+  const int64_t last = io.capacity - 2;      // the last slot with a next frame behind it
+  const bool double_q = io.double_q != 0;
+  int n_bad = 0;
+
+  // what this thread owns of the gradient
+  const int u2 = tid / TPU, k2 = (tid % TPU) * KPT;       // dW2 [u2][k2 .. k2 + KPT), db2 [u2] on the first of the unit's threads
+  float gW2[KPT], gB2 = 0.f;
+#pragma unroll
+  for (int i = 0; i < KPT; ++i) gW2[i] = 0.f;
+  const int u1 = tid / kS, j1 = tid % kS;                 // dW1 [u1][j1] (tid < S H), db1 [u1] where j1 == 0
+  float gW1 = 0.f, gB1 = 0.f;
+  const int aq = tid / H, kq = tid % H;                   // dWq [aq][kq] (tid < A H); dbq [tid - A H] on the two threads behind
+  float gWq = 0.f, gBq = 0.f;
+  float loss = 0.f;
+  const float inv_rows = 1.f / (float)B;
+
+  for (int r0 = 0; r0 < B; r0 += kUB) {
+    const int rows = B - r0 < kUB ? B - r0 : kUB;
+    // ---- the block's ring slots (clamped into [0, capacity - 2]: no read leaves the ring), reward, mask, action
+    if (tid < kUB) {
+      int64_t i = 0;
+      bool bad = false;
+      float rew = 0.f, msk = 0.f;
+      int a = 0;
+      if (tid < rows) {
+        i = io.idx[r0 + tid];
+        bad = i < 0 || i > last;
+        i = i < 0 ? 0 : (i > last ? last : i);
+        rew = (float)io.ring_rewards[i];
+        msk = (float)io.ring_masks[i];
+        a = io.ring_actions[i] == 1 ? 1 : 0;
+      }
+      n_bad += __popcll(__ballot(bad ? 1 : 0));
+      sIdx[tid] = (int)i;
+      sRew[tid] = rew;
+      sMsk[tid] = msk;
+      sAct[tid] = a;
+    }
+    __syncthreads();
+    // ---- the next states: the TARGET network's q, and with double_q the online network's
+    gather_states(io.ring_frames, sIdx, 1, rows, sXT, tid);
+    __syncthreads();
+    block_layer<H, GATE, false>(sXT, tW1, tB1, nullptr, sH1T, kS, tid);
+    __syncthreads();
+    block_layer<H, GATE, false>(sH1T, tW2, tB2, nullptr, sH2T, H, tid);
+    __syncthreads();
+    block_head<H>(sH2T, tWq, tBq, sQN, tid);
+    if (double_q) {
+      __syncthreads();
+      block_layer<H, GATE, false>(sXT, sW1, sB1, nullptr, sH1T, kS, tid);
+      __syncthreads();
+      block_layer<H, GATE, false>(sH1T, sW2, sB2, nullptr, sH2T, H, tid);
+      __syncthreads();
+      block_head<H>(sH2T, sWq, sBq, sQO, tid);
+    }
+    __syncthreads();
+    // ---- q_target = r + ((gamma q_next) m) (DQN_agent.py:94), kept by the row's thread
+    float tgt = 0.f;
+    if (tid < rows) {
+      const float qn0 = sQN[tid], qn1 = sQN[kUB + tid];
+      float qn;
+      if (double_q) qn = sQO[kUB + tid] > sQO[tid] ? qn1 : qn0;        // torch.argmax: the first maximum
+      else qn = fmaxf(qn0, qn1);
+      tgt = __fadd_rn(sRew[tid], __fmul_rn(__fmul_rn(gamma, qn), sMsk[tid]));
+      io.out_q_target[r0 + tid] = tgt;
+    }
+    // ---- the states: the online forward (x^T's and h^T's readers are behind the barrier above)
+    gather_states(io.ring_frames, sIdx, 0, rows, sXT, tid);
+    __syncthreads();
+    block_layer<H, GATE, false>(sXT, sW1, sB1, nullptr, sH1T, kS, tid);
+    __syncthreads();
+    block_layer<H, GATE, false>(sH1T, sW2, sB2, nullptr, sH2T, H, tid);
+    __syncthreads();
+    // ---- q of the action taken, dq = (q_a - q_target) / B, the loss
+    if (tid < kUB) {
+      float d = 0.f;
+      if (tid < rows) {
+        const int a = sAct[tid];
+        const float* wr = sWq + a * H;
+        float acc = 0.f;
+#pragma unroll 8
+        for (int k = 0; k < H; ++k) acc = fmaf(sH2T[k * kLD + tid], wr[k], acc);
+        const float diff = (acc + sBq[a]) - tgt;
+        io.out_td[r0 + tid] = -diff;
+        loss = fmaf(diff, diff, loss);
+        d = diff * inv_rows;
+      }
+      sD[tid] = d;
+    }
+    __syncthreads();
+    // ---- dz2 = dq wq[a] gate'(h2); the head's gradient
+    for (int i = tid; i < H * kUB; i += 256) {
+      const int k = i / kUB, r = i % kUB;
+      sG2T[k * kLD + r] = gate_back<GATE>(sD[r] * sWq[sAct[r] * H + k], sH2T[k * kLD + r]);
+    }
+    if (tid < kA * H) {
+#pragma unroll 1
+      for (int r = 0; r < kUB; r += 4) {
+        const f32x4 h = *reinterpret_cast<const f32x4*>(&sH2T[kq * kLD + r]);
+#pragma unroll
+        for (int c = 0; c < 4; ++c) gWq = fmaf(sAct[r + c] == aq ? sD[r + c] : 0.f, h[c], gWq);
+      }
+    } else if (tid < kA * H + kA) {
+#pragma unroll 1
+      for (int r = 0; r < kUB; ++r) gBq += sAct[r] == tid - kA * H ? sD[r] : 0.f;
+    }
+    __syncthreads();
+    // ---- dW2 += dz2 h1^T, db2 += dz2; dz1 = (dz2 W2) gate'(h1) into h2^T's place (its readers are behind the barrier)
+#pragma unroll 1
+    for (int r = 0; r < kUB; r += 4) {
+      const f32x4 dz = *reinterpret_cast<const f32x4*>(&sG2T[u2 * kLD + r]);
+#pragma unroll
+      for (int i = 0; i < KPT; ++i) {
+        const f32x4 h = *reinterpret_cast<const f32x4*>(&sH1T[(k2 + i) * kLD + r]);
+#pragma unroll
+        for (int c = 0; c < 4; ++c) gW2[i] = fmaf(dz[c], h[c], gW2[i]);
+      }
+      if (k2 == 0) {
+#pragma unroll
+        for (int c = 0; c < 4; ++c) gB2 += dz[c];
+      }
+    }
+    block_layer<H, GATE, true>(sG2T, sW2N, nullptr, sH1T, sH2T, H, tid);
+    __syncthreads();
+    // ---- dW1 += dz1 x^T, db1 += dz1
+    if (tid < kS * H) {
+#pragma unroll 1
+      for (int r = 0; r < kUB; r += 4) {
+        const f32x4 dz = *reinterpret_cast<const f32x4*>(&sH2T[u1 * kLD + r]);
+        const f32x4 x = *reinterpret_cast<const f32x4*>(&sXT[j1 * kLD + r]);
+#pragma unroll
+        for (int c = 0; c < 4; ++c) gW1 = fmaf(dz[c], x[c], gW1);
+        if (j1 == 0) {
+#pragma unroll
+          for (int c = 0; c < 4; ++c) gB1 += dz[c];
+        }
+      }
+    }
+    __syncthreads();       // (the next block rewrites the slots, x^T and h2^T)
+  }
+
+  // ---- every element of the six tensors, nothing between them
+  float* __restrict__ Gd = io.grad;
+#pragma unroll
+  for (int i = 0; i < KPT; ++i) Gd[net.w2 + u2 * H + k2 + i] = gW2[i];
+  if (k2 == 0) Gd[net.b2 + u2] = gB2;
+  if (tid < kS * H) {
+    Gd[net.w1 + tid] = gW1;
+    if (j1 == 0) Gd[net.b1 + u1] = gB1;
+  }
+  if (tid < kA * H) Gd[net.wq + tid] = gWq;
+  else if (tid < kA * H + kA) Gd[net.bq + tid - kA * H] = gBq;
+  if (tid < kUB) sRed[tid] = loss;
+  __syncthreads();
+  if (tid == 0) {
+    float s = 0.f;
+    for (int i = 0; i < kUB; ++i) s += sRed[i];
+    io.out_loss[0] = 0.5f * (s * inv_rows);
+    if (n_bad) *io.err = *io.err + n_bad;
+  }
+}
+
+bool offsets_ok(const dra_q_mlp_net* net) { return offsets_nonnegative({net->w1, net->b1, net->w2, net->b2, net->wq, net->bq}); }
+
+}  // namespace
+
+DRA_API int dra_dqn_mlp_supported(int state_dim, int n_actions, int hidden, int t_len, int gate) {
+  if (cartpole_mlp_supported(state_dim, n_actions, hidden, 1, gate)) return DRA_EINVAL;
+  return t_len < 1 || t_len > kMaxK ? DRA_EINVAL : DRA_OK;
+}
+
+DRA_API int dra_dqn_mlp_update_supported(int state_dim, int n_actions, int hidden, int batch, int gate) {
+  if (cartpole_mlp_supported(state_dim, n_actions, hidden, 1, gate)) return DRA_EINVAL;
+  return batch < 1 || batch > kMaxB ? DRA_EINVAL : DRA_OK;
+}
+
+DRA_API int dra_dqn_mlp_act(const dra_q_mlp_net* net, const dra_dqn_mlp_act_io* io, void* stream) {
+  if (!net || !io || !net->param) return DRA_EINVAL;
+  if (io->n_env != 1 || dra_dqn_mlp_supported(net->state_dim, net->n_actions, net->hidden, io->t_len, net->gate)) return DRA_EINVAL;
+  if (!offsets_ok(net) || io->horizon < 1 || io->ring_cap < 1 || io->capacity < 1) return DRA_EINVAL;
+  if (!io->env_state || !io->env_counter || !io->ep_steps || !io->ep_return || !io->env_seed || !io->step_counter || !io->ep_count ||
+      !io->ep_ring || !io->explore || !io->random_action || !io->slot0 || !io->ring_frames || !io->ring_actions ||
+      !io->ring_rewards || !io->ring_masks || !io->out_q || !io->out_action || !io->err)
+    return DRA_EINVAL;
+  return dispatch_hidden_gate(net->hidden, net->gate, [&](auto h, auto g) {
+    constexpr int H = decltype(h)::value, GATE = decltype(g)::value;
+    return launch_one_workgroup<&dqn_mlp_act_kernel<H, GATE>>(act_lds_floats(H) * sizeof(float), net, io, stream);
+  });
+}
+
+DRA_API int dra_dqn_mlp_update(const dra_q_mlp_net* net, const dra_dqn_mlp_update_io* io, void* stream) {
+  if (!net || !io || !net->param || !net->target) return DRA_EINVAL;
+  if (dra_dqn_mlp_update_supported(net->state_dim, net->n_actions, net->hidden, io->batch, net->gate)) return DRA_EINVAL;
+  if (!offsets_ok(net) || io->capacity < 2 || io->capacity > 0x7fffffff) return DRA_EINVAL;
+  if (!io->ring_frames || !io->ring_actions || !io->ring_rewards || !io->ring_masks || !io->idx || !io->grad || !io->out_q_target ||
+      !io->out_td || !io->out_loss || !io->err)
+    return DRA_EINVAL;
+  return dispatch_hidden_gate(net->hidden, net->gate, [&](auto h, auto g) {
+    constexpr int H = decltype(h)::value, GATE = decltype(g)::value;
+    return launch_one_workgroup<&dqn_mlp_update_kernel<H, GATE>>(update_lds_floats(H) * sizeof(float), net, io, stream);
+  });
+}

@@ -1,0 +1,316 @@
+"""Host side of csrc/dqn_mlp.hip: dqn_feature (examples.py:11-52) over ONE device-resident cart-pole environment and the HBM
+replay ring.
+
+`shape(network)` is q_mlp's (VanillaNet over a two-layer FCBody of one width with a relu or tanh gate and a plain biased
+fc_head); `why_not(agent)` names the first condition that keeps a DQNAgent on its host path; `Step(agent, shape)` is the agent
+step without a host round trip (DQN_agent.py:101-138): the host makes the draws in the reference's order
+(support.plan_actor_epsilon_greedy, then UniformReplay.advance / draw_indices) and stages them in ONE block at fixed addresses,
+dra_dqn_mlp_act runs the sgd_update_frequency transitions and appends them to the ring, dra_dqn_mlp_update gathers the minibatch
+and writes the gradient into the optimiser's flat buffer (config.fused_dqn_update False: ring.gather and the modules on the
+same indices), then the fused clip + optimizer step -- after WARMUP eager steps replayed from captured graphs (graphs.Region:
+acting alone while total_steps <= exploration_steps, acting + update + clip / step afterwards; single streams, no parallel
+branches).  The target copy runs eagerly between replays.  There is no CPU / eager-PyTorch implementation here: without the HIP
+library every call raises.
+"""
+import ctypes
+
+import numpy as np
+import torch
+
+from ._lib import DraError, lib, stream_ptr
+from .device_env import DeviceCartPoleVec, _RolloutVec
+from .graphs import Region
+from .q_mlp import Net, _fields, shape      # noqa: F401  (the net struct is dra_q_mlp_net as it is)
+from .support import Config, StagedUpload, plan_actor_epsilon_greedy
+
+SWITCH = 'fused_dqn_feature'
+NETWORK = "VanillaNet over a two-layer relu / tanh FCBody with a plain head"
+MAX_K, MAX_B = 8, 256
+
+
+class ActIO(ctypes.Structure):
+    """Mirror of dra_dqn_mlp_act_io (include/deeprl_amd.h)."""
+    _fields_ = [("env_state", ctypes.c_void_p), ("env_counter", ctypes.c_void_p), ("ep_steps", ctypes.c_void_p),
+                ("ep_return", ctypes.c_void_p), ("env_seed", ctypes.c_void_p), ("step_counter", ctypes.c_void_p),
+                ("ep_count", ctypes.c_void_p), ("ep_ring", ctypes.c_void_p),
+                ("explore", ctypes.c_void_p), ("random_action", ctypes.c_void_p), ("slot0", ctypes.c_void_p),
+                ("ring_frames", ctypes.c_void_p), ("ring_actions", ctypes.c_void_p), ("ring_rewards", ctypes.c_void_p),
+                ("ring_masks", ctypes.c_void_p), ("out_q", ctypes.c_void_p), ("out_action", ctypes.c_void_p),
+                ("err", ctypes.c_void_p),
+                ("horizon", ctypes.c_int64), ("ring_cap", ctypes.c_int64), ("capacity", ctypes.c_int64),
+                ("reward_coef", ctypes.c_double), ("t_len", ctypes.c_int32), ("n_env", ctypes.c_int32)]
+
+
+class UpdateIO(ctypes.Structure):
+    """Mirror of dra_dqn_mlp_update_io."""
+    _fields_ = [("ring_frames", ctypes.c_void_p), ("ring_actions", ctypes.c_void_p), ("ring_rewards", ctypes.c_void_p),
+                ("ring_masks", ctypes.c_void_p), ("idx", ctypes.c_void_p), ("grad", ctypes.c_void_p),
+                ("out_q_target", ctypes.c_void_p), ("out_td", ctypes.c_void_p), ("out_loss", ctypes.c_void_p),
+                ("err", ctypes.c_void_p), ("capacity", ctypes.c_int64), ("discount", ctypes.c_double),
+                ("batch", ctypes.c_int32), ("double_q", ctypes.c_int32)]
+
+
+def supported(state_dim, n_actions, hidden, t_len, gate):
+    """dra_dqn_mlp_supported: the shapes (t_len = transitions per launch) the acting kernel is built for."""
+    return lib.dra_dqn_mlp_supported.raw(int(state_dim), int(n_actions), int(hidden), int(t_len), int(gate)) == 0
+
+
+def update_supported(state_dim, n_actions, hidden, batch, gate):
+    """dra_dqn_mlp_update_supported: the shapes the update kernel is built for."""
+    return lib.dra_dqn_mlp_update_supported.raw(int(state_dim), int(n_actions), int(hidden), int(batch), int(gate)) == 0
+
+
+def _plain_optimizer(opt):
+    """One parameter group under torch's RMSprop or Adam without momentum, weight decay, amsgrad or maximize."""
+    if len(opt.param_groups) != 1:
+        return False
+    g = opt.param_groups[0]
+    if g.get('weight_decay', 0) != 0 or g.get('maximize', False):
+        return False
+    if isinstance(opt, torch.optim.RMSprop):
+        return g.get('momentum', 0) == 0
+    return type(opt) is torch.optim.Adam and not g.get('amsgrad', False)
+
+
+def _fresh_cartpole(agent):
+    """The one envs.CartPole of the actor's Task when nobody has stepped it, else None and the reason."""
+    from .envs import CartPole
+    task = getattr(agent.actor, '_task', None)
+    envs = _RolloutVec._host_envs(task, agent.config)
+    if envs is None or len(envs) != 1 or type(envs[0]) is not CartPole:
+        return None, "the task is not one envs.CartPole environment, or there is no device"
+    env = envs[0]
+    if agent.actor._state is not None or env.c != 0 or env.steps != 0 or isinstance(env.s, str):
+        return None, "the environment has already been stepped on the host"
+    return env, None
+
+
+def why_not(agent, supported_fn=supported, update_supported_fn=update_supported):
+    """None when DQNAgent may run `agent` on the kernels, else the first reason it may not."""
+    from .normalizers import RescaleNormalizer
+    from .replay import PrioritizedReplay, UniformReplay
+    cfg = agent.config
+    if getattr(cfg, SWITCH, False) is not True:
+        return "config.%s is not on" % SWITCH
+    if type(agent).__name__ != 'DQNAgent':
+        return "the agent is a %s, not a plain DQNAgent" % type(agent).__name__
+    rp = agent._inner_replay()
+    if isinstance(rp, PrioritizedReplay):
+        return "the replay is a PrioritizedReplay"
+    if type(rp) is not UniformReplay:
+        return "the replay is not a UniformReplay"
+    if int(rp.n_step) != 1 or int(getattr(cfg, 'n_step', 1)) != 1:
+        return "n_step is not 1"
+    if int(rp.history_length) != 1 or int(getattr(cfg, 'history_length', 1)) != 1:
+        return "history_length is not 1"
+    if cfg.noisy_linear:
+        return "noisy_linear is on"
+    if cfg.async_actor:
+        return "async_actor is on"
+    shp = shape(agent.network)
+    if shp is None:
+        return "the network is not %s" % NETWORK
+    if getattr(agent, '_fused', None) is None or getattr(agent, '_target_flat', None) is None or not _plain_optimizer(agent.optimizer):
+        return "the optimizer is not one plain RMSprop or Adam over every parameter"
+    owned = agent._fused.flat.params
+    if any(all(p is not q for q in owned) for _, p in _fields(agent.network)):
+        return "one optimiser does not own every parameter the kernel reads"
+    if getattr(agent, 'grad_hook', None) is not None:
+        return "a grad_hook is installed"
+    dp = getattr(agent, 'dp', None)
+    if dp is not None and dp.active:
+        return "the agent is data parallel"
+    if shape(agent.target_network) != shp:
+        return "the target network is not %s of the online network's shape" % NETWORK
+    flat, target = agent._fused.flat, agent._target_flat
+    if ([flat.offset_of(p) for _, p in _fields(agent.network)] != [target.offset_of(p) for _, p in _fields(agent.target_network)]):
+        return "the online and the target parameters are laid out differently in their flat buffers"
+    rn, sn = cfg.reward_normalizer, cfg.state_normalizer
+    if type(rn) is not RescaleNormalizer or rn.coef != 1.0:
+        return "the reward normaliser is not RescaleNormalizer(1.0)"
+    if type(sn) is not RescaleNormalizer or sn.coef != 1.0:
+        return "the state normaliser is not RescaleNormalizer(1.0)"
+    k, b = int(cfg.sgd_update_frequency), int(rp.batch_size)
+    if not supported_fn(shp[0], shp[1], shp[2], k, shp[3]):
+        return "dra_dqn_mlp_act is not built for state_dim %d, %d actions, hidden %d, %d transitions per step" % (shp[0], shp[1], shp[2], k)
+    if k > int(rp.memory_size) or int(rp.memory_size) < 2:
+        return "the replay holds fewer slots than an agent step feeds"
+    if getattr(cfg, 'fused_dqn_update', True) is not False and not update_supported_fn(shp[0], shp[1], shp[2], b, shp[3]):
+        return "dra_dqn_mlp_update is not built for minibatches of %d" % b
+    return _fresh_cartpole(agent)[1]
+
+
+def adopt(agent):
+    """A Step with the actor's environment on the device when configuration, agent and task allow it; else None (the host path;
+    with the switch on the reason is logged once)."""
+    why = why_not(agent)
+    if why is not None:
+        if getattr(agent.config, SWITCH, False) is True:
+            getattr(agent.logger, 'warning', agent.logger.info)(DeviceCartPoleVec.HOST_NOTE % why)
+        return None
+    return Step(agent, shape(agent.network))
+
+
+class Step:
+    """One DQNAgent step on the kernels: see the module's docstring.  `regions`: the two captured regions by name."""
+    WARMUP = 2
+
+    def __init__(self, agent, shp):
+        from .device_env import EpisodeRing
+        cfg = agent.config
+        dev = Config.DEVICE
+        self.agent, self.shape = agent, shp
+        self.k, self.batch = int(cfg.sgd_update_frequency), int(agent._inner_replay().batch_size)
+        self.launches = 0
+        # the environment moves as reset() leaves it (DQN_agent.py:24-25: the actor's first transition resets it)
+        task = agent.actor._task
+        task.reset()
+        self.vec = DeviceCartPoleVec(task, buffers=lambda t_len, n, f: {})
+        agent.actor._task = self.vec
+        agent.task = self.vec           # (device_env.EpisodeRing reads the episodes through agent.task)
+        self.episodes = EpisodeRing(agent, 0, 1)
+        rp = agent._inner_replay()
+        self.ring = rp.device_ring((4,), np.float64, np.int64)
+        if self.ring.frame_bytes != 32 or self.ring.action_bytes != 8:
+            raise DraError("dqn_mlp: the replay ring holds frames of %d and actions of %d bytes" % (self.ring.frame_bytes, self.ring.action_bytes))
+        self.capacity = int(rp.memory_size)
+        # ONE staged block at fixed addresses: int64 first slot | int64 indices [B] | int64 random actions [K] | uint8 flags [K]
+        k, b = self.k, self.batch
+        self._o_idx, self._o_rand, self._o_flag = 8, 8 + 8 * b, 8 + 8 * b + 8 * k
+        self._up = StagedUpload(self._o_flag + (k + 7) // 8 * 8, torch.uint8, dev)
+        d = self._up.dev
+        self.slot0 = d[:8].view(torch.int64)
+        self.idx = d[self._o_idx:self._o_rand].view(torch.int64)
+        self.random_action = d[self._o_rand:self._o_flag].view(torch.int64)
+        self.explore = d[self._o_flag:self._o_flag + k]
+        self.step_dev = torch.zeros(1, dtype=torch.int64, device=dev)      # the kernel's own step counter (the ring rows' stamp)
+        self.err = torch.zeros(1, dtype=torch.int32, device=dev)           # staged words a kernel found out of range
+        self.out_q = torch.zeros((k, 2), dtype=torch.float32, device=dev)
+        self.out_action = torch.zeros(k, dtype=torch.int64, device=dev)
+        self.q_target = torch.zeros(b, dtype=torch.float32, device=dev)
+        self.td = torch.zeros(b, dtype=torch.float32, device=dev)
+        self.loss = torch.zeros(1, dtype=torch.float32, device=dev)
+        self.static = None              # the module-path update's minibatch buffers (ring.gather refills them in place)
+        self.regions = dict(act=Region("the dqn_feature acting launch", cfg, self.WARMUP),
+                            learn=Region("the dqn_feature agent step", cfg, self.WARMUP, opts=(agent._fused,)))
+        self.last_draws = None          # (explore, random_action, first slot, indices or None) of the last step, as drawn
+
+    # -- the structs ---------------------------------------------------------------------------------------------------
+    def net_struct(self):
+        agent = self.agent
+        flat = agent._fused.flat
+        n = Net()
+        n.param, n.target = flat.flat.data_ptr(), agent._target_flat.flat.data_ptr()
+        for field, p in _fields(agent.network):
+            setattr(n, field, flat.offset_of(p))
+        n.state_dim, n.n_actions, n.hidden, n.gate = self.shape
+        return n
+
+    def act(self):
+        """dra_dqn_mlp_act on the current stream (after prepare())."""
+        v, io = self.vec, ActIO()
+        io.env_state, io.env_counter, io.env_seed = v.env_state.data_ptr(), v.env_counter.data_ptr(), v.env_seed.data_ptr()
+        io.ep_steps, io.ep_return = v.ep_steps.data_ptr(), v.ep_return.data_ptr()
+        io.ep_count, io.ep_ring, io.ring_cap = v.ep_count.data_ptr(), v.ep_ring.data_ptr(), v.ring_cap
+        io.step_counter, io.err = self.step_dev.data_ptr(), self.err.data_ptr()
+        io.explore, io.random_action, io.slot0 = self.explore.data_ptr(), self.random_action.data_ptr(), self.slot0.data_ptr()
+        io.ring_frames, io.ring_actions, io.ring_rewards, io.ring_masks = self.ring.pointers()
+        io.out_q, io.out_action = self.out_q.data_ptr(), self.out_action.data_ptr()
+        io.horizon, io.capacity, io.reward_coef = v.horizon, self.capacity, float(self.agent.config.reward_normalizer.coef)
+        io.t_len, io.n_env = self.k, 1
+        net = self.net_struct()
+        lib.dra_dqn_mlp_act(ctypes.byref(net), ctypes.byref(io), stream_ptr())
+        self.launches += 1
+
+    def update(self):
+        """dra_dqn_mlp_update on the staged indices: the gradient lands in the optimiser's flat gradient buffer."""
+        cfg, io = self.agent.config, UpdateIO()
+        io.ring_frames, io.ring_actions, io.ring_rewards, io.ring_masks = self.ring.pointers()
+        io.idx, io.grad = self.idx.data_ptr(), self.agent._fused.flat.grad.data_ptr()
+        io.out_q_target, io.out_td, io.out_loss = self.q_target.data_ptr(), self.td.data_ptr(), self.loss.data_ptr()
+        io.err, io.capacity = self.err.data_ptr(), self.capacity
+        io.discount, io.batch, io.double_q = float(cfg.discount) ** int(cfg.n_step), self.batch, int(bool(cfg.double_q))
+        net = self.net_struct()
+        lib.dra_dqn_mlp_update(ctypes.byref(net), ctypes.byref(io), stream_ptr())
+        return self.loss
+
+    def module_update(self):
+        """config.fused_dqn_update False: ring.gather on the staged indices, the modules' forwards, the TD kernel, autograd."""
+        agent = self.agent
+        rp = agent._inner_replay()
+        self.static = g = rp.gather(self.idx, out=self.static)
+        tr = rp.TransitionCLS(state=g['state'], action=g['action'], reward=g['reward'], next_state=g['next_state'], mask=g['mask'])
+        out, (net_out, grad) = agent._loss_grad(tr, None)
+        agent._fused.zero_grad()
+        agent._backward(net_out, grad)
+        return out['loss']
+
+    # -- one agent step ------------------------------------------------------------------------------------------------
+    def prepare(self):
+        """The step's draws in the reference's order -- per transition the epsilon of DQN_agent.py:34-39 and epsilon_greedy's
+        two draws, then the feed's bookkeeping, then (total_steps > exploration_steps) the minibatch's rejection loop -- staged
+        with one copy.  -> whether the step updates."""
+        agent = self.agent
+        cfg, actor, rp = agent.config, agent.actor, agent._inner_replay()
+        k = self.k
+        explore, rand = plan_actor_epsilon_greedy(cfg.random_action_prob, k, self.shape[1], actor._total_steps, cfg.exploration_steps)
+        actor._total_steps += k
+        slot0 = int(rp.pos)
+        rp.advance(k)
+        self.episodes.begin(k)
+        agent.total_steps += k
+        learn = agent.total_steps > cfg.exploration_steps
+        idx = rp.draw_indices() if learn else None
+        raw = self._up.stage().numpy()
+        raw[:8].view(np.int64)[0] = slot0
+        if idx is not None:
+            raw[self._o_idx:self._o_rand].view(np.int64)[...] = idx
+        raw[self._o_rand:self._o_flag].view(np.int64)[...] = rand
+        raw[self._o_flag:self._o_flag + k] = explore
+        self._up.send()
+        self.last_draws = (explore, rand, slot0, idx)
+        return learn
+
+    def _learn(self):
+        cfg = self.agent.config
+        self.act()
+        loss = self.update() if getattr(cfg, 'fused_dqn_update', True) is not False else self.module_update()
+        self.agent._fused.step(cfg.gradient_clip)
+        return loss
+
+    def step(self):
+        agent = self.agent
+        cfg = agent.config
+        learn = self.prepare()
+        region, body = (self.regions['learn'], self._learn) if learn else (self.regions['act'], self.act)
+        key = agent._fused.hyper_signature() if learn else None
+        if region.due(key) and (region.graph is not None or region.capture(body, key)):
+            out = region.replay()
+        else:
+            out = body()
+        if learn:
+            agent.last_loss = out
+        # DQN_agent.py:136-138, after the update of the step: eager, between graph replays
+        if agent.total_steps / cfg.sgd_update_frequency % cfg.target_network_update_freq == 0:
+            agent.sync_target()
+        self.episodes.end()
+
+    # -- what the host reads back where it synchronises anyway ----------------------------------------------------------
+    def check(self):
+        """Raises when a kernel clamped a staged slot or index (a host bookkeeping error: the run's results are not the
+        reference's)."""
+        n = int(self.err.item())
+        if n:
+            raise DraError("dqn_mlp: %d staged ring slots / indices were outside the ring and have been clamped" % n)
+
+    def drain(self):
+        self.check()
+        return self.episodes.drain()
+
+    def state_dict(self):
+        torch.cuda.current_stream().synchronize()
+        return dict(self.episodes.state_dict(), step=int(self.step_dev.item()))
+
+    def load_state_dict(self, state):
+        self.episodes.load_state_dict(state)
+        self.step_dev.fill_(int(state['step']))

@@ -1196,6 +1196,67 @@ int dra_oc_mlp_update_supported(int state_dim, int n_actions, int hidden, int ro
 int dra_oc_mlp_rollout(const dra_oc_mlp_net* net, const dra_oc_mlp_rollout_io* io, void* stream);
 int dra_oc_mlp_update(const dra_oc_mlp_net* net, const dra_oc_mlp_update_io* io, void* stream);
 
+/* ---- dqn_mlp: dqn_feature (examples.py:11-52, DQN_agent.py:14-138) over ONE device-resident cart-pole environment and the HBM
+ * replay ring (dra_ring_pointers: fp64 observations of 32 bytes, int64 actions, fp64 rewards, int32 masks).  The networks are
+ * dra_q_mlp_net's: VanillaNet over a two-layer FCBody of one width, online and target in two flat buffers of equal layout.
+ * Everything that changes from agent step to agent step -- the first ring slot, the exploration draws, the sampled indices -- is
+ * read from device memory, so a captured launch sees the values staged last.
+ *
+ * DQN_agent.py:23-45, t_len times, in ONE launch of one workgroup: q of the ONLINE network on the observation narrowed to float32,
+ * action = random_action[k] where explore[k] else the FIRST maximum of q (np.argmax), environment step with the auto reset, and
+ * ring row (*slot0 + k) % capacity = (the fp64 observation the action was chosen on, action, reward_coef * reward, 1 - done);
+ * for every episode that ended one appended row of ep_ring, as dra_q_mlp_rollout appends it (environment 0).  No parameter is
+ * written.  *step_counter advances by t_len.  A *slot0 outside [0, capacity) is taken as 0 and counted in *err. */
+typedef struct dra_dqn_mlp_act_io {
+  double* env_state;            /* [1][4] (in/out) */
+  int64_t* env_counter;         /* [1] (in/out) */
+  int32_t* ep_steps;            /* [1] (in/out) */
+  double* ep_return;            /* [1] (in/out) */
+  const int64_t* env_seed;      /* [1] */
+  int64_t* step_counter;        /* [1] (in/out) */
+  int64_t* ep_count;            /* [1] (in/out) */
+  double* ep_ring;              /* [ring_cap][3] */
+  const uint8_t* explore;       /* [t_len]: nonzero = take random_action */
+  const int64_t* random_action; /* [t_len] */
+  const int64_t* slot0;         /* [1]: the replay's cursor before the step */
+  double* ring_frames;          /* [capacity][4] */
+  int64_t* ring_actions;        /* [capacity] */
+  double* ring_rewards;         /* [capacity] */
+  int32_t* ring_masks;          /* [capacity] */
+  float* out_q;                 /* [t_len][2] */
+  int64_t* out_action;          /* [t_len] */
+  int32_t* err;                 /* [1] (in/out): staged words that were out of range */
+  int64_t horizon, ring_cap, capacity;
+  double reward_coef;
+  int32_t t_len, n_env;         /* 1 <= t_len <= 8, n_env == 1 */
+} dra_dqn_mlp_act_io;
+/* DQN_agent.py:81-99, 128-133 and the whole backward in ONE launch of one workgroup: for b < batch the ring rows at idx[b] (state
+ * = frame idx, next state = frame idx + 1, both narrowed to float32, action, reward and mask narrowed to float32), q_next = max_a
+ * of the TARGET network on the next state -- double_q: the target's value at the FIRST maximum of the ONLINE network's --,
+ * q_target = reward + ((discount * q_next) * mask) in fp32, td = q_target - q[a] of the ONLINE network on the state, loss = 0.5
+ * mean td^2 and its gradient with respect to w1 b1 w2 b2 wq bq, written (every element, nothing between the tensors) into `grad`
+ * at the parameters' offsets.  Fixed summation order, no atomics.  An idx outside [0, capacity - 2] is clamped into it and
+ * counted in *err.  1 <= batch <= 256 (dra_dqn_mlp_update_supported). */
+typedef struct dra_dqn_mlp_update_io {
+  const double* ring_frames;    /* [capacity][4] */
+  const int64_t* ring_actions;  /* [capacity] (1 = the second action, anything else the first) */
+  const double* ring_rewards;   /* [capacity] */
+  const int32_t* ring_masks;    /* [capacity] */
+  const int64_t* idx;           /* [batch] */
+  float* grad;                  /* the flat gradient buffer (device) */
+  float* out_q_target;          /* [batch] */
+  float* out_td;                /* [batch] */
+  float* out_loss;              /* [1] */
+  int32_t* err;                 /* [1] (in/out) */
+  int64_t capacity;
+  double discount;
+  int32_t batch, double_q;
+} dra_dqn_mlp_update_io;
+int dra_dqn_mlp_supported(int state_dim, int n_actions, int hidden, int t_len, int gate);          /* the acting launch; 0 = yes */
+int dra_dqn_mlp_update_supported(int state_dim, int n_actions, int hidden, int batch, int gate);   /* the update; 0 = yes */
+int dra_dqn_mlp_act(const dra_q_mlp_net* net, const dra_dqn_mlp_act_io* io, void* stream);
+int dra_dqn_mlp_update(const dra_q_mlp_net* net, const dra_dqn_mlp_update_io* io, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

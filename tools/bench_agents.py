@@ -20,6 +20,8 @@ after a warm-up.  Prints one JSON object per line: agent steps/s, env steps/s, g
             `_module_update` = config.fused_nstep_update False; `_host` = the switch off: python environments)
             option_critic_feature examples.py:450-468 (5 workers, classic-CartPole-v0, config.fused_oc_feature True;
             `_module_update` = config.fused_oc_update False; `_host` = the switch off: python environments)
+  config 1  dqn_feature examples.py:11-52 (one classic-CartPole-v0 environment, config.fused_dqn_feature True;
+            `_module_update` = config.fused_dqn_update False; `_host` = the switch off: the python environment and ring feeds)
   ddpg_continuous examples.py:554-583, td3_continuous examples.py:587-617 (one host environment, (400, 300) relu MLPs, Adam 1e-3,
             minibatch 100, a 1M ring; warm_up shortened to 1000 so that the timed window is all updates; the default is
             config.fused_dpg_update True: csrc/dpg_mlp.hip; `_modules` = the switch off: torch modules and optimisers)
@@ -195,6 +197,24 @@ def n_step_dqn_feature(workers=5, **switches):
     return d.NStepDQNAgent(c), dict(env_per_step=5 * workers, updates_per_step=1)
 
 
+def dqn_feature(**switches):
+    c = d.Config()
+    c.merge(dict(game="classic-CartPole-v0", log_level=0, tag="bench", n_step=1, replay_cls=d.UniformReplay, async_replay=False,
+                 **switches))
+    c.task_fn = lambda: d.Task(c.game, seed=1)
+    c.eval_env = d.Task(c.game, seed=2)
+    c.optimizer_fn = lambda p: torch.optim.RMSprop(p, 0.001)
+    c.network_fn = lambda: d.VanillaNet(c.action_dim, d.FCBody(c.state_dim))
+    c.history_length, c.batch_size, c.discount = 1, 10, 0.99
+    kw = dict(memory_size=int(1e4), batch_size=c.batch_size, n_step=c.n_step, discount=c.discount, history_length=1)
+    c.replay_fn = lambda: d.ReplayWrapper(c.replay_cls, kw, c.async_replay)
+    c.random_action_prob = d.LinearSchedule(1.0, 0.1, 1e4)
+    c.target_network_update_freq, c.exploration_steps, c.double_q = 200, 1000, False
+    c.sgd_update_frequency, c.gradient_clip, c.async_actor = 4, 5, False
+    # (warm: past exploration_steps -- 250 agent steps -- and the graph captures, so that the timed window is all updates)
+    return d.DQNAgent(c), dict(env_per_step=4, updates_per_step=1, warm=300)
+
+
 def option_critic_pixel(workers=16, device=True, **switches):
     c = d.Config()
     c.merge(dict(game="BreakoutNoFrameskip-v4", log_level=0, tag="bench", device_env=device, **switches))
@@ -307,6 +327,10 @@ CASES = {
     "option_critic_feature": lambda: option_critic_feature(5, fused_oc_feature=True),
     "option_critic_feature_module_update": lambda: option_critic_feature(5, fused_oc_feature=True, fused_oc_update=False),
     "option_critic_feature_host": lambda: option_critic_feature(5),   # 5 python cart-poles, one module forward and three draws per step
+    # one device-resident cart-pole feeding the HBM replay ring, one acting and one update launch (csrc/dqn_mlp.hip) + captured graphs
+    "dqn_feature": lambda: dqn_feature(fused_dqn_feature=True),
+    "dqn_feature_module_update": lambda: dqn_feature(fused_dqn_feature=True, fused_dqn_update=False),
+    "dqn_feature_host": lambda: dqn_feature(),   # the switch off: the python cart-pole, four module forwards and ring feeds per step
     "ppo_continuous_1": lambda: ppo_continuous(1),
     "ppo_continuous_16": lambda: ppo_continuous(16),                                  # device environments + persistent kernels
     "ppo_continuous_16_host": lambda: ppo_continuous(16, device=False),               # host environments, persistent update kernel
