@@ -277,6 +277,12 @@ class DQNAgent(BaseAgent):
         if getattr(config, 'fused_dqn_feature', False) is True:
             from . import dqn_mlp
             self._feature = dqn_mlp.adopt(self)
+        # categorical_dqn_feature / quantile_regression_dqn_feature, examples.py:164-193 / 101-127 (opt-in,
+        # config.fused_dist_feature): the same Step over the distributional kernels (csrc/dist_mlp.hip) for CategoricalDQNAgent and
+        # QuantileRegressionDQNAgent; any other agent class keeps its path and is told why
+        if getattr(config, 'fused_dist_feature', False) is True and self._feature is None:
+            from . import dist_mlp
+            self._feature = dist_mlp.adopt(self)
 
     def _device_noisy_actor(self):
         """noisy_actor.NoisyActor when `config.device_noisy_actor` is on and the agent is eligible (Rainbow over one synthetic

@@ -60,6 +60,28 @@ def update_supported(state_dim, n_actions, hidden, batch, gate):
     return lib.dra_dqn_mlp_update_supported.raw(int(state_dim), int(n_actions), int(hidden), int(batch), int(gate)) == 0
 
 
+class Kind:
+    """What tells this entry's device path from its siblings over the same Step (dist_mlp.py: the distributional heads): the
+    switches, the agent classes, the network's shape and fields, the two kernels' shape tables.  `shape(network)` -> a tuple that
+    starts (state_dim, n_actions, hidden, gate); its first N_SUPPORTED fields are what the `*_supported` tables read."""
+    ENTRY, SWITCH, UPDATE_SWITCH = 'dqn_feature', SWITCH, 'fused_dqn_update'
+    AGENTS, NOT_AGENT = ('DQNAgent',), "the agent is a %s, not a plain DQNAgent"
+    NETWORK, ACT, UPDATE, N_SUPPORTED = NETWORK, 'dra_dqn_mlp_act', 'dra_dqn_mlp_update', 4
+    ASYNC_ACTOR = False      # whether config.async_actor may be on (the Step runs in the sync path's order)
+    shape, fields = staticmethod(shape), staticmethod(_fields)
+    supported, update_supported = staticmethod(supported), staticmethod(update_supported)
+
+    @staticmethod
+    def extra(agent, shp):
+        """A reason of the kind's own behind the shape checks, or None."""
+        return None
+
+    @classmethod
+    def fused_update(cls, cfg, shp):
+        """Whether the update runs on the kind's update kernel (else: ring.gather and the modules on the same indices)."""
+        return getattr(cfg, cls.UPDATE_SWITCH, True) is not False
+
+
 def _plain_optimizer(opt):
     """One parameter group under torch's RMSprop or Adam without momentum, weight decay, amsgrad or maximize."""
     if len(opt.param_groups) != 1:
@@ -85,15 +107,17 @@ def _fresh_cartpole(agent):
     return env, None
 
 
-def why_not(agent, supported_fn=supported, update_supported_fn=update_supported):
-    """None when DQNAgent may run `agent` on the kernels, else the first reason it may not."""
+def why_not(agent, supported_fn=None, update_supported_fn=None, kind=Kind):
+    """None when DQNAgent may run `agent` on the kernels of `kind`, else the first reason it may not."""
     from .normalizers import RescaleNormalizer
     from .replay import PrioritizedReplay, UniformReplay
     cfg = agent.config
-    if getattr(cfg, SWITCH, False) is not True:
-        return "config.%s is not on" % SWITCH
-    if type(agent).__name__ != 'DQNAgent':
-        return "the agent is a %s, not a plain DQNAgent" % type(agent).__name__
+    supported_fn, update_supported_fn = supported_fn or kind.supported, update_supported_fn or kind.update_supported
+    shape, _fields, NETWORK = kind.shape, kind.fields, kind.NETWORK
+    if getattr(cfg, kind.SWITCH, False) is not True:
+        return "config.%s is not on" % kind.SWITCH
+    if type(agent).__name__ not in kind.AGENTS:
+        return kind.NOT_AGENT % type(agent).__name__
     rp = agent._inner_replay()
     if isinstance(rp, PrioritizedReplay):
         return "the replay is a PrioritizedReplay"
@@ -101,11 +125,11 @@ def why_not(agent, supported_fn=supported, update_supported_fn=update_supported)
         return "the replay is not a UniformReplay"
     if int(rp.n_step) != 1 or int(getattr(cfg, 'n_step', 1)) != 1:
         return "n_step is not 1"
-    if int(rp.history_length) != 1 or int(getattr(cfg, 'history_length', 1)) != 1:
+    if int(rp.history_length) != 1 or int(getattr(cfg, 'history_length', None) or 1) != 1:
         return "history_length is not 1"
     if cfg.noisy_linear:
         return "noisy_linear is on"
-    if cfg.async_actor:
+    if cfg.async_actor and not kind.ASYNC_ACTOR:
         return "async_actor is on"
     shp = shape(agent.network)
     if shp is None:
@@ -130,30 +154,36 @@ def why_not(agent, supported_fn=supported, update_supported_fn=update_supported)
         return "the reward normaliser is not RescaleNormalizer(1.0)"
     if type(sn) is not RescaleNormalizer or sn.coef != 1.0:
         return "the state normaliser is not RescaleNormalizer(1.0)"
+    why = kind.extra(agent, shp)
+    if why is not None:
+        return why
     k, b = int(cfg.sgd_update_frequency), int(rp.batch_size)
-    if not supported_fn(shp[0], shp[1], shp[2], k, shp[3]):
-        return "dra_dqn_mlp_act is not built for state_dim %d, %d actions, hidden %d, %d transitions per step" % (shp[0], shp[1], shp[2], k)
+    if not supported_fn(shp[0], shp[1], shp[2], k, *shp[3:kind.N_SUPPORTED]):
+        return "%s is not built for state_dim %d, %d actions, hidden %d, %d transitions per step" % (kind.ACT, shp[0], shp[1], shp[2], k)
     if k > int(rp.memory_size) or int(rp.memory_size) < 2:
         return "the replay holds fewer slots than an agent step feeds"
-    if getattr(cfg, 'fused_dqn_update', True) is not False and not update_supported_fn(shp[0], shp[1], shp[2], b, shp[3]):
-        return "dra_dqn_mlp_update is not built for minibatches of %d" % b
+    if kind.fused_update(cfg, shp) and not update_supported_fn(shp[0], shp[1], shp[2], b, *shp[3:kind.N_SUPPORTED]):
+        return "%s is not built for minibatches of %d" % (kind.UPDATE, b)
     return _fresh_cartpole(agent)[1]
 
 
-def adopt(agent):
-    """A Step with the actor's environment on the device when configuration, agent and task allow it; else None (the host path;
-    with the switch on the reason is logged once)."""
-    why = why_not(agent)
+def adopt(agent, step_cls=None):
+    """A Step (or `step_cls`, a subclass with its own KIND) with the actor's environment on the device when configuration, agent
+    and task allow it; else None (the host path; with the switch on the reason is logged once)."""
+    step_cls = step_cls or Step
+    kind = step_cls.KIND
+    why = why_not(agent, kind=kind)
     if why is not None:
-        if getattr(agent.config, SWITCH, False) is True:
+        if getattr(agent.config, kind.SWITCH, False) is True:
             getattr(agent.logger, 'warning', agent.logger.info)(DeviceCartPoleVec.HOST_NOTE % why)
         return None
-    return Step(agent, shape(agent.network))
+    return step_cls(agent, kind.shape(agent.network))
 
 
 class Step:
     """One DQNAgent step on the kernels: see the module's docstring.  `regions`: the two captured regions by name."""
     WARMUP = 2
+    KIND = Kind
 
     def __init__(self, agent, shp):
         from .device_env import EpisodeRing
@@ -187,13 +217,18 @@ class Step:
         self.err = torch.zeros(1, dtype=torch.int32, device=dev)           # staged words a kernel found out of range
         self.out_q = torch.zeros((k, 2), dtype=torch.float32, device=dev)
         self.out_action = torch.zeros(k, dtype=torch.int64, device=dev)
+        self.make_outputs(dev)
+        self.static = None              # the module-path update's minibatch buffers (ring.gather refills them in place)
+        self.regions = dict(act=Region("the %s acting launch" % self.KIND.ENTRY, cfg, self.WARMUP),
+                            learn=Region("the %s agent step" % self.KIND.ENTRY, cfg, self.WARMUP, opts=(agent._fused,)))
+        self.last_draws = None          # (explore, random_action, first slot, indices or None) of the last step, as drawn
+
+    def make_outputs(self, dev):
+        """The update kernel's output buffers (a subclass has its own)."""
+        b = self.batch
         self.q_target = torch.zeros(b, dtype=torch.float32, device=dev)
         self.td = torch.zeros(b, dtype=torch.float32, device=dev)
         self.loss = torch.zeros(1, dtype=torch.float32, device=dev)
-        self.static = None              # the module-path update's minibatch buffers (ring.gather refills them in place)
-        self.regions = dict(act=Region("the dqn_feature acting launch", cfg, self.WARMUP),
-                            learn=Region("the dqn_feature agent step", cfg, self.WARMUP, opts=(agent._fused,)))
-        self.last_draws = None          # (explore, random_action, first slot, indices or None) of the last step, as drawn
 
     # -- the structs ---------------------------------------------------------------------------------------------------
     def net_struct(self):
@@ -206,8 +241,8 @@ class Step:
         n.state_dim, n.n_actions, n.hidden, n.gate = self.shape
         return n
 
-    def act(self):
-        """dra_dqn_mlp_act on the current stream (after prepare())."""
+    def act_io(self):
+        """dra_dqn_mlp_act_io over the environment, the staged draws and the ring."""
         v, io = self.vec, ActIO()
         io.env_state, io.env_counter, io.env_seed = v.env_state.data_ptr(), v.env_counter.data_ptr(), v.env_seed.data_ptr()
         io.ep_steps, io.ep_return = v.ep_steps.data_ptr(), v.ep_return.data_ptr()
@@ -218,7 +253,11 @@ class Step:
         io.out_q, io.out_action = self.out_q.data_ptr(), self.out_action.data_ptr()
         io.horizon, io.capacity, io.reward_coef = v.horizon, self.capacity, float(self.agent.config.reward_normalizer.coef)
         io.t_len, io.n_env = self.k, 1
-        net = self.net_struct()
+        return io
+
+    def act(self):
+        """dra_dqn_mlp_act on the current stream (after prepare())."""
+        net, io = self.net_struct(), self.act_io()
         lib.dra_dqn_mlp_act(ctypes.byref(net), ctypes.byref(io), stream_ptr())
         self.launches += 1
 
@@ -274,7 +313,7 @@ class Step:
     def _learn(self):
         cfg = self.agent.config
         self.act()
-        loss = self.update() if getattr(cfg, 'fused_dqn_update', True) is not False else self.module_update()
+        loss = self.update() if self.KIND.fused_update(cfg, self.shape) else self.module_update()
         self.agent._fused.step(cfg.gradient_clip)
         return loss
 
@@ -301,7 +340,7 @@ class Step:
         reference's)."""
         n = int(self.err.item())
         if n:
-            raise DraError("dqn_mlp: %d staged ring slots / indices were outside the ring and have been clamped" % n)
+            raise DraError("%s: %d staged ring slots / indices were outside the ring and have been clamped" % (self.KIND.ENTRY, n))
 
     def drain(self):
         self.check()

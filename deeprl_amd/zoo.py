@@ -51,6 +51,23 @@ ZOO = {
                     double_q=False, async_actor=True),
         normalizers=(ImageNormalizer, SignNormalizer),
         replay=dict(memory_size=int(1e6), with_n_step=True), eps=(1.0, 0.01, 1e6), beta=(0.4, 1.0)),
+    # examples.py:101-127 (fused_dist_feature=True moves the cart-pole, the replay's feed and the update onto the device: csrc/dist_mlp.hip)
+    "quantile_regression_dqn_feature": dict(
+        agent="QuantileRegressionDQNAgent", kw=dict(log_level=0), task=lambda c: Task(c.game), eval_task="same",
+        optimizer=_rmsprop(lr=0.001),
+        network=lambda c: N.QuantileNet(c.action_dim, c.num_quantiles, N.FCBody(c.state_dim)),
+        fields=dict(batch_size=10, discount=0.99, target_network_update_freq=200, exploration_steps=100, num_quantiles=20,
+                    gradient_clip=5, sgd_update_frequency=4, eval_interval=int(5e3), max_steps=1e5),
+        replay=dict(memory_size=int(1e4), fixed_cls=UniformReplay, fixed_async=True), eps=(1.0, 0.1, 1e4)),
+    # examples.py:164-193 (fused_dist_feature=True: as above)
+    "categorical_dqn_feature": dict(
+        agent="CategoricalDQNAgent", kw=dict(log_level=0), task=lambda c: Task(c.game), eval_task="same",
+        optimizer=_rmsprop(lr=0.001),
+        network=lambda c: N.CategoricalNet(c.action_dim, c.categorical_n_atoms, N.FCBody(c.state_dim)),
+        fields=dict(batch_size=10, discount=0.99, target_network_update_freq=200, exploration_steps=100,
+                    categorical_v_max=100, categorical_v_min=-100, categorical_n_atoms=50, gradient_clip=5,
+                    sgd_update_frequency=4, eval_interval=int(5e3), max_steps=1e5),
+        replay=dict(memory_size=int(1e4), fixed_cls=UniformReplay, fixed_async=True), eps=(1.0, 0.1, 1e4)),
     # examples.py:129-161
     "quantile_regression_dqn_pixel": dict(
         agent="QuantileRegressionDQNAgent", kw=dict(log_level=0), task=lambda c: Task(c.game), eval_task="same",
@@ -207,7 +224,7 @@ def config(name, **kwargs):
         kw = dict(memory_size=rp["memory_size"], batch_size=c.batch_size)
         if rp.get("with_n_step"):
             kw.update(n_step=c.n_step, discount=c.discount, history_length=c.history_length)
-        else:
+        elif "history_length" in rp:
             kw.update(history_length=rp["history_length"])
         cls = rp.get("fixed_cls") or c.replay_cls
         flag = rp["fixed_async"] if "fixed_async" in rp else c.async_replay

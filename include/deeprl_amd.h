@@ -1257,6 +1257,57 @@ int dra_dqn_mlp_update_supported(int state_dim, int n_actions, int hidden, int b
 int dra_dqn_mlp_act(const dra_q_mlp_net* net, const dra_dqn_mlp_act_io* io, void* stream);
 int dra_dqn_mlp_update(const dra_q_mlp_net* net, const dra_dqn_mlp_update_io* io, void* stream);
 
+/* ---- dist_mlp: categorical_dqn_feature (examples.py:164-193, CategoricalDQN_agent.py) and quantile_regression_dqn_feature
+ * (examples.py:101-127, QuantileRegressionDQN_agent.py) over ONE device-resident cart-pole environment and the HBM replay ring:
+ * dqn_mlp's two launches with a distributional head.  CategoricalNet / QuantileNet over a two-layer FCBody of one width, the
+ * head one plain biased layer of n_actions * n_atoms outputs (row a * n_atoms + j: atom / quantile j of action a); online and
+ * target in two flat buffers of equal layout.  state_dim 4, 2 actions, hidden in {16, 32, 64}, 2 <= n_atoms <= 51. */
+typedef struct dra_dist_mlp_net {
+  const float* param;                /* the optimiser's flat parameter buffer (device): the ONLINE network; read only */
+  const float* target;               /* the TARGET network's flat buffer, same offsets; read only (the acting launch does not read it) */
+  int32_t w1, b1, w2, b2;            /* body.layers[0..1]: float offsets into param / target (and the flat gradient buffer) */
+  int32_t wq, bq;                    /* the head [n_actions * n_atoms][hidden], [n_actions * n_atoms] */
+  int32_t gate;                      /* 1 relu, 2 tanh */
+  int32_t state_dim, n_actions, hidden;
+  int32_t head;                      /* 1 categorical (C51), 2 quantile (QR-DQN) */
+  int32_t n_atoms;                   /* atoms / quantiles per action */
+  double v_min, v_max;               /* categorical: the support, z = linspace(v_min, v_max, n_atoms) in fp64 narrowed to float32 */
+} dra_dist_mlp_net;
+/* The acting launch is dra_dqn_mlp_act's with dra_dqn_mlp_act_io as it is; the action values (out_q [t_len][2]) are sum_j
+ * softmax(logits)_j z_j (categorical) or the mean of the quantiles (quantile).
+ *
+ * The update, ONE launch of one workgroup: for b < batch the ring rows at idx[b] as in dra_dqn_mlp_update; the TARGET network's
+ * head on the next state; a_next = the FIRST maximum of its action values (categorical + double_q: of the ONLINE network's;
+ * quantile: of the quantile sums, double_q is not read).
+ *   categorical  Tz_j = clamp(reward + (discount * mask) * z_j, v_min, v_max); target_i = sum_j clamp(1 - |Tz_j - z_i| / delta, 0, 1)
+ *                p_next[a_next][j]; loss_vec[b] = sum_i target_i log(target_i + 1e-5) - target_i log_softmax(logits[a])_i;
+ *                loss = mean_b loss_vec.
+ *   quantile     target_j = reward + (discount * mask) * theta_next[a_next][j]; d = target_j - theta[a]_i; loss_vec[j] = mean_b
+ *                sum_i huber(d) |tau_i - 1[d < 0]|, tau_i = (2 i + 1) / (2 n_atoms); loss = mean_j loss_vec.
+ * and the gradient of loss with respect to w1 b1 w2 b2 wq bq, written (every element, nothing between the tensors) into `grad`
+ * at the parameters' offsets.  Fixed summation order, no atomics.  An idx outside [0, capacity - 2] is clamped into it and counted
+ * in *err.  1 <= batch <= 256 (dra_dist_mlp_update_supported: what fits the workgroup's 160 KiB of LDS). */
+typedef struct dra_dist_mlp_update_io {
+  const double* ring_frames;    /* [capacity][4] */
+  const int64_t* ring_actions;  /* [capacity] (1 = the second action, anything else the first) */
+  const double* ring_rewards;   /* [capacity] */
+  const int32_t* ring_masks;    /* [capacity] */
+  const int64_t* idx;           /* [batch] */
+  float* grad;                  /* the flat gradient buffer (device) */
+  float* out_loss;              /* [1] */
+  float* out_loss_vec;          /* categorical [batch]; quantile [n_atoms] */
+  float* out_q_next;            /* [batch][2]: the TARGET network's action values of the next states */
+  float* out_target;            /* [batch][n_atoms] */
+  int32_t* err;                 /* [1] (in/out) */
+  int64_t capacity;
+  double discount;
+  int32_t batch, double_q;
+} dra_dist_mlp_update_io;
+int dra_dist_mlp_supported(int state_dim, int n_actions, int hidden, int t_len, int gate, int head, int n_atoms);          /* 0 = yes */
+int dra_dist_mlp_update_supported(int state_dim, int n_actions, int hidden, int batch, int gate, int head, int n_atoms);   /* 0 = yes */
+int dra_dist_mlp_act(const dra_dist_mlp_net* net, const dra_dqn_mlp_act_io* io, void* stream);
+int dra_dist_mlp_update(const dra_dist_mlp_net* net, const dra_dist_mlp_update_io* io, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

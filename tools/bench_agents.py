@@ -22,6 +22,8 @@ after a warm-up.  Prints one JSON object per line: agent steps/s, env steps/s, g
             `_module_update` = config.fused_oc_update False; `_host` = the switch off: python environments)
   config 1  dqn_feature examples.py:11-52 (one classic-CartPole-v0 environment, config.fused_dqn_feature True;
             `_module_update` = config.fused_dqn_update False; `_host` = the switch off: the python environment and ring feeds)
+            categorical_dqn_feature examples.py:164-193, quantile_regression_dqn_feature examples.py:101-127 (the same, with
+            config.fused_dist_feature True and config.fused_dist_update True; `_module_update` = config.fused_dist_update False; `_host` = the switch off)
   ddpg_continuous examples.py:554-583, td3_continuous examples.py:587-617 (one host environment, (400, 300) relu MLPs, Adam 1e-3,
             minibatch 100, a 1M ring; warm_up shortened to 1000 so that the timed window is all updates; the default is
             config.fused_dpg_update True: csrc/dpg_mlp.hip; `_modules` = the switch off: torch modules and optimisers)
@@ -215,6 +217,29 @@ def dqn_feature(**switches):
     return d.DQNAgent(c), dict(env_per_step=4, updates_per_step=1, warm=300)
 
 
+def dist_feature(head, **switches):
+    c = d.Config()
+    c.merge(dict(game="classic-CartPole-v0", log_level=0, tag="bench", **switches))
+    c.task_fn = lambda: d.Task(c.game, seed=1)
+    c.eval_env = d.Task(c.game, seed=2)
+    c.optimizer_fn = lambda p: torch.optim.RMSprop(p, 0.001)
+    if head == "categorical":
+        c.categorical_v_max, c.categorical_v_min, c.categorical_n_atoms = 100, -100, 50
+        c.network_fn = lambda: d.CategoricalNet(c.action_dim, c.categorical_n_atoms, d.FCBody(c.state_dim))
+    else:
+        c.num_quantiles = 20
+        c.network_fn = lambda: d.QuantileNet(c.action_dim, c.num_quantiles, d.FCBody(c.state_dim))
+    c.batch_size, c.discount = 10, 0.99
+    kw = dict(memory_size=int(1e4), batch_size=c.batch_size)
+    c.replay_fn = lambda: d.ReplayWrapper(d.UniformReplay, kw, False)
+    c.random_action_prob = d.LinearSchedule(1.0, 0.1, 1e4)
+    c.target_network_update_freq, c.exploration_steps = 200, 100
+    c.sgd_update_frequency, c.gradient_clip = 4, 5
+    cls = d.CategoricalDQNAgent if head == "categorical" else d.QuantileRegressionDQNAgent
+    # (warm: past exploration_steps -- 25 agent steps -- and the graph captures, so that the timed window is all updates)
+    return cls(c), dict(env_per_step=4, updates_per_step=1, warm=120)
+
+
 def option_critic_pixel(workers=16, device=True, **switches):
     c = d.Config()
     c.merge(dict(game="BreakoutNoFrameskip-v4", log_level=0, tag="bench", device_env=device, **switches))
@@ -331,6 +356,13 @@ CASES = {
     "dqn_feature": lambda: dqn_feature(fused_dqn_feature=True),
     "dqn_feature_module_update": lambda: dqn_feature(fused_dqn_feature=True, fused_dqn_update=False),
     "dqn_feature_host": lambda: dqn_feature(),   # the switch off: the python cart-pole, four module forwards and ring feeds per step
+    # the two distributional entries on the same path (csrc/dist_mlp.hip): 50 atoms on [-100, 100] / 20 quantiles
+    "categorical_dqn_feature": lambda: dist_feature("categorical", fused_dist_feature=True, fused_dist_update=True),
+    "categorical_dqn_feature_module_update": lambda: dist_feature("categorical", fused_dist_feature=True, fused_dist_update=False),
+    "categorical_dqn_feature_host": lambda: dist_feature("categorical"),   # the switch off: the python cart-pole, module forwards, ops.c51_loss
+    "quantile_regression_dqn_feature": lambda: dist_feature("quantile", fused_dist_feature=True, fused_dist_update=True),
+    "quantile_regression_dqn_feature_module_update": lambda: dist_feature("quantile", fused_dist_feature=True, fused_dist_update=False),
+    "quantile_regression_dqn_feature_host": lambda: dist_feature("quantile"),   # the switch off
     "ppo_continuous_1": lambda: ppo_continuous(1),
     "ppo_continuous_16": lambda: ppo_continuous(16),                                  # device environments + persistent kernels
     "ppo_continuous_16_host": lambda: ppo_continuous(16, device=False),               # host environments, persistent update kernel
