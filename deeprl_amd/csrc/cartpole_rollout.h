@@ -1,5 +1,6 @@
-// What the one-workgroup rollout kernels over device-resident cart-poles share (cat_mlp.hip: a2c_feature, q_mlp.hip:
-// n_step_dqn_feature, oc_mlp.hip: option_critic_feature), stated ONCE:
+// What the one-workgroup rollout / acting kernels over device-resident cart-poles share (cat_mlp.hip: a2c_feature, q_mlp.hip:
+// n_step_dqn_feature, oc_mlp.hip: option_critic_feature, dqn_mlp.hip: dqn_feature, dist_mlp.hip: the C51 / QR-DQN entries), stated
+// ONCE:
 //
 //   CartPoleLanes    the environments in the registers of wave 0 (lane e = environment e) for the whole launch: load, observe,
 //                    advance (cartpole_step, the action / reward / mask row), append (the episode ring: an ending episode's
@@ -7,7 +8,9 @@
 //                    store.  A ring row is (stamp, environment id, episodic return): the kernel says what the stamp counts
 //                    (cat_mlp: sampler steps, T + 1 per rollout; q_mlp and oc_mlp: their step counter, T per rollout) and how
 //                    its lanes are numbered (cat_mlp: env0 + lane, q_mlp and oc_mlp: lane).
-//   BodyWeights<H>   the two-layer body's W1^T, W2^T, b1, b2 in LDS and their staging from a flat parameter buffer.
+//   BodyWeights<H>   the two-layer body's W1^T, W2^T, b1, b2 in LDS and their staging from a flat parameter buffer;
+//   QNetWeights<H>   the same with the Q head [A][H + 1] behind it (q_mlp.hip, dqn_mlp.hip).
+//   EpisodeRow       what append reads of a row in the kernels that write transitions to a replay ring (dqn_mlp.hip, dist_mlp.hip).
 //   the host checks  cartpole_mlp_supported, offsets_nonnegative, cartpole_io_ok, and the hidden x gate dispatch.
 //
 // Each kernel keeps its action choice (Gumbel-max / staged epsilon-greedy / option-critic's two inverse-CDF draws with the carried
@@ -47,6 +50,24 @@ struct BodyWeights {
   }
 };
 
+// a VanillaNet's weights in LDS (q_mlp.hip, dqn_mlp.hip): the body and the Q head [A][H + 1] with its bias; every region starts at a
+// multiple of 4 floats (16 bytes)
+__host__ __device__ constexpr size_t q_net_weight_floats(int H) { return body_weight_floats(H) + round_up4(kA * (H + 1)) + 4; }
+template <int H>
+struct QNetWeights {
+  BodyWeights<H> body;
+  float *wq, *bq;
+  __device__ explicit QNetWeights(float* base) : body(base), wq(base + body_weight_floats(H)), bq(wq + round_up4(kA * (H + 1))) {}
+  __device__ __forceinline__ void stage(const float* __restrict__ P, const dra_q_mlp_net& net, int tid) const {
+    body.stage(P, net, tid);
+    for (int i = tid; i < kA * H; i += 256) {
+      const int c = i / H, k = i - c * H;
+      wq[c * (H + 1) + k] = P[net.wq + c * H + k];
+    }
+    if (tid < kA) bq[tid] = P[net.bq + tid];
+  }
+};
+
 // where step t's row and ring rows go: read from the kernel's io struct once per step, AHEAD of the lanes' own block
 struct CartPoleRow {
   int64_t* out_action;
@@ -58,6 +79,16 @@ struct CartPoleRow {
   __device__ __forceinline__ explicit CartPoleRow(const Io& io)
       : out_action(io.out_action), out_reward(io.out_reward), out_mask(io.out_mask), ep_ring(io.ep_ring), horizon(io.horizon),
         ring_cap(io.ring_cap), N(io.n_env) {}
+};
+
+// what CartPoleLanes::append reads of a row where the transition itself goes to a replay ring (dqn_mlp.hip, dist_mlp.hip): the
+// episode ring alone
+struct EpisodeRow {
+  int64_t* out_action = nullptr;
+  float *out_reward = nullptr, *out_mask = nullptr;
+  double* ep_ring;
+  int64_t horizon, ring_cap;
+  int n_env = 1;
 };
 
 struct CartPoleLanes {

@@ -44,15 +44,6 @@ __device__ __forceinline__ float atom_value(double v_min, double v_max, int n, i
   return (float)((double)i * step + v_min);
 }
 
-// what CartPoleLanes::append reads of a row: the episode ring alone (the transition itself goes to the replay ring)
-struct EpisodeRow {
-  int64_t* out_action = nullptr;
-  float *out_reward = nullptr, *out_mask = nullptr;
-  double* ep_ring;
-  int64_t horizon, ring_cap;
-  int n_env = 1;
-};
-
 template <int H, int GATE, int HEAD>
 __global__ void __launch_bounds__(256)
 dist_mlp_act_kernel(dra_dist_mlp_net net, dra_dqn_mlp_act_io io) {

@@ -16,10 +16,11 @@
 // Both are q_mlp.hip's kernels with the replay between them: latency-bound chains over a few rows, plain fp32 VALU code, weights in
 // LDS once per launch, activations TRANSPOSED and read 16 bytes at a time, every dot product one FMA chain in ascending k.  The
 // update walks the rows in blocks of 64; every gradient element is owned by ONE thread that adds its rows in ascending order:
-// no atomics, the same bits on every launch.  Weights<H>, gate_back and block_layer are q_mlp.hip's, COPIED (DESIGN.md 4.15:
-// lifting them into a header is a change of its own; mlp_rollout.h's banner says what sharing them has cost before).
+// no atomics, the same bits on every launch.  The acting kernel's weights are cartpole_rollout.h's QNetWeights<H>; the update's
+// layers, gather and head forward are mlp_update_block.h's.  The staging of the two networks' bodies and the gradient bookkeeping
+// are written in place (mlp_rollout.h's banner: the figures).
 #include "common.h"
-#include "cartpole_rollout.h"
+#include "mlp_update_block.h"
 #include <math.h>
 
 namespace {
@@ -28,37 +29,9 @@ namespace {
 constexpr int kMaxK = 8;         // transitions of one launch
 constexpr int kNP = 8;           // row stride of the single environment's transposed activations (hidden_layer's row block)
 
-// one network's weights in LDS, in floats; every region starts at a multiple of 4 floats (16 bytes)
-__host__ __device__ constexpr size_t weight_floats(int H) {
-  return body_weight_floats(H) + round_up4(kA * (H + 1)) + 4;
-}
 __host__ __device__ constexpr size_t act_lds_floats(int H) {
-  return weight_floats(H) + 4 + (size_t)kS * kNP + 2 * (size_t)H * kNP;      // the weights, q [A], x^T [S][NP], h1^T, h2^T [H][NP]
+  return q_net_weight_floats(H) + 4 + (size_t)kS * kNP + 2 * (size_t)H * kNP;      // the weights, q [A], x^T [S][NP], h1^T, h2^T [H][NP]
 }
-
-template <int H>
-struct Weights {
-  BodyWeights<H> body;
-  float *wq, *bq;                           // the head [A][H + 1], its bias
-  __device__ explicit Weights(float* base) : body(base), wq(base + body_weight_floats(H)), bq(wq + round_up4(kA * (H + 1))) {}
-  __device__ __forceinline__ void stage(const float* __restrict__ P, const dra_q_mlp_net& net, int tid) const {
-    body.stage(P, net, tid);
-    for (int i = tid; i < kA * H; i += 256) {
-      const int c = i / H, k = i - c * H;
-      wq[c * (H + 1) + k] = P[net.wq + c * H + k];
-    }
-    if (tid < kA) bq[tid] = P[net.bq + tid];
-  }
-};
-
-// what CartPoleLanes::append reads of a row: the episode ring alone (the transition itself goes to the replay ring)
-struct EpisodeRow {
-  int64_t* out_action = nullptr;
-  float *out_reward = nullptr, *out_mask = nullptr;
-  double* ep_ring;
-  int64_t horizon, ring_cap;
-  int n_env = 1;
-};
 
 template <int H, int GATE>
 __global__ void __launch_bounds__(256)
@@ -67,8 +40,8 @@ dqn_mlp_act_kernel(dra_q_mlp_net net, dra_dqn_mlp_act_io io) {
   const int tid = threadIdx.x;
   const int K = io.t_len;
 
-  const Weights<H> online(lds);
-  float* sQ = lds + weight_floats(H);                 // [A] (+ pad)
+  const QNetWeights<H> online(lds);
+  float* sQ = lds + q_net_weight_floats(H);                 // [A] (+ pad)
   float* sXT = sQ + 4;                                // [S][NP]
   float* sH1T = sXT + kS * kNP;                       // [H][NP]
   float* sH2T = sH1T + H * kNP;                       // [H][NP]
@@ -155,77 +128,6 @@ __host__ __device__ constexpr size_t update_lds_floats(int H) {
          + (size_t)kS * H + (size_t)H * H + 2 * (size_t)H + (size_t)kA * H + 4        // target: W1^T, W2^T, b1, b2, head, its bias
          + 6 * kUB + 4 * kUB                                                          // idx, reward, mask, d, action, loss; the two q_next
          + (size_t)kS * kLD + 3 * (size_t)H * kLD;                                    // x^T, h1^T, h2^T (later dz1^T), dz2^T
-}
-
-template <int GATE>
-__device__ __forceinline__ float gate_back(float g, float h) {       // g * gate'(pre-activation), from the stored post-activation h
-  if constexpr (GATE == kGateRelu) return h > 0.f ? g : 0.f;
-  else return g * (1.f - h * h);
-}
-
-// hidden_layer (mlp_rollout.h) over one block of kUB rows with the row stride kLD.  BACK false: out = gate(b + in W); BACK true
-// (b unused): out = (in W) * gate'(post), post^T the stored post-activations.
-template <int H, int GATE, bool BACK>
-__device__ __forceinline__ void block_layer(const float* __restrict__ inT, const float* __restrict__ wT, const float* __restrict__ b,
-                                            const float* __restrict__ postT, float* __restrict__ outT, int K, int tid) {
-  constexpr int G = 256 / H;
-  const int u = tid & (H - 1), rg = tid / H;
-  const float bias = BACK ? 0.f : b[u];
-  for (int e0 = rg * kRB; e0 < kUB; e0 += G * kRB) {
-    float acc[kRB];
-#pragma unroll
-    for (int r = 0; r < kRB; ++r) acc[r] = 0.f;
-#pragma unroll 4
-    for (int k = 0; k < K; ++k) {
-      const float w = wT[k * H + u];
-      const f32x4 x0 = *reinterpret_cast<const f32x4*>(&inT[k * kLD + e0]);
-      const f32x4 x1 = *reinterpret_cast<const f32x4*>(&inT[k * kLD + e0 + 4]);
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        acc[r] = fmaf(x0[r], w, acc[r]);
-        acc[4 + r] = fmaf(x1[r], w, acc[4 + r]);
-      }
-    }
-    f32x4 y0, y1;
-    if constexpr (BACK) {
-      const f32x4 p0 = *reinterpret_cast<const f32x4*>(&postT[u * kLD + e0]);
-      const f32x4 p1 = *reinterpret_cast<const f32x4*>(&postT[u * kLD + e0 + 4]);
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        y0[r] = gate_back<GATE>(acc[r], p0[r]);
-        y1[r] = gate_back<GATE>(acc[4 + r], p1[r]);
-      }
-    } else {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        y0[r] = gate_f<GATE>(acc[r] + bias);
-        y1[r] = gate_f<GATE>(acc[4 + r] + bias);
-      }
-    }
-    *reinterpret_cast<f32x4*>(&outT[u * kLD + e0]) = y0;
-    *reinterpret_cast<f32x4*>(&outT[u * kLD + e0 + 4]) = y1;
-  }
-}
-
-// x^T of a block from the ring's fp64 frames at sIdx[row] + shift (256 threads: 64 rows x 4), zero behind the last row
-__device__ __forceinline__ void gather_states(const double* __restrict__ frames, const int* __restrict__ sIdx, int shift, int rows,
-                                              float* __restrict__ sXT, int tid) {
-  const int row = tid / kS, j = tid % kS;
-  sXT[j * kLD + row] = row < rows ? (float)frames[((int64_t)sIdx[row] + shift) * kS + j] : 0.f;
-}
-
-// q [A][kUB] of one block from h2^T: one output per thread, tid < A * kUB
-template <int H>
-__device__ __forceinline__ void block_head(const float* __restrict__ sH2T, const float* __restrict__ wq, const float* __restrict__ bq,
-                                           float* __restrict__ out, int tid) {
-  if (tid < kA * kUB) {
-    const int a = tid / kUB, r = tid % kUB;
-    const float* wr = wq + a * H;
-    float acc = 0.f;
-#pragma unroll 8
-    for (int k = 0; k < H; ++k) acc = fmaf(sH2T[k * kLD + r], wr[k], acc);
-    out[tid] = acc + bq[a];
-  }
 }
 
 template <int H, int GATE>
@@ -331,20 +233,20 @@ dqn_mlp_update_kernel(dra_q_mlp_net net, dra_dqn_mlp_update_io io) {
     }
     __syncthreads();
     // ---- the next states: the TARGET network's q, and with double_q the online network's
-    gather_states(io.ring_frames, sIdx, 1, rows, sXT, tid);
+    gather_states<kUB>(io.ring_frames, sIdx, 1, rows, sXT, tid);
     __syncthreads();
-    block_layer<H, GATE, false>(sXT, tW1, tB1, nullptr, sH1T, kS, tid);
+    block_layer<H, GATE, false, kUB>(sXT, tW1, tB1, nullptr, sH1T, kS, tid);
     __syncthreads();
-    block_layer<H, GATE, false>(sH1T, tW2, tB2, nullptr, sH2T, H, tid);
+    block_layer<H, GATE, false, kUB>(sH1T, tW2, tB2, nullptr, sH2T, H, tid);
     __syncthreads();
-    block_head<H>(sH2T, tWq, tBq, sQN, tid);
+    block_head<H, kUB>(sH2T, tWq, tBq, sQN, kA, kUB, tid);
     if (double_q) {
       __syncthreads();
-      block_layer<H, GATE, false>(sXT, sW1, sB1, nullptr, sH1T, kS, tid);
+      block_layer<H, GATE, false, kUB>(sXT, sW1, sB1, nullptr, sH1T, kS, tid);
       __syncthreads();
-      block_layer<H, GATE, false>(sH1T, sW2, sB2, nullptr, sH2T, H, tid);
+      block_layer<H, GATE, false, kUB>(sH1T, sW2, sB2, nullptr, sH2T, H, tid);
       __syncthreads();
-      block_head<H>(sH2T, sWq, sBq, sQO, tid);
+      block_head<H, kUB>(sH2T, sWq, sBq, sQO, kA, kUB, tid);
     }
     __syncthreads();
     // ---- q_target = r + ((gamma q_next) m) (DQN_agent.py:94), kept by the row's thread
@@ -358,11 +260,11 @@ dqn_mlp_update_kernel(dra_q_mlp_net net, dra_dqn_mlp_update_io io) {
       io.out_q_target[r0 + tid] = tgt;
     }
     // ---- the states: the online forward (x^T's and h^T's readers are behind the barrier above)
-    gather_states(io.ring_frames, sIdx, 0, rows, sXT, tid);
+    gather_states<kUB>(io.ring_frames, sIdx, 0, rows, sXT, tid);
     __syncthreads();
-    block_layer<H, GATE, false>(sXT, sW1, sB1, nullptr, sH1T, kS, tid);
+    block_layer<H, GATE, false, kUB>(sXT, sW1, sB1, nullptr, sH1T, kS, tid);
     __syncthreads();
-    block_layer<H, GATE, false>(sH1T, sW2, sB2, nullptr, sH2T, H, tid);
+    block_layer<H, GATE, false, kUB>(sH1T, sW2, sB2, nullptr, sH2T, H, tid);
     __syncthreads();
     // ---- q of the action taken, dq = (q_a - q_target) / B, the loss
     if (tid < kUB) {
@@ -413,7 +315,7 @@ dqn_mlp_update_kernel(dra_q_mlp_net net, dra_dqn_mlp_update_io io) {
         for (int c = 0; c < 4; ++c) gB2 += dz[c];
       }
     }
-    block_layer<H, GATE, true>(sG2T, sW2N, nullptr, sH1T, sH2T, H, tid);
+    block_layer<H, GATE, true, kUB>(sG2T, sW2N, nullptr, sH1T, sH2T, H, tid);
     __syncthreads();
     // ---- dW1 += dz1 x^T, db1 += dz1
     if (tid < kS * H) {

@@ -1,16 +1,35 @@
 // What the one-workgroup rollout kernels over small MLPs share (a2c_mlp.hip, cat_mlp.hip, q_mlp.hip, oc_mlp.hip): gate codes, row
 // rounding, one hidden layer over TRANSPOSED activations and the launch; ppo_mlp.hip and dpg_mlp.hip take the vector type, the gate
-// codes and softplus_f.  The three cart-pole kernels (cat_mlp.hip, q_mlp.hip, oc_mlp.hip) share more in cartpole_rollout.h: the environment lanes
-// (load, observe, step with the episode-ring append, store), the staging of a two-layer body's weights (BodyWeights<H>), the
-// shape / offset / io checks and the hidden x gate dispatch.
+// codes and softplus_f.  The cart-pole kernels (cat_mlp.hip, q_mlp.hip, oc_mlp.hip, dqn_mlp.hip, dist_mlp.hip) share more in
+// cartpole_rollout.h: the environment lanes (load, observe, step with the episode-ring append, store), the staging of a two-layer
+// body's weights (BodyWeights<H>; with the Q head QNetWeights<H>), the shape / offset / io checks and the hidden x gate dispatch.
+// Their whole-update kernels share the row-block pieces in mlp_update_block.h.
 //
 // Shared or not is decided by the generated code and the kernel trace, not by taste: a __forceinline__ function is optimised on
-// its own before it is inlined, and these kernels sit at the edge of the SGPR file (DESIGN.md 4.13 has every figure).  Shared:
-// the cart-pole pair above, at equal VGPRs / scratch / occupancy and SGPR spills at or below the text in place.  NOT shared:
-//   q_mlp_update_kernel's weight staging (through BodyWeights<H> its VGPRs go 71 -> 78 at H 16 tanh, occupancy 7 -> 6);
-//   q_mlp.hip's block_layer (folded into hidden_layer, q_mlp_update_kernel<16, tanh> goes from 71 to 77 VGPRs, 7 -> 6 waves);
-//   oc_mlp.hip's update restates that staging and block_layer for the same reason (its figures: DESIGN.md 4.14);
-//   the heads' dot products: each kernel has its own outputs per thread.
+// its own before it is inlined, and these kernels sit at the edge of the SGPR file (DESIGN.md 4.13 has every figure).  The bar for
+// every instantiation of every kernel, against the text in place: scratch 0, no VGPR spills, occupancy not below, VGPRs not above,
+// SGPR spills not above.  Shared at that bar:
+//   the cart-pole rollout pieces above;
+//   gate_back / block_layer / gather_states / block_head at row blocks 16 and 64 (H 32 / 64 equal; at H 16 x 64 rows a thread now
+//     carries 4 rows and no thread idles: q_mlp_update_kernel 65 / 71 -> 62 / 60 VGPRs (relu / tanh), 7 -> 8 waves; oc_mlp_update_kernel
+//     86 / 88 -> 66 / 68, 5 -> 7; dqn_mlp_update_kernel 69 / 96 -> 64 / 70, 7 / 5 -> 8 / 7);
+//   UpdateBody<H> (the online body's LDS layout and staging) in q_mlp_update_kernel and oc_mlp_update_kernel.
+// NOT shared, each written in place in the four update kernels:
+//   the body's gradient bookkeeping (owner indices, dW2 / db2 / dW1 / db1 accumulators, their stores).  As one struct with the
+//     same loop text it met the register bar everywhere but in dist_mlp_update_kernel's stores (H 16: 115 / 103 / 115 / 105 -> 117 /
+//     104 / 117 / 109 VGPRs), yet its row loops come out with the `k2 == 0` / `j1 == 0` sums as selects and one more branch, and
+//     the agents were SLOWER by more than the parent's spread (tools/bench_agents.py, medians of 3 alternating repeats, k
+//     env-steps/s, parent -> struct: option_critic_feature 235.5 -> 234.8; then, with oc_mlp in place again, n_step_dqn_feature
+//     282.5 -> 281.9 and quantile_regression_dqn_feature 45.39 -> 45.06);
+//   dqn_mlp_update_kernel's and dist_mlp_update_kernel's staging of TWO networks' bodies: through a form of UpdateBody that also
+//     holds the target's set (with or without the fill loops), dqn_mlp_update_kernel<64> goes 92 / 118 -> 96 / 122 VGPRs and
+//     dist_mlp_update_kernel's SGPR spills at H 16 go 20 / 2 / 20 -> 25 / 31 / 32 (relu c51 / relu qr / tanh c51);
+//   an update's staging through the rollout's BodyWeights<H> (q_mlp_update_kernel<16, tanh> went 71 -> 78 VGPRs, 7 -> 6 waves);
+//   block_layer folded into hidden_layer (q_mlp_update_kernel<16, tanh> went 71 -> 77 VGPRs, 7 -> 6 waves);
+//   the heads' dot products and gradients: each kernel has its own outputs per thread.
+// What moved such figures in these kernels and is worth knowing before the next attempt: the order of a struct's members (it is
+// the order of the values the register allocator sees), and an LDS pointer derived from a size_t count instead of continuing the
+// chain of int offsets (q_mlp_update_kernel<32, tanh> 95 -> 106 VGPRs, 5 -> 4 waves).
 #pragma once
 #include "common.h"
 #include <math.h>

@@ -26,10 +26,10 @@
 // decides for one row with its arrays in registers and optional outputs; here 64 lanes decide at once with their rows in LDS (the
 // option count is a run-time value: per-lane arrays indexed by it would live in scratch) and carry prev_option / is_initial in
 // registers across the steps.  What both share is what fixes the bits: inv_cdf_row (rollout_roles.h) and categorical_row
-// (common.h) are called, not rewritten.  block_layer / gate_back are q_mlp.hip's, restated for mlp_rollout.h's reason: a shared
-// __forceinline__ body has cost q_mlp_update_kernel occupancy before.
+// (common.h) are called, not rewritten.  The update's body staging and layers are mlp_update_block.h's; its gradient bookkeeping
+// is written in place (mlp_rollout.h's banner: the measurements).
 #include "common.h"
-#include "cartpole_rollout.h"
+#include "mlp_update_block.h"
 #include "rollout_roles.h"
 #include <math.h>
 
@@ -222,60 +222,10 @@ constexpr int kLD = kUB + 4;     // row stride of the transposed activations: 16
 constexpr int kMaxRows = 1024;   // the per-row terms stay in LDS
 
 __host__ __device__ constexpr size_t update_lds_floats(int H) {
-  return (size_t)kS * H + 2 * (size_t)H * H + 2 * (size_t)H + (size_t)kMaxJ * H      // W1^T, W2^T, W2, b1, b2, the heads' rows
+  return update_body_floats(H) + (size_t)kMaxJ * H                                   // W1^T, W2^T, W2, b1, b2; the heads' rows
          + 5 * (size_t)kMaxRows + 16                                                 // ret / g, gz, dlogit 0 / 1, option | prev; loss partials
          + (size_t)kMaxJ * kLD                                                       // the block's coefficients [output row][row]
          + (size_t)kS * kLD + 3 * (size_t)H * kLD;                                   // x^T, h1^T, h2^T (later dz1^T), dz2^T
-}
-
-template <int GATE>
-__device__ __forceinline__ float gate_back(float g, float h) {       // g * gate'(pre-activation), from the stored post-activation h
-  if constexpr (GATE == kGateRelu) return h > 0.f ? g : 0.f;
-  else return g * (1.f - h * h);
-}
-
-// q_mlp.hip's block_layer: hidden_layer over one block of kUB rows with the row stride kLD.  BACK false: out = gate(b + in W);
-// BACK true (b unused): out = (in W) * gate'(post), post^T the stored post-activations.
-template <int H, int GATE, bool BACK>
-__device__ __forceinline__ void block_layer(const float* __restrict__ inT, const float* __restrict__ wT, const float* __restrict__ b,
-                                            const float* __restrict__ postT, float* __restrict__ outT, int K, int tid) {
-  constexpr int G = 256 / H;
-  const int u = tid & (H - 1), rg = tid / H;
-  const float bias = BACK ? 0.f : b[u];
-  for (int e0 = rg * kRB; e0 < kUB; e0 += G * kRB) {
-    float acc[kRB];
-#pragma unroll
-    for (int r = 0; r < kRB; ++r) acc[r] = 0.f;
-#pragma unroll 4
-    for (int k = 0; k < K; ++k) {
-      const float w = wT[k * H + u];
-      const f32x4 x0 = *reinterpret_cast<const f32x4*>(&inT[k * kLD + e0]);
-      const f32x4 x1 = *reinterpret_cast<const f32x4*>(&inT[k * kLD + e0 + 4]);
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        acc[r] = fmaf(x0[r], w, acc[r]);
-        acc[4 + r] = fmaf(x1[r], w, acc[4 + r]);
-      }
-    }
-    f32x4 y0, y1;
-    if constexpr (BACK) {
-      const f32x4 p0 = *reinterpret_cast<const f32x4*>(&postT[u * kLD + e0]);
-      const f32x4 p1 = *reinterpret_cast<const f32x4*>(&postT[u * kLD + e0 + 4]);
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        y0[r] = gate_back<GATE>(acc[r], p0[r]);
-        y1[r] = gate_back<GATE>(acc[4 + r], p1[r]);
-      }
-    } else {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        y0[r] = gate_f<GATE>(acc[r] + bias);
-        y1[r] = gate_f<GATE>(acc[4 + r] + bias);
-      }
-    }
-    *reinterpret_cast<f32x4*>(&outT[u * kLD + e0]) = y0;
-    *reinterpret_cast<f32x4*>(&outT[u * kLD + e0 + 4]) = y1;
-  }
 }
 
 template <int H, int GATE>
@@ -290,12 +240,8 @@ oc_mlp_update_kernel(dra_oc_mlp_net net, dra_oc_mlp_update_io io) {
   const int OA = O * kA, J = 2 * O + OA;   // the heads' rows HERE in the order q [O], pi [O A], beta [O]: the order dh2 adds them in
   const float* __restrict__ P = net.param;
 
-  float* sW1 = lds;                       // [S][H]  (transposed: [k][unit])
-  float* sW2 = sW1 + kS * H;              // [H][H]  (transposed)
-  float* sW2N = sW2 + H * H;              // [H][H]  (as stored, [unit][k]: the backward's "transposed" operand)
-  float* sB1 = sW2N + H * H;              // [H]
-  float* sB2 = sB1 + H;                   // [H]
-  float* sWh = sB2 + H;                   // [J][H]: fc_q, fc_pi, fc_beta as stored
+  const UpdateBody<H> w(lds);             // W1^T, W2^T, W2 as stored, b1, b2
+  float* sWh = w.head;                    // [J][H]: fc_q, fc_pi, fc_beta as stored
   float* sRet = sWh + kMaxJ * H;          // [R]: the returns, then g = (q[option] - ret) / R of the row
   float* sGz = sRet + kMaxRows;           // [R]: dz_beta at prev_option
   float* sDl0 = sGz + kMaxRows;           // [R]: dlogit of action 0 / 1 of the chosen option
@@ -309,19 +255,7 @@ oc_mlp_update_kernel(dra_oc_mlp_net net, dra_oc_mlp_update_io io) {
   float* sG2T = sH2T + H * kLD;           // [H][kLD]: dz2^T
   float* sG = sRet;
 
-  for (int i = tid; i < kS * H; i += 256) {
-    const int k = i / H, u = i - k * H;
-    sW1[i] = P[net.w1 + u * kS + k];
-  }
-  for (int i = tid; i < H * H; i += 256) {
-    const int k = i / H, u = i - k * H;
-    sW2[i] = P[net.w2 + u * H + k];
-    sW2N[i] = P[net.w2 + i];
-  }
-  for (int i = tid; i < H; i += 256) {
-    sB1[i] = P[net.b1 + i];
-    sB2[i] = P[net.b2 + i];
-  }
+  w.stage(net, tid);
   for (int i = tid; i < J * H; i += 256) {
     const int j = i / H;
     sWh[i] = P[j < O ? net.wq + i : (j < O + OA ? net.wp + i - O * H : net.wb + i - (O + OA) * H)];
@@ -418,9 +352,9 @@ oc_mlp_update_kernel(dra_oc_mlp_net net, dra_oc_mlp_update_io io) {
       sC[j * kLD + c] = v;
     }
     __syncthreads();
-    block_layer<H, GATE, false>(sXT, sW1, sB1, nullptr, sH1T, kS, tid);
+    block_layer<H, GATE, false, kUB>(sXT, w.w1, w.b1, nullptr, sH1T, kS, tid);
     __syncthreads();
-    block_layer<H, GATE, false>(sH1T, sW2, sB2, nullptr, sH2T, H, tid);
+    block_layer<H, GATE, false, kUB>(sH1T, w.w2, w.b2, nullptr, sH2T, H, tid);
     __syncthreads();
     // ---- dz2 = (g Wq[o] + sum_a dlogit_a Wp[o A + a] + gz Wb[prev]) gate'(h2); the heads' gradient
     for (int i = tid; i < H * kUB; i += 256) {
@@ -468,7 +402,7 @@ oc_mlp_update_kernel(dra_oc_mlp_net net, dra_oc_mlp_update_io io) {
         for (int c = 0; c < 4; ++c) gB2 += dz[c];
       }
     }
-    block_layer<H, GATE, true>(sG2T, sW2N, nullptr, sH1T, sH2T, H, tid);
+    block_layer<H, GATE, true, kUB>(sG2T, w.w2n, nullptr, sH1T, sH2T, H, tid);
     __syncthreads();
     // ---- dW1 += dz1 x^T, db1 += dz1
     if (tid < kS * H) {

@@ -12,40 +12,23 @@
 //                          optimiser's flat gradient buffer at the parameters' own offsets.
 //
 // Both are chains of dependent layers over a few rows: latency-bound, nothing to spread over 256 CUs.  Plain fp32 VALU code as in
-// cat_mlp.hip (the rollout's environment lanes and body staging ARE cat_mlp.hip's: cartpole_rollout.h): weights are copied to LDS once per launch, activations are kept TRANSPOSED ([unit][row]) and read 16 bytes at a
-// time, every dot product is one FMA chain in ascending k.  The update walks the rows in blocks of 64; every gradient element is
-// owned by ONE thread that adds its rows in ascending order, block after block: no atomics, the same bits on every launch.
+// cat_mlp.hip (the rollout's environment lanes and weight staging ARE cartpole_rollout.h's): weights are copied to LDS once per
+// launch, activations are kept TRANSPOSED ([unit][row]) and read 16 bytes at a time, every dot product is one FMA chain in
+// ascending k.  The update walks the rows in blocks of 64 (its body staging and layers are mlp_update_block.h's); every gradient
+// element is owned by ONE thread that adds its rows in ascending order, block after block: no atomics, the same bits on every
+// launch.
 #include "common.h"
-#include "cartpole_rollout.h"
+#include "mlp_update_block.h"
 #include <math.h>
 
 namespace {
 
 // ---------------------------------------------------------------------------------------------------- the rollout
-// one network's weights in LDS, in floats; every region starts at a multiple of 4 floats (16 bytes)
-__host__ __device__ constexpr size_t weight_floats(int H) {
-  return body_weight_floats(H) + round_up4(kA * (H + 1)) + 4;
-}
 __host__ __device__ constexpr size_t rollout_lds_floats(int H, int N) {
-  return 2 * weight_floats(H)                                            // online, target
+  return 2 * q_net_weight_floats(H)                                            // online, target
          + round_up4(kA * kMaxN)                                         // q [N][A]
          + (size_t)kS * round_up8(N) + 2 * (size_t)H * round_up8(N);     // x^T [S][NP], h1^T, h2^T [H][NP]
 }
-
-template <int H>
-struct Weights {
-  BodyWeights<H> body;
-  float *wq, *bq;                           // the head [A][H + 1], its bias
-  __device__ explicit Weights(float* base) : body(base), wq(base + body_weight_floats(H)), bq(wq + round_up4(kA * (H + 1))) {}
-  __device__ __forceinline__ void stage(const float* __restrict__ P, const dra_q_mlp_net& net, int tid) const {
-    body.stage(P, net, tid);
-    for (int i = tid; i < kA * H; i += 256) {
-      const int c = i / H, k = i - c * H;
-      wq[c * (H + 1) + k] = P[net.wq + c * H + k];
-    }
-    if (tid < kA) bq[tid] = P[net.bq + tid];
-  }
-};
 
 template <int H, int GATE>
 __global__ void __launch_bounds__(256)
@@ -54,8 +37,8 @@ q_mlp_rollout_kernel(dra_q_mlp_net net, dra_q_mlp_rollout_io io) {
   const int tid = threadIdx.x;
   const int N = io.n_env, T = io.t_len, NP = round_up8(N);
 
-  const Weights<H> online(lds), target(lds + weight_floats(H));
-  float* sQ = lds + 2 * weight_floats(H);             // [N][A]
+  const QNetWeights<H> online(lds), target(lds + q_net_weight_floats(H));
+  float* sQ = lds + 2 * q_net_weight_floats(H);             // [N][A]
   float* sXT = sQ + round_up4(kA * kMaxN);            // [S][NP]
   float* sH1T = sXT + kS * NP;                        // [H][NP]
   float* sH2T = sH1T + H * NP;                        // [H][NP]
@@ -75,7 +58,7 @@ q_mlp_rollout_kernel(dra_q_mlp_net net, dra_q_mlp_rollout_io io) {
   const float reward = (float)(1.0 * io.reward_coef);
 
   for (int t = 0; t <= T; ++t) {
-    const Weights<H>& w = t < T ? online : target;          // NStepDQN_agent.py:56: the bootstrap is the TARGET network's
+    const QNetWeights<H>& w = t < T ? online : target;          // NStepDQN_agent.py:56: the bootstrap is the TARGET network's
     if (env_lane) lanes.observe(sXT, NP, io.out_state, N, T, t, tid);
     __syncthreads();
     hidden_layer<H, GATE, 256>(sXT, w.body.w1, w.body.b1, sH1T, kS, NP, tid);
@@ -123,59 +106,9 @@ constexpr int kLD = kUB + 4;     // row stride of the transposed activations: 16
 constexpr int kMaxRows = 1024;   // ret [rows] stays in LDS
 
 __host__ __device__ constexpr size_t update_lds_floats(int H) {
-  return (size_t)kS * H + 2 * (size_t)H * H + 2 * (size_t)H + (size_t)kA * H + 4      // W1^T, W2^T, W2, b1, b2, head, its bias
+  return update_body_floats(H) + (size_t)kA * H + 4                                   // W1^T, W2^T, W2, b1, b2; the head, its bias
          + kMaxRows + 3 * kUB                                                         // ret, d, action, the loss partials
          + (size_t)kS * kLD + 3 * (size_t)H * kLD;                                    // x^T, h1^T, h2^T (later dz1^T), dz2^T
-}
-
-template <int GATE>
-__device__ __forceinline__ float gate_back(float g, float h) {       // g * gate'(pre-activation), from the stored post-activation h
-  if constexpr (GATE == kGateRelu) return h > 0.f ? g : 0.f;
-  else return g * (1.f - h * h);
-}
-
-// hidden_layer (mlp_rollout.h) over one block of kUB rows with the row stride kLD.  BACK false: out = gate(b + in W); BACK true
-// (b unused): out = (in W) * gate'(post), post^T the stored post-activations.  Not folded into hidden_layer: mlp_rollout.h's banner.
-template <int H, int GATE, bool BACK>
-__device__ __forceinline__ void block_layer(const float* __restrict__ inT, const float* __restrict__ wT, const float* __restrict__ b,
-                                            const float* __restrict__ postT, float* __restrict__ outT, int K, int tid) {
-  constexpr int G = 256 / H;
-  const int u = tid & (H - 1), rg = tid / H;
-  const float bias = BACK ? 0.f : b[u];
-  for (int e0 = rg * kRB; e0 < kUB; e0 += G * kRB) {
-    float acc[kRB];
-#pragma unroll
-    for (int r = 0; r < kRB; ++r) acc[r] = 0.f;
-#pragma unroll 4
-    for (int k = 0; k < K; ++k) {
-      const float w = wT[k * H + u];
-      const f32x4 x0 = *reinterpret_cast<const f32x4*>(&inT[k * kLD + e0]);
-      const f32x4 x1 = *reinterpret_cast<const f32x4*>(&inT[k * kLD + e0 + 4]);
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        acc[r] = fmaf(x0[r], w, acc[r]);
-        acc[4 + r] = fmaf(x1[r], w, acc[4 + r]);
-      }
-    }
-    f32x4 y0, y1;
-    if constexpr (BACK) {
-      const f32x4 p0 = *reinterpret_cast<const f32x4*>(&postT[u * kLD + e0]);
-      const f32x4 p1 = *reinterpret_cast<const f32x4*>(&postT[u * kLD + e0 + 4]);
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        y0[r] = gate_back<GATE>(acc[r], p0[r]);
-        y1[r] = gate_back<GATE>(acc[4 + r], p1[r]);
-      }
-    } else {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        y0[r] = gate_f<GATE>(acc[r] + bias);
-        y1[r] = gate_f<GATE>(acc[4 + r] + bias);
-      }
-    }
-    *reinterpret_cast<f32x4*>(&outT[u * kLD + e0]) = y0;
-    *reinterpret_cast<f32x4*>(&outT[u * kLD + e0 + 4]) = y1;
-  }
 }
 
 template <int H, int GATE>
@@ -188,12 +121,8 @@ q_mlp_update_kernel(dra_q_mlp_net net, dra_q_mlp_update_io io) {
   const int N = io.n_env, T = io.t_len, R = T * N;
   const float* __restrict__ P = net.param;
 
-  float* sW1 = lds;                       // [S][H]  (transposed: [k][unit])
-  float* sW2 = sW1 + kS * H;              // [H][H]  (transposed)
-  float* sW2N = sW2 + H * H;              // [H][H]  (as stored, [unit][k]: the backward's "transposed" operand)
-  float* sB1 = sW2N + H * H;              // [H]
-  float* sB2 = sB1 + H;                   // [H]
-  float* sWq = sB2 + H;                   // [A][H]
+  const UpdateBody<H> w(lds);             // W1^T, W2^T, W2 as stored, b1, b2
+  float* sWq = w.head;                    // [A][H]
   float* sBq = sWq + kA * H;              // [A] (+ pad)
   float* sRet = sBq + 4;                  // [R]
   float* sD = sRet + kMaxRows;            // [kUB]: (q_a - ret) / R of the block's rows, 0 behind the last row
@@ -204,19 +133,7 @@ q_mlp_update_kernel(dra_q_mlp_net net, dra_q_mlp_update_io io) {
   float* sH2T = sH1T + H * kLD;           // [H][kLD]: h2^T, then dz1^T
   float* sG2T = sH2T + H * kLD;           // [H][kLD]: dz2^T
 
-  for (int i = tid; i < kS * H; i += 256) {
-    const int k = i / H, u = i - k * H;
-    sW1[i] = P[net.w1 + u * kS + k];
-  }
-  for (int i = tid; i < H * H; i += 256) {
-    const int k = i / H, u = i - k * H;
-    sW2[i] = P[net.w2 + u * H + k];
-    sW2N[i] = P[net.w2 + i];
-  }
-  for (int i = tid; i < H; i += 256) {
-    sB1[i] = P[net.b1 + i];
-    sB2[i] = P[net.b2 + i];
-  }
+  w.stage(net, tid);
   for (int i = tid; i < kA * H; i += 256) sWq[i] = P[net.wq + i];
   if (tid < kA) sBq[tid] = P[net.bq + tid];
   // ---- returns: NStepDQN_agent.py:58-60, one environment per thread, backwards from the bootstrap
@@ -251,9 +168,9 @@ q_mlp_update_kernel(dra_q_mlp_net net, dra_q_mlp_update_io io) {
       sXT[j * kLD + row] = r0 + row < R ? io.state[(int64_t)(r0 + row) * kS + j] : 0.f;
     }
     __syncthreads();
-    block_layer<H, GATE, false>(sXT, sW1, sB1, nullptr, sH1T, kS, tid);
+    block_layer<H, GATE, false, kUB>(sXT, w.w1, w.b1, nullptr, sH1T, kS, tid);
     __syncthreads();
-    block_layer<H, GATE, false>(sH1T, sW2, sB2, nullptr, sH2T, H, tid);
+    block_layer<H, GATE, false, kUB>(sH1T, w.w2, w.b2, nullptr, sH2T, H, tid);
     __syncthreads();
     // ---- q of the action taken, dq = (q_a - ret) / R, the loss
     if (tid < kUB) {
@@ -306,7 +223,7 @@ q_mlp_update_kernel(dra_q_mlp_net net, dra_q_mlp_update_io io) {
         for (int c = 0; c < 4; ++c) gB2 += dz[c];
       }
     }
-    block_layer<H, GATE, true>(sG2T, sW2N, nullptr, sH1T, sH2T, H, tid);
+    block_layer<H, GATE, true, kUB>(sG2T, w.w2n, nullptr, sH1T, sH2T, H, tid);
     __syncthreads();
     // ---- dW1 += dz1 x^T, db1 += dz1
     if (tid < kS * H) {
