@@ -11,9 +11,8 @@ import ctypes
 import torch
 
 from . import mlp_rollout
-from ._lib import lib
 from .device_env import DeviceContinuousVec
-from .mlp_rollout import GATES, body_params, fc_body, head_out      # noqa: F401  (GATES: this module's public name)
+from .mlp_rollout import GATES, body_params, fc_body, head_out, shape_table      # noqa: F401  (GATES: this module's public name)
 from .support import Config
 
 
@@ -58,9 +57,7 @@ def shape(network):
     return s_dim, a_dim, hidden, gate
 
 
-def supported(state_dim, action_dim, hidden, n_env, gate):
-    """dra_a2c_mlp_supported: the shapes the rollout kernel is built for."""
-    return lib.dra_a2c_mlp_supported.raw(int(state_dim), int(action_dim), int(hidden), int(n_env), int(gate)) == 0
+supported = shape_table('dra_a2c_mlp_supported')      # (state_dim, action_dim, hidden, n_env, gate): the rollout kernel
 
 
 def _fields(net):

@@ -146,6 +146,47 @@ class BaseAgent:
             self.states = self.config.state_normalizer(self.task.reset())
 
 
+def _write_side(filename, suffix, state):
+    """`<filename><suffix>`: the pickle of `state`, what a device path keeps next to the reference's two checkpoint files."""
+    with open(filename + suffix, 'wb') as f:
+        pickle.dump(state, f)
+
+
+def _read_side(filename, suffix):
+    """The dict _write_side left, or None where there is no such file (checkpoints of the reference itself have none)."""
+    if not os.path.isfile(filename + suffix):
+        return None
+    with open(filename + suffix, 'rb') as f:
+        return pickle.load(f)
+
+
+class _DeviceEpisodes:
+    """In front of BaseAgent, for the agents whose training episodes may end on the device (device_env.EpisodeRing): whatever
+    reads the log -- eval_episodes, close, and save in the agents' own methods -- drains the ring first."""
+
+    def _episode_ring(self):
+        """What drains: an EpisodeRing, something with its drain() / episodes(), or None on a path without one."""
+        return self._episodes
+
+    def drain_episodes(self):
+        """EpisodeRing.drain: logs the episodes that ended on the device since the last drain -> their (step, return) pairs."""
+        ring = self._episode_ring()
+        return ring.drain() if ring is not None else []
+
+    def episodes(self):
+        """EpisodeRing.episodes: (step, episodic return) of the training episodes that ended since the previous call."""
+        ring = self._episode_ring()
+        return ring.episodes() if ring is not None else []
+
+    def eval_episodes(self):
+        self.drain_episodes()
+        return super().eval_episodes()
+
+    def close(self):
+        self.drain_episodes()
+        super().close()
+
+
 class BaseActor:
     """BaseAgent.py:108-182 without the process: `step()` returns `sgd_update_frequency`
     transitions, in the order the reference's sync path (`async_actor=False`) produces them."""
@@ -235,7 +276,7 @@ class DQNActor(BaseActor):
         return entry
 
 
-class DQNAgent(BaseAgent):
+class DQNAgent(_DeviceEpisodes, BaseAgent):
     """DQN_agent.py:48-138."""
     ActorCLS = DQNActor
     _feature = None     # dqn_mlp.Step on the cart-pole device path (config.fused_dqn_feature), None on every other path
@@ -486,16 +527,15 @@ class DQNAgent(BaseAgent):
             self._feature.drain()
         BaseAgent.save(self, filename)
         if self._feature is not None:
-            with open(filename + '.envs', 'wb') as f:
-                pickle.dump(self._feature.state_dict(), f)
+            _write_side(filename, '.envs', self._feature.state_dict())
 
     def load(self, filename):
         if self._learner is not None:
             self._learner.synchronize()
         BaseAgent.load(self, filename)
-        if self._feature is not None and os.path.isfile(filename + '.envs'):
-            with open(filename + '.envs', 'rb') as f:
-                self._feature.load_state_dict(pickle.load(f))
+        state = _read_side(filename, '.envs') if self._feature is not None else None
+        if state is not None:
+            self._feature.load_state_dict(state)
         if self._learner is not None:     # parameters changed behind the learner: actor copies are stale
             torch.cuda.synchronize()
             self._learner.invalidate_actor_copy()
@@ -581,20 +621,18 @@ class DQNAgent(BaseAgent):
 
     def eval_episodes(self):
         self.sync_host()
-        self.drain_episodes()
         return super().eval_episodes()
 
-    def drain_episodes(self):
-        """EpisodeRing.drain on the cart-pole device path: logs the episodes that ended on the device since the last drain -> their
-        (step, return) pairs; nothing on every other path."""
-        return self._feature.drain() if getattr(self, '_feature', None) is not None else []
+    def _episode_ring(self):
+        """The cart-pole device path's Step (its drain() runs check() first); None on every other path."""
+        return getattr(self, '_feature', None)
 
     def episodes(self):
-        """EpisodeRing.episodes: (step, episodic return) of the training episodes that ended since the previous call."""
-        if getattr(self, '_feature', None) is None:
+        step = self._episode_ring()
+        if step is None:
             return []
-        self._feature.check()
-        return self._feature.episodes.episodes()
+        step.check()
+        return step.episodes.episodes()
 
     def close(self):
         self.drain_episodes()
@@ -1051,7 +1089,7 @@ def _device_state_fn(agent):
     return norm
 
 
-class A2CAgent(BaseAgent):
+class A2CAgent(_DeviceEpisodes, BaseAgent):
     """A2C_agent.py:12-64."""
 
     def __init__(self, config):
@@ -1090,13 +1128,8 @@ class A2CAgent(BaseAgent):
         self._cat_rollout = mlp_rollout.adopt(self, cat_mlp.Rollout)
 
     def close(self):
-        self.drain_episodes()
-        close_obj(self.task)
+        super().close()
         self.dp.close()
-
-    def eval_episodes(self):
-        self.drain_episodes()
-        return BaseAgent.eval_episodes(self)
 
     def save(self, filename):
         """The reference's two files (BaseAgent.py:24-27); on the device rollout paths also `<filename>.sampler`: seed and position
@@ -1108,14 +1141,12 @@ class A2CAgent(BaseAgent):
             state = self.dp.sampler_state()
             if self._cat_rollout is not None:
                 state.update(self._episodes.state_dict())
-            with open(filename + '.sampler', 'wb') as f:
-                pickle.dump(state, f)
+            _write_side(filename, '.sampler', state)
 
     def load(self, filename):
         BaseAgent.load(self, filename)
-        if self._device_rollout() is not None and os.path.isfile(filename + '.sampler'):
-            with open(filename + '.sampler', 'rb') as f:
-                state = pickle.load(f)
+        state = _read_side(filename, '.sampler') if self._device_rollout() is not None else None
+        if state is not None:
             self.dp.load_sampler_state(state, Config.DEVICE)
             self._noise_seed = self.dp.noise_seed
             if self._cat_rollout is not None:
@@ -1123,13 +1154,6 @@ class A2CAgent(BaseAgent):
 
     # -- a2c_feature over device-resident cart-pole environments: device_env.EpisodeRing ------------------------------------
     _cat_steps = property(lambda self: self._episodes.steps)      # (agent steps on the device path)
-    def drain_episodes(self):
-        """EpisodeRing.drain: logs the episodes that ended on the device since the last drain -> their (step, return) pairs."""
-        return self._episodes.drain()
-
-    def episodes(self):
-        """EpisodeRing.episodes: (step, episodic return) of the training episodes that ended since the previous call."""
-        return self._episodes.episodes()
 
     def _device_rollout(self):
         return self._mlp_rollout or self._cat_rollout
@@ -1290,7 +1314,7 @@ class A2CAgent(BaseAgent):
         self.last_loss = self._learn(seen, actions, values, rewards_l, masks_l)
 
 
-class _TargetRolloutAgent(BaseAgent):
+class _TargetRolloutAgent(_DeviceEpisodes, BaseAgent):
     """What NStepDQNAgent and OptionCriticAgent share: a target network in a flat buffer of its own, over synthetic Atari
     emulators the device path of a pixel_rollout._TargetRollout, and over device-resident cart-poles the step, episode ring and
     save / load of their feature entries (each agent brings its mlp_rollout.Rollout and its _feature_learn)."""
@@ -1331,14 +1355,6 @@ class _TargetRolloutAgent(BaseAgent):
     # mlp_rollout.Rollout (`_feature`, None on every other path) and device_env.EpisodeRing (`_episodes`) --------------------
     _feature = None
 
-    def close(self):
-        self.drain_episodes()
-        BaseAgent.close(self)
-
-    def eval_episodes(self):
-        self.drain_episodes()
-        return BaseAgent.eval_episodes(self)
-
     def _feature_state(self):
         """What `<filename>.envs` holds besides the environments' arrays and the device step counter."""
         return {}
@@ -1354,27 +1370,26 @@ class _TargetRolloutAgent(BaseAgent):
         BaseAgent.save(self, filename)
         if self._feature is not None:
             torch.cuda.current_stream().synchronize()
-            with open(filename + '.envs', 'wb') as f:
-                pickle.dump(dict(self._episodes.state_dict(), step=int(self._feature.step_dev.item()), **self._feature_state()), f)
+            _write_side(filename, '.envs', dict(self._episodes.state_dict(), step=int(self._feature.step_dev.item()), **self._feature_state()))
 
     def load(self, filename):
         BaseAgent.load(self, filename)
-        if self._feature is not None and os.path.isfile(filename + '.envs'):
-            with open(filename + '.envs', 'rb') as f:
-                state = pickle.load(f)
+        state = _read_side(filename, '.envs') if self._feature is not None else None
+        if state is not None:
             self._episodes.load_state_dict(state)
             self._feature.step_dev.fill_(int(state['step']))
             self._load_feature_state(state)
 
     _dev_steps = property(lambda self: self._episodes.steps)      # (agent steps on the device path)
     _step_host = property(lambda self: self._episodes.stamp)      # (the host's copy of the kernel's step counter)
-    def drain_episodes(self):
-        """EpisodeRing.drain: logs the episodes that ended on the device since the last drain -> their (step, return) pairs."""
-        return self._episodes.drain()
 
-    def episodes(self):
-        """EpisodeRing.episodes: (step, episodic return) of the training episodes that ended since the previous call."""
-        return self._episodes.episodes()
+    def _scan_returns(self, b):
+        """The module paths' returns over the buffers `b` a rollout left, by the scan kernel from the target's bootstrap -> [T * N, 1]."""
+        t_len, n = b['action'].shape
+        value = torch.zeros((t_len + 1, n, 1), device=b['reward'].device)
+        value[t_len] = b['bootstrap'].view(n, 1)
+        _, rets = ops.gae(b['reward'].view(t_len, n, 1), b['mask'].view(t_len, n, 1), value, self.config.discount, 1.0, False)
+        return rets.view(t_len * n, 1)
 
     def _step_feature(self):
         """step() over device_env.DeviceCartPoleVec: the host makes the rollout's draws in the reference's order and stages them
@@ -1438,11 +1453,9 @@ class NStepDQNAgent(_TargetRolloutAgent):
             loss = rollout.update(b, config.discount)
         else:       # the module path on the rollout's buffers: returns by the scan kernel, one batched forward, autograd
             t_len, n = b['action'].shape
-            value = torch.zeros((t_len + 1, n, 1), device=b['reward'].device)
-            value[t_len] = b['bootstrap'].view(n, 1)
-            _, rets = ops.gae(b['reward'].view(t_len, n, 1), b['mask'].view(t_len, n, 1), value, config.discount, 1.0, False)
+            rets = self._scan_returns(b)
             q_a = self.network(b['state'].view(t_len * n, -1))['q'].gather(1, b['action'].view(t_len * n, 1))
-            diff = q_a.detach() - rets.view(t_len * n, 1)
+            diff = q_a.detach() - rets
             loss = 0.5 * diff.pow(2).mean()
             self._fused.zero_grad()
             q_a.backward(diff / (t_len * n))
@@ -1560,14 +1573,13 @@ class PPOAgent(BaseAgent):
         noise of the device rollout, without which a restored agent would replay the noise of its first rollouts."""
         BaseAgent.save(self, filename)
         if self.dp.is_main:
-            with open(filename + '.sampler', 'wb') as f:
-                pickle.dump(self.dp.sampler_state(), f)
+            _write_side(filename, '.sampler', self.dp.sampler_state())
 
     def load(self, filename):
         BaseAgent.load(self, filename)
-        if os.path.isfile(filename + '.sampler'):      # (checkpoints of the reference itself have no such file)
-            with open(filename + '.sampler', 'rb') as f:
-                self.dp.load_sampler_state(pickle.load(f), Config.DEVICE)
+        state = _read_side(filename, '.sampler')
+        if state is not None:
+            self.dp.load_sampler_state(state, Config.DEVICE)
             self._noise_seed = self.dp.noise_seed
 
     def _step_device(self):
@@ -2059,10 +2071,7 @@ class OptionCriticAgent(_TargetRolloutAgent):
         else:
             t_len, n = b['action'].shape
             rows = t_len * n
-            value = torch.zeros((t_len + 1, n, 1), device=b['reward'].device)
-            value[t_len] = b['bootstrap'].view(n, 1)
-            _, rets = ops.gae(b['reward'].view(t_len, n, 1), b['mask'].view(t_len, n, 1), value, config.discount, 1.0, False)
-            ret = rets.view(rows, 1)
+            ret = self._scan_returns(b)
             q_s = b['q'].view(rows, -1)
             option, prev, action = b['option'].view(rows, 1), b['prev_option'].view(rows, 1), b['action'].view(rows, 1)
             eps = rollout.eps.view(t_len, 1).expand(t_len, n).reshape(rows, 1)

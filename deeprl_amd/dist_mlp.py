@@ -15,8 +15,7 @@ import ctypes
 import torch
 
 from . import dqn_mlp
-from ._lib import lib, stream_ptr
-from .mlp_rollout import body_params, fc_body, head_out
+from .mlp_rollout import body_params, fc_body, head_out, shape_table
 
 SWITCH = 'fused_dist_feature'
 NETWORK = "CategoricalNet / QuantileNet over a two-layer relu / tanh FCBody with a plain head"
@@ -79,15 +78,9 @@ def _fields(net):
     return list(zip(("w1", "b1", "w2", "b2", "wq", "bq"), body_params(net.body) + [layer.weight, layer.bias]))
 
 
-def supported(state_dim, n_actions, hidden, t_len, gate, head, n_atoms):
-    """dra_dist_mlp_supported: the shapes (t_len = transitions per launch) the acting kernel is built for."""
-    return lib.dra_dist_mlp_supported.raw(int(state_dim), int(n_actions), int(hidden), int(t_len), int(gate), int(head), int(n_atoms)) == 0
-
-
-def update_supported(state_dim, n_actions, hidden, batch, gate, head, n_atoms):
-    """dra_dist_mlp_update_supported: the shapes the update kernel is built for (what fits its workgroup's LDS)."""
-    return lib.dra_dist_mlp_update_supported.raw(int(state_dim), int(n_actions), int(hidden), int(batch), int(gate), int(head),
-                                                 int(n_atoms)) == 0
+# (state_dim, n_actions, hidden, t_len = transitions per launch | batch, gate, head, n_atoms); the update's: what fits its workgroup's LDS
+supported = shape_table('dra_dist_mlp_supported')
+update_supported = shape_table('dra_dist_mlp_update_supported')
 
 
 def support(config, head):
@@ -106,6 +99,7 @@ class Kind(dqn_mlp.Kind):
     # examples.py leaves config.async_actor at the Config's default (True) in both entries, and for these two agents it is a no-op on
     # the host path (agents.py's module docstring): the Step keeps that path's order, so the field does not decide anything here
     ASYNC_ACTOR = True
+    Net, DIMS = Net, ("state_dim", "n_actions", "hidden", "gate", "head", "n_atoms")
     shape, fields = staticmethod(shape), staticmethod(_fields)
     supported, update_supported = staticmethod(supported), staticmethod(update_supported)
 
@@ -139,8 +133,9 @@ def why_not(agent, supported_fn=None, update_supported_fn=None):
 
 
 class Step(dqn_mlp.Step):
-    """dqn_mlp.Step over the distributional kernels: the net struct, the two launches, the module-path update and the update's
-    output buffers are this class's; prepare, step, the captured regions, check, drain and the state dict are the parent's."""
+    """dqn_mlp.Step over the distributional kernels: the net struct's support, the update's io and its output buffers are this
+    class's; the two launches (by Kind.ACT / Kind.UPDATE), the module-path update, prepare, step, the captured regions, check,
+    drain and the state dict are the parent's."""
     KIND = Kind
 
     def make_outputs(self, dev):
@@ -150,46 +145,16 @@ class Step(dqn_mlp.Step):
         self.q_next, self.target = f(self.batch, 2), f(self.batch, n)
 
     def net_struct(self):
-        agent = self.agent
-        flat = agent._fused.flat
-        n = Net()
-        n.param, n.target = flat.flat.data_ptr(), agent._target_flat.flat.data_ptr()
-        for field, p in _fields(agent.network):
-            setattr(n, field, flat.offset_of(p))
-        n.state_dim, n.n_actions, n.hidden, n.gate, n.head, n.n_atoms = self.shape
-        n.v_min, n.v_max = support(agent.config, n.head)
+        n = dqn_mlp.Step.net_struct(self)
+        n.v_min, n.v_max = support(self.agent.config, n.head)
         return n
-
-    def act(self):
-        """dra_dist_mlp_act on the current stream (after prepare())."""
-        net, io = self.net_struct(), self.act_io()
-        lib.dra_dist_mlp_act(ctypes.byref(net), ctypes.byref(io), stream_ptr())
-        self.launches += 1
 
     def update(self):
         """dra_dist_mlp_update on the staged indices: the gradient lands in the optimiser's flat gradient buffer."""
-        cfg, io = self.agent.config, UpdateIO()
-        io.ring_frames, io.ring_actions, io.ring_rewards, io.ring_masks = self.ring.pointers()
-        io.idx, io.grad = self.idx.data_ptr(), self.agent._fused.flat.grad.data_ptr()
+        io = UpdateIO()
         io.out_loss, io.out_loss_vec = self.loss.data_ptr(), self.loss_vec.data_ptr()
         io.out_q_next, io.out_target = self.q_next.data_ptr(), self.target.data_ptr()
-        io.err, io.capacity = self.err.data_ptr(), self.capacity
-        io.discount, io.batch, io.double_q = float(cfg.discount) ** int(cfg.n_step), self.batch, int(bool(cfg.double_q))
-        net = self.net_struct()
-        lib.dra_dist_mlp_update(ctypes.byref(net), ctypes.byref(io), stream_ptr())
-        return self.loss
-
-    def module_update(self):
-        """config.fused_dist_update False: ring.gather on the staged indices, the modules' forwards, ops.c51_loss / ops.qr_loss,
-        autograd."""
-        agent = self.agent
-        rp = agent._inner_replay()
-        self.static = g = rp.gather(self.idx, out=self.static)
-        tr = rp.TransitionCLS(state=g['state'], action=g['action'], reward=g['reward'], next_state=g['next_state'], mask=g['mask'])
-        out, (net_out, grad) = agent._loss_grad(tr, None)
-        agent._fused.zero_grad()
-        agent._backward(net_out, grad)
-        return out['loss']
+        return self.launch_update(io)
 
 
 def adopt(agent):

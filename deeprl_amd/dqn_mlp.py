@@ -20,6 +20,7 @@ import torch
 from ._lib import DraError, lib, stream_ptr
 from .device_env import DeviceCartPoleVec, _RolloutVec
 from .graphs import Region
+from .mlp_rollout import fill_net, shape_table, target_why_not, unowned
 from .q_mlp import Net, _fields, shape      # noqa: F401  (the net struct is dra_q_mlp_net as it is)
 from .support import Config, StagedUpload, plan_actor_epsilon_greedy
 
@@ -50,14 +51,8 @@ class UpdateIO(ctypes.Structure):
                 ("batch", ctypes.c_int32), ("double_q", ctypes.c_int32)]
 
 
-def supported(state_dim, n_actions, hidden, t_len, gate):
-    """dra_dqn_mlp_supported: the shapes (t_len = transitions per launch) the acting kernel is built for."""
-    return lib.dra_dqn_mlp_supported.raw(int(state_dim), int(n_actions), int(hidden), int(t_len), int(gate)) == 0
-
-
-def update_supported(state_dim, n_actions, hidden, batch, gate):
-    """dra_dqn_mlp_update_supported: the shapes the update kernel is built for."""
-    return lib.dra_dqn_mlp_update_supported.raw(int(state_dim), int(n_actions), int(hidden), int(batch), int(gate)) == 0
+supported = shape_table('dra_dqn_mlp_supported')      # (state_dim, n_actions, hidden, t_len = transitions per launch, gate)
+update_supported = shape_table('dra_dqn_mlp_update_supported')        # (state_dim, n_actions, hidden, batch, gate)
 
 
 class Kind:
@@ -68,6 +63,7 @@ class Kind:
     AGENTS, NOT_AGENT = ('DQNAgent',), "the agent is a %s, not a plain DQNAgent"
     NETWORK, ACT, UPDATE, N_SUPPORTED = NETWORK, 'dra_dqn_mlp_act', 'dra_dqn_mlp_update', 4
     ASYNC_ACTOR = False      # whether config.async_actor may be on (the Step runs in the sync path's order)
+    Net, DIMS = Net, ("state_dim", "n_actions", "hidden", "gate")      # the net struct and its fields that hold shape(network)
     shape, fields = staticmethod(shape), staticmethod(_fields)
     supported, update_supported = staticmethod(supported), staticmethod(update_supported)
 
@@ -136,19 +132,17 @@ def why_not(agent, supported_fn=None, update_supported_fn=None, kind=Kind):
         return "the network is not %s" % NETWORK
     if getattr(agent, '_fused', None) is None or getattr(agent, '_target_flat', None) is None or not _plain_optimizer(agent.optimizer):
         return "the optimizer is not one plain RMSprop or Adam over every parameter"
-    owned = agent._fused.flat.params
-    if any(all(p is not q for q in owned) for _, p in _fields(agent.network)):
-        return "one optimiser does not own every parameter the kernel reads"
+    why = unowned(agent, _fields)
+    if why is not None:
+        return why
     if getattr(agent, 'grad_hook', None) is not None:
         return "a grad_hook is installed"
     dp = getattr(agent, 'dp', None)
     if dp is not None and dp.active:
         return "the agent is data parallel"
-    if shape(agent.target_network) != shp:
-        return "the target network is not %s of the online network's shape" % NETWORK
-    flat, target = agent._fused.flat, agent._target_flat
-    if ([flat.offset_of(p) for _, p in _fields(agent.network)] != [target.offset_of(p) for _, p in _fields(agent.target_network)]):
-        return "the online and the target parameters are laid out differently in their flat buffers"
+    why = target_why_not(agent, shape, _fields, shp, "the target network is not %s of the online network's shape" % NETWORK)
+    if why is not None:
+        return why
     rn, sn = cfg.reward_normalizer, cfg.state_normalizer
     if type(rn) is not RescaleNormalizer or rn.coef != 1.0:
         return "the reward normaliser is not RescaleNormalizer(1.0)"
@@ -232,14 +226,8 @@ class Step:
 
     # -- the structs ---------------------------------------------------------------------------------------------------
     def net_struct(self):
-        agent = self.agent
-        flat = agent._fused.flat
-        n = Net()
-        n.param, n.target = flat.flat.data_ptr(), agent._target_flat.flat.data_ptr()
-        for field, p in _fields(agent.network):
-            setattr(n, field, flat.offset_of(p))
-        n.state_dim, n.n_actions, n.hidden, n.gate = self.shape
-        return n
+        a, kind = self.agent, self.KIND
+        return fill_net(kind.Net(), a._fused.flat, kind.fields(a.network), kind.DIMS, self.shape, a._target_flat)
 
     def act_io(self):
         """dra_dqn_mlp_act_io over the environment, the staged draws and the ring."""
@@ -256,25 +244,32 @@ class Step:
         return io
 
     def act(self):
-        """dra_dqn_mlp_act on the current stream (after prepare())."""
+        """The kind's acting kernel (dra_dqn_mlp_act) on the current stream (after prepare())."""
         net, io = self.net_struct(), self.act_io()
-        lib.dra_dqn_mlp_act(ctypes.byref(net), ctypes.byref(io), stream_ptr())
+        getattr(lib, self.KIND.ACT)(ctypes.byref(net), ctypes.byref(io), stream_ptr())
         self.launches += 1
 
-    def update(self):
-        """dra_dqn_mlp_update on the staged indices: the gradient lands in the optimiser's flat gradient buffer."""
-        cfg, io = self.agent.config, UpdateIO()
+    def launch_update(self, io):
+        """The kind's update kernel on the staged indices over `io`, an update io struct with its outputs set: the ring, the
+        indices, the optimiser's flat gradient buffer and the scalars are filled here.  -> self.loss"""
+        cfg = self.agent.config
         io.ring_frames, io.ring_actions, io.ring_rewards, io.ring_masks = self.ring.pointers()
         io.idx, io.grad = self.idx.data_ptr(), self.agent._fused.flat.grad.data_ptr()
-        io.out_q_target, io.out_td, io.out_loss = self.q_target.data_ptr(), self.td.data_ptr(), self.loss.data_ptr()
         io.err, io.capacity = self.err.data_ptr(), self.capacity
         io.discount, io.batch, io.double_q = float(cfg.discount) ** int(cfg.n_step), self.batch, int(bool(cfg.double_q))
         net = self.net_struct()
-        lib.dra_dqn_mlp_update(ctypes.byref(net), ctypes.byref(io), stream_ptr())
+        getattr(lib, self.KIND.UPDATE)(ctypes.byref(net), ctypes.byref(io), stream_ptr())
         return self.loss
 
+    def update(self):
+        """dra_dqn_mlp_update on the staged indices: the gradient lands in the optimiser's flat gradient buffer."""
+        io = UpdateIO()
+        io.out_q_target, io.out_td, io.out_loss = self.q_target.data_ptr(), self.td.data_ptr(), self.loss.data_ptr()
+        return self.launch_update(io)
+
     def module_update(self):
-        """config.fused_dqn_update False: ring.gather on the staged indices, the modules' forwards, the TD kernel, autograd."""
+        """The kind's update switch False: ring.gather on the staged indices, then the agent's own _loss_grad (the modules'
+        forwards, the TD kernel -- ops.c51_loss / ops.qr_loss for dist_mlp's kinds --, autograd)."""
         agent = self.agent
         rp = agent._inner_replay()
         self.static = g = rp.gather(self.idx, out=self.static)

@@ -23,7 +23,7 @@ import torch
 from . import mlp_rollout
 from ._lib import lib, stream_ptr
 from .device_env import DeviceCartPoleVec
-from .mlp_rollout import GATES, body_params, fc_body, head_out      # noqa: F401  (GATES: this module's public name)
+from .mlp_rollout import GATES, body_params, fc_body, head_out, shape_table      # noqa: F401  (GATES: this module's public name)
 from .support import Config, StagedUpload
 
 _OFFSETS = ("w1", "b1", "w2", "b2", "wq", "bq", "wp", "bp", "wb", "bb")
@@ -75,15 +75,8 @@ def shape(network):
     return s_dim, n_act, hidden, gate, n_opt
 
 
-def supported(state_dim, n_actions, hidden, n_env, gate, n_options):
-    """dra_oc_mlp_supported: the shapes the rollout kernel is built for."""
-    return lib.dra_oc_mlp_supported.raw(int(state_dim), int(n_actions), int(hidden), int(n_env), int(gate), int(n_options)) == 0
-
-
-def update_supported(state_dim, n_actions, hidden, rows, gate, n_options):
-    """dra_oc_mlp_update_supported: the shapes (rows = rollout length x environments) the update kernel is built for."""
-    return lib.dra_oc_mlp_update_supported.raw(int(state_dim), int(n_actions), int(hidden), int(rows), int(gate),
-                                               int(n_options)) == 0
+supported = shape_table('dra_oc_mlp_supported')       # (state_dim, n_actions, hidden, n_env, gate, n_options): the rollout kernel
+update_supported = shape_table('dra_oc_mlp_update_supported')     # (.., rows = rollout length x environments, gate, n_options)
 
 
 def _fields(net):
@@ -102,16 +95,7 @@ def why_not(agent, supported_fn=supported):
     why = mlp_rollout.why_not(Rollout, agent, lambda s, a, h, n, g: supported_fn(s, a, h, n, g, shp[4]))
     if why is not None:
         return why
-    cfg = agent.config
-    if shape(agent.target_network) != shp:
-        return "the network is not %s" % Rollout.NETWORK
-    flat, target = agent._fused.flat, agent._target_flat
-    if ([flat.offset_of(p) for _, p in _fields(agent.network)] != [target.offset_of(p) for _, p in _fields(agent.target_network)]):
-        return "the online and the target parameters are laid out differently in their flat buffers"
-    n, t_len = int(cfg.num_workers), int(cfg.rollout_length)
-    if getattr(cfg, 'fused_oc_update', True) is not False and not update_supported(shp[0], shp[1], shp[2], t_len * n, shp[3], shp[4]):
-        return "dra_oc_mlp_update is not built for %d rows (rollout length %d x %d environments)" % (t_len * n, t_len, n)
-    return None
+    return Rollout.target_why_not(agent, shp)
 
 
 def update(net, b, eps, discount, termination_regularizer, entropy_weight, grad):
@@ -130,7 +114,7 @@ def update(net, b, eps, discount, termination_regularizer, entropy_weight, grad)
     lib.dra_oc_mlp_update(ctypes.byref(net), ctypes.byref(io), stream_ptr())
 
 
-class Rollout(mlp_rollout.Rollout):
+class Rollout(mlp_rollout.TargetRollout):
     """dra_oc_mlp_rollout over a DeviceCartPoleVec, the agent's flat parameter buffer and its target network's.  Random draws: one
     uniform_() [T, N, 3] per rollout on torch's device generator, turned into options and actions by inverse CDF -- the
     documented deviation of pixel_rollout._OCRollout: inverse CDF of staged uniforms, not Categorical.sample()'s own stream."""
@@ -138,14 +122,13 @@ class Rollout(mlp_rollout.Rollout):
     NETWORK = "OptionCriticNet over a two-layer relu / tanh FCBody with three plain heads"
     NOT_TASK = "the task is not a vector of at most 64 envs.CartPole environments under RescaleNormalizer(1.0), or there is no device"
     Net, IO, DIMS, ACTION_VIEW = Net, RolloutIO, ("state_dim", "n_actions", "hidden", "gate", "n_options"), ()
+    UPDATE, UPDATE_SWITCH, update_supported = 'dra_oc_mlp_update', 'fused_oc_update', staticmethod(update_supported)
     network_shape, fields, supported, why_not = staticmethod(shape), staticmethod(_fields), staticmethod(supported), staticmethod(why_not)
 
     def __init__(self, agent, shp):
-        mlp_rollout.Rollout.__init__(self, agent, shp)
+        mlp_rollout.TargetRollout.__init__(self, agent, shp)
         self._eps_up = None
         self.eps = self.uniform = self.prev_option = self.is_initial = None
-        # the kernel's own step counter: the ring rows carry it (device_env.EpisodeRing turns it into a step number)
-        self.step_dev = torch.zeros(1, dtype=torch.int64, device=Config.DEVICE)
 
     def attach(self):
         """The environments move to the device with the buffers these kernels leave (and the update's outputs)."""
@@ -163,14 +146,6 @@ class Rollout(mlp_rollout.Rollout):
         self.is_initial = torch.ones(n, dtype=torch.bool, device=dev)
         return self.prev_option, self.is_initial
 
-    def net_struct(self):
-        n = mlp_rollout.Rollout.net_struct(self)
-        n.target = self.agent._target_flat.flat.data_ptr()
-        return n
-
-    def buffers(self, t_len):
-        return self.agent.task.buffers(t_len)
-
     def prepare(self, t_len):
         """config.random_option_prob(num_workers) once per rollout step -- the reference's calls in its order -- staged into the
         persistent [T] buffer the kernel reads, and one uniform_() [T, N, 3] on torch's device generator into a persistent buffer
@@ -185,17 +160,9 @@ class Rollout(mlp_rollout.Rollout):
         self.uniform.uniform_()
         return eps
 
-    def run(self, t_len):
-        """One rollout launch on the current stream (after prepare(t_len)); returns the task's buffers of t_len."""
-        io = RolloutIO()
-        b = self.agent.task.fill_io(io, self.agent, t_len)
-        io.step_counter, io.bootstrap = self.step_dev.data_ptr(), b['bootstrap'].data_ptr()
+    def fill_own(self, io):
         io.eps, io.uniform = self.eps.data_ptr(), self.uniform.data_ptr()
         io.prev_option, io.is_initial = self.prev_option.data_ptr(), self.is_initial.data_ptr()
-        net = self.net_struct()
-        lib.dra_oc_mlp_rollout(ctypes.byref(net), ctypes.byref(io), stream_ptr())
-        self.launches += 1
-        return b
 
     def update(self, b, cfg):
         """dra_oc_mlp_update on the buffers run() left: the gradient lands in the optimiser's flat gradient buffer.  -> loss [4]."""

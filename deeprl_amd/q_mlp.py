@@ -16,7 +16,7 @@ import torch
 from . import mlp_rollout
 from ._lib import lib, stream_ptr
 from .device_env import DeviceCartPoleVec
-from .mlp_rollout import GATES, body_params, fc_body, head_out      # noqa: F401  (GATES: this module's public name)
+from .mlp_rollout import GATES, body_params, fc_body, head_out, shape_table      # noqa: F401  (GATES: this module's public name)
 from .support import Config, StagedUpload, plan_epsilon_greedy
 
 
@@ -64,14 +64,8 @@ def shape(network):
     return s_dim, n_actions, hidden, gate
 
 
-def supported(state_dim, n_actions, hidden, n_env, gate):
-    """dra_q_mlp_supported: the shapes the rollout kernel is built for."""
-    return lib.dra_q_mlp_supported.raw(int(state_dim), int(n_actions), int(hidden), int(n_env), int(gate)) == 0
-
-
-def update_supported(state_dim, n_actions, hidden, rows, gate):
-    """dra_q_mlp_update_supported: the shapes (rows = rollout length x environments) the update kernel is built for."""
-    return lib.dra_q_mlp_update_supported.raw(int(state_dim), int(n_actions), int(hidden), int(rows), int(gate)) == 0
+supported = shape_table('dra_q_mlp_supported')                    # (state_dim, n_actions, hidden, n_env, gate): the rollout kernel
+update_supported = shape_table('dra_q_mlp_update_supported')      # (.., rows = rollout length x environments, gate): the update kernel
 
 
 def _fields(net):
@@ -84,16 +78,7 @@ def why_not(agent, supported_fn=supported):
     why = mlp_rollout.why_not(Rollout, agent, supported_fn)
     if why is not None:
         return why
-    cfg, shp = agent.config, shape(agent.network)
-    if shape(agent.target_network) != shp:
-        return "the network is not %s" % Rollout.NETWORK
-    flat, target = agent._fused.flat, agent._target_flat
-    if ([flat.offset_of(p) for _, p in _fields(agent.network)] != [target.offset_of(p) for _, p in _fields(agent.target_network)]):
-        return "the online and the target parameters are laid out differently in their flat buffers"
-    n, t_len = int(cfg.num_workers), int(cfg.rollout_length)
-    if getattr(cfg, 'fused_nstep_update', True) is not False and not update_supported(shp[0], shp[1], shp[2], t_len * n, shp[3]):
-        return "dra_q_mlp_update is not built for %d rows (rollout length %d x %d environments)" % (t_len * n, t_len, n)
-    return None
+    return Rollout.target_why_not(agent, shape(agent.network))
 
 
 def update(net, state, action, reward, mask, bootstrap, discount, grad, out_ret, out_loss):
@@ -107,33 +92,24 @@ def update(net, state, action, reward, mask, bootstrap, discount, grad, out_ret,
     lib.dra_q_mlp_update(ctypes.byref(net), ctypes.byref(io), stream_ptr())
 
 
-class Rollout(mlp_rollout.Rollout):
+class Rollout(mlp_rollout.TargetRollout):
     """dra_q_mlp_rollout over a DeviceCartPoleVec, the agent's flat parameter buffer and its target network's."""
     SWITCH, ENTRY, VEC, OPT_IN = 'fused_nstep_feature', 'dra_q_mlp_rollout', DeviceCartPoleVec, True
     NETWORK = "VanillaNet over a two-layer relu / tanh FCBody with a plain head"
     NOT_TASK = "the task is not a vector of at most 64 envs.CartPole environments under RescaleNormalizer(1.0), or there is no device"
     Net, IO, DIMS, ACTION_VIEW = Net, RolloutIO, ("state_dim", "n_actions", "hidden", "gate"), ()
+    UPDATE, UPDATE_SWITCH, update_supported = 'dra_q_mlp_update', 'fused_nstep_update', staticmethod(update_supported)
     network_shape, fields, supported, why_not = staticmethod(shape), staticmethod(_fields), staticmethod(supported), staticmethod(why_not)
 
     def __init__(self, agent, shp):
-        mlp_rollout.Rollout.__init__(self, agent, shp)
+        mlp_rollout.TargetRollout.__init__(self, agent, shp)
         self._up = None
         self.explore = self.random_action = None
-        # the kernel's own step counter: the ring rows carry it (device_env.EpisodeRing turns it into a step number)
-        self.step_dev = torch.zeros(1, dtype=torch.int64, device=Config.DEVICE)
 
     def attach(self):
         """The environments move to the device with the buffers these kernels leave (and the update's two outputs)."""
         self.agent.task = DeviceCartPoleVec(self.agent.task, buffers=lambda t_len, n, f: dict(
             q=f(t_len, n, 2), reward=f(t_len, n), mask=f(t_len, n), bootstrap=f(n), ret=f(t_len, n), loss=f(1)))
-
-    def net_struct(self):
-        n = mlp_rollout.Rollout.net_struct(self)
-        n.target = self.agent._target_flat.flat.data_ptr()
-        return n
-
-    def buffers(self, t_len):
-        return self.agent.task.buffers(t_len)
 
     def prepare(self, t_len):
         """Draws the rollout's exploration (support.plan_epsilon_greedy: NStepDQN_agent.py:34-35's calls in their order, so that
@@ -153,16 +129,8 @@ class Rollout(mlp_rollout.Rollout):
         self._up.send()
         return explore, rand
 
-    def run(self, t_len):
-        """One rollout launch on the current stream (after prepare(t_len)); returns the task's buffers of t_len."""
-        io = RolloutIO()
-        b = self.agent.task.fill_io(io, self.agent, t_len)
-        io.step_counter, io.bootstrap = self.step_dev.data_ptr(), b['bootstrap'].data_ptr()
+    def fill_own(self, io):
         io.explore, io.random_action = self.explore.data_ptr(), self.random_action.data_ptr()
-        net = self.net_struct()
-        lib.dra_q_mlp_rollout(ctypes.byref(net), ctypes.byref(io), stream_ptr())
-        self.launches += 1
-        return b
 
     def update(self, b, discount):
         """dra_q_mlp_update on the buffers run() left: the gradient lands in the optimiser's flat gradient buffer."""

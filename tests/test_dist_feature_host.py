@@ -304,11 +304,12 @@ def test_adoption_logs_the_reason_once_and_keeps_the_host_path():
 
 
 def test_step_overrides_only_what_differs():
-    """dist_mlp.Step is dqn_mlp.Step but for the net struct, the two launches, the module-path update and the output buffers."""
+    """dist_mlp.Step is dqn_mlp.Step but for the net struct, the update's io and the output buffers."""
     from deeprl_amd import dist_mlp, dqn_mlp
     own = {k for k in vars(dist_mlp.Step) if not k.startswith("__")}
-    assert own == {"KIND", "make_outputs", "net_struct", "act", "update", "module_update"}
-    for k in ("prepare", "step", "_learn", "check", "drain", "state_dict", "load_state_dict", "act_io", "__init__"):
+    assert own == {"KIND", "make_outputs", "net_struct", "update"}
+    for k in ("prepare", "step", "_learn", "check", "drain", "state_dict", "load_state_dict", "act_io", "__init__", "act",
+              "module_update"):
         assert getattr(dist_mlp.Step, k) is getattr(dqn_mlp.Step, k), k
 
 

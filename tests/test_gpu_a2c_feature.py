@@ -12,6 +12,7 @@ import os
 import numpy as np
 import pytest
 import torch
+from feature_kernel_harness import GAME, GUARD, dra, _as_int, _guarded, _body, _line_events      # noqa: F401  (dra: the fixture)
 from parity_log import record_parity
 
 import a2c_feature_cases as K
@@ -22,16 +23,6 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden", "a2c_feature")
 FIXTURE = os.path.join(GOLDEN, "a2c_feature_step.npz")
-GAME = "classic-CartPole-v0"
-
-
-@pytest.fixture(scope="module")
-def dra():
-    if not torch.cuda.is_available():
-        pytest.skip("GPU tests need an MI355X")
-    import deeprl_amd as d
-    d.select_device(0)
-    return d
 
 
 class _Rec:
@@ -102,15 +93,6 @@ def test_cartpole_step_matches_host_bit_for_bit(dra, n, horizon):
 
 
 # ------------------------------------------------------------------------------------------ rollout kernel
-GUARD = 8       # elements behind every buffer's stated size, filled with a sentinel that must survive
-
-
-def _guarded(shape, dtype, dev, fill):
-    n = int(np.prod(shape))
-    full = torch.full((n + GUARD,), fill, dtype=dtype, device=dev)
-    return full, full[:n].view(*shape)
-
-
 def _net_struct(params, dev, hidden, gate, padded):
     from deeprl_amd import cat_mlp
     offs, chunks, off = {}, [], 0
@@ -168,11 +150,6 @@ def _launch(dra, case, start):
     return out, (net, io, full, view)
 
 
-def _body(out, k):
-    shape = out["spec"][k][0]
-    return out[k][:int(np.prod(shape))].reshape(shape)
-
-
 @pytest.mark.parametrize("case", K.ROLLOUT_CASES, ids=K.case_id)
 def test_rollout_kernel_matches_restatement(dra, case):
     """dra_cat_mlp_rollout against the restatement: actions equal (the host suite asserts a Gumbel margin >= 1e-4 for every case);
@@ -225,10 +202,6 @@ def test_rollout_refuses_unsupported_shapes_and_launches_nothing(dra):
     assert refused(hidden=48) and refused(hidden=128) and refused(state_dim=5) and refused(n_actions=3) and refused(gate=3)
     assert refused(n_env=65) and refused(n_env=0) and refused(t_len=0) and refused(horizon=0) and refused(ring_cap=0)
     assert refused(w2=-1) and refused(n_global=case[2] - 1) and refused(out_v=None) and refused(ep_ring=None)
-
-
-def _as_int(t):
-    return t.view(torch.int64) if t.dtype == torch.float64 else (t.view(torch.int32) if t.dtype == torch.float32 else t)
 
 
 # ------------------------------------------------------------------------------------------ update against the reference
@@ -355,15 +328,6 @@ def device_run(dra):
         return _run(dra, mp, True, True)
     finally:
         mp.undo()
-
-
-def _line_events(lines):
-    out = []
-    for ln in lines:
-        if 'episodic_return_train' in ln:
-            w = ln.replace(',', '').split()
-            out.append((int(w[1]), float(w[3])))
-    return out
 
 
 def test_agent_device_rollout_equals_host_environments(dra, monkeypatch, device_run):

@@ -10,6 +10,8 @@ import os
 import numpy as np
 import pytest
 import torch
+from feature_kernel_harness import (      # noqa: F401  (dra: the fixture)
+    GAME, GATE, GUARD, dra, _Rec, _fraction, _within, _bits, _guarded, _flat, _tails_intact, _body, _line_events)
 from parity_log import record_parity
 
 import dqn_feature_cases as K
@@ -20,100 +22,18 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden", "dqn_feature")
 FIXTURE = os.path.join(GOLDEN, "dqn_feature_steps.npz")
-GAME = "classic-CartPole-v0"
-GATE = {"relu": 1, "tanh": 2}
-GUARD = 8       # elements behind every buffer's stated size, filled with a sentinel that must survive
-
-
-@pytest.fixture(scope="module")
-def dra():
-    if not torch.cuda.is_available():
-        pytest.skip("GPU tests need an MI355X")
-    import deeprl_amd as d
-    d.select_device(0)
-    return d
-
-
-class _Rec:
-    """A logger that keeps the episodic-return lines and the warnings."""
-
-    def __init__(self):
-        self.lines, self.warnings = [], []
-
-    def info(self, msg, *a, **k):
-        self.lines.append(str(msg))
-
-    def warning(self, msg, *a, **k):
-        self.warnings.append(str(msg))
-
-    def add_scalar(self, *a, **k):
-        pass
-    add_histogram = add_scalar
-
-
-def _fraction(got, want, what):
-    """Largest error as a fraction of 1e-5 of the tensor's largest magnitude, floor 1.0."""
-    got, want = np.asarray(got, dtype=np.float64), np.asarray(want, dtype=np.float64)
-    assert got.shape == want.shape, (what, got.shape, want.shape)
-    err = float(np.max(np.abs(got - want))) if want.size else 0.0
-    bar = 1e-5 * max(float(np.abs(want).max()) if want.size else 0.0, 1.0)
-    print("%s: max abs error %.3e (bar %.3e)" % (what, err, bar))
-    return err / bar
-
-
-def _within(got, want, what):
-    f = _fraction(got, want, what)
-    assert f <= 1.0, (what, f)
-    return f
-
-
-def _bits(x):
-    x = np.ascontiguousarray(x)
-    return x.view({1: np.uint8, 4: np.uint32, 8: np.uint64}[x.dtype.itemsize])
-
-
-def _guarded(shape, dtype, dev, fill):
-    n = int(np.prod(shape))
-    full = torch.full((n + GUARD,), fill, dtype=dtype, device=dev)
-    return full, full[:n].view(*shape)
-
-
-def _flat(params, padded, fill=np.nan):
-    """(float32 flat array, offsets per key): tensors back to back, or -- padded -- behind a leading gap with `fill` between."""
-    offs, chunks, off = {}, [], 0
-    if padded:
-        chunks.append(np.full(3, fill, dtype=np.float32))
-        off = 3
-    for k in R.KEYS:
-        v = np.asarray(params[k], dtype=np.float32).reshape(-1)
-        offs[k] = off
-        pad = ((-v.size) % 4 + 1) if padded else 0
-        chunks += [v, np.full(pad, fill, dtype=np.float32)]
-        off += v.size + pad
-    return np.concatenate(chunks), offs
 
 
 def _net_struct(params, target, dev, hidden, gate, padded):
     from deeprl_amd import dqn_mlp
-    flat, offs = _flat(params, padded)
-    tflat, _ = _flat(target if target is not None else params, padded)
+    flat, offs = _flat(R.KEYS, params, padded)
+    tflat, _ = _flat(R.KEYS, target if target is not None else params, padded)
     flat, tflat = torch.from_numpy(flat).to(dev), torch.from_numpy(tflat).to(dev)
     net = dqn_mlp.Net()
     net.param, net.target = flat.data_ptr(), tflat.data_ptr()
     net.w1, net.b1, net.w2, net.b2, net.wq, net.bq = [offs[k] for k in R.KEYS]
     net.state_dim, net.n_actions, net.hidden, net.gate = 4, 2, hidden, GATE[gate]
     return net, flat, tflat, offs
-
-
-def _tails_intact(out):
-    for k, (shape, dt, fill) in out["spec"].items():
-        tail = out[k][int(np.prod(shape)):]
-        assert tail.size == GUARD and (np.isnan(tail).all() if fill != fill else (tail == fill).all()), k
-
-
-def _body(out, k):
-    shape = out["spec"][k][0]
-    return out[k][:int(np.prod(shape))].reshape(shape)
 
 
 # ------------------------------------------------------------------------------------------ the acting kernel
@@ -431,15 +351,6 @@ def device_run(dra):
         return _run(dra, mp, True, True)
     finally:
         mp.undo()
-
-
-def _line_events(lines):
-    out = []
-    for ln in lines:
-        if 'episodic_return_train' in ln:
-            w = ln.replace(',', '').split()
-            out.append((int(w[1]), float(w[3])))
-    return out
 
 
 def _params_within(a, others, bar=2e-4):
