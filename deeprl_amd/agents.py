@@ -324,6 +324,11 @@ class DQNAgent(_DeviceEpisodes, BaseAgent):
         if getattr(config, 'fused_dist_feature', False) is True and self._feature is None:
             from . import dist_mlp
             self._feature = dist_mlp.adopt(self)
+        # rainbow_feature, examples.py:231-280 (opt-in, config.fused_rainbow_feature): the same Step over csrc/rainbow_mlp.hip for a
+        # CategoricalDQNAgent with noisy layers, an n-step PrioritizedReplay and double_q
+        if getattr(config, 'fused_rainbow_feature', False) is True and self._feature is None:
+            from . import rainbow_mlp
+            self._feature = rainbow_mlp.adopt(self)
 
     def _device_noisy_actor(self):
         """noisy_actor.NoisyActor when `config.device_noisy_actor` is on and the agent is eligible (Rainbow over one synthetic

@@ -19,7 +19,7 @@ import torch
 
 from ._lib import DraError, lib, stream_ptr
 from .device_env import DeviceCartPoleVec, _RolloutVec
-from .graphs import Region
+from .graphs import Region, _fused_noisy
 from .mlp_rollout import fill_net, shape_table, target_why_not, unowned
 from .q_mlp import Net, _fields, shape      # noqa: F401  (the net struct is dra_q_mlp_net as it is)
 from .support import Config, StagedUpload, plan_actor_epsilon_greedy
@@ -63,6 +63,10 @@ class Kind:
     AGENTS, NOT_AGENT = ('DQNAgent',), "the agent is a %s, not a plain DQNAgent"
     NETWORK, ACT, UPDATE, N_SUPPORTED = NETWORK, 'dra_dqn_mlp_act', 'dra_dqn_mlp_update', 4
     ASYNC_ACTOR = False      # whether config.async_actor may be on (the Step runs in the sync path's order)
+    # what a kind's kernels take beyond dqn_feature's own configuration (rainbow_mlp.py: all three)
+    PRIORITIZED = False      # the replay is a PrioritizedReplay (else: a UniformReplay)
+    MAX_N_STEP = 1           # the longest n-step window the update kernel folds
+    NOISY = False            # config.noisy_linear is on, the layers on csrc/noisy.hip (else: off)
     Net, DIMS = Net, ("state_dim", "n_actions", "hidden", "gate")      # the net struct and its fields that hold shape(network)
     shape, fields = staticmethod(shape), staticmethod(_fields)
     supported, update_supported = staticmethod(supported), staticmethod(update_supported)
@@ -115,15 +119,28 @@ def why_not(agent, supported_fn=None, update_supported_fn=None, kind=Kind):
     if type(agent).__name__ not in kind.AGENTS:
         return kind.NOT_AGENT % type(agent).__name__
     rp = agent._inner_replay()
-    if isinstance(rp, PrioritizedReplay):
+    if kind.PRIORITIZED:
+        if type(rp) is not PrioritizedReplay:
+            return "the replay is not a PrioritizedReplay"
+        if rp.ordered_updates:
+            return "the replay has ordered_updates forced"
+    elif isinstance(rp, PrioritizedReplay):
         return "the replay is a PrioritizedReplay"
-    if type(rp) is not UniformReplay:
+    elif type(rp) is not UniformReplay:
         return "the replay is not a UniformReplay"
-    if int(rp.n_step) != 1 or int(getattr(cfg, 'n_step', 1)) != 1:
-        return "n_step is not 1"
+    if kind.MAX_N_STEP == 1:
+        if int(rp.n_step) != 1 or int(getattr(cfg, 'n_step', 1)) != 1:
+            return "n_step is not 1"
+    elif int(rp.n_step) != int(getattr(cfg, 'n_step', 1)) or not 1 <= int(rp.n_step) <= kind.MAX_N_STEP:
+        return "n_step is not between 1 and %d, or the replay's is not the configuration's" % kind.MAX_N_STEP
     if int(rp.history_length) != 1 or int(getattr(cfg, 'history_length', None) or 1) != 1:
         return "history_length is not 1"
-    if cfg.noisy_linear:
+    if kind.NOISY:
+        if not cfg.noisy_linear:
+            return "noisy_linear is off"
+        if not _fused_noisy(cfg, agent.network):
+            return "the noisy layers are not on csrc/noisy.hip (config.fused_noisy)"
+    elif cfg.noisy_linear:
         return "noisy_linear is on"
     if cfg.async_actor and not kind.ASYNC_ACTOR:
         return "async_actor is on"
@@ -201,7 +218,8 @@ class Step:
         # ONE staged block at fixed addresses: int64 first slot | int64 indices [B] | int64 random actions [K] | uint8 flags [K]
         k, b = self.k, self.batch
         self._o_idx, self._o_rand, self._o_flag = 8, 8 + 8 * b, 8 + 8 * b + 8 * k
-        self._up = StagedUpload(self._o_flag + (k + 7) // 8 * 8, torch.uint8, dev)
+        self._o_tail = self._o_flag + (k + 7) // 8 * 8
+        self._up = StagedUpload(self._o_tail + self.staged_tail(), torch.uint8, dev)
         d = self._up.dev
         self.slot0 = d[:8].view(torch.int64)
         self.idx = d[self._o_idx:self._o_rand].view(torch.int64)
@@ -216,6 +234,10 @@ class Step:
         self.regions = dict(act=Region("the %s acting launch" % self.KIND.ENTRY, cfg, self.WARMUP),
                             learn=Region("the %s agent step" % self.KIND.ENTRY, cfg, self.WARMUP, opts=(agent._fused,)))
         self.last_draws = None          # (explore, random_action, first slot, indices or None) of the last step, as drawn
+
+    def staged_tail(self):
+        """Bytes a kind stages behind the parent's block, from self._o_tail on (rainbow_mlp.py: the probabilities and beta)."""
+        return 0
 
     def make_outputs(self, dev):
         """The update kernel's output buffers (a subclass has its own)."""
@@ -324,10 +346,14 @@ class Step:
             out = body()
         if learn:
             agent.last_loss = out
+            self.after_learn()
         # DQN_agent.py:136-138, after the update of the step: eager, between graph replays
         if agent.total_steps / cfg.sgd_update_frequency % cfg.target_network_update_freq == 0:
             agent.sync_target()
         self.episodes.end()
+
+    def after_learn(self):
+        """What a kind runs eagerly behind the learn region of a step that updated (rainbow_mlp.py: the priorities' commit)."""
 
     # -- what the host reads back where it synchronises anyway ----------------------------------------------------------
     def check(self):

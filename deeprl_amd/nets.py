@@ -789,6 +789,15 @@ class _NoiseBlock:
         for _, m in self.layers:
             m.noise_changed()
 
+    def _rows_upload(self, rows):
+        if rows not in self._rows:
+            self._rows[rows] = StagedUpload((rows, self.numel), torch.float32, self.device, self.SLOTS)
+        return self._rows[rows]
+
+    def rows_block(self, rows):
+        """The static device block draw_rows(rows) fills, WITHOUT a draw (the generator stays where it is)."""
+        return self._rows_upload(int(rows)).dev
+
     def draw_rows(self, rows):
         """`rows` successive draw()s -- the reset_noise() calls of the transitions of one agent step (DQN_agent.py:28-29) -- into
         one pinned [rows][numel] block that reaches a static device block with ONE asynchronous copy: the generator ends where
@@ -796,9 +805,7 @@ class _NoiseBlock:
         get row rows - 1, as after the last of those calls.  Returns the device block (dra_noisy_linear_fwd_rows reads the rows
         self.numel floats apart; a layer's vectors start at self.slices[...][0] of each row)."""
         rows = int(rows)
-        if rows not in self._rows:
-            self._rows[rows] = StagedUpload((rows, self.numel), torch.float32, self.device, self.SLOTS)
-        up = self._rows[rows]
+        up = self._rows_upload(rows)
         host = up.stage()
         for r in range(rows):
             self._draw_into(host[r])

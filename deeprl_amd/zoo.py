@@ -87,6 +87,19 @@ ZOO = {
                     gradient_clip=0.5, max_steps=int(2e7)),
         normalizers=(ImageNormalizer, SignNormalizer),
         replay=dict(memory_size=int(1e6), history_length=4, fixed_cls=UniformReplay, fixed_async=True), eps=(1.0, 0.01, 1e6)),
+    # examples.py:231-280 (noisy_linear is set on the Config behind merge(kwargs), not through setdefault: a field; NOISY_LAYER_STD
+    # stays at the class's value.  fused_rainbow_feature=True moves the cart-pole, the replay's feed and the update onto the device:
+    # csrc/rainbow_mlp.hip)
+    "rainbow_feature": dict(
+        agent="CategoricalDQNAgent", kw=dict(log_level=0, n_step=3, replay_cls=PrioritizedReplay, async_replay=True),
+        task=lambda c: Task(c.game), eval_task="same", optimizer=_rmsprop(lr=0.001),
+        network=lambda c: N.RainbowNet(c.action_dim, c.categorical_n_atoms, N.FCBody(c.state_dim, noisy_linear=c.noisy_linear),
+                                       noisy_linear=c.noisy_linear),
+        fields=dict(max_steps=1e5, noisy_linear=True, categorical_v_max=100, categorical_v_min=-100, categorical_n_atoms=50,
+                    discount=0.99, batch_size=32, replay_eps=0.01, replay_alpha=0.5, target_network_update_freq=200,
+                    exploration_steps=1000, double_q=True, sgd_update_frequency=4, eval_interval=int(5e3), async_actor=True,
+                    gradient_clip=10),
+        replay=dict(memory_size=int(1e4), with_n_step=True, history_length=1), eps=(1.0, 0.1, 1e4), beta=(0.4, 1)),
     # examples.py:283-336 (Config.NOISY_LAYER_STD is a CLASS attribute the entry point raises to 0.5 when it runs)
     "rainbow_pixel": dict(
         agent="CategoricalDQNAgent",
@@ -223,7 +236,8 @@ def config(name, **kwargs):
     if rp:
         kw = dict(memory_size=rp["memory_size"], batch_size=c.batch_size)
         if rp.get("with_n_step"):
-            kw.update(n_step=c.n_step, discount=c.discount, history_length=c.history_length)
+            # (rainbow_feature hands the replay a literal history_length and leaves the Config's alone)
+            kw.update(n_step=c.n_step, discount=c.discount, history_length=rp.get("history_length", c.history_length))
         elif "history_length" in rp:
             kw.update(history_length=rp["history_length"])
         cls = rp.get("fixed_cls") or c.replay_cls

@@ -1308,6 +1308,73 @@ int dra_dist_mlp_update_supported(int state_dim, int n_actions, int hidden, int 
 int dra_dist_mlp_act(const dra_dist_mlp_net* net, const dra_dqn_mlp_act_io* io, void* stream);
 int dra_dist_mlp_update(const dra_dist_mlp_net* net, const dra_dist_mlp_update_io* io, void* stream);
 
+/* ---- rainbow_mlp: rainbow_feature (examples.py:231-280: CategoricalDQNAgent, RainbowNet over FCBody(noisy_linear=True), n-step
+ * PrioritizedReplay, double_q) over ONE device-resident cart-pole environment and the HBM replay ring: dist_mlp's two launches
+ * over four NoisyLinear layers and the dueling head.  A layer's effective parameters are formed in the kernels from its RAW noise
+ * vectors: W = w_mu + w_sigma * (f(e_out) (x) f(e_in)), b = b_mu + b_sigma * f(e_b), f(x) = sign(x) sqrt|x| (network_utils.py:66-83).
+ * state_dim 4, 2 actions, hidden in {16, 32, 64}, 2 <= n_atoms <= 51. */
+typedef struct dra_rainbow_mlp_layer {
+  int32_t w_mu, w_sigma, b_mu, b_sigma;   /* float offsets into param / target (and the flat gradient buffer) */
+  int32_t e_in, e_out, e_b;               /* float offsets of noise_in, noise_out_weight, noise_out_bias in a noise row */
+  int32_t reserved;
+} dra_rainbow_mlp_layer;
+typedef struct dra_rainbow_mlp_net {
+  const float* param;                /* the optimiser's flat parameter buffer (device): the ONLINE network; read only */
+  const float* target;               /* the TARGET network's flat buffer, same offsets; read only (the acting launch does not read it) */
+  const float* noise;                /* the ONLINE network's raw noise: acting [t_len] rows noise_stride floats apart (transition k
+                                        runs under row k), the update one row; read when the launch runs, so a captured launch
+                                        sees the draw uploaded last */
+  const float* target_noise;         /* the TARGET network's raw noise, one row of the same layout (the update alone reads it) */
+  dra_rainbow_mlp_layer l1, l2;      /* body.layers[0] [hidden][4], body.layers[1] [hidden][hidden] */
+  dra_rainbow_mlp_layer value;       /* fc_value [n_atoms][hidden] */
+  dra_rainbow_mlp_layer advantage;   /* fc_advantage [n_actions * n_atoms][hidden] (row a * n_atoms + j: atom j of action a) */
+  int32_t noise_stride;              /* floats between two noise rows of the acting launch */
+  int32_t gate;                      /* 1 relu, 2 tanh */
+  int32_t state_dim, n_actions, hidden, n_atoms;
+  double v_min, v_max;               /* the support, z = linspace(v_min, v_max, n_atoms) in fp64 narrowed to float32 */
+} dra_rainbow_mlp_net;
+/* The acting launch is dra_dqn_mlp_act's with dra_dqn_mlp_act_io as it is; the action values (out_q [t_len][2]) are sum_j
+ * softmax(v + adv_a - mean_a adv)_j z_j under noise row k.  (Under noisy layers epsilon is 0, DQN_agent.py:34-35: the host stages
+ * explore = 0.)
+ *
+ * The update, ONE launch of one workgroup: for b < batch the n-step transition at DATA index idx[b] (replay.py:112-140): state =
+ * frame idx, next state = frame idx + n_step, action of row idx, reward = the fold cum = r_i + (m_i * step_discount) * cum over i =
+ * n_step - 1 .. 0 in fp64 narrowed to float32, mask = the product of the n_step masks.  The TARGET network under target_noise on the
+ * next states; a_next = the FIRST maximum of its action values (double_q: of the ONLINE network's under `noise`); Tz_j = clamp(reward
+ * + (discount * mask) * z_j, v_min, v_max); target_i = sum_j clamp(1 - |Tz_j - z_i| / delta, 0, 1) p_next[a_next][j]; loss_vec[b] =
+ * sum_i target_i log(target_i + 1e-5) - target_i log_softmax(logits[a])_i of the ONLINE network under the same `noise` on the state;
+ * prio[b] = (|loss_vec[b]| + replay_eps) ** replay_alpha; weights[b] = (prob[b] * batch + 1e-6) ** -*beta divided by their maximum
+ * (DQN_agent.py:120-127); loss = mean_b loss_vec[b] weights[b], and its gradient with respect to the sixteen tensors (w_mu, w_sigma,
+ * b_mu, b_sigma of the four layers), written (every element, nothing between the tensors) into `grad` at the parameters' offsets.
+ * Fixed summation order, no atomics.  An idx outside [0, capacity - 1 - n_step] is clamped into it and counted in *err.
+ * 1 <= batch <= 64, 1 <= n_step <= 8 (dra_rainbow_mlp_update_supported: what fits the workgroup's 160 KiB of LDS). */
+typedef struct dra_rainbow_mlp_update_io {
+  const double* ring_frames;    /* [capacity][4] */
+  const int64_t* ring_actions;  /* [capacity] (1 = the second action, anything else the first) */
+  const double* ring_rewards;   /* [capacity] */
+  const int32_t* ring_masks;    /* [capacity] */
+  const int64_t* idx;           /* [batch]: data indices */
+  const float* prob;            /* [batch]: sampling probabilities */
+  const float* beta;            /* [1] (device): read when the launch runs */
+  float* grad;                  /* the flat gradient buffer (device) */
+  float* out_loss;              /* [1] */
+  float* out_loss_vec;          /* [batch]: the unweighted KL */
+  float* out_prio;              /* [batch]: the new priorities, in sample order */
+  float* out_weights;           /* [batch] */
+  float* out_q_next;            /* [batch][2]: the TARGET network's action values of the next states */
+  float* out_target;            /* [batch][n_atoms] */
+  int32_t* err;                 /* [1] (in/out) */
+  int64_t capacity;
+  double discount;              /* the bootstrap factor: config.discount ** n_step */
+  double step_discount;         /* the fold's: the replay's discount */
+  double replay_eps, replay_alpha;
+  int32_t batch, double_q, n_step, reserved;
+} dra_rainbow_mlp_update_io;
+int dra_rainbow_mlp_supported(int state_dim, int n_actions, int hidden, int t_len, int gate, int n_atoms);                        /* 0 = yes */
+int dra_rainbow_mlp_update_supported(int state_dim, int n_actions, int hidden, int batch, int gate, int n_atoms, int n_step);    /* 0 = yes */
+int dra_rainbow_mlp_act(const dra_rainbow_mlp_net* net, const dra_dqn_mlp_act_io* io, void* stream);
+int dra_rainbow_mlp_update(const dra_rainbow_mlp_net* net, const dra_rainbow_mlp_update_io* io, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

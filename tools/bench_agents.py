@@ -24,6 +24,9 @@ after a warm-up.  Prints one JSON object per line: agent steps/s, env steps/s, g
             `_module_update` = config.fused_dqn_update False; `_host` = the switch off: the python environment and ring feeds)
             categorical_dqn_feature examples.py:164-193, quantile_regression_dqn_feature examples.py:101-127 (the same, with
             config.fused_dist_feature True and config.fused_dist_update True; `_module_update` = config.fused_dist_update False; `_host` = the switch off)
+            rainbow_feature examples.py:231-280 (noisy RainbowNet, 50 atoms, n_step 3, PrioritizedReplay, double_q, minibatch 32;
+            config.fused_rainbow_feature True and config.fused_rainbow_update True; `_module_update` = config.fused_rainbow_update
+            False; `_host` = the switch off)
   ddpg_continuous examples.py:554-583, td3_continuous examples.py:587-617 (one host environment, (400, 300) relu MLPs, Adam 1e-3,
             minibatch 100, a 1M ring; warm_up shortened to 1000 so that the timed window is all updates; the default is
             config.fused_dpg_update True: csrc/dpg_mlp.hip; `_modules` = the switch off: torch modules and optimisers)
@@ -40,6 +43,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import deeprl_amd as d  # noqa: E402
 import deeprl_amd.agents as agents_mod  # noqa: E402
+from deeprl_amd import zoo  # noqa: E402
 
 
 class _Quiet:
@@ -240,6 +244,12 @@ def dist_feature(head, **switches):
     return cls(c), dict(env_per_step=4, updates_per_step=1, warm=120)
 
 
+def rainbow_feature(**switches):
+    agent = zoo.agent("rainbow_feature", game="classic-CartPole-v0", tag="bench", async_replay=False, **switches)
+    # (warm: past exploration_steps -- 250 agent steps -- and the graph captures, so that the timed window is all updates)
+    return agent, dict(env_per_step=4, updates_per_step=1, warm=300)
+
+
 def option_critic_pixel(workers=16, device=True, **switches):
     c = d.Config()
     c.merge(dict(game="BreakoutNoFrameskip-v4", log_level=0, tag="bench", device_env=device, **switches))
@@ -363,6 +373,10 @@ CASES = {
     "quantile_regression_dqn_feature": lambda: dist_feature("quantile", fused_dist_feature=True, fused_dist_update=True),
     "quantile_regression_dqn_feature_module_update": lambda: dist_feature("quantile", fused_dist_feature=True, fused_dist_update=False),
     "quantile_regression_dqn_feature_host": lambda: dist_feature("quantile"),   # the switch off
+    # rainbow_feature on the same Step (csrc/rainbow_mlp.hip): noisy layers, PER, n_step 3, double_q
+    "rainbow_feature": lambda: rainbow_feature(fused_rainbow_feature=True, fused_rainbow_update=True),
+    "rainbow_feature_module_update": lambda: rainbow_feature(fused_rainbow_feature=True, fused_rainbow_update=False),
+    "rainbow_feature_host": lambda: rainbow_feature(),   # the switch off: the python cart-pole, per transition a noise draw and four noisy modules
     "ppo_continuous_1": lambda: ppo_continuous(1),
     "ppo_continuous_16": lambda: ppo_continuous(16),                                  # device environments + persistent kernels
     "ppo_continuous_16_host": lambda: ppo_continuous(16, device=False),               # host environments, persistent update kernel
