@@ -1,6 +1,6 @@
 // What the one-workgroup rollout / acting kernels over device-resident cart-poles share (cat_mlp.hip: a2c_feature, q_mlp.hip:
-// n_step_dqn_feature, oc_mlp.hip: option_critic_feature, dqn_mlp.hip: dqn_feature, dist_mlp.hip: the C51 / QR-DQN entries), stated
-// ONCE:
+// n_step_dqn_feature, oc_mlp.hip: option_critic_feature, dqn_mlp.hip: dqn_feature, dist_mlp.hip: the C51 / QR-DQN entries,
+// rainbow_mlp.hip: rainbow_feature), stated ONCE:
 //
 //   CartPoleLanes    the environments in the registers of wave 0 (lane e = environment e) for the whole launch: load, observe,
 //                    advance (cartpole_step, the action / reward / mask row), append (the episode ring: an ending episode's
@@ -10,7 +10,9 @@
 //                    its lanes are numbered (cat_mlp: env0 + lane, q_mlp and oc_mlp: lane).
 //   BodyWeights<H>   the two-layer body's W1^T, W2^T, b1, b2 in LDS and their staging from a flat parameter buffer;
 //   QNetWeights<H>   the same with the Q head [A][H + 1] behind it (q_mlp.hip, dqn_mlp.hip).
-//   EpisodeRow       what append reads of a row in the kernels that write transitions to a replay ring (dqn_mlp.hip, dist_mlp.hip).
+//   EpisodeRow       what append reads of a row in the kernels that write transitions to a replay ring (dqn_mlp.hip, dist_mlp.hip,
+//                    rainbow_mlp.hip); the rest of their acting frame -- the ring cursor, the wave-0 block, the epilogue, the io
+//                    check -- is replay_act.h's ReplayActor over these lanes.
 //   the host checks  cartpole_mlp_supported, offsets_nonnegative, cartpole_io_ok, and the hidden x gate dispatch.
 //
 // Each kernel keeps its action choice (Gumbel-max / staged epsilon-greedy / option-critic's two inverse-CDF draws with the carried
@@ -81,7 +83,7 @@ struct CartPoleRow {
         ring_cap(io.ring_cap), N(io.n_env) {}
 };
 
-// what CartPoleLanes::append reads of a row where the transition itself goes to a replay ring (dqn_mlp.hip, dist_mlp.hip): the
+// what CartPoleLanes::append reads of a row where the transition itself goes to a replay ring (replay_act.h's episode_row): the
 // episode ring alone
 struct EpisodeRow {
   int64_t* out_action = nullptr;

@@ -5,43 +5,34 @@
 //
 //   dist_mlp_act_kernel      DQN_agent.py:23-45 with CategoricalDQN_agent.py:22-24 / QuantileRegressionDQN_agent.py:18-20 as the
 //                            action values: wave a carries action a, lane j its atom j -- the logit, and over the wave the softmax
-//                            and sum_j p_j z_j (categorical) or the quantiles' mean.  The staged epsilon-greedy draws, the first
-//                            maximum, the fp64 environment step, the ring row, the episode ring and the counters are
-//                            dqn_mlp_act_kernel's.
+//                            and sum_j p_j z_j (categorical: c51_block.h) or the quantiles' mean.  The staged epsilon-greedy
+//                            draws, the first maximum, the fp64 environment step, the ring row, the episode ring and the
+//                            counters are dqn_mlp_act_kernel's: replay_act.h.
 //   dist_mlp_update_kernel   CategoricalDQN_agent.py:60-89 / QuantileRegressionDQN_agent.py:55-77 and the whole backward as ONE
 //                            launch of one workgroup over row blocks of 16 (the two heads leave no room for dqn_mlp's 64: the
 //                            budget is update_lds_floats): the minibatch gathered from the ring, the target
 //                            network's (categorical + double_q: and the online network's) forward of the next states, the
-//                            projected target distribution or the target quantiles, the online forward of the states, the loss
-//                            and its gradient with respect to all six tensors in the optimiser's flat gradient buffer.
+//                            projected target distribution (c51_block.h) or the target quantiles, the online forward of the
+//                            states, the loss and its gradient with respect to all six tensors in the optimiser's flat gradient
+//                            buffer.
 //
 // Plain fp32 VALU code, weights in LDS once per launch, every dot product one FMA chain in ascending k, every gradient element
 // owned by ONE thread that adds its rows in ascending order: no atomics, the same bits on every launch.
 #include "common.h"
+#include "c51_block.h"
 #include "mlp_update_block.h"
+#include "replay_act.h"
 #include <math.h>
 
 namespace {
 
 constexpr int kHeadCategorical = 1, kHeadQuantile = 2;
-constexpr int kMaxAtoms = 51;    // atoms / quantiles per action (one lane each in the acting kernel: at most 64)
 constexpr size_t kLdsBytes = 160 * 1024;
 
 // ---------------------------------------------------------------------------------------------------- acting
-constexpr int kMaxK = 8;         // transitions of one launch
-constexpr int kNP = 8;           // row stride of the single environment's transposed activations (hidden_layer's row block)
-
 __host__ __device__ constexpr size_t act_lds_floats(int H, int N) {
   return body_weight_floats(H) + (size_t)round_up4(kA * N * (H + 1)) + round_up4(kA * N) + round_up4(N)      // body, head, bias, z
-         + 4 + (size_t)kS * kNP + 2 * (size_t)H * kNP;                                                       // q, x^T, h1^T, h2^T
-}
-
-// z = np.linspace(v_min, v_max, n) narrowed to float32 (what tensor(config.atoms) uploads): arange * step + start in fp64, the
-// last one v_max itself
-__device__ __forceinline__ float atom_value(double v_min, double v_max, int n, int i) {
-  if (i == n - 1) return (float)v_max;
-  const double step = (v_max - v_min) / (double)(n - 1);
-  return (float)((double)i * step + v_min);
+         + (size_t)act_scratch_floats(H);
 }
 
 template <int H, int GATE, int HEAD>
@@ -55,17 +46,10 @@ dist_mlp_act_kernel(dra_dist_mlp_net net, dra_dqn_mlp_act_io io) {
   float* wq = lds + body_weight_floats(H);            // [M][H + 1]: lanes read consecutive rows, one bank apart
   float* bq = wq + round_up4(M * (H + 1));            // [M]
   float* sZ = bq + round_up4(M);                      // [N]
-  float* sQ = sZ + round_up4(N);                      // [A] (+ pad)
-  float* sXT = sQ + 4;                                // [S][NP]
-  float* sH1T = sXT + kS * kNP;                       // [H][NP]
-  float* sH2T = sH1T + H * kNP;                       // [H][NP]
-  const int act_floats = 4 + kS * kNP + 2 * H * kNP;
-  for (int i = tid; i < act_floats; i += 256) sQ[i] = 0.f;      // (rows 1..7 of x^T stay zero: one environment)
-  const int64_t t0 = *io.step_counter;                // (rewritten by thread 0 behind the last barrier)
-  const int64_t cap = io.capacity;
-  int64_t slot0 = *io.slot0;
-  const bool bad_slot = slot0 < 0 || slot0 >= cap;
-  if (bad_slot) slot0 = 0;
+  const ActScratch<H> s(sZ + round_up4(N));
+  s.zero(tid);
+  ReplayActor actor;
+  actor.begin(io, tid);                               // (ahead of the staging, for the register allocator: mlp_rollout.h's banner)
   const float* __restrict__ P = net.param;
   body.stage(P, net, tid);
   for (int i = tid; i < M * H; i += 256) {
@@ -78,26 +62,15 @@ dist_mlp_act_kernel(dra_dist_mlp_net net, dra_dqn_mlp_act_io io) {
   }
   __syncthreads();                                    // (thread 0 writes x^T next, over what other threads zeroed)
 
-  CartPoleLanes lanes;                               // lane 0 of wave 0 carries the environment
-  lanes.load(io, tid);
-  EpisodeRow ep;
-  ep.ep_ring = io.ep_ring;
-  ep.horizon = io.horizon;
-  ep.ring_cap = io.ring_cap;
-  const CartPoleRow row(ep);
+  const CartPoleRow row = episode_row(io);
   const double reward = 1.0 * io.reward_coef;         // what config.reward_normalizer(1.0) feeds
 
   for (int k = 0; k < K; ++k) {
-    if (tid == 0) {
-      sXT[0 * kNP] = (float)lanes.st.x;
-      sXT[1 * kNP] = (float)lanes.st.xd;
-      sXT[2 * kNP] = (float)lanes.st.th;
-      sXT[3 * kNP] = (float)lanes.st.thd;
-    }
+    actor.observe(s.xT, kNP, tid);
     __syncthreads();
-    hidden_layer<H, GATE, 256>(sXT, body.w1, body.b1, sH1T, kS, kNP, tid);
+    hidden_layer<H, GATE, 256>(s.xT, body.w1, body.b1, s.h1T, kS, kNP, tid);
     __syncthreads();
-    hidden_layer<H, GATE, 256>(sH1T, body.w2, body.b2, sH2T, H, kNP, tid);
+    hidden_layer<H, GATE, 256>(s.h1T, body.w2, body.b2, s.h2T, H, kNP, tid);
     __syncthreads();
     // ---- the head: wave a = action a, lane j = atom j; the action value over the wave
     if (tid < kA * kWave) {
@@ -108,54 +81,24 @@ dist_mlp_act_kernel(dra_dist_mlp_net net, dra_dqn_mlp_act_io io) {
         const float* wr = wq + (a * N + j) * (H + 1);
         float acc = 0.f;
 #pragma unroll 8
-        for (int i = 0; i < H; ++i) acc = fmaf(sH2T[i * kNP], wr[i], acc);
+        for (int i = 0; i < H; ++i) acc = fmaf(s.h2T[i * kNP], wr[i], acc);
         l = acc + bq[a * N + j];
       }
-      float q;
-      if constexpr (HEAD == kHeadCategorical) {
-        const float m = wave_max(live ? l : -INFINITY);
-        const float e = live ? expf(l - m) : 0.f;
-        const float s = wave_sum(e);
-        q = wave_sum(live ? (e / s) * sZ[j] : 0.f);
-      } else {
-        q = wave_sum(live ? l : 0.f) / (float)N;
-      }
+      float q, p;
+      if constexpr (HEAD == kHeadCategorical) q = wave_softmax_value(l, live, sZ + j, p);
+      else q = wave_sum(live ? l : 0.f) / (float)N;
       if (j == 0) {
-        sQ[a] = q;
+        s.q[a] = q;
         io.out_q[k * kA + a] = q;
       }
     }
     __syncthreads();
-    // ---- epsilon-greedy action (torch_utils.py:51-58 with the draws made ahead), the ring row, environment step: wave 0
-    if (tid < 64) {
-      bool done = false;
-      double ended = 0.0;
-      if (tid == 0) {
-        int arg = sQ[1] > sQ[0] ? 1 : 0;                          // np.argmax: the first maximum
-        if (io.explore[k]) arg = io.random_action[k] == 1 ? 1 : 0;
-        const int64_t slot = (slot0 + k) % cap;
-        double* frame = io.ring_frames + slot * kS;               // the observation the action was chosen on
-        frame[0] = lanes.st.x;
-        frame[1] = lanes.st.xd;
-        frame[2] = lanes.st.th;
-        frame[3] = lanes.st.thd;
-        done = cartpole_step(lanes.st, lanes.counter, lanes.ep_steps, lanes.ep_return, lanes.seed, arg, io.horizon, ended);
-        io.ring_actions[slot] = arg;
-        io.ring_rewards[slot] = reward;
-        io.ring_masks[slot] = done ? 0 : 1;
-        io.out_action[k] = arg;
-      }
-      lanes.append(row, done, ended, t0 + k, 0, tid);
-    }
+    actor.step(io, row, s.q, reward, k, tid);
     // (thread 0 writes the next observation into x^T next: layer 1 of this step, its only reader, is three barriers back; q is
     // rewritten behind the three barriers of the next step)
   }
   __syncthreads();
-  lanes.store(io, tid);
-  if (tid == 0) {
-    *io.step_counter = t0 + K;
-    if (bad_slot) *io.err = *io.err + 1;
-  }
+  actor.finish(io, K, tid);
 }
 
 // ---------------------------------------------------------------------------------------------------- the update
@@ -379,16 +322,7 @@ dist_mlp_update_kernel(dra_dist_mlp_net net, dra_dist_mlp_update_io io) {
       const float gm = __fmul_rn(gamma, sMsk[r]);
       float t;
       if constexpr (CAT) {
-        // CategoricalDQN_agent.py:72-78: sum_j clamp(1 - |clamp(r + gamma m z_j) - z_i| / delta, 0, 1) p_j
-        const float* p = sL + an * N * kLL + r;
-        const float zi = sZ[i];
-        t = 0.f;
-        for (int j = 0; j < N; ++j) {
-          float tz = __fadd_rn(sRew[r], __fmul_rn(gm, sZ[j]));
-          tz = fminf(fmaxf(tz, v_min), v_max);
-          const float w = fminf(fmaxf(1.f - fabsf(tz - zi) / delta, 0.f), 1.f);
-          t = fmaf(w, p[j * kLL], t);
-        }
+        t = c51_project(sZ, sL + an * N * kLL + r, kLL, N, sZ[i], sRew[r], gm, v_min, v_max, delta);      // CategoricalDQN_agent.py:72-78
       } else {
         t = __fadd_rn(sRew[r], __fmul_rn(gm, sL[(an * N + i) * kLL + r]));
       }
@@ -583,7 +517,6 @@ int dispatch_hidden_gate_head(int hidden, int gate, int head, F&& f) {
 
 }  // namespace
 
-static_assert(kMaxAtoms <= kWave, "the acting kernel gives every atom of an action one lane of a wave");
 static_assert(update_lds_floats(64, kMaxAtoms) * sizeof(float) <= kLdsBytes, "the update's LDS at the largest shape");
 static_assert(kUB % 4 == 0 && kUB * kS <= 256 && kA * kUB <= 256, "the row block");
 
@@ -601,14 +534,9 @@ DRA_API int dra_dist_mlp_update_supported(int state_dim, int n_actions, int hidd
 
 DRA_API int dra_dist_mlp_act(const dra_dist_mlp_net* net, const dra_dqn_mlp_act_io* io, void* stream) {
   if (!net || !io || !net->param) return DRA_EINVAL;
-  if (io->n_env != 1 ||
-      dra_dist_mlp_supported(net->state_dim, net->n_actions, net->hidden, io->t_len, net->gate, net->head, net->n_atoms))
+  if (dra_dist_mlp_supported(net->state_dim, net->n_actions, net->hidden, io->t_len, net->gate, net->head, net->n_atoms))
     return DRA_EINVAL;
-  if (!net_ok(net) || io->horizon < 1 || io->ring_cap < 1 || io->capacity < 1) return DRA_EINVAL;
-  if (!io->env_state || !io->env_counter || !io->ep_steps || !io->ep_return || !io->env_seed || !io->step_counter || !io->ep_count ||
-      !io->ep_ring || !io->explore || !io->random_action || !io->slot0 || !io->ring_frames || !io->ring_actions ||
-      !io->ring_rewards || !io->ring_masks || !io->out_q || !io->out_action || !io->err)
-    return DRA_EINVAL;
+  if (!net_ok(net) || !replay_act_io_ok(io)) return DRA_EINVAL;
   return dispatch_hidden_gate_head(net->hidden, net->gate, net->head, [&](auto h, auto g, auto hd) {
     constexpr int H = decltype(h)::value, GATE = decltype(g)::value, HEAD = decltype(hd)::value;
     return launch_one_workgroup<&dist_mlp_act_kernel<H, GATE, HEAD>>(act_lds_floats(H, net->n_atoms) * sizeof(float), net, io, stream);

@@ -16,22 +16,19 @@
 // Both are q_mlp.hip's kernels with the replay between them: latency-bound chains over a few rows, plain fp32 VALU code, weights in
 // LDS once per launch, activations TRANSPOSED and read 16 bytes at a time, every dot product one FMA chain in ascending k.  The
 // update walks the rows in blocks of 64; every gradient element is owned by ONE thread that adds its rows in ascending order:
-// no atomics, the same bits on every launch.  The acting kernel's weights are cartpole_rollout.h's QNetWeights<H>; the update's
-// layers, gather and head forward are mlp_update_block.h's.  The staging of the two networks' bodies and the gradient bookkeeping
-// are written in place (mlp_rollout.h's banner: the figures).
+// no atomics, the same bits on every launch.  The acting kernel's weights are cartpole_rollout.h's QNetWeights<H>, its frame (the
+// scratch, the ring cursor, the wave-0 block, the epilogue, the io check) is replay_act.h's, shared with dist_mlp.hip and
+// rainbow_mlp.hip; the update's layers, gather and head forward are mlp_update_block.h's.  The staging of the two networks' bodies
+// and the gradient bookkeeping are written in place (mlp_rollout.h's banner: the figures).
 #include "common.h"
 #include "mlp_update_block.h"
+#include "replay_act.h"
 #include <math.h>
 
 namespace {
 
 // ---------------------------------------------------------------------------------------------------- acting
-constexpr int kMaxK = 8;         // transitions of one launch
-constexpr int kNP = 8;           // row stride of the single environment's transposed activations (hidden_layer's row block)
-
-__host__ __device__ constexpr size_t act_lds_floats(int H) {
-  return q_net_weight_floats(H) + 4 + (size_t)kS * kNP + 2 * (size_t)H * kNP;      // the weights, q [A], x^T [S][NP], h1^T, h2^T [H][NP]
-}
+__host__ __device__ constexpr size_t act_lds_floats(int H) { return q_net_weight_floats(H) + (size_t)act_scratch_floats(H); }
 
 template <int H, int GATE>
 __global__ void __launch_bounds__(256)
@@ -41,81 +38,39 @@ dqn_mlp_act_kernel(dra_q_mlp_net net, dra_dqn_mlp_act_io io) {
   const int K = io.t_len;
 
   const QNetWeights<H> online(lds);
-  float* sQ = lds + q_net_weight_floats(H);                 // [A] (+ pad)
-  float* sXT = sQ + 4;                                // [S][NP]
-  float* sH1T = sXT + kS * kNP;                       // [H][NP]
-  float* sH2T = sH1T + H * kNP;                       // [H][NP]
-  const int act_floats = 4 + kS * kNP + 2 * H * kNP;
-  for (int i = tid; i < act_floats; i += 256) sQ[i] = 0.f;      // (rows 1..7 of x^T stay zero: one environment)
-  const int64_t t0 = *io.step_counter;                // (rewritten by thread 0 behind the last barrier)
-  const int64_t cap = io.capacity;
-  int64_t slot0 = *io.slot0;
-  const bool bad_slot = slot0 < 0 || slot0 >= cap;
-  if (bad_slot) slot0 = 0;
+  const ActScratch<H> s(lds + q_net_weight_floats(H));
+  s.zero(tid);
+  ReplayActor actor;
+  actor.begin(io, tid);                               // (ahead of the staging, for the register allocator: mlp_rollout.h's banner)
   online.stage(net.param, net, tid);
   __syncthreads();                                    // (thread 0 writes x^T next, over what other threads zeroed)
 
-  CartPoleLanes lanes;                               // lane 0 of wave 0 carries the environment
-  lanes.load(io, tid);
-  EpisodeRow ep;
-  ep.ep_ring = io.ep_ring;
-  ep.horizon = io.horizon;
-  ep.ring_cap = io.ring_cap;
-  const CartPoleRow row(ep);
+  const CartPoleRow row = episode_row(io);
   const double reward = 1.0 * io.reward_coef;         // what config.reward_normalizer(1.0) feeds
 
   for (int k = 0; k < K; ++k) {
-    if (tid == 0) {
-      sXT[0 * kNP] = (float)lanes.st.x;
-      sXT[1 * kNP] = (float)lanes.st.xd;
-      sXT[2 * kNP] = (float)lanes.st.th;
-      sXT[3 * kNP] = (float)lanes.st.thd;
-    }
+    actor.observe(s.xT, kNP, tid);
     __syncthreads();
-    hidden_layer<H, GATE, 256>(sXT, online.body.w1, online.body.b1, sH1T, kS, kNP, tid);
+    hidden_layer<H, GATE, 256>(s.xT, online.body.w1, online.body.b1, s.h1T, kS, kNP, tid);
     __syncthreads();
-    hidden_layer<H, GATE, 256>(sH1T, online.body.w2, online.body.b2, sH2T, H, kNP, tid);
+    hidden_layer<H, GATE, 256>(s.h1T, online.body.w2, online.body.b2, s.h2T, H, kNP, tid);
     __syncthreads();
     if (tid < kA) {
       const float* wr = online.wq + tid * (H + 1);
       float acc = 0.f;
 #pragma unroll 8
-      for (int j = 0; j < H; ++j) acc = fmaf(sH2T[j * kNP], wr[j], acc);
+      for (int j = 0; j < H; ++j) acc = fmaf(s.h2T[j * kNP], wr[j], acc);
       acc += online.bq[tid];
-      sQ[tid] = acc;
+      s.q[tid] = acc;
       io.out_q[k * kA + tid] = acc;
     }
     __syncthreads();
-    // ---- epsilon-greedy action (torch_utils.py:51-58 with the draws made ahead), the ring row, environment step: wave 0
-    if (tid < 64) {
-      bool done = false;
-      double ended = 0.0;
-      if (tid == 0) {
-        int arg = sQ[1] > sQ[0] ? 1 : 0;                          // np.argmax: the first maximum
-        if (io.explore[k]) arg = io.random_action[k] == 1 ? 1 : 0;
-        const int64_t slot = (slot0 + k) % cap;
-        double* frame = io.ring_frames + slot * kS;               // the observation the action was chosen on
-        frame[0] = lanes.st.x;
-        frame[1] = lanes.st.xd;
-        frame[2] = lanes.st.th;
-        frame[3] = lanes.st.thd;
-        done = cartpole_step(lanes.st, lanes.counter, lanes.ep_steps, lanes.ep_return, lanes.seed, arg, io.horizon, ended);
-        io.ring_actions[slot] = arg;
-        io.ring_rewards[slot] = reward;
-        io.ring_masks[slot] = done ? 0 : 1;
-        io.out_action[k] = arg;
-      }
-      lanes.append(row, done, ended, t0 + k, 0, tid);
-    }
+    actor.step(io, row, s.q, reward, k, tid);
     // (thread 0 writes the next observation into x^T next: layer 1 of this step, its only reader, is three barriers back; q is
     // rewritten behind the three barriers of the next step)
   }
   __syncthreads();
-  lanes.store(io, tid);
-  if (tid == 0) {
-    *io.step_counter = t0 + K;
-    if (bad_slot) *io.err = *io.err + 1;
-  }
+  actor.finish(io, K, tid);
 }
 
 // ---------------------------------------------------------------------------------------------------- the update
@@ -371,12 +326,8 @@ DRA_API int dra_dqn_mlp_update_supported(int state_dim, int n_actions, int hidde
 
 DRA_API int dra_dqn_mlp_act(const dra_q_mlp_net* net, const dra_dqn_mlp_act_io* io, void* stream) {
   if (!net || !io || !net->param) return DRA_EINVAL;
-  if (io->n_env != 1 || dra_dqn_mlp_supported(net->state_dim, net->n_actions, net->hidden, io->t_len, net->gate)) return DRA_EINVAL;
-  if (!offsets_ok(net) || io->horizon < 1 || io->ring_cap < 1 || io->capacity < 1) return DRA_EINVAL;
-  if (!io->env_state || !io->env_counter || !io->ep_steps || !io->ep_return || !io->env_seed || !io->step_counter || !io->ep_count ||
-      !io->ep_ring || !io->explore || !io->random_action || !io->slot0 || !io->ring_frames || !io->ring_actions ||
-      !io->ring_rewards || !io->ring_masks || !io->out_q || !io->out_action || !io->err)
-    return DRA_EINVAL;
+  if (dra_dqn_mlp_supported(net->state_dim, net->n_actions, net->hidden, io->t_len, net->gate)) return DRA_EINVAL;
+  if (!offsets_ok(net) || !replay_act_io_ok(io)) return DRA_EINVAL;
   return dispatch_hidden_gate(net->hidden, net->gate, [&](auto h, auto g) {
     constexpr int H = decltype(h)::value, GATE = decltype(g)::value;
     return launch_one_workgroup<&dqn_mlp_act_kernel<H, GATE>>(act_lds_floats(H) * sizeof(float), net, io, stream);

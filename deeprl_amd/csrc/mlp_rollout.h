@@ -3,7 +3,9 @@
 // codes and softplus_f.  The cart-pole kernels (cat_mlp.hip, q_mlp.hip, oc_mlp.hip, dqn_mlp.hip, dist_mlp.hip) share more in
 // cartpole_rollout.h: the environment lanes (load, observe, step with the episode-ring append, store), the staging of a two-layer
 // body's weights (BodyWeights<H>; with the Q head QNetWeights<H>), the shape / offset / io checks and the hidden x gate dispatch.
-// Their whole-update kernels share the row-block pieces in mlp_update_block.h.
+// Their whole-update kernels share the row-block pieces in mlp_update_block.h.  The three kernels that act into a replay ring
+// (dqn_mlp.hip, dist_mlp.hip, rainbow_mlp.hip) share their acting frame in replay_act.h, the two categorical files their atoms,
+// projection and one-wave softmax in c51_block.h.
 //
 // Shared or not is decided by the generated code and the kernel trace, not by taste: a __forceinline__ function is optimised on
 // its own before it is inlined, and these kernels sit at the edge of the SGPR file (DESIGN.md 4.13 has every figure).  The bar for
@@ -13,7 +15,18 @@
 //   gate_back / block_layer / gather_states / block_head at row blocks 16 and 64 (H 32 / 64 equal; at H 16 x 64 rows a thread now
 //     carries 4 rows and no thread idles: q_mlp_update_kernel 65 / 71 -> 62 / 60 VGPRs (relu / tanh), 7 -> 8 waves; oc_mlp_update_kernel
 //     86 / 88 -> 66 / 68, 5 -> 7; dqn_mlp_update_kernel 69 / 96 -> 64 / 70, 7 / 5 -> 8 / 7);
-//   UpdateBody<H> (the online body's LDS layout and staging) in q_mlp_update_kernel and oc_mlp_update_kernel.
+//   UpdateBody<H> (the online body's LDS layout and staging) in q_mlp_update_kernel and oc_mlp_update_kernel;
+//   replay_act.h's ReplayActor (begin / observe / step / finish), ActScratch<H> and episode_row in the three replay acting kernels,
+//     c51_block.h's atom_value / c51_project / wave_softmax_value in dist_mlp.hip and rainbow_mlp.hip: all 48 instances of the three
+//     files hold the bar (profiles/replay_act_kernel_resources.txt).  35 are equal; SGPR spills fell in dqn_mlp_act_kernel<32> (5 / 7
+//     -> 4 / 4), in three of dist_mlp_act_kernel's twelve (27 -> 25 at H 16 / 32 tanh qr, 8 -> 6 at H 64 relu c51; one VGPR less at
+//     H 16 relu) and in all six of rainbow_mlp_act_kernel (160 / 164 / 145 / 149 / 161 / 165 -> 141 / 145 / 139 / 143 / 151 / 155; 153
+//     -> 130 VGPRs at H 16 / 32 relu).  The form that holds it is the PLACE of begin(): behind the scratch's zeroing and ahead of the
+//     weights' staging in dqn_mlp and dist_mlp, ahead of the zeroing in rainbow_mlp.  Zeroing first in rainbow_mlp_act_kernel: 149 ->
+//     166 (H 32 tanh), 161 -> 174 (H 64 relu); begin() behind the atoms: 165 -> 166 (H 64 tanh); begin() first in
+//     dqn_mlp_act_kernel: 4 / 4 / 5 / 7 / 4 / 4 -> 12 in all six; in dist_mlp_act_kernel: nine of twelve above (6 -> 12 at relu qr);
+//     begin() behind the staging's barrier there: 9 -> 23 (H 64 tanh qr).  The members' order, the order inside begin() and the
+//     softmax in place or shared moved nothing.
 // NOT shared, each written in place in the four update kernels:
 //   the body's gradient bookkeeping (owner indices, dW2 / db2 / dW1 / db1 accumulators, their stores).  As one struct with the
 //     same loop text it met the register bar everywhere but in dist_mlp_update_kernel's stores (H 16: 115 / 103 / 115 / 105 -> 117 /

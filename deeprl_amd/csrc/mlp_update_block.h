@@ -1,7 +1,8 @@
 // The row-block pieces of a one-workgroup whole-update kernel over a two-layer cart-pole MLP, stated ONCE and templated on the row
 // block UB (q_mlp.hip, oc_mlp.hip, dqn_mlp.hip: UB 64; dist_mlp.hip: UB 16): gate_back, block_layer, gather_states, block_head, the
-// online body's LDS layout and staging (UpdateBody<H>: q_mlp.hip, oc_mlp.hip).  Heads, losses and the gradient bookkeeping stay in
-// their kernels: what is NOT shared, with the figures that decided it, is in mlp_rollout.h's banner.
+// online body's LDS layout and staging (UpdateBody<H>: q_mlp.hip, oc_mlp.hip, rainbow_mlp.hip).  Heads, losses and the gradient
+// bookkeeping stay in their kernels (the categorical projection and one-wave softmax of dist_mlp.hip / rainbow_mlp.hip: c51_block.h):
+// what is NOT shared, with the figures that decided it, is in mlp_rollout.h's banner.
 // Row stride of every transposed activation: UB + 4 floats (16-byte aligned rows, consecutive units 4 banks apart).
 #pragma once
 #include "cartpole_rollout.h"

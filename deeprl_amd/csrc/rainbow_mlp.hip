@@ -11,7 +11,8 @@
 //                               combination q = v + (adv - mean_a adv), the softmax and sum_j p_j z_j over the wave.  The action is
 //                               the first maximum unless the staged explore word says otherwise (the host stages 0: epsilon is 0
 //                               under noisy layers); the fp64 environment step, the ring row, the episode ring and the counters are
-//                               dqn_mlp_act_kernel's.
+//                               dqn_mlp_act_kernel's: replay_act.h.  The atoms, the one-wave softmax with its expectation (here and
+//                               in the update's target and double_q passes) and the projection are dist_mlp.hip's: c51_block.h.
 //   rainbow_mlp_update_kernel   DQN_agent.py:114-134 with CategoricalDQN_agent.py:60-89 and the whole backward as ONE launch of one
 //                               workgroup.  Both networks' effective weights do not fit the LDS next to each other
 //                               (update_lds_floats), so the TARGET network (under the target's noise) runs over ALL
@@ -24,12 +25,13 @@
 // Plain fp32 VALU code, every dot product one FMA chain in ascending k, every gradient element owned by ONE thread that adds its
 // rows in ascending order: no atomics, the same bits on every launch.
 #include "common.h"
+#include "c51_block.h"
 #include "mlp_update_block.h"
+#include "replay_act.h"
 #include <math.h>
 
 namespace {
 
-constexpr int kMaxAtoms = 51;    // atoms per action (one lane each: at most 64)
 constexpr size_t kLdsBytes = 160 * 1024;
 static_assert(kA == 2, "the dueling mean and the head's waves are written for two actions");
 
@@ -116,20 +118,10 @@ __device__ __forceinline__ float dueling_logit(const float* raw, int N, int ld, 
   return raw[j * ld + r] + ((a ? a1 : a0) - mean);
 }
 
-// z = np.linspace(v_min, v_max, n) narrowed to float32 (dist_mlp.hip's atom_value)
-__device__ __forceinline__ float atom_value(double v_min, double v_max, int n, int i) {
-  if (i == n - 1) return (float)v_max;
-  const double step = (v_max - v_min) / (double)(n - 1);
-  return (float)((double)i * step + v_min);
-}
-
 // ---------------------------------------------------------------------------------------------------- acting
-constexpr int kMaxK = 8;         // transitions of one launch
-constexpr int kNP = 8;           // row stride of the single environment's transposed activations (hidden_layer's row block)
-
 __host__ __device__ constexpr size_t act_lds_floats(int H, int N) {
   return body_weight_floats(H) + (size_t)round_up4((1 + kA) * N * (H + 1)) + 2 * (size_t)round_up4((1 + kA) * N)    // body, heads, bias, raw
-         + round_up4(N) + noise_f_floats(H, N) + 4 + (size_t)kS * kNP + 2 * (size_t)H * kNP;                         // z, f, q, x^T, h^T
+         + round_up4(N) + noise_f_floats(H, N) + (size_t)act_scratch_floats(H);                                      // z, f
 }
 
 template <int H, int GATE>
@@ -146,46 +138,27 @@ rainbow_mlp_act_kernel(dra_rainbow_mlp_net net, dra_dqn_mlp_act_io io) {
   float* sZ = sRaw + round_up4(R);                    // [N]
   float* sF = sZ + round_up4(N);
   const NoiseF<H> f(sF, N);
-  float* sQ = sF + noise_f_floats(H, N);              // [A] (+ pad)
-  float* sXT = sQ + 4;                                // [S][NP]
-  float* sH1T = sXT + kS * kNP;                       // [H][NP]
-  float* sH2T = sH1T + H * kNP;                       // [H][NP]
-  const int act_floats = 4 + kS * kNP + 2 * H * kNP;
-  for (int i = tid; i < act_floats; i += 256) sQ[i] = 0.f;      // (rows 1..7 of x^T stay zero: one environment)
-  const int64_t t0 = *io.step_counter;                // (rewritten by thread 0 behind the last barrier)
-  const int64_t cap = io.capacity;
-  int64_t slot0 = *io.slot0;
-  const bool bad_slot = slot0 < 0 || slot0 >= cap;
-  if (bad_slot) slot0 = 0;
+  const ActScratch<H> s(sF + noise_f_floats(H, N));
+  ReplayActor actor;
+  actor.begin(io, tid);                               // (ahead of the zeroing, for the register allocator: mlp_rollout.h's banner)
+  s.zero(tid);
   const float* __restrict__ P = net.param;
   for (int i = tid; i < N; i += 256) sZ[i] = atom_value(net.v_min, net.v_max, N, i);
-
-  CartPoleLanes lanes;                               // lane 0 of wave 0 carries the environment
-  lanes.load(io, tid);
-  EpisodeRow ep;
-  ep.ep_ring = io.ep_ring;
-  ep.horizon = io.horizon;
-  ep.ring_cap = io.ring_cap;
-  const CartPoleRow row(ep);
+  const CartPoleRow row = episode_row(io);
   const double reward = 1.0 * io.reward_coef;         // what config.reward_normalizer(1.0) feeds
 
   for (int k = 0; k < K; ++k) {
     __syncthreads();                                  // (the zeroing above; the last transition's readers of f, x^T and q)
     // ---- the transition's reset_noise(): row k of the block, then the effective weights under it
     f.load(net.noise + (int64_t)k * net.noise_stride, net, N, tid);
-    if (tid == 0) {
-      sXT[0 * kNP] = (float)lanes.st.x;
-      sXT[1 * kNP] = (float)lanes.st.xd;
-      sXT[2 * kNP] = (float)lanes.st.th;
-      sXT[3 * kNP] = (float)lanes.st.thd;
-    }
+    actor.observe(s.xT, kNP, tid);
     __syncthreads();
     stage_body<H>(P, net, f, body.w1, body.w2, nullptr, body.b1, body.b2, tid);
     stage_heads<H>(P, net, f, wh, bh, H + 1, N, tid);
     __syncthreads();
-    hidden_layer<H, GATE, 256>(sXT, body.w1, body.b1, sH1T, kS, kNP, tid);
+    hidden_layer<H, GATE, 256>(s.xT, body.w1, body.b1, s.h1T, kS, kNP, tid);
     __syncthreads();
-    hidden_layer<H, GATE, 256>(sH1T, body.w2, body.b2, sH2T, H, kNP, tid);
+    hidden_layer<H, GATE, 256>(s.h1T, body.w2, body.b2, s.h2T, H, kNP, tid);
     __syncthreads();
     // ---- the heads: wave 0 the value head, wave 1 + a the advantage head of action a; lane j = atom j
     if (tid < (1 + kA) * kWave) {
@@ -195,7 +168,7 @@ rainbow_mlp_act_kernel(dra_rainbow_mlp_net net, dra_dqn_mlp_act_io io) {
         const float* wr = wh + c * (H + 1);
         float acc = 0.f;
 #pragma unroll 8
-        for (int i = 0; i < H; ++i) acc = fmaf(sH2T[i * kNP], wr[i], acc);
+        for (int i = 0; i < H; ++i) acc = fmaf(s.h2T[i * kNP], wr[i], acc);
         sRaw[c] = acc + bh[c];
       }
     }
@@ -204,45 +177,18 @@ rainbow_mlp_act_kernel(dra_rainbow_mlp_net net, dra_dqn_mlp_act_io io) {
     if (tid < kA * kWave) {
       const int a = tid / kWave, j = tid % kWave;
       const bool live = j < N;
-      const float l = live ? dueling_logit(sRaw, N, 1, a, j, 0) : -INFINITY;
-      const float m = wave_max(l);
-      const float e = live ? expf(l - m) : 0.f;
-      const float s = wave_sum(e);
-      const float q = wave_sum(live ? (e / s) * sZ[j] : 0.f);
+      float p;
+      const float q = wave_softmax_value(live ? dueling_logit(sRaw, N, 1, a, j, 0) : -INFINITY, live, sZ + j, p);
       if (j == 0) {
-        sQ[a] = q;
+        s.q[a] = q;
         io.out_q[k * kA + a] = q;
       }
     }
     __syncthreads();
-    // ---- the action (torch_utils.py:51-58 with the draws made ahead), the ring row, environment step: wave 0
-    if (tid < 64) {
-      bool done = false;
-      double ended = 0.0;
-      if (tid == 0) {
-        int arg = sQ[1] > sQ[0] ? 1 : 0;                          // np.argmax: the first maximum
-        if (io.explore[k]) arg = io.random_action[k] == 1 ? 1 : 0;
-        const int64_t slot = (slot0 + k) % cap;
-        double* frame = io.ring_frames + slot * kS;               // the observation the action was chosen on
-        frame[0] = lanes.st.x;
-        frame[1] = lanes.st.xd;
-        frame[2] = lanes.st.th;
-        frame[3] = lanes.st.thd;
-        done = cartpole_step(lanes.st, lanes.counter, lanes.ep_steps, lanes.ep_return, lanes.seed, arg, io.horizon, ended);
-        io.ring_actions[slot] = arg;
-        io.ring_rewards[slot] = reward;
-        io.ring_masks[slot] = done ? 0 : 1;
-        io.out_action[k] = arg;
-      }
-      lanes.append(row, done, ended, t0 + k, 0, tid);
-    }
+    actor.step(io, row, s.q, reward, k, tid);
   }
   __syncthreads();
-  lanes.store(io, tid);
-  if (tid == 0) {
-    *io.step_counter = t0 + K;
-    if (bad_slot) *io.err = *io.err + 1;
-  }
+  actor.finish(io, K, tid);
 }
 
 // ---------------------------------------------------------------------------------------------------- the update
@@ -342,12 +288,8 @@ rainbow_mlp_update_kernel(dra_rainbow_mlp_net net, dra_rainbow_mlp_update_io io)
     for (int p = wave; p < kA * rows; p += 4) {
       const int a = p / rows, r = p - a * rows;
       const bool live = lane < N;
-      const float l = live ? dueling_logit(sL, N, kLL, a, lane, r) : -INFINITY;
-      const float m = wave_max(l);
-      const float e = live ? expf(l - m) : 0.f;
-      const float s = wave_sum(e);
-      const float pj = e / s;
-      const float q = wave_sum(live ? pj * sZ[lane] : 0.f);
+      float pj;
+      const float q = wave_softmax_value(live ? dueling_logit(sL, N, kLL, a, lane, r) : -INFINITY, live, sZ + lane, pj);
       if (live) sPN[(a * N + lane) * kLP + r0 + r] = pj;
       if (lane == 0) {
         sQN[a * kMaxB + r0 + r] = q;
@@ -424,11 +366,8 @@ rainbow_mlp_update_kernel(dra_rainbow_mlp_net net, dra_rainbow_mlp_update_io io)
       for (int p = wave; p < kA * rows; p += 4) {
         const int a = p / rows, r = p - a * rows;
         const bool live = lane < N;
-        const float l = live ? dueling_logit(sL, N, kLL, a, lane, r) : -INFINITY;
-        const float m = wave_max(l);
-        const float e = live ? expf(l - m) : 0.f;
-        const float s = wave_sum(e);
-        const float q = wave_sum(live ? (e / s) * sZ[lane] : 0.f);
+        float pj;
+        const float q = wave_softmax_value(live ? dueling_logit(sL, N, kLL, a, lane, r) : -INFINITY, live, sZ + lane, pj);
         if (lane == 0) sQO[a * kUB + r] = q;
       }
       __syncthreads();
@@ -441,14 +380,7 @@ rainbow_mlp_update_kernel(dra_rainbow_mlp_net net, dra_rainbow_mlp_update_io io)
       if (r < rows) {
         const int an = double_q ? (sQO[kUB + r] > sQO[r] ? 1 : 0) : (sQN[kMaxB + r0 + r] > sQN[r0 + r] ? 1 : 0);
         const float gm = __fmul_rn(gamma, sMsk[r]);
-        const float* p = sPN + an * N * kLP + r0 + r;
-        const float zi = sZ[i];
-        for (int j = 0; j < N; ++j) {
-          float tz = __fadd_rn(sRew[r], __fmul_rn(gm, sZ[j]));
-          tz = fminf(fmaxf(tz, v_min), v_max);
-          const float w = fminf(fmaxf(1.f - fabsf(tz - zi) / delta, 0.f), 1.f);
-          t = fmaf(w, p[j * kLP], t);
-        }
+        t = c51_project(sZ, sPN + an * N * kLP + r0 + r, kLP, N, sZ[i], sRew[r], gm, v_min, v_max, delta);
         io.out_target[(int64_t)(r0 + r) * N + i] = t;
       }
       sT[i * kLL + r] = t;
@@ -618,7 +550,6 @@ int atoms_supported(int n_atoms) { return n_atoms < 2 || n_atoms > kMaxAtoms ? D
 
 }  // namespace
 
-static_assert(kMaxAtoms <= kWave, "every atom of an action has one lane of a wave");
 static_assert(act_lds_floats(64, kMaxAtoms) * sizeof(float) <= kLdsBytes, "the acting launch's LDS at the largest shape");
 static_assert(update_lds_floats(64, kMaxAtoms) * sizeof(float) <= kLdsBytes, "the update's LDS at the largest shape");
 static_assert(kUB % 4 == 0 && kUB * kS <= 256 && kMaxB % kUB == 0 && kMaxB <= 256 && (1 + kA) * kMaxAtoms <= 256, "the row block");
@@ -638,13 +569,8 @@ DRA_API int dra_rainbow_mlp_update_supported(int state_dim, int n_actions, int h
 
 DRA_API int dra_rainbow_mlp_act(const dra_rainbow_mlp_net* net, const dra_dqn_mlp_act_io* io, void* stream) {
   if (!net || !io || !net->param || !net->noise) return DRA_EINVAL;
-  if (io->n_env != 1 || dra_rainbow_mlp_supported(net->state_dim, net->n_actions, net->hidden, io->t_len, net->gate, net->n_atoms))
-    return DRA_EINVAL;
-  if (!net_ok(net) || io->horizon < 1 || io->ring_cap < 1 || io->capacity < 1) return DRA_EINVAL;
-  if (!io->env_state || !io->env_counter || !io->ep_steps || !io->ep_return || !io->env_seed || !io->step_counter || !io->ep_count ||
-      !io->ep_ring || !io->explore || !io->random_action || !io->slot0 || !io->ring_frames || !io->ring_actions ||
-      !io->ring_rewards || !io->ring_masks || !io->out_q || !io->out_action || !io->err)
-    return DRA_EINVAL;
+  if (dra_rainbow_mlp_supported(net->state_dim, net->n_actions, net->hidden, io->t_len, net->gate, net->n_atoms)) return DRA_EINVAL;
+  if (!net_ok(net) || !replay_act_io_ok(io)) return DRA_EINVAL;
   return dispatch_hidden_gate(net->hidden, net->gate, [&](auto h, auto g) {
     constexpr int H = decltype(h)::value, GATE = decltype(g)::value;
     return launch_one_workgroup<&rainbow_mlp_act_kernel<H, GATE>>(act_lds_floats(H, net->n_atoms) * sizeof(float), net, io, stream);

@@ -11,7 +11,7 @@ import numpy as np
 import pytest
 import torch
 from feature_kernel_harness import (      # noqa: F401  (dra: the fixture)
-    GAME, GATE, GUARD, dra, _Rec, _fraction, _within, _bits, _guarded, _flat, _tails_intact, _body, _line_events)
+    GAME, GATE, GUARD, dra, _Rec, _fraction, _within, _bits, _guarded, _flat, _line_events, _launch_replay_act, _check_act_case)
 from parity_log import record_parity
 
 import dqn_feature_cases as K
@@ -39,45 +39,10 @@ def _net_struct(params, target, dev, hidden, gate, padded):
 # ------------------------------------------------------------------------------------------ the acting kernel
 def _launch_act(dra, case, start):
     """One dra_dqn_mlp_act from the case's start -> dict of host arrays (guards included) and the return code."""
-    from deeprl_amd import dqn_mlp
-    from deeprl_amd._lib import lib, stream_ptr
-    dev = dra.Config.DEVICE
+    from deeprl_amd._lib import lib
     hidden, gate, k_len, cap, slot0, horizon, padded = case[:7]
-    net, flat, tflat, _ = _net_struct(start["params"], None, dev, hidden, gate, padded)
-    nan = float("nan")
-    spec = dict(env_state=((1, 4), torch.float64, nan), env_counter=((1,), torch.int64, -7), ep_steps=((1,), torch.int32, -7),
-                ep_return=((1,), torch.float64, nan), env_seed=((1,), torch.int64, -7), step=((1,), torch.int64, -7),
-                ep_count=((1,), torch.int64, -7), ep_ring=((K.EP_RING_CAP, 3), torch.float64, nan),
-                explore=((k_len,), torch.uint8, 9), random_action=((k_len,), torch.int64, -7), slot0=((1,), torch.int64, -7),
-                frames=((cap, 4), torch.float64, nan), actions=((cap,), torch.int64, -1), rewards=((cap,), torch.float64, nan),
-                masks=((cap,), torch.int32, -1), q=((k_len, 2), torch.float32, nan), action=((k_len,), torch.int64, -7),
-                err=((1,), torch.int32, -7))
-    full, view = {}, {}
-    for k, (shape, dt, fill) in spec.items():
-        full[k], view[k] = _guarded(shape, dt, dev, fill)
-    view["env_state"].copy_(torch.from_numpy(start["raw"]).view(1, 4))
-    view["env_counter"].zero_(); view["ep_steps"].zero_(); view["ep_return"].zero_(); view["err"].zero_()
-    view["env_seed"].fill_(start["seed"])
-    view["step"].fill_(K.STEP0); view["ep_count"].fill_(K.EP_RING_COUNT0); view["slot0"].fill_(slot0)
-    view["explore"].copy_(torch.from_numpy(start["explore"].astype(np.uint8)))
-    view["random_action"].copy_(torch.from_numpy(start["random_action"]))
-    io = dqn_mlp.ActIO()
-    io.env_state, io.env_counter, io.ep_steps = view["env_state"].data_ptr(), view["env_counter"].data_ptr(), view["ep_steps"].data_ptr()
-    io.ep_return, io.env_seed, io.step_counter = view["ep_return"].data_ptr(), view["env_seed"].data_ptr(), view["step"].data_ptr()
-    io.ep_count, io.ep_ring = view["ep_count"].data_ptr(), view["ep_ring"].data_ptr()
-    io.explore, io.random_action, io.slot0 = view["explore"].data_ptr(), view["random_action"].data_ptr(), view["slot0"].data_ptr()
-    io.ring_frames, io.ring_actions = view["frames"].data_ptr(), view["actions"].data_ptr()
-    io.ring_rewards, io.ring_masks = view["rewards"].data_ptr(), view["masks"].data_ptr()
-    io.out_q, io.out_action, io.err = view["q"].data_ptr(), view["action"].data_ptr(), view["err"].data_ptr()
-    io.horizon, io.ring_cap, io.capacity, io.reward_coef, io.t_len, io.n_env = horizon, K.EP_RING_CAP, cap, 1.0, k_len, 1
-    before = flat.cpu().numpy().copy(), tflat.cpu().numpy().copy()
-    rc = lib.dra_dqn_mlp_act.raw(ctypes.byref(net), ctypes.byref(io), stream_ptr())
-    torch.cuda.synchronize()
-    out = {k: v.cpu().numpy() for k, v in full.items()}
-    out["rc"], out["spec"] = rc, spec
-    # (both parameter buffers are read only)
-    assert np.array_equal(_bits(flat.cpu().numpy()), _bits(before[0])) and np.array_equal(_bits(tflat.cpu().numpy()), _bits(before[1]))
-    return out
+    net, flat, tflat, _ = _net_struct(start["params"], None, dra.Config.DEVICE, hidden, gate, padded)
+    return _launch_replay_act(dra, lib.dra_dqn_mlp_act, net, (flat, tflat), K, start, k_len, cap, slot0, horizon)
 
 
 @pytest.mark.parametrize("case", K.ACT_CASES, ids=K.act_id)
@@ -89,28 +54,8 @@ def test_act_kernel_matches_restatement(dra, case):
     bits everywhere."""
     hidden, gate, k_len, cap, slot0, horizon, padded = case[:7]
     want, env, start = K.restated_act(case)
-    out = _launch_act(dra, case, start)
-    assert out["rc"] == 0 and int(_body(out, "err")[0]) == 0
-    assert np.array_equal(_body(out, "action"), want["action"])
-    ring = want["ring"]
-    assert np.array_equal(_bits(_body(out, "frames")), _bits(ring["frames"]))
-    assert np.array_equal(_body(out, "actions"), ring["actions"]) and np.array_equal(_body(out, "masks"), ring["masks"])
-    assert np.array_equal(_bits(_body(out, "rewards")), _bits(ring["rewards"]))
-    assert np.array_equal(_bits(_body(out, "env_state")), _bits(want["raw"].reshape(1, 4)))
-    assert int(_body(out, "env_counter")[0]) == env.c and int(_body(out, "ep_steps")[0]) == env.steps
-    assert np.array_equal(_bits(_body(out, "ep_return")), _bits(np.asarray([env.ret], dtype=np.float64)))
-    assert int(_body(out, "step")[0]) == K.STEP0 + k_len and int(_body(out, "slot0")[0]) == slot0
-    assert int(_body(out, "ep_count")[0]) == K.EP_RING_COUNT0 + len(want["events"])
-    ep = np.full((K.EP_RING_CAP, 3), np.nan)
-    for i, ev in enumerate(want["events"]):
-        ep[(K.EP_RING_COUNT0 + i) % K.EP_RING_CAP] = ev
-    assert np.array_equal(_bits(_body(out, "ep_ring")), _bits(ep))
-    eq = _within(_body(out, "q"), want["q"], "q")
-    record_parity("dqn_mlp acting kernel vs restatement %s (fraction of the bar)" % K.act_id(case), q=eq)
-    _tails_intact(out)
-    again = _launch_act(dra, case, start)
-    for k in out["spec"]:
-        assert np.array_equal(_bits(out[k]), _bits(again[k])), k
+    _check_act_case(lambda: _launch_act(dra, case, start), want, env, K, k_len, slot0,
+                    "dqn_mlp acting kernel vs restatement %s (fraction of the bar)" % K.act_id(case))
 
 
 # ------------------------------------------------------------------------------------------ the update kernel

@@ -12,7 +12,8 @@ import numpy as np
 import pytest
 import torch
 from feature_kernel_harness import (      # noqa: F401  (dra: the fixture)
-    GATE, GUARD, dra, _fraction, _bits, _guarded, _flat, _tails_intact, _body)
+    GATE, GUARD, dra, _fraction, _bits, _guarded, _flat, _body, _launch_replay_act, _check_act, _check_act_case,
+    _check_bad_slots)
 from parity_log import record_parity
 
 import rainbow_feature_cases as K
@@ -60,74 +61,18 @@ def _net_struct(params, target, noise_rows, target_noise, dev, spec, hidden, gat
 
 # ------------------------------------------------------------------------------------------ the acting kernel
 def _launch_act(dra, start, hidden, gate, k_len, cap, slot0, horizon, padded):
-    """One dra_rainbow_mlp_act from a case's start -> dict of host arrays (guards included) and the return code."""
-    from deeprl_amd import rainbow_mlp
-    from deeprl_amd._lib import lib, stream_ptr
-    dev = dra.Config.DEVICE
+    """One dra_rainbow_mlp_act from a case's start -> dict of host arrays (guards included) and the return code; the parameter and
+    the noise buffers are read only."""
+    from deeprl_amd._lib import lib
     kk = max(k_len, 1)
     rows = (list(start["noise_rows"]) + [start["noise_rows"][-1]] * kk)[:kk]
-    net, keep, _ = _net_struct(start["params"], None, rows, None, dev, start["spec"], hidden, gate, padded)
-    nan = float("nan")
-    spec = dict(env_state=((1, 4), torch.float64, nan), env_counter=((1,), torch.int64, -7), ep_steps=((1,), torch.int32, -7),
-                ep_return=((1,), torch.float64, nan), env_seed=((1,), torch.int64, -7), step=((1,), torch.int64, -7),
-                ep_count=((1,), torch.int64, -7), ep_ring=((K.EP_RING_CAP, 3), torch.float64, nan),
-                explore=((kk,), torch.uint8, 9), random_action=((kk,), torch.int64, -7), slot0=((1,), torch.int64, -7),
-                frames=((cap, 4), torch.float64, nan), actions=((cap,), torch.int64, -1), rewards=((cap,), torch.float64, nan),
-                masks=((cap,), torch.int32, -1), q=((kk, 2), torch.float32, nan), action=((kk,), torch.int64, -7),
-                err=((1,), torch.int32, -7))
-    full, view = {}, {}
-    for k, (shape, dt, fill) in spec.items():
-        full[k], view[k] = _guarded(shape, dt, dev, fill)
-    view["env_state"].copy_(torch.from_numpy(start["raw"]).view(1, 4))
-    view["env_counter"].zero_(); view["ep_steps"].zero_(); view["ep_return"].zero_(); view["err"].zero_()
-    view["env_seed"].fill_(start["seed"])
-    view["step"].fill_(K.STEP0); view["ep_count"].fill_(K.EP_RING_COUNT0); view["slot0"].fill_(slot0)
-    n_draws = min(kk, len(start["explore"]))
-    view["explore"].zero_(); view["random_action"].zero_()
-    view["explore"][:n_draws].copy_(torch.from_numpy(start["explore"][:n_draws].astype(np.uint8)))
-    view["random_action"][:n_draws].copy_(torch.from_numpy(start["random_action"][:n_draws]))
-    io = rainbow_mlp.ActIO()
-    io.env_state, io.env_counter, io.ep_steps = view["env_state"].data_ptr(), view["env_counter"].data_ptr(), view["ep_steps"].data_ptr()
-    io.ep_return, io.env_seed, io.step_counter = view["ep_return"].data_ptr(), view["env_seed"].data_ptr(), view["step"].data_ptr()
-    io.ep_count, io.ep_ring = view["ep_count"].data_ptr(), view["ep_ring"].data_ptr()
-    io.explore, io.random_action, io.slot0 = view["explore"].data_ptr(), view["random_action"].data_ptr(), view["slot0"].data_ptr()
-    io.ring_frames, io.ring_actions = view["frames"].data_ptr(), view["actions"].data_ptr()
-    io.ring_rewards, io.ring_masks = view["rewards"].data_ptr(), view["masks"].data_ptr()
-    io.out_q, io.out_action, io.err = view["q"].data_ptr(), view["action"].data_ptr(), view["err"].data_ptr()
-    io.horizon, io.ring_cap, io.capacity, io.reward_coef, io.t_len, io.n_env = horizon, K.EP_RING_CAP, cap, 1.0, k_len, 1
-    before = [t.cpu().numpy().copy() for t in keep]
-    rc = lib.dra_rainbow_mlp_act.raw(ctypes.byref(net), ctypes.byref(io), stream_ptr())
-    torch.cuda.synchronize()
-    out = {k: v.cpu().numpy() for k, v in full.items()}
-    out["rc"], out["spec"] = rc, spec
-    # (the parameter and noise buffers are read only)
-    assert all(np.array_equal(_bits(t.cpu().numpy()), _bits(b)) for t, b in zip(keep, before))
-    return out
+    net, keep, _ = _net_struct(start["params"], None, rows, None, dra.Config.DEVICE, start["spec"], hidden, gate, padded)
+    return _launch_replay_act(dra, lib.dra_rainbow_mlp_act, net, keep, K, start, k_len, cap, slot0, horizon)
 
 
 def _launch_act_case(dra, case, start, slot0=None):
     hidden, gate, n, k_len, cap, s0, horizon, padded, _ = case
     return _launch_act(dra, start, hidden, gate, k_len, cap, s0 if slot0 is None else slot0, horizon, padded)
-
-
-def _check_act(out, want, env, k_len, slot0):
-    assert out["rc"] == 0 and int(_body(out, "err")[0]) == 0
-    assert np.array_equal(_body(out, "action"), want["action"])
-    ring = want["ring"]
-    assert np.array_equal(_bits(_body(out, "frames")), _bits(ring["frames"]))
-    assert np.array_equal(_body(out, "actions"), ring["actions"]) and np.array_equal(_body(out, "masks"), ring["masks"])
-    assert np.array_equal(_bits(_body(out, "rewards")), _bits(ring["rewards"]))
-    assert np.array_equal(_bits(_body(out, "env_state")), _bits(want["raw"].reshape(1, 4)))
-    assert int(_body(out, "env_counter")[0]) == env.c and int(_body(out, "ep_steps")[0]) == env.steps
-    assert np.array_equal(_bits(_body(out, "ep_return")), _bits(np.asarray([env.ret], dtype=np.float64)))
-    assert int(_body(out, "step")[0]) == K.STEP0 + k_len and int(_body(out, "slot0")[0]) == slot0
-    assert int(_body(out, "ep_count")[0]) == K.EP_RING_COUNT0 + len(want["events"])
-    ep = np.full((K.EP_RING_CAP, 3), np.nan)
-    for i, ev in enumerate(want["events"]):
-        ep[(K.EP_RING_COUNT0 + i) % K.EP_RING_CAP] = ev
-    assert np.array_equal(_bits(_body(out, "ep_ring")), _bits(ep))
-    _tails_intact(out)
-    return _fraction(_body(out, "q"), want["q"], "q")
 
 
 @pytest.mark.parametrize("case", K.ACT_CASES, ids=K.act_id)
@@ -139,13 +84,8 @@ def test_act_kernel_matches_restatement(dra, case):
     case has NaN between the noise vectors and between the rows); a second launch from the same start gives the same bits."""
     hidden, gate, n, k_len, cap, slot0, horizon, padded, _ = case
     want, env, start = K.restated_act(case)
-    out = _launch_act_case(dra, case, start)
-    eq = _check_act(out, want, env, k_len, slot0)
-    record_parity("rainbow_mlp acting kernel vs restatement %s (fraction of the bar)" % K.act_id(case), q=eq)
-    assert eq <= 1.0
-    again = _launch_act_case(dra, case, start)
-    for k in out["spec"]:
-        assert np.array_equal(_bits(out[k]), _bits(again[k])), k
+    _check_act_case(lambda: _launch_act_case(dra, case, start), want, env, K, k_len, slot0,
+                    "rainbow_mlp acting kernel vs restatement %s (fraction of the bar)" % K.act_id(case))
 
 
 def test_act_reads_noise_row_k_at_transition_k(dra):
@@ -155,7 +95,7 @@ def test_act_reads_noise_row_k_at_transition_k(dra):
     want, env, start = K.flip_case()
     f = K.FLIP
     out = _launch_act(dra, start, f["hidden"], f["gate"], f["k"], 64, 0, 200, False)
-    assert _check_act(out, want, env, f["k"], 0) <= 1.0
+    assert _check_act(out, want, env, K, f["k"], 0) <= 1.0
     assert list(_body(out, "action")) == [k % 2 for k in range(f["k"])]
     for fixed in (0, f["k"] - 1):
         rows = [start["noise_rows"][fixed]] * f["k"]
@@ -166,7 +106,7 @@ def test_act_reads_noise_row_k_at_transition_k(dra):
         alone["ring"] = ring
         assert alone["margin"] >= K.MARGIN and not np.array_equal(alone["action"], want["action"])
         got = _launch_act(dra, dict(start, noise_rows=rows), f["hidden"], f["gate"], f["k"], 64, 0, 200, False)
-        assert _check_act(got, alone, e, f["k"], 0) <= 1.0
+        assert _check_act(got, alone, e, K, f["k"], 0) <= 1.0
 
 
 def test_act_takes_the_staged_random_action_where_told(dra):
@@ -184,7 +124,7 @@ def test_act_takes_the_staged_random_action_where_told(dra):
     want["ring"] = ring
     assert want["margin"] >= 100 * K.MARGIN
     out = _launch_act_case(dra, case, dict(start, explore=explore, random_action=rand))
-    assert _check_act(out, want, env, k_len, slot0) <= 1.0
+    assert _check_act(out, want, env, K, k_len, slot0) <= 1.0
     assert list(_body(out, "action")[1:3]) == [1, 0]
 
 
@@ -193,13 +133,7 @@ def test_act_counts_a_first_slot_outside_the_ring(dra):
     slot 0 bit for bit, and nothing outside the ring is written."""
     case = next(c for c in K.ACT_CASES if c[3] == 4 and c[2] == 50 and c[0] == 16)
     _, _, start = K.restated_act(case)
-    want = _launch_act_case(dra, case, start, slot0=0)
-    for bad in (-1, case[4], case[4] + 1000):
-        got = _launch_act_case(dra, case, start, slot0=bad)
-        assert got["rc"] == 0 and int(_body(got, "err")[0]) == 1 and int(_body(want, "err")[0]) == 0
-        for k in ("frames", "actions", "rewards", "masks", "q", "action", "env_state", "ep_ring", "step", "ep_count"):
-            assert np.array_equal(_bits(got[k]), _bits(want[k])), k
-        _tails_intact(got)
+    _check_bad_slots(lambda slot0: _launch_act_case(dra, case, start, slot0=slot0), case[4])
 
 
 # ------------------------------------------------------------------------------------------ the update kernel
