@@ -1839,11 +1839,13 @@ def _f32(x):
     return x.float() if isinstance(x, torch.Tensor) else tensor(x)
 
 
-class _DeterministicPolicyAgent(BaseAgent):
+class _DeterministicPolicyAgent(_DeviceEpisodes, BaseAgent):
     """What DDPG_agent.py:13-100 and TD3_agent.py:13-108 share: one environment, a deterministic policy perturbed by a
     random process (uniform actions during warm-up), every transition fed to the uniform replay -- here the HBM ring:
     17-float states and 6-float actions are just small "frames" -- one sampled minibatch per step once warm, and a
-    polyak-averaged target network.  Sub-classes provide `warm()` and `learn(batch)`."""
+    polyak-averaged target network.  Sub-classes provide `warm()` and `learn(batch)`.
+    With config.fused_dpg_env = True (and fused_dpg_update) an envs.Pendulum / envs.SyntheticContinuous task moves to the device
+    and a step is dpg_env.EnvStep's: one acting launch that writes the transition into the ring, the gather, the fused update."""
 
     def __init__(self, config):
         BaseAgent.__init__(self, config)
@@ -1858,8 +1860,24 @@ class _DeterministicPolicyAgent(BaseAgent):
         self.state = None
 
     def close(self):
+        self.drain_episodes()
         close_obj(self.replay)
         close_obj(self.task)
+
+    def _episode_ring(self):
+        return getattr(self, '_dpg_env', None) or None
+
+    def _fused_env(self):
+        """dpg_env.EnvStep when `config.fused_dpg_env` is on and agent, task and replay allow it (decided once, ahead of the
+        first step; a refusal is logged in ONE warning), else None: the host step below, unchanged."""
+        env = getattr(self, '_dpg_env', False)
+        if env is False:
+            env = None
+            if getattr(self.config, 'fused_dpg_env', False) is True:
+                from . import dpg_env
+                env = dpg_env.adopt(self)
+            self._dpg_env = env
+        return env
 
     def _flat_pair(self, target, src):
         """Both networks' parameters re-homed (once) into one flat fp32 buffer each, same tensor order and offsets; the
@@ -1923,6 +1941,10 @@ class _DeterministicPolicyAgent(BaseAgent):
 
     def step(self):
         config = self.config
+        env = self._fused_env()
+        if env is not None:
+            env.step()
+            return
         if self.state is None:
             self.random_process.reset_states()
             self.state = config.state_normalizer(self.task.reset())
@@ -1944,11 +1966,13 @@ class _DeterministicPolicyAgent(BaseAgent):
                 # loads: no cast launches), reward and mask as the gather's own fp32 outputs
                 ring = getattr(self.replay, 'replay', self.replay)
                 g = ring.gather(ring.draw_indices(), want_f32=True)
-                fused.learn(g['state'], g['action'], g['reward_f32'], g['next_state'], g['mask_f32'],
+                # (the view: a one-dimensional action space comes back [B] from the ring and the kernels take [B, A]; no-op for A > 1)
+                fused.learn(g['state'], g['action'].view(len(g['reward_f32']), -1), g['reward_f32'], g['next_state'], g['mask_f32'],
                             policy_step=self._policy_step())
                 return
             tr = self.replay.sample()
-            self.learn(_f32(tr.state), _f32(tr.action), _f32(tr.reward).unsqueeze(-1), _f32(tr.next_state),
+            # (the view serves one-dimensional action spaces only, as above: the critic concatenates [B, S] with [B, A])
+            self.learn(_f32(tr.state), _f32(tr.action).view(len(tr.reward), -1), _f32(tr.reward).unsqueeze(-1), _f32(tr.next_state),
                        _f32(tr.mask).unsqueeze(-1))
 
 

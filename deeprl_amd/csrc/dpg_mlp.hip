@@ -19,6 +19,7 @@
 // needs to be a multiple of 16 or 4: every operand outside a tensor is replaced by zero where it is loaded.
 #include "common.h"
 #include "cont_env.h"
+#include "pendulum_env.h"
 #include "mlp_rollout.h"
 #include <math.h>
 
@@ -484,6 +485,122 @@ dpg_act_kernel(dra_dpg_net net, const void* __restrict__ state, int64_t state_st
   actor_forward<GATE>(net, d, sX, sA, sB, ldh, nullptr, nullptr, out, row0);
 }
 
+// ------------------------------------------------------------------------------------------------ acting on a device environment
+// One agent transition (dra_dpg_env_act_io in the header): dpg_act_kernel's forward on ONE row -- the same LDS layout, the same
+// actor_forward, hence the same bits -- then the behaviour action, the ring row and the environment step in wave 0.  The fp64
+// scratch (observation [kMaxS], action [kMaxA]) lies BEHIND the forward's tiles in the dynamic region: a static array in front of
+// it would move the tiles off their 16-byte alignment and fwd_layer onto its other path.
+constexpr int kEnvPendulum = 0, kEnvSynthetic = 1;
+constexpr int kModeWarmup = 0, kModeGauss = 1, kModeOU = 2;
+__host__ __device__ constexpr size_t env_act_lds_floats(int h1, int h2) { return pass_lds_floats(h1, h2, 2) + 2 * (kMaxS + kMaxA); }
+
+template <int GATE>
+__global__ void __launch_bounds__(kThreads)
+dpg_env_act_kernel(dra_dpg_net net, dra_dpg_env_act_io io) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  const Dims d = {net.state_dim, net.action_dim, net.h1, net.h2, 1};
+  const int tid = threadIdx.x, ldh = ld_hidden(d.H1, d.H2);
+  float* sX = lds;
+  float* sA = sX + kRows * kLdX;
+  float* sB = sA + kRows * ldh;
+  double* sObs = reinterpret_cast<double*>(lds + pass_lds_floats(d.H1, d.H2, 2));
+  double* sAct = sObs + kMaxS;
+  const bool pendulum = io.env_kind == kEnvPendulum;
+
+  // ---- the observation the action is chosen on
+  PendulumState pst = {0.0, 0.0};
+  if (pendulum) {
+    if (tid == 0) {
+      pst.th = io.env_state[0];
+      pst.thd = io.env_state[1];
+      pendulum_observe(pst, sObs);
+    }
+  } else if (tid < d.S) {
+    sObs[tid] = io.env_state[tid];
+  }
+  __syncthreads();
+  for (int i = tid; i < kRows * d.S; i += kThreads) {        // load_rows of dpg_act_kernel with n = 1: the rows behind it are zeros
+    const int r = i / d.S, c = i - r * d.S;
+    sX[r * kLdX + c] = r == 0 ? (float)sObs[c] : 0.f;
+  }
+  __syncthreads();
+  actor_forward<GATE>(net, d, sX, sA, sB, ldh, nullptr, nullptr, io.out_action, 0);
+
+  if (tid >= 64) return;       // (no workgroup barrier below: wave 0 alone)
+  // ---- the behaviour action (DDPG_agent.py:62-69), lane dd = dimension dd
+  const int64_t mode = *io.mode;
+  double x_next = 0.0;
+  if (tid < d.A) {
+    const double a = (double)sX[d.S + tid], v = io.v[tid];
+    double x = io.ou_x[tid], act;
+    if (mode == kModeWarmup) act = v;
+    else if (mode == kModeGauss) act = a + v;
+    else {
+      x = (x + ((io.ou_theta * (io.ou_mu - x)) * io.ou_dt)) + v;
+      act = a + x;
+    }
+    const double lo = io.bounds[0], hi = io.bounds[1];
+    act = act < lo ? lo : (act > hi ? hi : act);
+    sAct[tid] = act;
+    x_next = x;
+  }
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");      // the wave's lanes read each other's actions below
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+
+  // ---- the ring row and the environment step
+  int64_t slot = *io.slot;
+  const bool bad_slot = slot < 0 || slot >= io.capacity;
+  if (bad_slot) slot = 0;
+  if (tid < d.S) io.ring_frames[slot * d.S + tid] = sObs[tid];
+  if (tid < d.A) io.ring_actions[slot * d.A + tid] = sAct[tid];
+  const uint64_t seed = (uint64_t)*io.env_seed;
+  int64_t counter = *io.env_counter;
+  double ep_return = *io.ep_return, reward = 0.0, ended = 0.0;
+  int32_t ep_steps = *io.ep_steps;
+  bool done = false;
+  if (pendulum) {
+    if (tid == 0) {
+      done = pendulum_step(pst, counter, ep_steps, ep_return, seed, sAct[0], io.horizon, reward, ended);
+      io.env_state[0] = pst.th;
+      io.env_state[1] = pst.thd;
+    }
+    done = __shfl((int)done, 0, 64) != 0;
+  } else {
+    // envs.py SyntheticContinuous.step: every lane forms the mean action and the terminal, lane j the component j
+    double m = 0.0;
+    for (int dd = 0; dd < d.A; ++dd) m += (double)fminf(fmaxf((float)sAct[dd], -1.f), 1.f);
+    m = m / (double)d.A;
+    counter = counter + 1;
+    done = cenv_done(seed, counter, io.horizon);
+    if (tid < d.S) io.env_state[tid] = cenv_next_state(seed, counter, tid, sObs[tid], m, done);
+    reward = cenv_reward(seed, counter);
+    ep_return = ep_return + reward;
+    if (done) {
+      ended = ep_return;
+      ep_return = 0.0;
+    }
+  }
+  if (tid < d.A) io.ou_x[tid] = done ? io.ou_x0[tid] : x_next;
+  if (tid == 0) {
+    io.ring_rewards[slot] = reward;
+    io.ring_masks[slot] = done ? 0 : 1;
+    const int64_t t = *io.step_counter, n_ep = *io.ep_count;
+    if (done) {
+      double* row = io.ep_ring + (n_ep % io.ring_cap) * 3;
+      row[0] = (double)t;
+      row[1] = 0.0;
+      row[2] = ended;
+      *io.ep_count = n_ep + 1;
+    }
+    *io.step_counter = t + 1;
+    *io.env_counter = counter;
+    *io.ep_steps = ep_steps;
+    *io.ep_return = ep_return;
+    if (bad_slot) *io.err = *io.err + 1;
+  }
+}
+
 // ------------------------------------------------------------------------------------------------ weight gradient + Adam
 // One job = one Linear layer: dz [B][N], x [B][ld_x] (K columns used), W [N][K] at off_w, b [N] at off_b.  The bias is column K of
 // [W | b] (x's column K is 1): tiles_k = ceil((K + 1) / 16).
@@ -625,6 +742,16 @@ int launch_act(const dra_dpg_net* net, const void* state, int64_t stride, int in
   return DRA_OK;
 }
 
+template <int GATE>
+int launch_env_act(const dra_dpg_net* net, const dra_dpg_env_act_io* io, void* stream) {
+  const size_t bytes = env_act_lds_floats(net->h1, net->h2) * sizeof(float);
+  static DraLdsAttr lds_attr;
+  if (int rc = dra_grant_lds(lds_attr, reinterpret_cast<const void*>(&dpg_env_act_kernel<GATE>), bytes)) return rc;
+  hipLaunchKernelGGL((dpg_env_act_kernel<GATE>), dim3(1), dim3(kThreads), bytes, dra_stream(stream), *net, *io);
+  DRA_LAUNCH_CHECK();
+  return DRA_OK;
+}
+
 }  // namespace
 
 DRA_API int dra_dpg_supported(int batch, int state_dim, int action_dim, int h1, int h2, int gate, int n_critics) {
@@ -690,4 +817,21 @@ DRA_API int dra_dpg_act(const dra_dpg_net* net, const void* state, int64_t state
   if (state_stride < net->state_dim) return DRA_EINVAL;
   return net->gate == kGateRelu ? launch_act<kGateRelu>(net, state, state_stride, in_f64, n, out_action, stream)
                                 : launch_act<kGateTanh>(net, state, state_stride, in_f64, n, out_action, stream);
+}
+
+DRA_API int dra_dpg_env_act_supported(int env_kind, int state_dim, int action_dim, int h1, int h2, int gate) {
+  if (dra_dpg_supported(1, state_dim, action_dim, h1, h2, gate, 1)) return DRA_EINVAL;
+  if (env_kind == kEnvPendulum) return state_dim == kPendulumS && action_dim == kPendulumA ? DRA_OK : DRA_EINVAL;
+  return env_kind == kEnvSynthetic ? DRA_OK : DRA_EINVAL;
+}
+
+DRA_API int dra_dpg_env_act(const dra_dpg_net* net, const dra_dpg_env_act_io* io, void* stream) {
+  if (check_net(net) || !io) return DRA_EINVAL;
+  if (dra_dpg_env_act_supported(io->env_kind, net->state_dim, net->action_dim, net->h1, net->h2, net->gate)) return DRA_EINVAL;
+  if (io->horizon < 1 || io->ring_cap < 1 || io->capacity < 1) return DRA_EINVAL;
+  if (!io->env_state || !io->env_counter || !io->ep_steps || !io->ep_return || !io->env_seed || !io->step_counter || !io->ep_count ||
+      !io->ep_ring || !io->mode || !io->slot || !io->bounds || !io->v || !io->ou_x || !io->ou_x0 || !io->ring_frames ||
+      !io->ring_actions || !io->ring_rewards || !io->ring_masks || !io->out_action || !io->err)
+    return DRA_EINVAL;
+  return net->gate == kGateRelu ? launch_env_act<kGateRelu>(net, io, stream) : launch_env_act<kGateTanh>(net, io, stream);
 }

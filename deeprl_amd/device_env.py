@@ -397,6 +397,47 @@ class DeviceCartPoleVec(_RolloutVec):
         self.drained = int(d["drained"])
 
 
+class DevicePendulumVec(DeviceCartPoleVec):
+    """The ONE continuous-control environment of a DDPGAgent / TD3Agent's Task, resident on the device (ddpg_continuous /
+    td3_continuous, examples.py:554-617, under config.fused_dpg_env): an envs.Pendulum -- env_state [1][2] = (theta, theta'), the
+    observation [cos, sin, theta'] is formed by the kernel (csrc/pendulum_env.h) -- or an envs.SyntheticContinuous -- env_state
+    [1][state_dim], csrc/cont_env.h; ep_steps stays 0.  DeviceCartPoleVec's surface as it is: counter, seed, episode steps /
+    return, the episode ring and `drain()`; dra_dpg_env_act (dpg_env.EnvStep) walks one transition per launch and writes it
+    straight into the replay ring."""
+    DRIVER = "DDPGAgent / TD3Agent"
+    HOST_NOTE = 'fused_dpg_env is on but the environment stays on the host and this agent keeps its host step: %s'
+
+    def __init__(self, task):
+        _RolloutVec.__init__(self, task)
+        self._more_buffers = lambda t_len, n, f: {}
+        env = task.env.envs[0]
+        dev = Config.DEVICE
+        self.ring_cap = int(self.RING_CAP)
+        self.env_state = torch.from_numpy(np.asarray(env.s, dtype=np.float64).reshape(1, -1).copy()).to(dev)
+        self.env_counter = torch.tensor([env.c], dtype=torch.int64, device=dev)
+        # (a SyntheticContinuous ends its episodes by a hash of the counter and counts no episode steps)
+        from .envs import Pendulum
+        self.ep_steps = torch.tensor([env.steps if type(env) is Pendulum else 0], dtype=torch.int32, device=dev)
+        self.ep_return = torch.tensor([env.ret], dtype=torch.float64, device=dev)
+        self.env_seed = torch.tensor([env.seed], dtype=torch.int64, device=dev)
+        self._ring_buf = torch.zeros(3 * self.ring_cap + 1, dtype=torch.float64, device=dev)      # DeviceCartPoleVec's layout
+        self.ep_ring = self._ring_buf[:3 * self.ring_cap].view(self.ring_cap, 3)
+        self.ep_count = self._ring_buf[3 * self.ring_cap:].view(torch.int64)
+        self._ring_host = torch.zeros(3 * self.ring_cap + 1, dtype=torch.float64).pin_memory()
+        self.drained = 0
+        self._retire_host()
+
+    @staticmethod
+    def eligible(task, config):
+        from .envs import Pendulum, SyntheticContinuous
+        from .normalizers import RescaleNormalizer
+        envs = _RolloutVec._host_envs(task, config)
+        if envs is None or len(envs) != 1 or type(envs[0]) not in (Pendulum, SyntheticContinuous):
+            return False
+        sn, rn = config.state_normalizer, config.reward_normalizer
+        return type(sn) is RescaleNormalizer and sn.coef == 1.0 and type(rn) is RescaleNormalizer and rn.coef == 1.0
+
+
 class EpisodeRing:
     """The host's reader of DeviceCartPoleVec's episode ring, owned by the agent that drives the rollouts.  The kernel stamps a row
     with its own counter: t_len + `bootstrap_stamps` per rollout (A2C: 1, the sampler's bootstrap slot; n-step DQN: 0).  `stamp`

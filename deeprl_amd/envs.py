@@ -286,6 +286,78 @@ class CartPole:
         return self.s.copy(), 1.0, done, info
 
 
+def cenv_u3(seed, c, j):
+    """csrc/cont_env.h cenv_u(seed, stream 3, c, j) on python integers: the reset stream's uniform in [0, 1)."""
+    h = _mix64_int((((seed * 8 + 4) & _M64) * 0x9E3779B97F4A7C15 + c * 64 + j) & _M64)
+    return float(h >> 11) * 1.1102230246251565e-16
+
+
+def pendulum_sincos(th):
+    """(sin th, cos th) for th in [-pi, pi): psin / pcos at th / 8 (|th / 8| <= 0.393, inside their range), then the double-angle
+    step three times, one rounding per operation (csrc/pendulum_env.h pendulum_sincos).  Within 4e-15 of libm."""
+    h = th * 0.125
+    s, c = psin(h), pcos(h)
+    for _ in range(3):
+        t = 2.0 * s
+        s, c = t * c, 1.0 - t * s
+    return s, c
+
+
+class Pendulum:
+    """Torque-limited pendulum swing-up: the published equations with the constants of gym's Pendulum-v0 (g 10, m = l = 1, dt 0.05,
+    |theta'| <= 8, 200 steps, no terminal state but the step limit; reward -(theta^2 + 0.1 theta'^2 + 0.001 u^2) on the state and
+    torque BEFORE the step) -- the host statement of csrc/pendulum_env.h, bit for bit: python fp64 scalars in the same operation
+    order, sine and cosine by pendulum_sincos, reset states from the counter hash (stream 3 of seed at the environment's total step
+    counter c: theta = -pi + 2 pi U_0, theta' = -1 + 2 U_1).  theta is KEPT wrapped to [-pi, pi).  The action space is [-1, 1] and
+    the applied torque u = 2 clip(a, -1, 1): an actor that ends in tanh reaches the full torque range.  Observation
+    [cos theta, sin theta, theta'].  Parity with gym's own pendulum is not pinned:
+        u = 2 clip(a);  reward = -((th th + 0.1 (thd thd)) + 0.001 (u u))
+        thd = thd + (15 sin th + 3 u) 0.05;  th = th + thd 0.05 (the NEW, unclipped velocity);  thd = clip(thd, -8, 8);  wrap th"""
+    PI, TWO_PI, MAX_SPEED = 3.141592653589793, 6.283185307179586, 8.0
+    state_dim, action_dim = 3, 1
+
+    def __init__(self, seed=0, horizon=200):
+        self.seed, self.horizon = int(seed), int(horizon)
+        self.c = 0
+        self.s = None
+        self.steps = 0
+        self.ret = 0.0
+
+    def _obs(self):
+        th, thd = float(self.s[0]), float(self.s[1])
+        sn, cs = pendulum_sincos(th)
+        return np.asarray([cs, sn, thd], dtype=np.float64)
+
+    def reset(self):
+        sd, c = self.seed & _M64, self.c
+        self.s = np.asarray([-self.PI + self.TWO_PI * cenv_u3(sd, c, 0), -1.0 + 2.0 * cenv_u3(sd, c, 1)], dtype=np.float64)
+        self.steps = 0
+        self.ret = 0.0
+        return self._obs()
+
+    def step(self, action):
+        th, thd = float(self.s[0]), float(self.s[1])
+        a = float(np.asarray(action, dtype=np.float64).reshape(-1)[0])
+        a = -1.0 if a < -1.0 else (1.0 if a > 1.0 else a)
+        u = 2.0 * a
+        reward = -(((th * th) + 0.1 * (thd * thd)) + 0.001 * (u * u))
+        sn, _ = pendulum_sincos(th)
+        thd = thd + (15.0 * sn + 3.0 * u) * 0.05
+        th = th + thd * 0.05
+        thd = -self.MAX_SPEED if thd < -self.MAX_SPEED else (self.MAX_SPEED if thd > self.MAX_SPEED else thd)
+        if th >= self.PI:
+            th = th - self.TWO_PI
+        elif th < -self.PI:
+            th = th + self.TWO_PI
+        self.s = np.asarray([th, thd], dtype=np.float64)
+        self.c += 1
+        self.steps += 1
+        self.ret += reward
+        done = bool(self.steps >= self.horizon)
+        info = {'episodic_return': self.ret if done else None}
+        return self._obs(), reward, done, info
+
+
 class DummyVecEnv:
     """envs.py:126-150: serial vector env with auto-reset on done."""
 
@@ -475,6 +547,12 @@ class Task:
             self.env = DummyVecEnv([CartPole(seed + i, horizon=synthetic_done_period or 200) for i in range(num_envs)])
             self.observation_space, self.action_space = Box(-np.inf, np.inf, (4,)), Discrete(2)
             self.state_dim, self.action_dim = 4, 2
+            return
+        if name == 'classic-Pendulum-v0':
+            # the pendulum stated in this package (Pendulum above), by an explicit name as well
+            self.env = DummyVecEnv([Pendulum(seed + i, horizon=synthetic_done_period or 200) for i in range(num_envs)])
+            self.observation_space, self.action_space = Box(-np.inf, np.inf, (3,)), Box(-1.0, 1.0, (1,))
+            self.state_dim, self.action_dim = 3, 1
             return
         explicit = name.startswith('synthetic-')
         real = None if explicit else _real_task_envs(name, num_envs, seed, episode_life)

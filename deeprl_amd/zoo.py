@@ -16,6 +16,7 @@ import torch.nn.functional as F
 from deeprl_amd import agents as A, nets as N
 from deeprl_amd.envs import Task
 from deeprl_amd.normalizers import ImageNormalizer, MeanStdNormalizer, SignNormalizer
+from deeprl_amd.random_process import GaussianProcess, OrnsteinUhlenbeckProcess
 from deeprl_amd.replay import PrioritizedReplay, ReplayWrapper, UniformReplay
 from deeprl_amd.support import Config, LinearSchedule, generate_tag, run_steps
 
@@ -192,6 +193,29 @@ ZOO = {
         fields=dict(discount=0.99, use_gae=True, gae_tau=0.95, gradient_clip=0.5, rollout_length=2048, optimization_epochs=10,
                     mini_batch_size=64, ppo_ratio_clip=0.2, log_interval=2048, max_steps=3e6, target_kl=0.01),
         normalizers=(MeanStdNormalizer, None)),
+    # examples.py:554-579 (the network owns its two optimisers; a plain UniformReplay, no wrapper.  fused_dpg_update=True runs the
+    # update on csrc/dpg_mlp.hip, fused_dpg_env=True with it moves an envs.Pendulum / SyntheticContinuous task onto the device)
+    "ddpg_continuous": dict(
+        agent="DDPGAgent", kw=dict(log_level=0), task=lambda c: Task(c.game), eval_task="same",
+        network=lambda c: N.DeterministicActorCriticNet(
+            c.state_dim, c.action_dim, actor_body=N.FCBody(c.state_dim, (400, 300), gate=F.relu),
+            critic_body=N.FCBody(c.state_dim + c.action_dim, (400, 300), gate=F.relu),
+            actor_opt_fn=_adam(lr=1e-3), critic_opt_fn=_adam(lr=1e-3)),
+        random_process=lambda c: OrnsteinUhlenbeckProcess(size=(c.action_dim,), std=LinearSchedule(0.2)),
+        fields=dict(max_steps=int(1e6), eval_interval=int(1e4), eval_episodes=20, discount=0.99, warm_up=int(1e4),
+                    target_network_mix=5e-3),
+        replay=dict(memory_size=int(1e6), batch_size=100, plain_cls=UniformReplay)),
+    # examples.py:583-617
+    "td3_continuous": dict(
+        agent="TD3Agent", kw=dict(log_level=0), task=lambda c: Task(c.game), eval_task="same",
+        network=lambda c: N.TD3Net(
+            c.action_dim, actor_body_fn=lambda: N.FCBody(c.state_dim, (400, 300), gate=F.relu),
+            critic_body_fn=lambda: N.FCBody(c.state_dim + c.action_dim, (400, 300), gate=F.relu),
+            actor_opt_fn=_adam(lr=1e-3), critic_opt_fn=_adam(lr=1e-3)),
+        random_process=lambda c: GaussianProcess(size=(c.action_dim,), std=LinearSchedule(0.1)),
+        fields=dict(max_steps=int(1e6), eval_interval=int(1e4), eval_episodes=20, discount=0.99, td3_noise=0.2,
+                    td3_noise_clip=0.5, td3_delay=2, warm_up=int(1e4), target_network_mix=5e-3),
+        replay=dict(memory_size=int(1e6), batch_size=100, fixed_cls=UniformReplay, fixed_async=True)),
 }
 
 
@@ -224,6 +248,8 @@ def config(name, **kwargs):
         c.random_action_prob = LinearSchedule(*spec["eps"])
     if "option_eps" in spec:        # option-critic's epsilon over options (OptionCritic_agent.py:55)
         c.random_option_prob = LinearSchedule(*spec["option_eps"])
+    if "random_process" in spec:    # the deterministic-policy agents' exploration noise (DDPG_agent.py:22)
+        c.random_process_fn = lambda: spec["random_process"](c)
     if "beta" in spec:
         c.replay_beta = LinearSchedule(spec["beta"][0], spec["beta"][1], c.max_steps)
     norm = spec.get("normalizers")
@@ -234,16 +260,20 @@ def config(name, **kwargs):
             c.reward_normalizer = norm[1]()
     rp = spec.get("replay")
     if rp:
-        kw = dict(memory_size=rp["memory_size"], batch_size=c.batch_size)
+        kw = dict(memory_size=rp["memory_size"], batch_size=rp["batch_size"] if "batch_size" in rp else c.batch_size)
         if rp.get("with_n_step"):
             # (rainbow_feature hands the replay a literal history_length and leaves the Config's alone)
             kw.update(n_step=c.n_step, discount=c.discount, history_length=rp.get("history_length", c.history_length))
         elif "history_length" in rp:
             kw.update(history_length=rp["history_length"])
-        cls = rp.get("fixed_cls") or c.replay_cls
-        flag = rp["fixed_async"] if "fixed_async" in rp else c.async_replay
         c.replay_kwargs = kw
-        c.replay_fn = lambda: ReplayWrapper(cls, kw, flag)
+        if "plain_cls" in rp:       # (ddpg_continuous hands the agent the replay itself, not a wrapper)
+            plain = rp["plain_cls"]
+            c.replay_fn = lambda: plain(**kw)
+        else:
+            cls = rp.get("fixed_cls") or c.replay_cls
+            flag = rp["fixed_async"] if "fixed_async" in rp else c.async_replay
+            c.replay_fn = lambda: ReplayWrapper(cls, kw, flag)
     if max_steps is not None:
         c.max_steps = max_steps
     for k, v in overrides.items():

@@ -996,6 +996,44 @@ int dra_dpg_actor_update(const dra_dpg_net* online, const dra_dpg_batch* batch, 
 /* out_action [n][action_dim] = tanh(actor(state)) for n <= 128 rows: one launch */
 int dra_dpg_act(const dra_dpg_net* net, const void* state, int64_t state_stride, int in_f64, int n, float* out_action,
                 void* stream);
+/* ONE agent transition of DDPG_agent.py:62-74 / TD3_agent.py:62-71 over ONE device-resident environment in ONE launch of one
+ * workgroup: the observation of the environment narrowed to float32 through the online actor (dra_dpg_act's forward on one row:
+ * out_action has its bits), the behaviour action in fp64 from the staged vector v --
+ *   *mode 0 (warm-up): v;   1 (Gaussian): (double)a + v;   2 (Ornstein-Uhlenbeck): x = (x + ((ou_theta (ou_mu - x)) ou_dt)) + v,
+ *   (double)a + x, with x = ou_x [A] carried in device memory
+ * -- clipped to [bounds[0], bounds[1]]; ring row *slot = (the fp64 observation the action was chosen on, the fp64 action [A], the
+ * fp64 reward, 1 - done); the environment step with the auto reset; for an episode that ended one appended row of ep_ring
+ * (*step_counter, 0, episodic return) and ou_x <- ou_x0 (in every mode).  *step_counter advances by one.  A *slot outside
+ * [0, capacity) is taken as 0 and counted in *err.  No parameter is written.
+ * env_kind 0: the pendulum of csrc/pendulum_env.h (env_state [2] = theta, theta'; state_dim 3, action_dim 1);
+ * env_kind 1: the synthetic continuous environment of csrc/cont_env.h (env_state [state_dim]; ep_steps is not used). */
+typedef struct dra_dpg_env_act_io {
+  double* env_state;            /* (in/out) */
+  int64_t* env_counter;         /* [1] (in/out) */
+  int32_t* ep_steps;            /* [1] (in/out) */
+  double* ep_return;            /* [1] (in/out) */
+  const int64_t* env_seed;      /* [1] */
+  int64_t* step_counter;        /* [1] (in/out) */
+  int64_t* ep_count;            /* [1] (in/out) */
+  double* ep_ring;              /* [ring_cap][3] */
+  const int64_t* mode;          /* [1] staged */
+  const int64_t* slot;          /* [1] staged: the replay's cursor before the step */
+  const double* bounds;         /* [2] staged: the action space's low and high */
+  const double* v;              /* [action_dim] staged */
+  double* ou_x;                 /* [action_dim] (in/out) */
+  const double* ou_x0;          /* [action_dim] */
+  double* ring_frames;          /* [capacity][state_dim] */
+  double* ring_actions;         /* [capacity][action_dim] */
+  double* ring_rewards;         /* [capacity] */
+  int32_t* ring_masks;          /* [capacity] */
+  float* out_action;            /* [action_dim]: tanh(actor(observation)) */
+  int32_t* err;                 /* [1] (in/out): staged words that were out of range */
+  int64_t horizon, ring_cap, capacity;
+  double ou_theta, ou_mu, ou_dt;
+  int32_t env_kind, reserved;
+} dra_dpg_env_act_io;
+int dra_dpg_env_act_supported(int env_kind, int state_dim, int action_dim, int h1, int h2, int gate);   /* 0 = yes; host only */
+int dra_dpg_env_act(const dra_dpg_net* net, const dra_dpg_env_act_io* io, void* stream);
 
 /* ---- cat_mlp: a2c_feature (examples.py:340-358) over device-resident cart-pole environments (csrc/cartpole_env.h,
  * deeprl_amd/envs.py CartPole: the same function bit for bit).

@@ -150,9 +150,11 @@ def a2c_feature(workers=5, device=True, **switches):
     return d.A2CAgent(c), dict(env_per_step=5 * workers, updates_per_step=1)
 
 
-def dpg_continuous(kind, fused=True):
+def dpg_continuous(kind, fused=True, game="synthetic-continuous-HalfCheetah", device=False):
+    """device: config.fused_dpg_env -- the environment on the device, one acting launch per transition (csrc/dpg_mlp.hip
+    dra_dpg_env_act); game 'classic-Pendulum-v0': envs.Pendulum, the family's learning check."""
     c = d.Config()
-    c.merge(dict(game="synthetic-continuous-HalfCheetah", log_level=0, tag="bench", fused_dpg_update=fused))
+    c.merge(dict(game=game, log_level=0, tag="bench", fused_dpg_update=fused, fused_dpg_env=device))
     c.task_fn = lambda: d.Task(c.game, seed=1)
     c.eval_env = d.Task(c.game, seed=2)
     adam = lambda p: torch.optim.Adam(p, lr=1e-3)
@@ -385,6 +387,12 @@ CASES = {
     "ddpg_continuous_modules": lambda: dpg_continuous("ddpg", fused=False),     # torch modules, two torch.optim.Adam
     "td3_continuous": lambda: dpg_continuous("td3"),
     "td3_continuous_modules": lambda: dpg_continuous("td3", fused=False),
+    "ddpg_continuous_device": lambda: dpg_continuous("ddpg", device=True),      # + the environment and the ring feed on the device
+    "td3_continuous_device": lambda: dpg_continuous("td3", device=True),
+    "ddpg_pendulum": lambda: dpg_continuous("ddpg", game="classic-Pendulum-v0", device=True),
+    "ddpg_pendulum_host": lambda: dpg_continuous("ddpg", game="classic-Pendulum-v0"),
+    "td3_pendulum": lambda: dpg_continuous("td3", game="classic-Pendulum-v0", device=True),
+    "td3_pendulum_host": lambda: dpg_continuous("td3", game="classic-Pendulum-v0"),
 }
 
 
@@ -392,10 +400,17 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--cases", default=",".join(CASES))
     ap.add_argument("--seconds", type=float, default=6.0)
+    ap.add_argument("--repeats", type=int, default=1,
+                    help="walk the whole case list this many times; the lines then carry the pass's number as 'repeat'")
     a = ap.parse_args()
     agents_mod.get_logger = lambda *x, **k: _Quiet()
     d.select_device(0)
     d.random_seed(0)
+    for repeat in range(1, a.repeats + 1):
+        run_cases(a, dict(repeat=repeat) if a.repeats > 1 else {})
+
+
+def run_cases(a, tag):
     for name in a.cases.split(","):
         try:
             agent, meta = CASES[name]()
@@ -410,7 +425,7 @@ def main():
                 n += 1
             torch.cuda.synchronize()
             dt = time.perf_counter() - t0
-            print(json.dumps({"case": name, "agent_steps": n, "seconds": round(dt, 2), "agent_steps_per_s": round(n / dt, 2),
+            print(json.dumps({**tag, "case": name, "agent_steps": n, "seconds": round(dt, 2), "agent_steps_per_s": round(n / dt, 2),
                               "env_steps_per_s": round(n * meta["env_per_step"] / dt, 1),
                               "updates_per_s": round(n * meta["updates_per_step"] / dt, 1)}), flush=True)
             if hasattr(agent, "close"):
@@ -423,7 +438,7 @@ def main():
                 torch.cuda.empty_cache()
         except Exception as e:
             import traceback
-            print(json.dumps({"case": name, "error": repr(e), "trace": traceback.format_exc()[-600:]}), flush=True)
+            print(json.dumps({**tag, "case": name, "error": repr(e), "trace": traceback.format_exc()[-600:]}), flush=True)
 
 
 if __name__ == "__main__":
