@@ -96,7 +96,10 @@ class BaseAgent:
         return ret
 
     def eval_episodes(self):
-        returns = np.asarray([np.sum(self.eval_episode()) for _ in range(self.config.eval_episodes)])
+        return self._report_eval(np.asarray([np.sum(self.eval_episode()) for _ in range(self.config.eval_episodes)]))
+
+    def _report_eval(self, returns):
+        """BaseAgent.py:70-77 behind the episodes themselves: mean and standard error, the two records, the dict."""
         mean, sem = returns.mean(), returns.std() / np.sqrt(len(returns))
         self.logger.info('steps %d, episodic_return_test %.2f(%.2f)' % (self.total_steps, mean, sem))
         self.logger.add_scalar('episodic_return_test', mean, self.total_steps)
@@ -624,9 +627,28 @@ class DQNAgent(_DeviceEpisodes, BaseAgent):
         if getattr(self, '_pipe', None) is not None:
             self._pipe.sync_host()
 
+    def _fused_eval(self):
+        """The cart-pole device path's Step when config.fused_eval is on and config.eval_env lives (from the first call on) on the
+        device too: evaluation is then ONE launch and one copy (dqn_mlp.Step.evaluate); None on every other path, and where the
+        evaluation environment has to stay on the host (one warning says why)."""
+        step = getattr(self, '_feature', None)
+        if step is None or getattr(self.config, 'fused_eval', False) is not True:
+            return None
+        return step if step.eval_vec() is not None else None
+
+    def eval_episode(self):
+        step = self._fused_eval()
+        if step is None:
+            return super().eval_episode()
+        return float(step.evaluate(1)[0])
+
     def eval_episodes(self):
         self.sync_host()
-        return super().eval_episodes()
+        step = self._fused_eval()
+        if step is None:
+            return super().eval_episodes()
+        self.drain_episodes()
+        return self._report_eval(np.asarray([np.sum(r) for r in step.evaluate(self.config.eval_episodes)]))
 
     def _episode_ring(self):
         """The cart-pole device path's Step (its drain() runs check() first); None on every other path."""

@@ -16,11 +16,15 @@
 //                            states, the loss and its gradient with respect to all six tensors in the optimiser's flat gradient
 //                            buffer.
 //
+//   dist_mlp_eval_kernel     the acting kernel's staging and forward over eval_act.h's loop (config.fused_eval): n_episodes greedy
+//                            episodes of the evaluation environment in ONE launch.
+//
 // Plain fp32 VALU code, weights in LDS once per launch, every dot product one FMA chain in ascending k, every gradient element
 // owned by ONE thread that adds its rows in ascending order: no atomics, the same bits on every launch.
 #include "common.h"
 #include "c51_block.h"
 #include "mlp_update_block.h"
+#include "eval_act.h"
 #include "replay_act.h"
 #include <math.h>
 
@@ -99,6 +103,71 @@ dist_mlp_act_kernel(dra_dist_mlp_net net, dra_dqn_mlp_act_io io) {
   }
   __syncthreads();
   actor.finish(io, K, tid);
+}
+
+// ---------------------------------------------------------------------------------------------------- evaluation
+// dist_mlp_act_kernel's staging and forward over eval_act.h's loop: greedy, no ring row, until n_episodes episodes have ended.
+template <int H, int GATE, int HEAD>
+__global__ void __launch_bounds__(256)
+dist_mlp_eval_kernel(dra_dist_mlp_net net, dra_mlp_eval_io io) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  const int tid = threadIdx.x;
+  const int K = io.n_episodes * (int)io.horizon, N = net.n_atoms, M = kA * N;      // (K <= 65536: dra_mlp_eval_supported)
+
+  const BodyWeights<H> body(lds);
+  float* wq = lds + body_weight_floats(H);            // [M][H + 1]: lanes read consecutive rows, one bank apart
+  float* bq = wq + round_up4(M * (H + 1));            // [M]
+  float* sZ = bq + round_up4(M);                      // [N]
+  const ActScratch<H> s(sZ + round_up4(N));
+  int* done_word = eval_done_word(s);
+  s.zero(tid);
+  EvalActor actor;
+  actor.begin(io, tid);
+  const float* __restrict__ P = net.param;
+  body.stage(P, net, tid);
+  for (int i = tid; i < M * H; i += 256) {
+    const int c = i / H, k = i - c * H;
+    wq[c * (H + 1) + k] = P[net.wq + i];
+  }
+  for (int i = tid; i < M; i += 256) bq[i] = P[net.bq + i];
+  if constexpr (HEAD == kHeadCategorical) {
+    for (int i = tid; i < N; i += 256) sZ[i] = atom_value(net.v_min, net.v_max, N, i);
+  }
+  __syncthreads();                                    // (thread 0 writes x^T next, over what other threads zeroed)
+
+  for (int k = 0; k < K; ++k) {
+    actor.observe(s.xT, kNP, tid);
+    __syncthreads();
+    hidden_layer<H, GATE, 256>(s.xT, body.w1, body.b1, s.h1T, kS, kNP, tid);
+    __syncthreads();
+    hidden_layer<H, GATE, 256>(s.h1T, body.w2, body.b2, s.h2T, H, kNP, tid);
+    __syncthreads();
+    // ---- the head: wave a = action a, lane j = atom j; the action value over the wave
+    if (tid < kA * kWave) {
+      const int a = tid / kWave, j = tid % kWave;
+      const bool live = j < N;
+      float l = 0.f;
+      if (live) {
+        const float* wr = wq + (a * N + j) * (H + 1);
+        float acc = 0.f;
+#pragma unroll 8
+        for (int i = 0; i < H; ++i) acc = fmaf(s.h2T[i * kNP], wr[i], acc);
+        l = acc + bq[a * N + j];
+      }
+      float q, p;
+      if constexpr (HEAD == kHeadCategorical) q = wave_softmax_value(l, live, sZ + j, p);
+      else q = wave_sum(live ? l : 0.f) / (float)N;
+      if (j == 0) {
+        s.q[a] = q;
+        if (io.out_q) io.out_q[k * kA + a] = q;
+      }
+    }
+    __syncthreads();
+    actor.step(io, s.q, done_word, tid);
+    __syncthreads();
+    if (*done_word >= io.n_episodes) break;           // every thread reads the same word: eval_act.h's banner
+  }
+  actor.finish(io, tid);                              // (thread 0's own words: nothing to wait for)
 }
 
 // ---------------------------------------------------------------------------------------------------- the update
@@ -540,6 +609,16 @@ DRA_API int dra_dist_mlp_act(const dra_dist_mlp_net* net, const dra_dqn_mlp_act_
   return dispatch_hidden_gate_head(net->hidden, net->gate, net->head, [&](auto h, auto g, auto hd) {
     constexpr int H = decltype(h)::value, GATE = decltype(g)::value, HEAD = decltype(hd)::value;
     return launch_one_workgroup<&dist_mlp_act_kernel<H, GATE, HEAD>>(act_lds_floats(H, net->n_atoms) * sizeof(float), net, io, stream);
+  });
+}
+
+DRA_API int dra_dist_mlp_eval(const dra_dist_mlp_net* net, const dra_mlp_eval_io* io, void* stream) {
+  if (!net || !io || !net->param) return DRA_EINVAL;
+  if (dra_dist_mlp_supported(net->state_dim, net->n_actions, net->hidden, 1, net->gate, net->head, net->n_atoms)) return DRA_EINVAL;
+  if (!net_ok(net) || !mlp_eval_io_ok(io)) return DRA_EINVAL;
+  return dispatch_hidden_gate_head(net->hidden, net->gate, net->head, [&](auto h, auto g, auto hd) {
+    constexpr int H = decltype(h)::value, GATE = decltype(g)::value, HEAD = decltype(hd)::value;
+    return launch_one_workgroup<&dist_mlp_eval_kernel<H, GATE, HEAD>>(act_lds_floats(H, net->n_atoms) * sizeof(float), net, io, stream);
   });
 }
 

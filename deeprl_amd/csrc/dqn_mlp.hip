@@ -13,6 +13,10 @@
 //                           forward of the states, 0.5 mean (q_target - q_a)^2 and its gradient with respect to all six tensors,
 //                           written into the optimiser's flat gradient buffer at the parameters' own offsets.
 //
+//   dqn_mlp_eval_kernel     BaseAgent.py:38-60 over DQN_agent.py:70-76 as ONE launch of one workgroup (config.fused_eval): the acting
+//                           kernel's staging and forward over eval_act.h's loop -- greedy, no ring row -- until n_episodes episodes
+//                           of the evaluation environment have ended.
+//
 // Both are q_mlp.hip's kernels with the replay between them: latency-bound chains over a few rows, plain fp32 VALU code, weights in
 // LDS once per launch, activations TRANSPOSED and read 16 bytes at a time, every dot product one FMA chain in ascending k.  The
 // update walks the rows in blocks of 64; every gradient element is owned by ONE thread that adds its rows in ascending order:
@@ -22,6 +26,7 @@
 // and the gradient bookkeeping are written in place (mlp_rollout.h's banner: the figures).
 #include "common.h"
 #include "mlp_update_block.h"
+#include "eval_act.h"
 #include "replay_act.h"
 #include <math.h>
 
@@ -71,6 +76,48 @@ dqn_mlp_act_kernel(dra_q_mlp_net net, dra_dqn_mlp_act_io io) {
   }
   __syncthreads();
   actor.finish(io, K, tid);
+}
+
+// ---------------------------------------------------------------------------------------------------- evaluation
+// dqn_mlp_act_kernel's staging and forward over eval_act.h's loop: greedy, no ring row, until n_episodes episodes have ended.
+template <int H, int GATE>
+__global__ void __launch_bounds__(256)
+dqn_mlp_eval_kernel(dra_q_mlp_net net, dra_mlp_eval_io io) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  const int tid = threadIdx.x;
+  const int K = io.n_episodes * (int)io.horizon;      // (<= 65536: dra_mlp_eval_supported)
+
+  const QNetWeights<H> online(lds);
+  const ActScratch<H> s(lds + q_net_weight_floats(H));
+  int* done_word = eval_done_word(s);
+  s.zero(tid);
+  EvalActor actor;
+  actor.begin(io, tid);
+  online.stage(net.param, net, tid);
+  __syncthreads();                                    // (thread 0 writes x^T next, over what other threads zeroed)
+
+  for (int k = 0; k < K; ++k) {
+    actor.observe(s.xT, kNP, tid);
+    __syncthreads();
+    hidden_layer<H, GATE, 256>(s.xT, online.body.w1, online.body.b1, s.h1T, kS, kNP, tid);
+    __syncthreads();
+    hidden_layer<H, GATE, 256>(s.h1T, online.body.w2, online.body.b2, s.h2T, H, kNP, tid);
+    __syncthreads();
+    if (tid < kA) {
+      const float* wr = online.wq + tid * (H + 1);
+      float acc = 0.f;
+#pragma unroll 8
+      for (int j = 0; j < H; ++j) acc = fmaf(s.h2T[j * kNP], wr[j], acc);
+      acc += online.bq[tid];
+      s.q[tid] = acc;
+      if (io.out_q) io.out_q[k * kA + tid] = acc;
+    }
+    __syncthreads();
+    actor.step(io, s.q, done_word, tid);
+    __syncthreads();
+    if (*done_word >= io.n_episodes) break;           // every thread reads the same word: eval_act.h's banner
+  }
+  actor.finish(io, tid);                              // (thread 0's own words: nothing to wait for)
 }
 
 // ---------------------------------------------------------------------------------------------------- the update
@@ -331,6 +378,18 @@ DRA_API int dra_dqn_mlp_act(const dra_q_mlp_net* net, const dra_dqn_mlp_act_io* 
   return dispatch_hidden_gate(net->hidden, net->gate, [&](auto h, auto g) {
     constexpr int H = decltype(h)::value, GATE = decltype(g)::value;
     return launch_one_workgroup<&dqn_mlp_act_kernel<H, GATE>>(act_lds_floats(H) * sizeof(float), net, io, stream);
+  });
+}
+
+DRA_API int dra_mlp_eval_supported(int n_episodes, int64_t horizon) { return mlp_eval_supported(n_episodes, horizon); }
+
+DRA_API int dra_dqn_mlp_eval(const dra_q_mlp_net* net, const dra_mlp_eval_io* io, void* stream) {
+  if (!net || !io || !net->param) return DRA_EINVAL;
+  if (cartpole_mlp_supported(net->state_dim, net->n_actions, net->hidden, 1, net->gate)) return DRA_EINVAL;
+  if (!offsets_ok(net) || !mlp_eval_io_ok(io)) return DRA_EINVAL;
+  return dispatch_hidden_gate(net->hidden, net->gate, [&](auto h, auto g) {
+    constexpr int H = decltype(h)::value, GATE = decltype(g)::value;
+    return launch_one_workgroup<&dqn_mlp_eval_kernel<H, GATE>>(act_lds_floats(H) * sizeof(float), net, io, stream);
   });
 }
 

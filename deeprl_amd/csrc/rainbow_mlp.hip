@@ -22,11 +22,16 @@
 //                               the projection, the KL per row, priorities and importance weights (DQN_agent.py:120-127), and the
 //                               gradient of mean_b(KL_b w_b) through the dueling combination with respect to all 16 tensors.
 //
+//   rainbow_mlp_eval_kernel     the acting kernel's forward over eval_act.h's loop (config.fused_eval): n_episodes greedy episodes of
+//                               the evaluation environment in ONE launch under ONE noise row (the online network's own buffers),
+//                               the effective weights formed once, ahead of the loop.
+//
 // Plain fp32 VALU code, every dot product one FMA chain in ascending k, every gradient element owned by ONE thread that adds its
 // rows in ascending order: no atomics, the same bits on every launch.
 #include "common.h"
 #include "c51_block.h"
 #include "mlp_update_block.h"
+#include "eval_act.h"
 #include "replay_act.h"
 #include <math.h>
 
@@ -189,6 +194,75 @@ rainbow_mlp_act_kernel(dra_rainbow_mlp_net net, dra_dqn_mlp_act_io io) {
   }
   __syncthreads();
   actor.finish(io, K, tid);
+}
+
+// ---------------------------------------------------------------------------------------------------- evaluation
+// rainbow_mlp_act_kernel's staging and forward over eval_act.h's loop: greedy, no ring row, until n_episodes episodes have ended.
+// The host's eval_step runs the module forward between two reset_noise(): ONE row of noise (net.noise: the online network's own
+// buffers), so the effective weights are formed ONCE, ahead of the loop.
+template <int H, int GATE>
+__global__ void __launch_bounds__(256)
+rainbow_mlp_eval_kernel(dra_rainbow_mlp_net net, dra_mlp_eval_io io) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  const int tid = threadIdx.x;
+  const int K = io.n_episodes * (int)io.horizon, N = net.n_atoms, R = (1 + kA) * N;      // (K <= 65536: dra_mlp_eval_supported)
+
+  const BodyWeights<H> body(lds);
+  float* wh = lds + body_weight_floats(H);            // [R][H + 1]: lanes read consecutive rows, one bank apart
+  float* bh = wh + round_up4(R * (H + 1));            // [R]
+  float* sRaw = bh + round_up4(R);                    // [R]: the heads' outputs of the step
+  float* sZ = sRaw + round_up4(R);                    // [N]
+  float* sF = sZ + round_up4(N);
+  const NoiseF<H> f(sF, N);
+  const ActScratch<H> s(sF + noise_f_floats(H, N));
+  int* done_word = eval_done_word(s);
+  EvalActor actor;
+  actor.begin(io, tid);
+  s.zero(tid);
+  const float* __restrict__ P = net.param;
+  for (int i = tid; i < N; i += 256) sZ[i] = atom_value(net.v_min, net.v_max, N, i);
+  f.load(net.noise, net, N, tid);
+  __syncthreads();                                    // (f's readers; thread 0 writes x^T next, over what other threads zeroed)
+  stage_body<H>(P, net, f, body.w1, body.w2, nullptr, body.b1, body.b2, tid);
+  stage_heads<H>(P, net, f, wh, bh, H + 1, N, tid);
+
+  for (int k = 0; k < K; ++k) {
+    actor.observe(s.xT, kNP, tid);
+    __syncthreads();                                  // (the first step: the effective weights too)
+    hidden_layer<H, GATE, 256>(s.xT, body.w1, body.b1, s.h1T, kS, kNP, tid);
+    __syncthreads();
+    hidden_layer<H, GATE, 256>(s.h1T, body.w2, body.b2, s.h2T, H, kNP, tid);
+    __syncthreads();
+    // ---- the heads: wave 0 the value head, wave 1 + a the advantage head of action a; lane j = atom j
+    if (tid < (1 + kA) * kWave) {
+      const int w = tid / kWave, j = tid % kWave;
+      if (j < N) {
+        const int c = w * N + j;
+        const float* wr = wh + c * (H + 1);
+        float acc = 0.f;
+#pragma unroll 8
+        for (int i = 0; i < H; ++i) acc = fmaf(s.h2T[i * kNP], wr[i], acc);
+        sRaw[c] = acc + bh[c];
+      }
+    }
+    __syncthreads();
+    // ---- wave a: the dueling logits of action a, the softmax and the action value over the wave
+    if (tid < kA * kWave) {
+      const int a = tid / kWave, j = tid % kWave;
+      const bool live = j < N;
+      float p;
+      const float q = wave_softmax_value(live ? dueling_logit(sRaw, N, 1, a, j, 0) : -INFINITY, live, sZ + j, p);
+      if (j == 0) {
+        s.q[a] = q;
+        if (io.out_q) io.out_q[k * kA + a] = q;
+      }
+    }
+    __syncthreads();
+    actor.step(io, s.q, done_word, tid);
+    __syncthreads();
+    if (*done_word >= io.n_episodes) break;           // every thread reads the same word: eval_act.h's banner
+  }
+  actor.finish(io, tid);                              // (thread 0's own words: nothing to wait for)
 }
 
 // ---------------------------------------------------------------------------------------------------- the update
@@ -574,6 +648,16 @@ DRA_API int dra_rainbow_mlp_act(const dra_rainbow_mlp_net* net, const dra_dqn_ml
   return dispatch_hidden_gate(net->hidden, net->gate, [&](auto h, auto g) {
     constexpr int H = decltype(h)::value, GATE = decltype(g)::value;
     return launch_one_workgroup<&rainbow_mlp_act_kernel<H, GATE>>(act_lds_floats(H, net->n_atoms) * sizeof(float), net, io, stream);
+  });
+}
+
+DRA_API int dra_rainbow_mlp_eval(const dra_rainbow_mlp_net* net, const dra_mlp_eval_io* io, void* stream) {
+  if (!net || !io || !net->param || !net->noise) return DRA_EINVAL;
+  if (dra_rainbow_mlp_supported(net->state_dim, net->n_actions, net->hidden, 1, net->gate, net->n_atoms)) return DRA_EINVAL;
+  if (!net_ok(net) || !mlp_eval_io_ok(io)) return DRA_EINVAL;
+  return dispatch_hidden_gate(net->hidden, net->gate, [&](auto h, auto g) {
+    constexpr int H = decltype(h)::value, GATE = decltype(g)::value;
+    return launch_one_workgroup<&rainbow_mlp_eval_kernel<H, GATE>>(act_lds_floats(H, net->n_atoms) * sizeof(float), net, io, stream);
   });
 }
 

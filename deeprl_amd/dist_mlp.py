@@ -96,6 +96,7 @@ class Kind(dqn_mlp.Kind):
     AGENTS = ('CategoricalDQNAgent', 'QuantileRegressionDQNAgent')
     NOT_AGENT = "the agent is a %s, not a CategoricalDQNAgent or a QuantileRegressionDQNAgent"
     NETWORK, ACT, UPDATE, N_SUPPORTED = NETWORK, 'dra_dist_mlp_act', 'dra_dist_mlp_update', 6
+    EVAL = 'dra_dist_mlp_eval'
     # examples.py leaves config.async_actor at the Config's default (True) in both entries, and for these two agents it is a no-op on
     # the host path (agents.py's module docstring): the Step keeps that path's order, so the field does not decide anything here
     ASYNC_ACTOR = True

@@ -9,7 +9,9 @@ dra_dqn_mlp_act runs the sgd_update_frequency transitions and appends them to th
 and writes the gradient into the optimiser's flat buffer (config.fused_dqn_update False: ring.gather and the modules on the
 same indices), then the fused clip + optimizer step -- after WARMUP eager steps replayed from captured graphs (graphs.Region:
 acting alone while total_steps <= exploration_steps, acting + update + clip / step afterwards; single streams, no parallel
-branches).  The target copy runs eagerly between replays.  There is no CPU / eager-PyTorch implementation here: without the HIP
+branches).  The target copy runs eagerly between replays.  With config.fused_eval, `Step.evaluate(n)` runs n greedy episodes of
+config.eval_env -- moved onto the device on first use -- as ONE launch of the kind's evaluation kernel (csrc/eval_act.h) and one
+copy back; an evaluation environment that cannot move stays on the host (EVAL_HOST_NOTE).  There is no CPU / eager-PyTorch implementation here: without the HIP
 library every call raises.
 """
 import ctypes
@@ -51,6 +53,18 @@ class UpdateIO(ctypes.Structure):
                 ("batch", ctypes.c_int32), ("double_q", ctypes.c_int32)]
 
 
+class EvalIO(ctypes.Structure):
+    """Mirror of dra_mlp_eval_io: the evaluation launch of all three kinds (dqn_mlp, dist_mlp, rainbow_mlp)."""
+    _fields_ = [("env_state", ctypes.c_void_p), ("env_counter", ctypes.c_void_p), ("ep_steps", ctypes.c_void_p),
+                ("ep_return", ctypes.c_void_p), ("env_seed", ctypes.c_void_p), ("out_return", ctypes.c_void_p),
+                ("out_length", ctypes.c_void_p), ("out_steps", ctypes.c_void_p), ("out_q", ctypes.c_void_p),
+                ("horizon", ctypes.c_int64), ("n_episodes", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+EVAL_SWITCH = 'fused_eval'
+EVAL_HOST_NOTE = 'fused_eval is on but the evaluation environment stays on the host and this agent keeps the host evaluation: %s'
+eval_supported = shape_table('dra_mlp_eval_supported')      # (n_episodes, horizon)
+
 supported = shape_table('dra_dqn_mlp_supported')      # (state_dim, n_actions, hidden, t_len = transitions per launch, gate)
 update_supported = shape_table('dra_dqn_mlp_update_supported')        # (state_dim, n_actions, hidden, batch, gate)
 
@@ -62,6 +76,7 @@ class Kind:
     ENTRY, SWITCH, UPDATE_SWITCH = 'dqn_feature', SWITCH, 'fused_dqn_update'
     AGENTS, NOT_AGENT = ('DQNAgent',), "the agent is a %s, not a plain DQNAgent"
     NETWORK, ACT, UPDATE, N_SUPPORTED = NETWORK, 'dra_dqn_mlp_act', 'dra_dqn_mlp_update', 4
+    EVAL = 'dra_dqn_mlp_eval'      # config.fused_eval: eval_episodes greedy episodes in one launch (Step.evaluate)
     ASYNC_ACTOR = False      # whether config.async_actor may be on (the Step runs in the sync path's order)
     # what a kind's kernels take beyond dqn_feature's own configuration (rainbow_mlp.py: all three)
     PRIORITIZED = False      # the replay is a PrioritizedReplay (else: a UniformReplay)
@@ -75,6 +90,11 @@ class Kind:
     def extra(agent, shp):
         """A reason of the kind's own behind the shape checks, or None."""
         return None
+
+    @staticmethod
+    def eval_net(agent, net):
+        """What a kind changes in Step.net_struct()'s struct for the evaluation launch (rainbow_mlp.py: the noise it runs under)."""
+        return net
 
     @classmethod
     def fused_update(cls, cfg, shp):
@@ -234,6 +254,10 @@ class Step:
         self.regions = dict(act=Region("the %s acting launch" % self.KIND.ENTRY, cfg, self.WARMUP),
                             learn=Region("the %s agent step" % self.KIND.ENTRY, cfg, self.WARMUP, opts=(agent._fused,)))
         self.last_draws = None          # (explore, random_action, first slot, indices or None) of the last step, as drawn
+        # config.fused_eval: the evaluation environment on the device (None: not decided yet, False: it stays on the host)
+        self._eval_vec, self._eval_bufs = None, {}
+        self.eval_launches = self.eval_copies = self.eval_steps = 0
+        self.eval_lengths, self.eval_debug_q, self.eval_q = None, False, None
 
     def staged_tail(self):
         """Bytes a kind stages behind the parent's block, from self._o_tail on (rainbow_mlp.py: the probabilities and beta)."""
@@ -355,6 +379,80 @@ class Step:
     def after_learn(self):
         """What a kind runs eagerly behind the learn region of a step that updated (rainbow_mlp.py: the priorities' commit)."""
 
+    # -- evaluation (config.fused_eval): config.eval_episodes greedy episodes of config.eval_env in ONE launch -------------
+    def _eval_why_not(self, n):
+        """None when config.eval_env may move onto the device for evaluations of `n` episodes, else the reason."""
+        from .envs import CartPole
+        task = self.agent.config.eval_env
+        if task is self.vec or task is self.vec.task:
+            return "the evaluation environment is the actor's task"
+        envs = _RolloutVec._host_envs(task, self.agent.config)
+        if envs is None or len(envs) != 1 or type(envs[0]) is not CartPole:
+            return "the evaluation environment is not an envs.Task over one envs.CartPole, or there is no device"
+        env = envs[0]
+        if env.c != 0 or env.steps != 0 or isinstance(env.s, str):
+            return "the evaluation environment has already been stepped on the host"
+        if not eval_supported(n, env.horizon):
+            return "%s is not built for %d episodes of at most %d steps" % (self.KIND.EVAL, n, env.horizon)
+        return None
+
+    def eval_vec(self, n=None):
+        """The evaluation environment on the device (a DeviceCartPoleVec whose episode ring goes unused), or None where it stays
+        on the host.  Decided on first use: an eligible config.eval_env moves as reset() leaves it and its host object retires,
+        as the actor's task does in __init__; a refusal is logged in ONE warning."""
+        if self._eval_vec is None:
+            n = int(self.agent.config.eval_episodes if n is None else n)
+            why = self._eval_why_not(n)
+            if why is None:
+                task = self.agent.config.eval_env
+                task.reset()
+                self._eval_vec = DeviceCartPoleVec(task, buffers=lambda t_len, n_env, f: {})
+            else:
+                getattr(self.agent.logger, 'warning', self.agent.logger.info)(EVAL_HOST_NOTE % why)
+                self._eval_vec = False
+        return self._eval_vec or None
+
+    def _eval_buffers(self, n):
+        """ONE device block per episode count -- fp64 returns [n] | int64 steps | int32 lengths [n] -- and its pinned host twin, so
+        that what an evaluation leaves comes back in one copy."""
+        if n not in self._eval_bufs:
+            words = n + 1 + (n + 1) // 2
+            dev = torch.zeros(words, dtype=torch.float64, device=Config.DEVICE)
+            host = torch.zeros(words, dtype=torch.float64).pin_memory()
+            self._eval_bufs[n] = (dev, host)
+        return self._eval_bufs[n]
+
+    def evaluate(self, n):
+        """`n` greedy episodes of the device evaluation environment in ONE launch of the kind's evaluation kernel on the current
+        stream (behind whatever the step queued) and ONE copy back -> the episodic returns, fp64 [n].  self.eval_lengths and
+        self.eval_steps hold the episodes' lengths and their sum; with self.eval_debug_q set, self.eval_q [n * horizon][2] takes
+        the action values per step on the device (rows behind eval_steps are NaN)."""
+        n = int(n)
+        vec = self.eval_vec(n)
+        if vec is None:
+            raise DraError("%s: the evaluation environment is not on the device" % self.KIND.ENTRY)
+        if not eval_supported(n, vec.horizon):
+            raise DraError("%s is not built for %d episodes of at most %d steps" % (self.KIND.EVAL, n, vec.horizon))
+        dev, host = self._eval_buffers(n)
+        io = EvalIO()
+        io.env_state, io.env_counter, io.env_seed = vec.env_state.data_ptr(), vec.env_counter.data_ptr(), vec.env_seed.data_ptr()
+        io.ep_steps, io.ep_return = vec.ep_steps.data_ptr(), vec.ep_return.data_ptr()
+        io.out_return, io.out_steps, io.out_length = dev.data_ptr(), dev[n:].data_ptr(), dev[n + 1:].data_ptr()
+        io.horizon, io.n_episodes = vec.horizon, n
+        if self.eval_debug_q:
+            self.eval_q = torch.full((n * vec.horizon, 2), float('nan'), dtype=torch.float32, device=Config.DEVICE)
+            io.out_q = self.eval_q.data_ptr()
+        net = self.KIND.eval_net(self.agent, self.net_struct())      # the ONLINE network as the host's eval_step reads it
+        getattr(lib, self.KIND.EVAL)(ctypes.byref(net), ctypes.byref(io), stream_ptr())
+        self.eval_launches += 1
+        host.copy_(dev, non_blocking=True)
+        torch.cuda.current_stream().synchronize()
+        self.eval_copies += 1
+        raw = host.numpy()
+        self.eval_steps = int(raw[n:n + 1].view(np.int64)[0])
+        self.eval_lengths = raw[n + 1:].view(np.int32)[:n].copy()
+        return raw[:n].copy()
+
     # -- what the host reads back where it synchronises anyway ----------------------------------------------------------
     def check(self):
         """Raises when a kernel clamped a staged slot or index (a host bookkeeping error: the run's results are not the
@@ -369,8 +467,16 @@ class Step:
 
     def state_dict(self):
         torch.cuda.current_stream().synchronize()
-        return dict(self.episodes.state_dict(), step=int(self.step_dev.item()))
+        state = dict(self.episodes.state_dict(), step=int(self.step_dev.item()))
+        if self._eval_vec:              # the evaluation environment's arrays, once it lives on the device
+            state['eval_env'] = self._eval_vec.state_dict()
+        return state
 
     def load_state_dict(self, state):
         self.episodes.load_state_dict(state)
         self.step_dev.fill_(int(state['step']))
+        if state.get('eval_env') is not None and getattr(self.agent.config, EVAL_SWITCH, False) is True:
+            vec = self.eval_vec()
+            if vec is None:
+                raise DraError("%s: the checkpoint holds a device evaluation environment, this agent's stays on the host" % self.KIND.ENTRY)
+            vec.load_state_dict(state['eval_env'])

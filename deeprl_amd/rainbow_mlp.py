@@ -128,6 +128,7 @@ class Kind(dqn_mlp.Kind):
     ENTRY, SWITCH, UPDATE_SWITCH = 'rainbow_feature', SWITCH, 'fused_rainbow_update'
     AGENTS, NOT_AGENT = ('CategoricalDQNAgent',), "the agent is a %s, not a CategoricalDQNAgent"
     NETWORK, ACT, UPDATE, N_SUPPORTED = NETWORK, 'dra_rainbow_mlp_act', 'dra_rainbow_mlp_update', 5
+    EVAL = 'dra_rainbow_mlp_eval'
     ASYNC_ACTOR = True       # (the entry sets it; for this agent class it is a no-op on the host path: dist_mlp.Kind)
     PRIORITIZED, MAX_N_STEP, NOISY = True, MAX_N_STEP, True
     Net, DIMS = Net, ("state_dim", "n_actions", "hidden", "gate", "n_atoms")
@@ -135,6 +136,13 @@ class Kind(dqn_mlp.Kind):
     supported = staticmethod(supported)
     # (dqn_mlp.why_not knows no window: extra() asks the table again with the replay's n_step)
     update_supported = staticmethod(lambda *dims: update_supported(*dims, 1))
+
+    @staticmethod
+    def eval_net(agent, net):
+        """Evaluation runs under the ONLINE network's own noise buffers (its last reset_noise()), as ONE row: what the host's
+        eval_step sees through self.network(state), and what the update launch reads."""
+        net.noise = agent.network.noise_block().flat.data_ptr()
+        return net
 
     @staticmethod
     def extra(agent, shp):

@@ -1413,6 +1413,35 @@ int dra_rainbow_mlp_update_supported(int state_dim, int n_actions, int hidden, i
 int dra_rainbow_mlp_act(const dra_rainbow_mlp_net* net, const dra_dqn_mlp_act_io* io, void* stream);
 int dra_rainbow_mlp_update(const dra_rainbow_mlp_net* net, const dra_rainbow_mlp_update_io* io, void* stream);
 
+/* ---- evaluation of the three kinds above (BaseAgent.py:60-77: config.eval_episodes greedy episodes of config.eval_env) in ONE
+ * launch of one workgroup over ONE device-resident cart-pole that is not the actor's.  The launch first does what Task.reset()
+ * does (a reset at *env_counter, episode steps and return 0: whatever ep_steps / ep_return held does not survive), then steps
+ * the environment under the FIRST maximum of the ONLINE network's action values (no exploration word is read, no replay-ring or
+ * episode-ring row and no step counter is written; net->target is not read) with the auto reset on done, until n_episodes
+ * episodes have ended: episode e leaves out_return[e] and out_length[e].  The environment's words are left as the last auto
+ * reset left them, *out_steps is the number of environment steps taken (the sum of the lengths).  out_q, where given, takes the
+ * action values of step k in row k; rows behind *out_steps are not written.  dra_rainbow_mlp_eval forms the effective weights
+ * ONCE, from net->noise as ONE row (the online network's own buffers: what its module forward uses between two reset_noise()).
+ * 1 <= n_episodes <= 256, horizon >= 1, n_episodes * horizon <= 65536 (dra_mlp_eval_supported); anything else is DRA_EINVAL and
+ * nothing is written. */
+typedef struct dra_mlp_eval_io {
+  double* env_state;            /* [1][4] (in/out) */
+  int64_t* env_counter;         /* [1] (in/out) */
+  int32_t* ep_steps;            /* [1] (in/out) */
+  double* ep_return;            /* [1] (in/out) */
+  const int64_t* env_seed;      /* [1] */
+  double* out_return;           /* [n_episodes] */
+  int32_t* out_length;          /* [n_episodes] */
+  int64_t* out_steps;           /* [1] */
+  float* out_q;                 /* [n_episodes * horizon][2], or null */
+  int64_t horizon;
+  int32_t n_episodes, reserved;
+} dra_mlp_eval_io;
+int dra_mlp_eval_supported(int n_episodes, int64_t horizon);                                       /* 0 = yes */
+int dra_dqn_mlp_eval(const dra_q_mlp_net* net, const dra_mlp_eval_io* io, void* stream);
+int dra_dist_mlp_eval(const dra_dist_mlp_net* net, const dra_mlp_eval_io* io, void* stream);
+int dra_rainbow_mlp_eval(const dra_rainbow_mlp_net* net, const dra_mlp_eval_io* io, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

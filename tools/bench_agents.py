@@ -30,6 +30,14 @@ after a warm-up.  Prints one JSON object per line: agent steps/s, env steps/s, g
   ddpg_continuous examples.py:554-583, td3_continuous examples.py:587-617 (one host environment, (400, 300) relu MLPs, Adam 1e-3,
             minibatch 100, a 1M ring; warm_up shortened to 1000 so that the timed window is all updates; the default is
             config.fused_dpg_update True: csrc/dpg_mlp.hip; `_modules` = the switch off: torch modules and optimisers)
+
+Evaluation (config.fused_eval, csrc/eval_act.h) is timed by cases of its own, named explicitly with --cases (EVAL_CASES):
+  <entry>_eval  for the four cart-pole replay entries: ONE agent on its device path, past its warm-up; eval_episodes() with
+            config.fused_eval off (the host loop: the parent's path) and on (one launch, one copy), three timed calls each behind an
+            untimed one, as microseconds per evaluated environment step (host: the environment's own step counter; device:
+            out_steps), min-max over the calls
+  dqn_feature_run_steps_eval  run_steps of dqn_feature over 25 000 steps (evaluations at 0, 5 000, ..., 25 000), the same seed with
+            the switch off and on, three runs each: wall time and the share of it spent inside eval_episodes()
 """
 import argparse
 import json
@@ -396,6 +404,97 @@ CASES = {
 }
 
 
+def _eval_agent(name):
+    entry = name[:-len("_eval")]
+    return CASES[entry]()
+
+
+def _fresh_eval_env(agent, seed=2):
+    agent.config.eval_env = d.Task(agent.config.game, seed=seed)
+    return agent.config.eval_env
+
+
+def run_eval_case(name, tag, calls=3, warm=5000):
+    """<entry>_eval: see the module's docstring.  The agent trains for `warm` agent steps first, so that the evaluated episodes
+    are those of a run under way, not a fresh network's few steps."""
+    agent, meta = _eval_agent(name)
+    for _ in range(warm):
+        agent.step()
+    torch.cuda.synchronize()
+    cfg, step = agent.config, agent._feature
+    cfg.fused_eval = True
+    _fresh_eval_env(agent)
+    agent.eval_episodes()                       # (not timed: the environment's move onto the device, the first launch)
+    host_task = _fresh_eval_env(agent)          # (the device side keeps its own from here on)
+    cfg.fused_eval = False
+    agent.eval_episodes()                       # (not timed either)
+    out = {**tag, "case": name, "episodes": int(cfg.eval_episodes), "calls": calls, "trained_agent_steps": warm}
+    got = dict(host=([], [], []), device=([], [], []))
+    for _ in range(calls):                      # the two sides alternate
+        for side, switch in (("host", False), ("device", True)):
+            cfg.fused_eval = switch
+            before = int(host_task.env.envs[0].c)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            mean = agent.eval_episodes()['episodic_return_test']
+            torch.cuda.synchronize()
+            dt = time.perf_counter() - t0
+            n = int(step.eval_steps) if switch else int(host_task.env.envs[0].c) - before
+            us, steps, means = got[side]
+            us.append(dt * 1e6 / n)
+            steps.append(n)
+            means.append(float(mean))
+    assert step.eval_launches == calls + 1 == step.eval_copies
+    for side, (us, steps, means) in got.items():
+        out.update({side + "_us_per_step": [round(min(us), 2), round(max(us), 2)], side + "_steps": steps, side + "_mean_return": means})
+    out["host_over_device"] = [round(min(got["host"][0]) / max(got["device"][0]), 1), round(max(got["host"][0]) / min(got["device"][0]), 1)]
+    print(json.dumps(out), flush=True)
+    agent.close()
+
+
+def run_steps_eval_case(name, tag, runs=3, max_steps=25000):
+    """dqn_feature_run_steps_eval: see the module's docstring."""
+    import random
+    from deeprl_amd.support import run_steps
+    out = {**tag, "case": name, "max_steps": max_steps, "runs": runs}
+    for side, switch in (("host_eval", False), ("device_eval", True)):
+        wall, inside, last = [], [], []
+        for _ in range(runs):
+            d.random_seed(0)
+            torch.manual_seed(0)
+            random.seed(0)
+            agent = zoo.agent("dqn_feature", game="classic-CartPole-v0", tag="bench", async_replay=False, max_steps=max_steps,
+                              fused_dqn_feature=True, fused_eval=switch)
+            spent, means, evaluate = [0.0], [], agent.eval_episodes
+
+            def timed():
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                got = evaluate()
+                torch.cuda.synchronize()
+                spent[0] += time.perf_counter() - t0
+                means.append(float(got['episodic_return_test']))
+                return got
+            agent.eval_episodes = timed
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            run_steps(agent)
+            torch.cuda.synchronize()
+            wall.append(time.perf_counter() - t0)
+            inside.append(spent[0])
+            last.append(means)
+        out.update({side + "_wall_s": [round(min(wall), 3), round(max(wall), 3)],
+                    side + "_inside_eval_s": [round(min(inside), 3), round(max(inside), 3)],
+                    side + "_eval_share": [round(min(i / w for i, w in zip(inside, wall)), 3), round(max(i / w for i, w in zip(inside, wall)), 3)],
+                    side + "_mean_returns": last[0]})
+    print(json.dumps(out), flush=True)
+
+
+EVAL_CASES = {"dqn_feature_eval": run_eval_case, "categorical_dqn_feature_eval": run_eval_case,
+              "quantile_regression_dqn_feature_eval": run_eval_case, "rainbow_feature_eval": run_eval_case,
+              "dqn_feature_run_steps_eval": run_steps_eval_case}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--cases", default=",".join(CASES))
@@ -413,6 +512,9 @@ def main():
 def run_cases(a, tag):
     for name in a.cases.split(","):
         try:
+            if name in EVAL_CASES:
+                EVAL_CASES[name](name, tag)
+                continue
             agent, meta = CASES[name]()
             warm = 120 if "dqn" in name or "c51" in name or "rainbow" in name else 4      # DQN family: past exploration_steps; on-policy: past graph capture
             warm = meta.get("warm", warm)                                                 # (replay actor-critics: past warm_up)
