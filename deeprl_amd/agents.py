@@ -1941,6 +1941,30 @@ class _DeterministicPolicyAgent(_DeviceEpisodes, BaseAgent):
         """Whether this update also steps the actor and the targets (DDPG: always)."""
         return True
 
+    def _fused_eval(self):
+        """dpg_mlp.Update when config.fused_eval is on (with fused_dpg_update) and config.eval_env lives (from the first call on) on
+        the device: evaluation is then ONE launch and one copy (dpg_mlp.Update.evaluate); None on every other path, and where the
+        evaluation environment has to stay on the host (one warning says why)."""
+        if getattr(self.config, 'fused_eval', False) is not True:
+            return None
+        fused = self._fused_dpg()
+        if fused is None:
+            return None
+        return fused if fused.eval_vec() is not None else None
+
+    def eval_episode(self):
+        fused = self._fused_eval()
+        if fused is None:
+            return super().eval_episode()
+        return float(fused.evaluate(1)[0])
+
+    def eval_episodes(self):
+        fused = self._fused_eval()
+        if fused is None:
+            return super().eval_episodes()
+        self.drain_episodes()
+        return self._report_eval(np.asarray([np.sum(r) for r in fused.evaluate(self.config.eval_episodes)]))
+
     def eval_step(self, state):
         norm = self.config.state_normalizer
         norm.set_read_only()

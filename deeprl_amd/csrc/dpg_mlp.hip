@@ -601,6 +601,83 @@ dpg_env_act_kernel(dra_dpg_net net, dra_dpg_env_act_io io) {
   }
 }
 
+// ------------------------------------------------------------------------------------------------ evaluation on a device pendulum
+// n_episodes greedy episodes of `horizon` steps (dra_dpg_eval_io in the header) as ROWS of dpg_act_kernel's forward: the pendulum
+// has no terminal state but the step limit and draws its reset state from the total step counter, so episode e of an evaluation
+// that starts at counter c0 begins at pendulum_reset(c0 + e horizon), known before anything runs; the episodes are independent and
+// walk in lockstep.  Workgroup b owns the episodes [16 b, 16 b + 16): lane r of wave 0 carries episode 16 b + r in registers (its
+// state and its fp64 return) and row r of the tile -- the same LDS layout and the same actor_forward as dpg_act_kernel, so row r's
+// action has dra_dpg_act's bits for that observation.  The trip count is `horizon` for every thread of every workgroup: no thread
+// skips a barrier.  The environment's words are read by every workgroup when it starts and written once, by the workgroup that
+// is the last to have read them (a ticket in *io.arrive): nobody waits for anybody.
+template <int GATE>
+__global__ void __launch_bounds__(kThreads)
+dpg_eval_kernel(dra_dpg_net net, dra_dpg_eval_io io) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  const int n = io.n_episodes;
+  const Dims d = {kPendulumS, kPendulumA, net.h1, net.h2, n};      // (dra_dpg_eval_supported: the pendulum's sizes, known here)
+  const int tid = threadIdx.x, row0 = blockIdx.x * kRows, ldh = ld_hidden(d.H1, d.H2);
+  float* sX = lds;
+  float* sA = sX + kRows * kLdX;
+  float* sB = sA + kRows * ldh;
+  const int64_t horizon = io.horizon, c0 = *io.env_counter;
+  const uint64_t seed = (uint64_t)*io.env_seed;
+  const int e = row0 + tid;
+  const bool live = tid < kRows && e < n;
+
+  // ---- what Task.reset() does at the head of eval_episode: the episode's start state, return 0
+  PendulumState st = {0.0, 0.0};
+  double ret = 0.0;
+  if (live) pendulum_reset(st, seed, c0 + (int64_t)e * horizon);
+  for (int i = tid; i < kRows * d.S; i += kThreads) sX[(i / d.S) * kLdX + i % d.S] = 0.f;      // rows past n_episodes stay zeros
+  // ---- the environment as the host loop leaves it after its last auto reset.  It depends on c0 alone, so it is written here, ahead
+  // of the loop, by the workgroup that is the LAST to have read c0 and the seed (the ticket's release orders the reads in front of it)
+  if (tid == 0 && __hip_atomic_fetch_add(io.arrive, 1, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT) == (int)gridDim.x - 1) {
+    const int64_t c1 = c0 + (int64_t)n * horizon;
+    PendulumState fresh;
+    pendulum_reset(fresh, seed, c1);
+    io.env_state[0] = fresh.th;
+    io.env_state[1] = fresh.thd;
+    *io.env_counter = c1;
+    *io.ep_steps = 0;
+    *io.ep_return = 0.0;
+    *io.out_steps = (int64_t)n * horizon;
+    *io.arrive = 0;
+  }
+  __syncthreads();
+
+  for (int64_t t = 0; t < horizon; ++t) {
+    if (live) {
+      double obs[kPendulumS];
+      pendulum_observe(st, obs);
+#pragma unroll
+      for (int c = 0; c < kPendulumS; ++c) sX[tid * kLdX + c] = (float)obs[c];
+      if (io.out_state) {
+        double* row = io.out_state + ((int64_t)e * (horizon + 1) + t) * kPendulumVars;
+        row[0] = st.th;
+        row[1] = st.thd;
+      }
+    }
+    __syncthreads();
+    actor_forward<GATE>(net, d, sX, sA, sB, ldh, nullptr, nullptr, nullptr, row0);
+    if (live) {
+      const float a = sX[tid * kLdX + d.S];
+      if (io.out_action) io.out_action[(int64_t)e * horizon + t] = a;
+      ret = ret + pendulum_advance(st, (double)a);
+    }
+    __syncthreads();      // before the next observation overwrites sX
+  }
+
+  if (live) {
+    io.out_return[e] = ret;
+    if (io.out_state) {
+      double* row = io.out_state + ((int64_t)e * (horizon + 1) + horizon) * kPendulumVars;
+      row[0] = st.th;
+      row[1] = st.thd;
+    }
+  }
+}
+
 // ------------------------------------------------------------------------------------------------ weight gradient + Adam
 // One job = one Linear layer: dz [B][N], x [B][ld_x] (K columns used), W [N][K] at off_w, b [N] at off_b.  The bias is column K of
 // [W | b] (x's column K is 1): tiles_k = ceil((K + 1) / 16).
@@ -752,6 +829,17 @@ int launch_env_act(const dra_dpg_net* net, const dra_dpg_env_act_io* io, void* s
   return DRA_OK;
 }
 
+template <int GATE>
+int launch_eval(const dra_dpg_net* net, const dra_dpg_eval_io* io, void* stream) {
+  const size_t bytes = pass_lds_floats(net->h1, net->h2, 2) * sizeof(float);
+  static DraLdsAttr lds_attr;
+  if (int rc = dra_grant_lds(lds_attr, reinterpret_cast<const void*>(&dpg_eval_kernel<GATE>), bytes)) return rc;
+  hipLaunchKernelGGL((dpg_eval_kernel<GATE>), dim3((unsigned)((io->n_episodes + kRows - 1) / kRows)), dim3(kThreads), bytes,
+                     dra_stream(stream), *net, *io);
+  DRA_LAUNCH_CHECK();
+  return DRA_OK;
+}
+
 }  // namespace
 
 DRA_API int dra_dpg_supported(int batch, int state_dim, int action_dim, int h1, int h2, int gate, int n_critics) {
@@ -834,4 +922,18 @@ DRA_API int dra_dpg_env_act(const dra_dpg_net* net, const dra_dpg_env_act_io* io
       !io->ring_actions || !io->ring_rewards || !io->ring_masks || !io->out_action || !io->err)
     return DRA_EINVAL;
   return net->gate == kGateRelu ? launch_env_act<kGateRelu>(net, io, stream) : launch_env_act<kGateTanh>(net, io, stream);
+}
+
+DRA_API int dra_dpg_eval_supported(int n_episodes, int64_t horizon, int state_dim, int action_dim, int h1, int h2, int gate) {
+  if (n_episodes < 1 || n_episodes > kMaxB || horizon < 1 || horizon > 65536 || (int64_t)n_episodes * horizon > 65536) return DRA_EINVAL;
+  return dra_dpg_env_act_supported(kEnvPendulum, state_dim, action_dim, h1, h2, gate);
+}
+
+DRA_API int dra_dpg_eval(const dra_dpg_net* net, const dra_dpg_eval_io* io, void* stream) {
+  if (check_net(net) || !io) return DRA_EINVAL;
+  if (dra_dpg_eval_supported(io->n_episodes, io->horizon, net->state_dim, net->action_dim, net->h1, net->h2, net->gate)) return DRA_EINVAL;
+  if (!io->env_state || !io->env_counter || !io->ep_steps || !io->ep_return || !io->env_seed || !io->out_return || !io->out_steps ||
+      !io->arrive)
+    return DRA_EINVAL;
+  return net->gate == kGateRelu ? launch_eval<kGateRelu>(net, io, stream) : launch_eval<kGateTanh>(net, io, stream);
 }

@@ -4,7 +4,10 @@ forward as a few eager launches, behind the opt-in switch `config.fused_dpg_upda
 `shape(network)` says whether a network is one the kernels walk (DeterministicActorCriticNet / TD3Net, identity phi_body,
 two-layer FCBody stacks of one (H1, H2) and one relu or tanh gate, plain Linear layers with biases); `why_not(agent)` adds the
 agent-side conditions and names the first one that fails; `Update(agent)` owns the workspace, the Adam moments over the online
-flat parameter buffer and the step counts, builds the structs and issues the launches on the current stream.
+flat parameter buffer and the step counts, builds the structs and issues the launches on the current stream.  With
+`config.fused_eval` on top, `Update.evaluate(n)` runs n greedy episodes of config.eval_env -- an envs.Pendulum, moved onto the device
+on first use -- as the rows of ONE launch of dra_dpg_eval and one copy back; an evaluation environment that cannot move stays on
+the host (EVAL_HOST_NOTE).
 There is no CPU / eager implementation here: without the HIP library every call raises.
 """
 import ctypes
@@ -12,10 +15,12 @@ import ctypes
 import numpy as np
 import torch
 
-from ._lib import lib, stream_ptr
+from ._lib import DraError, lib, stream_ptr
 from .mlp_rollout import fc_body, head_out
 
 _I6 = ctypes.c_int32 * 6
+EVAL_SWITCH = 'fused_eval'
+EVAL_HOST_NOTE = 'fused_eval is on but the evaluation environment stays on the host and this agent keeps the host evaluation: %s'
 
 
 class Net(ctypes.Structure):
@@ -41,6 +46,15 @@ class Step(ctypes.Structure):
                 ("td3_noise", ctypes.c_float), ("td3_noise_clip", ctypes.c_float),
                 ("action_low", ctypes.c_float), ("action_high", ctypes.c_float),
                 ("noise_seed", ctypes.c_uint64), ("noise_counter", ctypes.c_int64)]
+
+
+class EvalIO(ctypes.Structure):
+    """Mirror of dra_dpg_eval_io."""
+    _fields_ = [("env_state", ctypes.c_void_p), ("env_counter", ctypes.c_void_p), ("ep_steps", ctypes.c_void_p),
+                ("ep_return", ctypes.c_void_p), ("env_seed", ctypes.c_void_p), ("out_return", ctypes.c_void_p),
+                ("out_steps", ctypes.c_void_p), ("arrive", ctypes.c_void_p), ("out_state", ctypes.c_void_p),
+                ("out_action", ctypes.c_void_p), ("horizon", ctypes.c_int64), ("n_episodes", ctypes.c_int32),
+                ("reserved", ctypes.c_int32)]
 
 
 def modules(network):
@@ -77,6 +91,13 @@ def shape(network):
 def supported(batch, state_dim, action_dim, h1, h2, gate, n_critics):
     """dra_dpg_supported: the shapes the kernels are built for (host-only: no GPU needed)."""
     return lib.dra_dpg_supported.raw(int(batch), int(state_dim), int(action_dim), int(h1), int(h2), int(gate), int(n_critics)) == 0
+
+
+def eval_supported(n_episodes, horizon, state_dim, action_dim, h1, h2, gate):
+    """dra_dpg_eval_supported: the launches the evaluation kernel is built for (host-only: no GPU needed)."""
+    if not 0 <= int(horizon) < 1 << 62 or not -(1 << 31) <= int(n_episodes) < 1 << 31:
+        return False
+    return lib.dra_dpg_eval_supported.raw(int(n_episodes), int(horizon), int(state_dim), int(action_dim), int(h1), int(h2), int(gate)) == 0
 
 
 def _plain_adam(opt):
@@ -161,6 +182,10 @@ class Update:
         self._act_in = torch.zeros(128 * shp[0], dtype=torch.float64, device=dev)
         space = agent.task.action_space
         self.low, self.high = float(np.asarray(space.low).reshape(-1)[0]), float(np.asarray(space.high).reshape(-1)[0])
+        # config.fused_eval: the evaluation environment on the device (None: not decided yet, False: it stays on the host)
+        self._eval_vec, self._eval_bufs, self._eval_arrive = None, {}, None
+        self.eval_launches = self.eval_copies = self.eval_steps = 0
+        self.eval_debug, self.eval_state, self.eval_action = False, None, None
 
     # ---- structs
     def _step(self, opt, t):
@@ -234,6 +259,86 @@ class Update:
                         out.data_ptr(), stream_ptr())
         self.launches += 1
         return out
+
+    # ---- evaluation (config.fused_eval): config.eval_episodes greedy episodes of config.eval_env as the rows of ONE launch
+    def _eval_why_not(self, n):
+        """None when config.eval_env may move onto the device for evaluations of `n` episodes, else the reason."""
+        from .device_env import _RolloutVec
+        from .envs import Pendulum
+        from .normalizers import RescaleNormalizer
+        agent = self.agent
+        cfg, task = agent.config, agent.config.eval_env
+        if task is agent.task or task is getattr(agent.task, 'task', None):
+            return "the evaluation environment is the agent's own task"
+        envs = _RolloutVec._host_envs(task, cfg)
+        if envs is None or len(envs) != 1 or type(envs[0]) is not Pendulum:
+            return "the evaluation environment is not an envs.Task over one envs.Pendulum, or there is no device"
+        env = envs[0]
+        if env.c != 0 or env.steps != 0 or isinstance(env.s, str):
+            return "the evaluation environment has already been stepped on the host"
+        sn, rn = cfg.state_normalizer, cfg.reward_normalizer
+        if type(sn) is not RescaleNormalizer or sn.coef != 1.0:
+            return "the state normaliser is not RescaleNormalizer(1.0)"
+        if type(rn) is not RescaleNormalizer or rn.coef != 1.0:
+            return "the reward normaliser is not RescaleNormalizer(1.0)"
+        if not eval_supported(n, env.horizon, *self.shape[:5]):
+            return "dra_dpg_eval is not built for %d episodes of %d steps with (S, A, H1, H2, gate) = %r" % (n, env.horizon, self.shape[:5])
+        return None
+
+    def eval_vec(self, n=None):
+        """The evaluation environment on the device (a DevicePendulumVec whose episode ring goes unused), or None where it stays on
+        the host.  Decided on first use: an eligible config.eval_env moves as reset() leaves it and its host object retires; a
+        refusal is logged in ONE warning and the host loop stays for good."""
+        if self._eval_vec is None:
+            from .device_env import DevicePendulumVec
+            n = int(self.agent.config.eval_episodes if n is None else n)
+            why = self._eval_why_not(n)
+            if why is None:
+                task = self.agent.config.eval_env
+                task.reset()
+                self._eval_vec = DevicePendulumVec(task)
+                self._eval_arrive = torch.zeros(1, dtype=torch.int32, device=self.flat.device)
+            else:
+                getattr(self.agent.logger, 'warning', self.agent.logger.info)(EVAL_HOST_NOTE % why)
+                self._eval_vec = False
+        return self._eval_vec or None
+
+    def _eval_buffers(self, n):
+        """ONE device block per episode count -- fp64 returns [n] | int64 steps -- and its pinned host twin: one copy back."""
+        if n not in self._eval_bufs:
+            dev = torch.zeros(n + 1, dtype=torch.float64, device=self.flat.device)
+            self._eval_bufs[n] = (dev, torch.zeros(n + 1, dtype=torch.float64).pin_memory())
+        return self._eval_bufs[n]
+
+    def evaluate(self, n):
+        """`n` greedy episodes of the device evaluation environment as the rows of ONE dra_dpg_eval launch on the current stream
+        (behind whatever the step queued) and ONE copy back -> the episodic returns, fp64 [n]; self.eval_steps holds the steps
+        walked.  With self.eval_debug set, self.eval_state [n][horizon + 1][2] (fp64) and self.eval_action [n][horizon] (fp32) take
+        the trajectory on the device."""
+        n = int(n)
+        vec = self.eval_vec(n)
+        if vec is None:
+            raise DraError("dpg_mlp: the evaluation environment is not on the device")
+        if not eval_supported(n, vec.horizon, *self.shape[:5]):
+            raise DraError("dra_dpg_eval is not built for %d episodes of %d steps" % (n, vec.horizon))
+        dev, host = self._eval_buffers(n)
+        io = EvalIO()
+        io.env_state, io.env_counter, io.env_seed = vec.env_state.data_ptr(), vec.env_counter.data_ptr(), vec.env_seed.data_ptr()
+        io.ep_steps, io.ep_return = vec.ep_steps.data_ptr(), vec.ep_return.data_ptr()
+        io.out_return, io.out_steps, io.arrive = dev.data_ptr(), dev[n:].data_ptr(), self._eval_arrive.data_ptr()
+        io.horizon, io.n_episodes = vec.horizon, n
+        if self.eval_debug:
+            self.eval_state = torch.full((n, vec.horizon + 1, 2), float('nan'), dtype=torch.float64, device=self.flat.device)
+            self.eval_action = torch.full((n, vec.horizon), float('nan'), dtype=torch.float32, device=self.flat.device)
+            io.out_state, io.out_action = self.eval_state.data_ptr(), self.eval_action.data_ptr()
+        lib.dra_dpg_eval(ctypes.byref(self.online), ctypes.byref(io), stream_ptr())      # the ONLINE actor, as eval_step reads it
+        self.eval_launches += 1
+        host.copy_(dev, non_blocking=True)
+        torch.cuda.current_stream().synchronize()
+        self.eval_copies += 1
+        raw = host.numpy()
+        self.eval_steps = int(raw[n:n + 1].view(np.int64)[0])
+        return raw[:n].copy()
 
     # ---- views for tests / logging (the head of the workspace: y, q [2], per-row loss)
     def last(self):

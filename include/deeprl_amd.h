@@ -1034,6 +1034,33 @@ typedef struct dra_dpg_env_act_io {
 } dra_dpg_env_act_io;
 int dra_dpg_env_act_supported(int env_kind, int state_dim, int action_dim, int h1, int h2, int gate);   /* 0 = yes; host only */
 int dra_dpg_env_act(const dra_dpg_net* net, const dra_dpg_env_act_io* io, void* stream);
+/* Evaluation of a DDPG / TD3 actor (BaseAgent.py:60-77: config.eval_episodes greedy episodes of config.eval_env) over a
+ * device-resident pendulum (csrc/pendulum_env.h) in ONE launch of ceil(n_episodes / 16) workgroups.  The pendulum ends an episode at
+ * the step limit only and draws its reset state from its total step counter, so episode e begins at pendulum_reset(c0 + e horizon),
+ * c0 = *env_counter -- whatever env_state, *ep_steps and *ep_return held does not survive, as with Task.reset() -- and the episodes
+ * run in lockstep as rows of dra_dpg_act's forward: every action has dra_dpg_act's bits for its observation.  out_return [e] is the
+ * in-order fp64 sum of the episode's rewards.  The environment is left as the host loop leaves it after its last auto reset:
+ * counter c0 + n_episodes horizon, the reset state at that counter, episode steps 0, episode return 0; *out_steps = n_episodes
+ * horizon.  Those words depend on c0 alone and are written once, by the workgroup that is the last to have read c0 (*arrive counts
+ * them and is left 0): no workgroup waits for another.  out_state / out_action are filled only when given.  No parameter is written.
+ * 1 <= n_episodes <= 128, horizon >= 1, n_episodes * horizon <= 65536, state_dim 3, action_dim 1, h1 / h2 / gate as for
+ * dra_dpg_env_act; anything else, or a null required pointer, is -EINVAL with nothing written. */
+typedef struct dra_dpg_eval_io {
+  double* env_state;            /* [2] (out) */
+  int64_t* env_counter;         /* [1] (in/out) */
+  int32_t* ep_steps;            /* [1] (out) */
+  double* ep_return;            /* [1] (out) */
+  const int64_t* env_seed;      /* [1] */
+  double* out_return;           /* [n_episodes] */
+  int64_t* out_steps;           /* [1] */
+  int32_t* arrive;              /* [1] (in/out): 0 before the first launch; every launch leaves it 0 */
+  double* out_state;            /* optional [n_episodes][horizon + 1][2]: the state before each step and the last one */
+  float* out_action;            /* optional [n_episodes][horizon] */
+  int64_t horizon;
+  int32_t n_episodes, reserved;
+} dra_dpg_eval_io;
+int dra_dpg_eval_supported(int n_episodes, int64_t horizon, int state_dim, int action_dim, int h1, int h2, int gate);   /* 0 = yes; host only */
+int dra_dpg_eval(const dra_dpg_net* net, const dra_dpg_eval_io* io, void* stream);
 
 /* ---- cat_mlp: a2c_feature (examples.py:340-358) over device-resident cart-pole environments (csrc/cartpole_env.h,
  * deeprl_amd/envs.py CartPole: the same function bit for bit).

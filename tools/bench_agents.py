@@ -38,6 +38,11 @@ Evaluation (config.fused_eval, csrc/eval_act.h) is timed by cases of its own, na
             out_steps), min-max over the calls
   dqn_feature_run_steps_eval  run_steps of dqn_feature over 25 000 steps (evaluations at 0, 5 000, ..., 25 000), the same seed with
             the switch off and on, three runs each: wall time and the share of it spent inside eval_episodes()
+  ddpg_continuous_eval, td3_continuous_eval  the same for the two continuous entries on classic-Pendulum-v0 (fused_dpg_update and
+            fused_dpg_env on, (400, 300) networks, 1 500 agent steps of training): eval_episodes() of 20 x 200 steps, the host loop
+            against the one launch of csrc/dpg_mlp.hip's dra_dpg_eval
+  ddpg_pendulum_run_steps_eval  run_steps of the zoo's ddpg_continuous on the pendulum over 20 000 steps (evaluations at 0, 10 000 and
+            20 000), the same seed with the switch off and on, three runs each
 """
 import argparse
 import json
@@ -404,9 +409,21 @@ CASES = {
 }
 
 
+# the continuous entries evaluate on the pendulum, on their device path, the zoo's 20 episodes (of 200 steps) a time
+DPG_EVAL = {"ddpg_continuous_eval": "ddpg_pendulum", "td3_continuous_eval": "td3_pendulum"}
+
+
 def _eval_agent(name):
-    entry = name[:-len("_eval")]
-    return CASES[entry]()
+    entry = DPG_EVAL.get(name, name[:-len("_eval")])
+    agent, meta = CASES[entry]()
+    if name in DPG_EVAL:
+        agent.config.eval_episodes = 20
+    return agent, meta
+
+
+def _eval_side(agent):
+    """What holds an agent's device evaluation and its counters: dqn_mlp.Step, or dpg_mlp.Update."""
+    return getattr(agent, '_feature', None) or agent._fused_dpg()
 
 
 def _fresh_eval_env(agent, seed=2):
@@ -416,12 +433,13 @@ def _fresh_eval_env(agent, seed=2):
 
 def run_eval_case(name, tag, calls=3, warm=5000):
     """<entry>_eval: see the module's docstring.  The agent trains for `warm` agent steps first, so that the evaluated episodes
-    are those of a run under way, not a fresh network's few steps."""
+    are those of a run under way, not a fresh network's few steps (the continuous entries: 1 500 steps, 500 past their warm-up)."""
     agent, meta = _eval_agent(name)
+    warm = 1500 if name in DPG_EVAL else warm
     for _ in range(warm):
         agent.step()
     torch.cuda.synchronize()
-    cfg, step = agent.config, agent._feature
+    cfg, step = agent.config, _eval_side(agent)
     cfg.fused_eval = True
     _fresh_eval_env(agent)
     agent.eval_episodes()                       # (not timed: the environment's move onto the device, the first launch)
@@ -453,9 +471,11 @@ def run_eval_case(name, tag, calls=3, warm=5000):
 
 
 def run_steps_eval_case(name, tag, runs=3, max_steps=25000):
-    """dqn_feature_run_steps_eval: see the module's docstring."""
+    """dqn_feature_run_steps_eval / ddpg_pendulum_run_steps_eval: see the module's docstring."""
     import random
     from deeprl_amd.support import run_steps
+    pendulum = name.startswith("ddpg_pendulum")
+    max_steps = 20000 if pendulum else max_steps
     out = {**tag, "case": name, "max_steps": max_steps, "runs": runs}
     for side, switch in (("host_eval", False), ("device_eval", True)):
         wall, inside, last = [], [], []
@@ -463,8 +483,12 @@ def run_steps_eval_case(name, tag, runs=3, max_steps=25000):
             d.random_seed(0)
             torch.manual_seed(0)
             random.seed(0)
-            agent = zoo.agent("dqn_feature", game="classic-CartPole-v0", tag="bench", async_replay=False, max_steps=max_steps,
-                              fused_dqn_feature=True, fused_eval=switch)
+            if pendulum:
+                agent = zoo.agent("ddpg_continuous", game="classic-Pendulum-v0", tag="bench", max_steps=max_steps, fused_dpg_update=True,
+                                  fused_dpg_env=True, fused_eval=switch)
+            else:
+                agent = zoo.agent("dqn_feature", game="classic-CartPole-v0", tag="bench", async_replay=False, max_steps=max_steps,
+                                  fused_dqn_feature=True, fused_eval=switch)
             spent, means, evaluate = [0.0], [], agent.eval_episodes
 
             def timed():
@@ -492,7 +516,9 @@ def run_steps_eval_case(name, tag, runs=3, max_steps=25000):
 
 EVAL_CASES = {"dqn_feature_eval": run_eval_case, "categorical_dqn_feature_eval": run_eval_case,
               "quantile_regression_dqn_feature_eval": run_eval_case, "rainbow_feature_eval": run_eval_case,
-              "dqn_feature_run_steps_eval": run_steps_eval_case}
+              "dqn_feature_run_steps_eval": run_steps_eval_case,
+              "ddpg_continuous_eval": run_eval_case, "td3_continuous_eval": run_eval_case,
+              "ddpg_pendulum_run_steps_eval": run_steps_eval_case}
 
 
 def main():
