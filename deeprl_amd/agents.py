@@ -321,6 +321,10 @@ class DQNAgent(_DeviceEpisodes, BaseAgent):
         if getattr(config, 'fused_dqn_feature', False) is True:
             from . import dqn_mlp
             self._feature = dqn_mlp.adopt(self)
+        # dqn_feature with n_step > 1 and / or a PrioritizedReplay (opt-in, config.fused_dqn_replay_feature): dqn_replay_mlp.Step
+        if getattr(config, 'fused_dqn_replay_feature', False) is True and self._feature is None:
+            from . import dqn_replay_mlp
+            self._feature = dqn_replay_mlp.adopt(self)
         # categorical_dqn_feature / quantile_regression_dqn_feature, examples.py:164-193 / 101-127 (opt-in,
         # config.fused_dist_feature): the same Step over the distributional kernels (csrc/dist_mlp.hip) for CategoricalDQNAgent and
         # QuantileRegressionDQNAgent; any other agent class keeps its path and is told why

@@ -11,7 +11,10 @@
 //                           from the ring by the staged indices (state = frame idx, next state = frame idx + 1), the TARGET
 //                           network's (double_q: and the online network's) forward of the next states, q_target, the online
 //                           forward of the states, 0.5 mean (q_target - q_a)^2 and its gradient with respect to all six tensors,
-//                           written into the optimiser's flat gradient buffer at the parameters' own offsets.
+//                           written into the optimiser's flat gradient buffer at the parameters' own offsets.  A template on its io
+//                           struct: over dra_dqn_replay_mlp_update_io (config.fused_dqn_replay_feature) the same block steps run over
+//                           an n-step window (replay.py:135-139's fold in fp64) with optional priorities and importance weights
+//                           (DQN_agent.py:120-127).
 //
 //   dqn_mlp_eval_kernel     BaseAgent.py:38-60 over DQN_agent.py:70-76 as ONE launch of one workgroup (config.fused_eval): the acting
 //                           kernel's staging and forward over eval_act.h's loop -- greedy, no ring row -- until n_episodes episodes
@@ -124,6 +127,7 @@ dqn_mlp_eval_kernel(dra_q_mlp_net net, dra_mlp_eval_io io) {
 constexpr int kUB = 64;          // rows of one block
 constexpr int kLD = kUB + 4;     // row stride of the transposed activations: 16-byte aligned, consecutive units 4 banks apart
 constexpr int kMaxB = 256;       // rows of one minibatch
+constexpr int kMaxNStep = 8;     // the longest window (rainbow_mlp.hip's)
 
 __host__ __device__ constexpr size_t update_lds_floats(int H) {
   return (size_t)kS * H + 2 * (size_t)H * H + 2 * (size_t)H + (size_t)kA * H + 4      // online: W1^T, W2^T, W2, b1, b2, head, its bias
@@ -131,11 +135,17 @@ __host__ __device__ constexpr size_t update_lds_floats(int H) {
          + 6 * kUB + 4 * kUB                                                          // idx, reward, mask, d, action, loss; the two q_next
          + (size_t)kS * kLD + 3 * (size_t)H * kLD;                                    // x^T, h1^T, h2^T (later dz1^T), dz2^T
 }
+// (the window's kernel: the minibatch's raw importance weights behind them)
+__host__ __device__ constexpr size_t replay_update_lds_floats(int H) { return update_lds_floats(H) + kMaxB; }
 
-template <int H, int GATE>
+// IO = dra_dqn_mlp_update_io: DQN_agent.py:81-99 over 1-step rows.  IO = dra_dqn_replay_mlp_update_io (WINDOW): the same block steps
+// over an n-step window (the fold of replay.py:135-139, the next state n_step frames on) and, where io.prob is set, the priorities and
+// importance weights of DQN_agent.py:120-127 (td_loss_kernel's arithmetic); with prob NULL and n_step 1 the 1-step kernel's bits.
+template <int H, int GATE, typename IO>
 __global__ void __launch_bounds__(256)
-dqn_mlp_update_kernel(dra_q_mlp_net net, dra_dqn_mlp_update_io io) {
+dqn_mlp_update_kernel(dra_q_mlp_net net, IO io) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
+  constexpr bool WINDOW = std::is_same<IO, dra_dqn_replay_mlp_update_io>::value;
   constexpr int TPU = 256 / H;       // threads that share one unit's row of dW2
   constexpr int KPT = H / TPU;       // columns of it each carries
   const int tid = threadIdx.x;
@@ -168,6 +178,7 @@ dqn_mlp_update_kernel(dra_q_mlp_net net, dra_dqn_mlp_update_io io) {
   float* sH1T = sXT + kS * kLD;           // [H][kLD]
   float* sH2T = sH1T + H * kLD;           // [H][kLD]: h2^T, then dz1^T
   float* sG2T = sH2T + H * kLD;           // [H][kLD]: dz2^T
+  float* sWgt = sG2T + H * kLD;           // [kMaxB] (WINDOW): (p B + 1e-6) ** -beta of every row of the minibatch
 
   for (int i = tid; i < kS * H; i += 256) {
     const int k = i / H, u = i - k * H;
@@ -195,7 +206,25 @@ dqn_mlp_update_kernel(dra_q_mlp_net net, dra_dqn_mlp_update_io io) {
     tBq[tid] = PT[net.bq + tid];
   }
   const float gamma = (float)io.discount;
-  const int64_t last = io.capacity - 2;      // the last slot with a next frame behind it
+  int n_step = 1;
+  bool weighted = false;
+  float w_max = 1.f, eps_p = 0.f, alpha = 0.f;
+  if constexpr (WINDOW) {
+    n_step = io.n_step;
+    weighted = io.prob != nullptr;
+    // DQN_agent.py:124-126: weights = (p B + 1e-6) ** -beta over the WHOLE minibatch ahead of the first block, later divided by
+    // their maximum (a maximum in a later block normalises the earlier ones)
+    if (weighted) {
+      const float beta = *io.beta;
+      if (tid < kMaxB) sWgt[tid] = tid < B ? powf(__fadd_rn(__fmul_rn(io.prob[tid], (float)B), 1e-6f), -beta) : 0.f;
+      __syncthreads();
+      w_max = sWgt[0];
+      for (int i = 1; i < B; ++i) w_max = fmaxf(w_max, sWgt[i]);
+      eps_p = (float)io.replay_eps;
+      alpha = (float)io.replay_alpha;
+    }
+  }
+  const int64_t last = io.capacity - 1 - n_step;      // the last slot with its window and next frame behind it
   const bool double_q = io.double_q != 0;
   int n_bad = 0;
 
@@ -213,7 +242,7 @@ dqn_mlp_update_kernel(dra_q_mlp_net net, dra_dqn_mlp_update_io io) {
 
   for (int r0 = 0; r0 < B; r0 += kUB) {
     const int rows = B - r0 < kUB ? B - r0 : kUB;
-    // ---- the block's ring slots (clamped into [0, capacity - 2]: no read leaves the ring), reward, mask, action
+    // ---- the block's ring slots (clamped into [0, capacity - 1 - n_step]: no read leaves the ring), reward, mask, action
     if (tid < kUB) {
       int64_t i = 0;
       bool bad = false;
@@ -223,8 +252,20 @@ dqn_mlp_update_kernel(dra_q_mlp_net net, dra_dqn_mlp_update_io io) {
         i = io.idx[r0 + tid];
         bad = i < 0 || i > last;
         i = i < 0 ? 0 : (i > last ? last : i);
-        rew = (float)io.ring_rewards[i];
-        msk = (float)io.ring_masks[i];
+        if constexpr (WINDOW) {      // the n-step fold (replay.py:135-139) in fp64, the AND of the window's masks
+          double cum = 0.0;
+          int cm = 1;
+          for (int s = n_step - 1; s >= 0; --s) {
+            const int m = io.ring_masks[i + s];
+            cum = io.ring_rewards[i + s] + ((double)m * io.step_discount) * cum;
+            cm = (cm && m) ? 1 : 0;
+          }
+          rew = (float)cum;
+          msk = (float)cm;
+        } else {
+          rew = (float)io.ring_rewards[i];
+          msk = (float)io.ring_masks[i];
+        }
         a = io.ring_actions[i] == 1 ? 1 : 0;
       }
       n_bad += __popcll(__ballot(bad ? 1 : 0));
@@ -235,7 +276,7 @@ dqn_mlp_update_kernel(dra_q_mlp_net net, dra_dqn_mlp_update_io io) {
     }
     __syncthreads();
     // ---- the next states: the TARGET network's q, and with double_q the online network's
-    gather_states<kUB>(io.ring_frames, sIdx, 1, rows, sXT, tid);
+    gather_states<kUB>(io.ring_frames, sIdx, n_step, rows, sXT, tid);
     __syncthreads();
     block_layer<H, GATE, false, kUB>(sXT, tW1, tB1, nullptr, sH1T, kS, tid);
     __syncthreads();
@@ -279,8 +320,20 @@ dqn_mlp_update_kernel(dra_q_mlp_net net, dra_dqn_mlp_update_io io) {
         for (int k = 0; k < H; ++k) acc = fmaf(sH2T[k * kLD + tid], wr[k], acc);
         const float diff = (acc + sBq[a]) - tgt;
         io.out_td[r0 + tid] = -diff;
-        loss = fmaf(diff, diff, loss);
-        d = diff * inv_rows;
+        if (weighted) {      // (WINDOW with prob set) the priority of the UNWEIGHTED td; loss of td w, dq = (q_a - q_target) w w / B
+          if constexpr (WINDOW) {
+            const float ad = fabsf(diff) + eps_p;
+            const float w = sWgt[r0 + tid] / w_max;
+            io.out_prio[r0 + tid] = alpha == 0.5f ? sqrtf(ad) : powf(ad, alpha);
+            io.out_weights[r0 + tid] = w;
+            const float lw = diff * w;
+            loss = fmaf(lw, lw, loss);
+            d = (lw * w) / (float)B;
+          }
+        } else {
+          loss = fmaf(diff, diff, loss);
+          d = diff * inv_rows;
+        }
       }
       sD[tid] = d;
     }
@@ -402,6 +455,25 @@ DRA_API int dra_dqn_mlp_update(const dra_q_mlp_net* net, const dra_dqn_mlp_updat
     return DRA_EINVAL;
   return dispatch_hidden_gate(net->hidden, net->gate, [&](auto h, auto g) {
     constexpr int H = decltype(h)::value, GATE = decltype(g)::value;
-    return launch_one_workgroup<&dqn_mlp_update_kernel<H, GATE>>(update_lds_floats(H) * sizeof(float), net, io, stream);
+    return launch_one_workgroup<&dqn_mlp_update_kernel<H, GATE, dra_dqn_mlp_update_io>>(update_lds_floats(H) * sizeof(float), net, io, stream);
+  });
+}
+
+DRA_API int dra_dqn_replay_mlp_update_supported(int state_dim, int n_actions, int hidden, int batch, int gate, int n_step) {
+  if (dra_dqn_mlp_update_supported(state_dim, n_actions, hidden, batch, gate)) return DRA_EINVAL;
+  return n_step < 1 || n_step > kMaxNStep ? DRA_EINVAL : DRA_OK;
+}
+
+DRA_API int dra_dqn_replay_mlp_update(const dra_q_mlp_net* net, const dra_dqn_replay_mlp_update_io* io, void* stream) {
+  if (!net || !io || !net->param || !net->target) return DRA_EINVAL;
+  if (dra_dqn_replay_mlp_update_supported(net->state_dim, net->n_actions, net->hidden, io->batch, net->gate, io->n_step)) return DRA_EINVAL;
+  if (!offsets_ok(net) || io->capacity < 1 + io->n_step || io->capacity > 0x7fffffff) return DRA_EINVAL;
+  if (!io->ring_frames || !io->ring_actions || !io->ring_rewards || !io->ring_masks || !io->idx || !io->grad || !io->out_q_target ||
+      !io->out_td || !io->out_loss || !io->err)
+    return DRA_EINVAL;
+  if (io->prob && (!io->beta || !io->out_prio || !io->out_weights)) return DRA_EINVAL;
+  return dispatch_hidden_gate(net->hidden, net->gate, [&](auto h, auto g) {
+    constexpr int H = decltype(h)::value, GATE = decltype(g)::value;
+    return launch_one_workgroup<&dqn_mlp_update_kernel<H, GATE, dra_dqn_replay_mlp_update_io>>(replay_update_lds_floats(H) * sizeof(float), net, io, stream);
   });
 }

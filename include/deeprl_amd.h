@@ -1321,6 +1321,40 @@ int dra_dqn_mlp_supported(int state_dim, int n_actions, int hidden, int t_len, i
 int dra_dqn_mlp_update_supported(int state_dim, int n_actions, int hidden, int batch, int gate);   /* the update; 0 = yes */
 int dra_dqn_mlp_act(const dra_q_mlp_net* net, const dra_dqn_mlp_act_io* io, void* stream);
 int dra_dqn_mlp_update(const dra_q_mlp_net* net, const dra_dqn_mlp_update_io* io, void* stream);
+/* dra_dqn_mlp_update over an n-step window with optional priorities (dqn_feature with n_step > 1 and / or a PrioritizedReplay:
+ * config.fused_dqn_replay_feature), ONE launch of one workgroup: for b < batch the n-step transition at DATA index idx[b]
+ * (replay.py:112-140): state = frame idx, next state = frame idx + n_step, action of row idx, reward = the fold cum = r_i + (m_i *
+ * step_discount) * cum over i = n_step - 1 .. 0 in fp64 narrowed to float32, mask = the product of the n_step masks; q_next,
+ * q_target (discount = config.discount ** n_step) and td as in dra_dqn_mlp_update.  With prob set (DQN_agent.py:120-127): prio[b] =
+ * (|td[b]| + replay_eps) ** replay_alpha of the UNWEIGHTED td (sqrtf where replay_alpha is 0.5), weights[b] = (prob[b] * batch +
+ * 1e-6) ** -*beta divided by their maximum over the whole minibatch, loss = 0.5 mean (td weights)^2, d loss / d q[a] = -(td weights)
+ * weights / batch.  With prob NULL no weight is applied and beta, out_prio and out_weights are not touched (they may be NULL); with
+ * n_step 1 on top every output and every gradient element has dra_dqn_mlp_update's bits.  The gradient is written as there.  An idx
+ * outside [0, capacity - 1 - n_step] is clamped into it and counted in *err.  1 <= batch <= 256, 1 <= n_step <= 8
+ * (dra_dqn_replay_mlp_update_supported). */
+typedef struct dra_dqn_replay_mlp_update_io {
+  const double* ring_frames;    /* [capacity][4] */
+  const int64_t* ring_actions;  /* [capacity] (1 = the second action, anything else the first) */
+  const double* ring_rewards;   /* [capacity] */
+  const int32_t* ring_masks;    /* [capacity] */
+  const int64_t* idx;           /* [batch]: data indices */
+  const float* prob;            /* [batch]: sampling probabilities, or NULL (no priorities: a uniform replay) */
+  const float* beta;            /* [1] (device): read when the launch runs; NULL allowed where prob is NULL */
+  float* grad;                  /* the flat gradient buffer (device) */
+  float* out_q_target;          /* [batch] */
+  float* out_td;                /* [batch]: the unweighted td */
+  float* out_loss;              /* [1] */
+  float* out_prio;              /* [batch]: the new priorities, in sample order (prob set) */
+  float* out_weights;           /* [batch] (prob set) */
+  int32_t* err;                 /* [1] (in/out) */
+  int64_t capacity;
+  double discount;              /* the bootstrap factor: config.discount ** n_step */
+  double step_discount;         /* the fold's: the replay's discount */
+  double replay_eps, replay_alpha;
+  int32_t batch, double_q, n_step, reserved;
+} dra_dqn_replay_mlp_update_io;
+int dra_dqn_replay_mlp_update_supported(int state_dim, int n_actions, int hidden, int batch, int gate, int n_step);   /* 0 = yes */
+int dra_dqn_replay_mlp_update(const dra_q_mlp_net* net, const dra_dqn_replay_mlp_update_io* io, void* stream);
 
 /* ---- dist_mlp: categorical_dqn_feature (examples.py:164-193, CategoricalDQN_agent.py) and quantile_regression_dqn_feature
  * (examples.py:101-127, QuantileRegressionDQN_agent.py) over ONE device-resident cart-pole environment and the HBM replay ring:

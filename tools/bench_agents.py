@@ -22,6 +22,9 @@ after a warm-up.  Prints one JSON object per line: agent steps/s, env steps/s, g
             `_module_update` = config.fused_oc_update False; `_host` = the switch off: python environments)
   config 1  dqn_feature examples.py:11-52 (one classic-CartPole-v0 environment, config.fused_dqn_feature True;
             `_module_update` = config.fused_dqn_update False; `_host` = the switch off: the python environment and ring feeds)
+            dqn_feature_per / dqn_feature_nstep: the same entry with n_step 3 over a PrioritizedReplay / a UniformReplay
+            (config.fused_dqn_replay_feature True and config.fused_dqn_replay_update True; `_module_update` =
+            config.fused_dqn_replay_update False; `_host` = the switch off)
             categorical_dqn_feature examples.py:164-193, quantile_regression_dqn_feature examples.py:101-127 (the same, with
             config.fused_dist_feature True and config.fused_dist_update True; `_module_update` = config.fused_dist_update False; `_host` = the switch off)
             rainbow_feature examples.py:231-280 (noisy RainbowNet, 50 atoms, n_step 3, PrioritizedReplay, double_q, minibatch 32;
@@ -220,7 +223,8 @@ def n_step_dqn_feature(workers=5, **switches):
 
 def dqn_feature(**switches):
     c = d.Config()
-    c.merge(dict(game="classic-CartPole-v0", log_level=0, tag="bench", n_step=1, replay_cls=d.UniformReplay, async_replay=False,
+    # (switches may name the entry's own replay options too: n_step, replay_cls -- the dqn_feature_per / _nstep cases)
+    c.merge(dict(dict(game="classic-CartPole-v0", log_level=0, tag="bench", n_step=1, replay_cls=d.UniformReplay, async_replay=False),
                  **switches))
     c.task_fn = lambda: d.Task(c.game, seed=1)
     c.eval_env = d.Task(c.game, seed=2)
@@ -229,6 +233,7 @@ def dqn_feature(**switches):
     c.history_length, c.batch_size, c.discount = 1, 10, 0.99
     kw = dict(memory_size=int(1e4), batch_size=c.batch_size, n_step=c.n_step, discount=c.discount, history_length=1)
     c.replay_fn = lambda: d.ReplayWrapper(c.replay_cls, kw, c.async_replay)
+    c.replay_eps, c.replay_alpha, c.replay_beta = 0.01, 0.5, d.LinearSchedule(0.4, 1.0, 1e5)      # (examples.py:39-41)
     c.random_action_prob = d.LinearSchedule(1.0, 0.1, 1e4)
     c.target_network_update_freq, c.exploration_steps, c.double_q = 200, 1000, False
     c.sgd_update_frequency, c.gradient_clip, c.async_actor = 4, 5, False
@@ -381,6 +386,15 @@ CASES = {
     "dqn_feature": lambda: dqn_feature(fused_dqn_feature=True),
     "dqn_feature_module_update": lambda: dqn_feature(fused_dqn_feature=True, fused_dqn_update=False),
     "dqn_feature_host": lambda: dqn_feature(),   # the switch off: the python cart-pole, four module forwards and ring feeds per step
+    # dqn_feature with its replay options (n_step 3; _per: a PrioritizedReplay) on the same path under config.fused_dqn_replay_feature
+    # (dra_dqn_replay_mlp_update); _host: the switch off, the parent's path for these options
+    "dqn_feature_per": lambda: dqn_feature(n_step=3, replay_cls=d.PrioritizedReplay, fused_dqn_replay_feature=True, fused_dqn_replay_update=True),
+    "dqn_feature_per_module_update": lambda: dqn_feature(n_step=3, replay_cls=d.PrioritizedReplay, fused_dqn_replay_feature=True,
+                                                         fused_dqn_replay_update=False),
+    "dqn_feature_per_host": lambda: dqn_feature(n_step=3, replay_cls=d.PrioritizedReplay),
+    "dqn_feature_nstep": lambda: dqn_feature(n_step=3, fused_dqn_replay_feature=True, fused_dqn_replay_update=True),
+    "dqn_feature_nstep_module_update": lambda: dqn_feature(n_step=3, fused_dqn_replay_feature=True, fused_dqn_replay_update=False),
+    "dqn_feature_nstep_host": lambda: dqn_feature(n_step=3),
     # the two distributional entries on the same path (csrc/dist_mlp.hip): 50 atoms on [-100, 100] / 20 quantiles
     "categorical_dqn_feature": lambda: dist_feature("categorical", fused_dist_feature=True, fused_dist_update=True),
     "categorical_dqn_feature_module_update": lambda: dist_feature("categorical", fused_dist_feature=True, fused_dist_update=False),
