@@ -20,6 +20,10 @@
 //                           kernel's staging and forward over eval_act.h's loop -- greedy, no ring row -- until n_episodes episodes
 //                           of the evaluation environment have ended.
 //
+//   dqn_mlp_act_lanes_kernel, dqn_mlp_update_kernel<.., LANES>   the two launches over n_lanes independent agents (seeds) of one shape:
+//                           workgroup (0, lane) reads ITS net and io struct from two tables and runs the single launch's text, so a
+//                           lane carries the single launch's bits.  Lanes share nothing and wait for nobody (the end of the file).
+//
 // Both are q_mlp.hip's kernels with the replay between them: latency-bound chains over a few rows, plain fp32 VALU code, weights in
 // LDS once per launch, activations TRANSPOSED and read 16 bytes at a time, every dot product one FMA chain in ascending k.  The
 // update walks the rows in blocks of 64; every gradient element is owned by ONE thread that adds its rows in ascending order:
@@ -38,9 +42,9 @@ namespace {
 // ---------------------------------------------------------------------------------------------------- acting
 __host__ __device__ constexpr size_t act_lds_floats(int H) { return q_net_weight_floats(H) + (size_t)act_scratch_floats(H); }
 
+// (the launch's body: dqn_mlp_act_kernel runs it on its kernel arguments, dqn_mlp_act_lanes_kernel on its lane's row of two tables)
 template <int H, int GATE>
-__global__ void __launch_bounds__(256)
-dqn_mlp_act_kernel(dra_q_mlp_net net, dra_dqn_mlp_act_io io) {
+__device__ __forceinline__ void dqn_mlp_act_body(const dra_q_mlp_net& net, const dra_dqn_mlp_act_io& io) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int tid = threadIdx.x;
   const int K = io.t_len;
@@ -79,6 +83,22 @@ dqn_mlp_act_kernel(dra_q_mlp_net net, dra_dqn_mlp_act_io io) {
   }
   __syncthreads();
   actor.finish(io, K, tid);
+}
+
+template <int H, int GATE>
+__global__ void __launch_bounds__(256)
+dqn_mlp_act_kernel(dra_q_mlp_net net, dra_dqn_mlp_act_io io) {
+  dqn_mlp_act_body<H, GATE>(net, io);
+}
+
+// Lane blockIdx.y of n_lanes independent agents: the workgroup reads ITS net and io struct from the two tables (uniform addresses:
+// scalar loads, as the single launch reads its kernel arguments) and runs the single launch's body.  Lanes share nothing.
+template <int H, int GATE>
+__global__ void __launch_bounds__(256)
+dqn_mlp_act_lanes_kernel(const dra_q_mlp_net* __restrict__ nets, const dra_dqn_mlp_act_io* __restrict__ ios) {
+  const dra_q_mlp_net net = nets[blockIdx.y];
+  const dra_dqn_mlp_act_io io = ios[blockIdx.y];
+  dqn_mlp_act_body<H, GATE>(net, io);
 }
 
 // ---------------------------------------------------------------------------------------------------- evaluation
@@ -141,9 +161,21 @@ __host__ __device__ constexpr size_t replay_update_lds_floats(int H) { return up
 // IO = dra_dqn_mlp_update_io: DQN_agent.py:81-99 over 1-step rows.  IO = dra_dqn_replay_mlp_update_io (WINDOW): the same block steps
 // over an n-step window (the fold of replay.py:135-139, the next state n_step frames on) and, where io.prob is set, the priorities and
 // importance weights of DQN_agent.py:120-127 (td_loss_kernel's arithmetic); with prob NULL and n_step 1 the 1-step kernel's bits.
-template <int H, int GATE, typename IO>
+//
+// LANES: the launch of seed_batch.py's n_lanes independent agents -- the arguments are two TABLES and workgroup (0, lane) reads its
+// row of each (uniform addresses: scalar loads, as the single launch reads its kernel arguments), then runs the text below as it
+// is.  A flag on this kernel and not a shared __device__ body: hoisted, dqn_mlp_update_kernel<16, tanh> went 70 -> 78 VGPRs (71 ->
+// 80 over the window's io) -- mlp_rollout.h's banner; with LANES false the figures are the parent's
+// (profiles/dqn_lanes_kernel_resources.txt).
+template <bool LANES, typename T> using lane_arg = std::conditional_t<LANES, const T*, T>;
+template <typename T> __device__ __forceinline__ const T& lane_struct(const T& v) { return v; }
+template <typename T> __device__ __forceinline__ T lane_struct(const T* table) { return table[blockIdx.y]; }
+
+template <int H, int GATE, typename IO, bool LANES = false>
 __global__ void __launch_bounds__(256)
-dqn_mlp_update_kernel(dra_q_mlp_net net, IO io) {
+dqn_mlp_update_kernel(lane_arg<LANES, dra_q_mlp_net> net_arg, lane_arg<LANES, IO> io_arg) {
+  const auto& net = lane_struct(net_arg);
+  const auto& io = lane_struct(io_arg);
   extern __shared__ __attribute__((aligned(16))) float lds[];
   constexpr bool WINDOW = std::is_same<IO, dra_dqn_replay_mlp_update_io>::value;
   constexpr int TPU = 256 / H;       // threads that share one unit's row of dW2
@@ -424,10 +456,15 @@ DRA_API int dra_dqn_mlp_update_supported(int state_dim, int n_actions, int hidde
   return batch < 1 || batch > kMaxB ? DRA_EINVAL : DRA_OK;
 }
 
+// what dra_dqn_mlp_act asks of its two structs (dra_dqn_mlp_act_lanes: of every lane's)
+static bool act_args_ok(const dra_q_mlp_net* net, const dra_dqn_mlp_act_io* io) {
+  if (!net->param) return false;
+  if (dra_dqn_mlp_supported(net->state_dim, net->n_actions, net->hidden, io->t_len, net->gate)) return false;
+  return offsets_ok(net) && replay_act_io_ok(io);
+}
+
 DRA_API int dra_dqn_mlp_act(const dra_q_mlp_net* net, const dra_dqn_mlp_act_io* io, void* stream) {
-  if (!net || !io || !net->param) return DRA_EINVAL;
-  if (dra_dqn_mlp_supported(net->state_dim, net->n_actions, net->hidden, io->t_len, net->gate)) return DRA_EINVAL;
-  if (!offsets_ok(net) || !replay_act_io_ok(io)) return DRA_EINVAL;
+  if (!net || !io || !act_args_ok(net, io)) return DRA_EINVAL;
   return dispatch_hidden_gate(net->hidden, net->gate, [&](auto h, auto g) {
     constexpr int H = decltype(h)::value, GATE = decltype(g)::value;
     return launch_one_workgroup<&dqn_mlp_act_kernel<H, GATE>>(act_lds_floats(H) * sizeof(float), net, io, stream);
@@ -446,13 +483,17 @@ DRA_API int dra_dqn_mlp_eval(const dra_q_mlp_net* net, const dra_mlp_eval_io* io
   });
 }
 
+// what dra_dqn_mlp_update asks of its two structs (dra_dqn_mlp_update_lanes: of every lane's)
+static bool update_args_ok(const dra_q_mlp_net* net, const dra_dqn_mlp_update_io* io) {
+  if (!net->param || !net->target) return false;
+  if (dra_dqn_mlp_update_supported(net->state_dim, net->n_actions, net->hidden, io->batch, net->gate)) return false;
+  if (!offsets_ok(net) || io->capacity < 2 || io->capacity > 0x7fffffff) return false;
+  return io->ring_frames && io->ring_actions && io->ring_rewards && io->ring_masks && io->idx && io->grad && io->out_q_target &&
+         io->out_td && io->out_loss && io->err;
+}
+
 DRA_API int dra_dqn_mlp_update(const dra_q_mlp_net* net, const dra_dqn_mlp_update_io* io, void* stream) {
-  if (!net || !io || !net->param || !net->target) return DRA_EINVAL;
-  if (dra_dqn_mlp_update_supported(net->state_dim, net->n_actions, net->hidden, io->batch, net->gate)) return DRA_EINVAL;
-  if (!offsets_ok(net) || io->capacity < 2 || io->capacity > 0x7fffffff) return DRA_EINVAL;
-  if (!io->ring_frames || !io->ring_actions || !io->ring_rewards || !io->ring_masks || !io->idx || !io->grad || !io->out_q_target ||
-      !io->out_td || !io->out_loss || !io->err)
-    return DRA_EINVAL;
+  if (!net || !io || !update_args_ok(net, io)) return DRA_EINVAL;
   return dispatch_hidden_gate(net->hidden, net->gate, [&](auto h, auto g) {
     constexpr int H = decltype(h)::value, GATE = decltype(g)::value;
     return launch_one_workgroup<&dqn_mlp_update_kernel<H, GATE, dra_dqn_mlp_update_io>>(update_lds_floats(H) * sizeof(float), net, io, stream);
@@ -475,5 +516,55 @@ DRA_API int dra_dqn_replay_mlp_update(const dra_q_mlp_net* net, const dra_dqn_re
   return dispatch_hidden_gate(net->hidden, net->gate, [&](auto h, auto g) {
     constexpr int H = decltype(h)::value, GATE = decltype(g)::value;
     return launch_one_workgroup<&dqn_mlp_update_kernel<H, GATE, dra_dqn_replay_mlp_update_io>>(replay_update_lds_floats(H) * sizeof(float), net, io, stream);
+  });
+}
+
+// ---------------------------------------------------------------------------------------------------- seed lanes
+// n_lanes independent dqn_feature agents of ONE shape as workgroups (0, lane) of the same launches (seed_batch.py).  The tables are
+// read by the host (every lane is checked as the single entry checks its arguments, ahead of the launch) AND by the kernels, from
+// the same addresses: pinned host memory that the device maps (hipHostMalloc, torch's pin_memory()), where HIP keeps a single
+// launch's kernel arguments as well.
+namespace {
+
+constexpr int kMaxLanes = 64;
+
+template <auto KERNEL, typename Net, typename Io>
+int launch_lanes(size_t bytes, const Net* nets, const Io* ios, int n_lanes, void* stream) {
+  static DraLdsAttr lds_attr;
+  if (int rc = dra_grant_lds(lds_attr, reinterpret_cast<const void*>(KERNEL), bytes)) return rc;
+  hipLaunchKernelGGL(KERNEL, dim3(1, (unsigned)n_lanes), dim3(256), bytes, dra_stream(stream), nets, ios);
+  DRA_LAUNCH_CHECK();
+  return DRA_OK;
+}
+
+bool same_shape(const dra_q_mlp_net* a, const dra_q_mlp_net* b) {
+  return a->state_dim == b->state_dim && a->n_actions == b->n_actions && a->hidden == b->hidden && a->gate == b->gate;
+}
+
+}  // namespace
+
+DRA_API int dra_dqn_mlp_lanes_supported(int state_dim, int n_actions, int hidden, int t_len, int batch, int gate, int n_lanes) {
+  if (n_lanes < 1 || n_lanes > kMaxLanes) return DRA_EINVAL;
+  if (dra_dqn_mlp_supported(state_dim, n_actions, hidden, t_len, gate)) return DRA_EINVAL;
+  return dra_dqn_mlp_update_supported(state_dim, n_actions, hidden, batch, gate);
+}
+
+DRA_API int dra_dqn_mlp_act_lanes(const dra_q_mlp_net* nets, const dra_dqn_mlp_act_io* ios, int n_lanes, void* stream) {
+  if (!nets || !ios || n_lanes < 1 || n_lanes > kMaxLanes) return DRA_EINVAL;
+  for (int l = 0; l < n_lanes; ++l)
+    if (!act_args_ok(nets + l, ios + l) || !same_shape(nets, nets + l)) return DRA_EINVAL;
+  return dispatch_hidden_gate(nets->hidden, nets->gate, [&](auto h, auto g) {
+    constexpr int H = decltype(h)::value, GATE = decltype(g)::value;
+    return launch_lanes<&dqn_mlp_act_lanes_kernel<H, GATE>>(act_lds_floats(H) * sizeof(float), nets, ios, n_lanes, stream);
+  });
+}
+
+DRA_API int dra_dqn_mlp_update_lanes(const dra_q_mlp_net* nets, const dra_dqn_mlp_update_io* ios, int n_lanes, void* stream) {
+  if (!nets || !ios || n_lanes < 1 || n_lanes > kMaxLanes) return DRA_EINVAL;
+  for (int l = 0; l < n_lanes; ++l)
+    if (!update_args_ok(nets + l, ios + l) || !same_shape(nets, nets + l)) return DRA_EINVAL;
+  return dispatch_hidden_gate(nets->hidden, nets->gate, [&](auto h, auto g) {
+    constexpr int H = decltype(h)::value, GATE = decltype(g)::value;
+    return launch_lanes<&dqn_mlp_update_kernel<H, GATE, dra_dqn_mlp_update_io, true>>(update_lds_floats(H) * sizeof(float), nets, ios, n_lanes, stream);
   });
 }

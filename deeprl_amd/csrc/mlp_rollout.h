@@ -27,7 +27,12 @@
 //     dqn_mlp_act_kernel: 4 / 4 / 5 / 7 / 4 / 4 -> 12 in all six; in dist_mlp_act_kernel: nine of twelve above (6 -> 12 at relu qr);
 //     begin() behind the staging's barrier there: 9 -> 23 (H 64 tanh qr).  The members' order, the order inside begin() and the
 //     softmax in place or shared moved nothing.
+//   dqn_mlp_act_kernel's whole body (dqn_mlp_act_body) under the single kernel and the seed lanes' dqn_mlp_act_lanes_kernel: all six
+//     single instances keep the parent's figures (profiles/dqn_lanes_kernel_resources.txt).
 // NOT shared, each written in place in the four update kernels:
+//   dqn_mlp_update_kernel's whole body under a lane kernel of its own: hoisted, <16, tanh> went 70 -> 78 VGPRs (71 -> 80 over the
+//     window's io), the other ten equal.  The lane form is a template flag on the kernel itself (LANES; false: the parent's text,
+//     arguments and figures);
 //   the body's gradient bookkeeping (owner indices, dW2 / db2 / dW1 / db1 accumulators, their stores).  As one struct with the
 //     same loop text it met the register bar everywhere but in dist_mlp_update_kernel's stores (H 16: 115 / 103 / 115 / 105 -> 117 /
 //     104 / 117 / 109 VGPRs), yet its row loops come out with the `k2 == 0` / `j1 == 0` sums as selects and one more branch, and

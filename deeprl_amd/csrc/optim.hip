@@ -891,6 +891,116 @@ DRA_API int dra_soft_update(float* target, const float* src, int64_t n, float ke
   return DRA_OK;
 }
 
+// ---- seed lanes (seed_batch.py): clip + RMSprop of n_lanes independent flat buffers of ONE length in ONE launch ---------------
+// Workgroup (x, lane) is rmsprop_step_kernel's workgroup x over lane's buffers.  Ahead of its step it forms the lane's clip
+// coefficient ITSELF, with nobody to wait for: every one of grad_sqnorm_kernel's kNormBlocks partials over the lane's gradient --
+// the same elements per thread in the same order, the same wave and LDS folds; the workgroups without an element give 0.0 there
+// too -- into LDS, then clip_coef_from_partials over them.  So a lane's parameters, running averages and norm carry the bits of
+// dra_grad_sqnorm + dra_rmsprop_step on that lane alone.  The gradient is read once per workgroup of the lane: n is small (at most
+// kLaneMaxFloats; dqn_feature's widest network has 4 610 parameters, 3 workgroups).  The table is read by the host and the
+// device (dqn_mlp.hip: seed lanes).
+constexpr int64_t kLaneMaxFloats = 1 << 16;
+constexpr int kOptimMaxLanes = 64;
+
+__global__ void __launch_bounds__(256)
+clip_rmsprop_step_lanes_kernel(const dra_optim_lane* __restrict__ lanes, float max_norm, float lr, float alpha, float eps, int centered) {
+  __shared__ double s_parts[kNormBlocks];
+  __shared__ double s_red[4];
+  const dra_optim_lane L = lanes[blockIdx.y];
+  const int64_t n = L.n, n4 = n >> 2;
+  float* __restrict__ p = L.param;
+  const float* __restrict__ g = L.grad;
+  float* __restrict__ sq = L.square_avg;
+  float* __restrict__ ga = L.grad_avg;
+  float coef = 1.f;
+  if (max_norm > 0.f) {       // (uniform)
+    for (int i = threadIdx.x; i < kNormBlocks; i += 256) s_parts[i] = 0.0;
+    const int64_t stride = (int64_t)kNormBlocks * 256;
+    const int live = n4 > 0 ? (int)((n4 + 255) / 256) : 1;      // grad_sqnorm_kernel's workgroups with an element (0: the tail's)
+    __syncthreads();
+    for (int vb = 0; vb < live; ++vb) {
+      float acc = 0.f;
+      for (int64_t i = (int64_t)vb * 256 + threadIdx.x; i < n4; i += stride) {
+        const float4 v = reinterpret_cast<const float4*>(g)[i];
+        acc += v.x * v.x + v.y * v.y + v.z * v.z + v.w * v.w;
+      }
+      for (int64_t i = (n4 << 2) + (int64_t)vb * 256 + threadIdx.x; i < n; i += stride) {
+        const float v = g[i];
+        acc += v * v;
+      }
+      const double d = wave_sum((double)acc);
+      if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = d;
+      __syncthreads();
+      if (threadIdx.x == 0) s_parts[vb] = (s_red[0] + s_red[1]) + (s_red[2] + s_red[3]);
+      __syncthreads();
+    }
+    coef = clip_coef_from_partials(s_parts, kNormBlocks, max_norm, L.out_norm);
+  }
+  // rmsprop_step_kernel's elements of workgroup blockIdx.x
+  const float oma = 1.f - alpha;
+  const int64_t i0 = (int64_t)blockIdx.x * (256 * kStepNV) + threadIdx.x;
+#pragma unroll
+  for (int v = 0; v < kStepNV; ++v) {
+    const int64_t i = i0 + 256 * v;
+    if (i < n4) {
+      float4 P = reinterpret_cast<float4*>(p)[i];
+      const float4 G = reinterpret_cast<const float4*>(g)[i];
+      float4 S = reinterpret_cast<float4*>(sq)[i];
+      float4 A = reinterpret_cast<float4*>(centered ? ga : sq)[i];
+      float* pp = &P.x; const float* gg = &G.x; float* ss = &S.x; float* aa = &A.x;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) rmsprop_elem(pp[k], gg[k], ss[k], aa[k], coef, alpha, oma, lr, eps, centered);
+      reinterpret_cast<float4*>(p)[i] = P;
+      reinterpret_cast<float4*>(sq)[i] = S;
+      if (centered) reinterpret_cast<float4*>(ga)[i] = A;
+    }
+  }
+  const int64_t t = (n4 << 2) + threadIdx.x;
+  if (blockIdx.x == 0 && t < n) {
+    float pv = p[t], sv = sq[t], av = centered ? ga[t] : 0.f;
+    rmsprop_elem(pv, g[t], sv, av, coef, alpha, oma, lr, eps, centered);
+    p[t] = pv;
+    sq[t] = sv;
+    if (centered) ga[t] = av;
+  }
+}
+
+DRA_API int dra_clip_rmsprop_step_lanes(const dra_optim_lane* lanes, int n_lanes, float max_norm, float lr, float alpha, float eps,
+                                        int centered, void* stream) {
+  if (!lanes || n_lanes < 1 || n_lanes > kOptimMaxLanes) return DRA_EINVAL;
+  for (int l = 0; l < n_lanes; ++l) {
+    const dra_optim_lane& L = lanes[l];
+    if (!L.param || !L.grad || !L.square_avg || (centered && !L.grad_avg) || (max_norm > 0.f && !L.out_norm)) return DRA_EINVAL;
+    if ((((uintptr_t)L.param) | ((uintptr_t)L.grad) | ((uintptr_t)L.square_avg) | ((uintptr_t)L.grad_avg)) & 15) return DRA_EINVAL;
+    if (L.n < 4 || L.n > kLaneMaxFloats || L.n != lanes[0].n) return DRA_EINVAL;
+  }
+  hipLaunchKernelGGL(clip_rmsprop_step_lanes_kernel, dim3((unsigned)step_blocks(lanes[0].n), (unsigned)n_lanes), dim3(256), 0,
+                     dra_stream(stream), lanes, max_norm, lr, alpha, eps, centered);
+  DRA_LAUNCH_CHECK();
+  return DRA_OK;
+}
+
+// The target sync of every lane (DQN_agent.py:136-138 per agent) in ONE launch: dst[i] = src[i] for i < n of lane blockIdx.y.
+__global__ void __launch_bounds__(256) copy_f32_lanes_kernel(const dra_copy_lane* __restrict__ lanes) {
+  const dra_copy_lane L = lanes[blockIdx.y];
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < L.n; i += (int64_t)gridDim.x * 256) L.dst[i] = L.src[i];
+}
+
+DRA_API int dra_copy_f32_lanes(const dra_copy_lane* lanes, int n_lanes, void* stream) {
+  if (!lanes || n_lanes < 1 || n_lanes > kOptimMaxLanes) return DRA_EINVAL;
+  int64_t most = 0;
+  for (int l = 0; l < n_lanes; ++l) {
+    if (!lanes[l].dst || !lanes[l].src || lanes[l].n < 0) return DRA_EINVAL;
+    most = lanes[l].n > most ? lanes[l].n : most;
+  }
+  if (most == 0) return DRA_OK;
+  const int64_t blocks = (most + 255) / 256;
+  hipLaunchKernelGGL(copy_f32_lanes_kernel, dim3((unsigned)(blocks > 1024 ? 1024 : blocks), (unsigned)n_lanes), dim3(256), 0,
+                     dra_stream(stream), lanes);
+  DRA_LAUNCH_CHECK();
+  return DRA_OK;
+}
+
 #ifdef DRA_TRACE
 extern "C" int dra_trace_set_optim(void* p) { return dra_trace_set_local(p); }
 #endif

@@ -372,7 +372,10 @@ class DeviceCartPoleVec(_RolloutVec):
         pending (the oldest have been overwritten)."""
         self._ring_host.copy_(self._ring_buf, non_blocking=True)
         torch.cuda.current_stream().synchronize()
-        host = self._ring_host.numpy()
+        return self.rows_since_drain(self._ring_host.numpy())
+
+    def rows_since_drain(self, host):
+        """drain() over `host`, a host copy of _ring_buf that the caller made (seed_batch.py: the rings of all lanes in one copy)."""
         count = int(host[3 * self.ring_cap:].view(np.int64)[0])
         pending = count - self.drained
         if pending > self.ring_cap:

@@ -180,19 +180,20 @@ def plan_epsilon_greedy(schedule, t_len, n_rows, n_actions, schedule_steps=1):
     return explore, random_action
 
 
-def plan_actor_epsilon_greedy(schedule, k, n_actions, actor_steps, exploration_steps):
+def plan_actor_epsilon_greedy(schedule, k, n_actions, actor_steps, exploration_steps, rng=np.random):
     """The exploration of k consecutive DQNActor transitions of ONE environment drawn up front (DQN_agent.py:34-40 with the 2-D
     branch of epsilon_greedy): per transition, epsilon = 1 while the actor's step count (actor_steps, then + 1 per transition) is
     below exploration_steps -- the schedule is NOT called there --, else schedule(); then randint(n_actions, size=1), then
     rand(1).  Neither draw depends on q, so the generator and the schedule end where the transition-by-transition loop leaves
     them, also when exploration_steps is crossed inside the k transitions.
+    `rng`: the generator the draws come from (the global stream, or a np.random.RandomState of the caller's: seed_batch.py).
     -> (explore bool [k] = dice < epsilon in float64, random_action int64 [k])."""
     explore = np.empty(k, dtype=np.bool_)
     random_action = np.empty(k, dtype=np.int64)
     for t in range(k):
         epsilon = 1 if actor_steps + t < exploration_steps else schedule()
-        random_action[t] = np.random.randint(n_actions, size=1)[0]
-        explore[t] = np.random.rand(1)[0] < epsilon
+        random_action[t] = rng.randint(n_actions, size=1)[0]
+        explore[t] = rng.rand(1)[0] < epsilon
     return explore, random_action
 
 

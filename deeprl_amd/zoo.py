@@ -291,6 +291,41 @@ def run(name, **kwargs):
     return ag
 
 
+def run_seeds(name, seeds, **kwargs):
+    """`name` once per seed, the seeds as lanes of the same device launches (deeprl_amd/seed_batch.py): per seed, random_seed(seed),
+    torch.manual_seed(seed) and config(name, fused_dqn_feature=True, **kwargs) over Task(game, seed=seed), stepped until
+    config.max_steps environment steps of EVERY lane -> per seed the list of (step, episodic_return) pairs of its training
+    episodes, each what the single run of that seed gives.  There is no evaluation on this path: eval_interval is forced to 0.
+    Only dqn_feature has a lane form, with n_step 1 and a UniformReplay: anything else raises a ValueError that names the
+    reason."""
+    from deeprl_amd.seed_batch import DQNFeatureSeeds
+    if name != "dqn_feature":
+        raise ValueError("run_seeds: only dqn_feature runs its seeds as lanes, %s has no lane form" % name)
+
+    def make_config(seed):
+        c = config(name, fused_dqn_feature=True, **dict(kwargs))
+        c.task_fn = lambda: Task(c.game, seed=seed)
+        c.eval_interval = 0
+        return c
+
+    batch = DQNFeatureSeeds(make_config, seeds)
+    try:
+        out = [[] for _ in batch.seeds]
+        max_steps = batch.lane(0).config.max_steps
+        if not max_steps:
+            raise ValueError("run_seeds steps until config.max_steps, which is not set")
+        while batch.total_steps < max_steps:
+            batch.step()
+            if batch.agent_steps % 1024 == 0:
+                for k, got in enumerate(out):
+                    got += batch.episodes(k)
+        for k, got in enumerate(out):
+            got += batch.episodes(k)
+        return out
+    finally:
+        batch.close()
+
+
 def _entry(name):
     def fn(**kwargs):
         return run(name, **kwargs)

@@ -486,6 +486,31 @@ int dra_adam_step_counter(float* param, const float* grad, float* exp_avg, float
                           const double* partials, int n_partials, float max_norm, float lr, float beta1, float beta2,
                           float eps, const int64_t* step_dev, float* out_norm, float* param_copy, void* stream);
 int dra_copy_f32(float* dst, const float* src, int64_t n, void* stream); /* DQN_agent.py:136-138 */
+/* Seed lanes (seed_batch.py: n_lanes independent agents of one configuration in the same launches; 1 <= n_lanes <= 64).  A lane
+ * table is an array of n_lanes structs that the HOST and the DEVICE both read at the address passed: pinned host memory that the
+ * device maps (hipHostMalloc, torch's pin_memory()).  The entry checks every lane on the host before it launches anything;
+ * workgroup (x, lane) reads its struct with scalar loads.  Lanes never wait for each other.
+ * dra_clip_rmsprop_step_lanes: per lane, dra_grad_sqnorm's partial sums, the clip coefficient and dra_rmsprop_step's update (centred or
+ * not) over the lane's flat buffers of n floats (4 <= n <= 65536, equal in every lane, 16-byte aligned) in ONE launch -- the same
+ * partition over dra_norm_partials() blocks folded in the same order, so a lane's parameters, running averages and *out_norm carry
+ * the bits of the two single launches on that lane.  max_norm <= 0: no clipping, out_norm is not written.
+ * dra_copy_f32_lanes: dst[i] = src[i], i < n, per lane (the target sync of every lane). */
+typedef struct dra_optim_lane {
+  float* param;          /* [n] (in/out) */
+  const float* grad;     /* [n] */
+  float* square_avg;     /* [n] (in/out) */
+  float* grad_avg;       /* [n] (in/out; centred only) */
+  float* out_norm;       /* [1]: the lane's gradient norm before clipping */
+  int64_t n;
+} dra_optim_lane;
+typedef struct dra_copy_lane {
+  float* dst;
+  const float* src;
+  int64_t n;
+} dra_copy_lane;
+int dra_clip_rmsprop_step_lanes(const dra_optim_lane* lanes, int n_lanes, float max_norm, float lr, float alpha, float eps,
+                                int centered, void* stream);
+int dra_copy_f32_lanes(const dra_copy_lane* lanes, int n_lanes, void* stream);
 /* polyak averaging of the target network (DDPG_agent.py:26-30, TD3_agent.py:28-32) over the two networks' flat parameter
  * buffers (16-byte aligned): target[i] = target[i] * keep + src[i] * mix with keep = f32(1 - mix); each product is rounded
  * before the add, as the reference's `target_param * (1.0 - mix) + param * mix` is.  One launch. */
@@ -1321,6 +1346,12 @@ int dra_dqn_mlp_supported(int state_dim, int n_actions, int hidden, int t_len, i
 int dra_dqn_mlp_update_supported(int state_dim, int n_actions, int hidden, int batch, int gate);   /* the update; 0 = yes */
 int dra_dqn_mlp_act(const dra_q_mlp_net* net, const dra_dqn_mlp_act_io* io, void* stream);
 int dra_dqn_mlp_update(const dra_q_mlp_net* net, const dra_dqn_mlp_update_io* io, void* stream);
+/* The two launches over n_lanes independent agents of ONE network shape (seed lanes, above: the tables' memory, 1 <= n_lanes <= 64): workgroup (0, lane) runs dra_dqn_mlp_act / dra_dqn_mlp_update on nets[lane] and ios[lane], to the bit.
+ * DRA_EINVAL, and nothing is launched, for a null table, an n_lanes outside the range, a lane the single entry refuses, or a lane
+ * whose state_dim / n_actions / hidden / gate are not lane 0's. */
+int dra_dqn_mlp_lanes_supported(int state_dim, int n_actions, int hidden, int t_len, int batch, int gate, int n_lanes);   /* 0 = yes */
+int dra_dqn_mlp_act_lanes(const dra_q_mlp_net* nets, const dra_dqn_mlp_act_io* ios, int n_lanes, void* stream);
+int dra_dqn_mlp_update_lanes(const dra_q_mlp_net* nets, const dra_dqn_mlp_update_io* ios, int n_lanes, void* stream);
 /* dra_dqn_mlp_update over an n-step window with optional priorities (dqn_feature with n_step > 1 and / or a PrioritizedReplay:
  * config.fused_dqn_replay_feature), ONE launch of one workgroup: for b < batch the n-step transition at DATA index idx[b]
  * (replay.py:112-140): state = frame idx, next state = frame idx + n_step, action of row idx, reward = the fold cum = r_i + (m_i *

@@ -46,6 +46,11 @@ Evaluation (config.fused_eval, csrc/eval_act.h) is timed by cases of its own, na
             against the one launch of csrc/dpg_mlp.hip's dra_dpg_eval
   ddpg_pendulum_run_steps_eval  run_steps of the zoo's ddpg_continuous on the pendulum over 20 000 steps (evaluations at 0, 10 000 and
             20 000), the same seed with the switch off and on, three runs each
+
+Seed lanes (deeprl_amd/seed_batch.py), named explicitly with --cases too (SEED_CASES):
+  dqn_feature_seeds1 / 4 / 16 / 64  the dqn_feature case's configuration once per seed, the seeds as lanes of the same launches;
+            env_steps_per_s is the aggregate over the lanes, prepare_us_per_lane_step the host's draws and staging per lane and agent
+            step (time.perf_counter around DQNFeatureSeeds.prepare)
 """
 import argparse
 import json
@@ -222,11 +227,23 @@ def n_step_dqn_feature(workers=5, **switches):
 
 
 def dqn_feature(**switches):
+    return d.DQNAgent(dqn_feature_config(**switches)), dict(env_per_step=4, updates_per_step=1, warm=300)
+
+
+def dqn_feature_seeds(n):
+    """dqn_feature_seedsN: N seeds of the dqn_feature case as lanes of the same launches (deeprl_amd/seed_batch.py), the
+    environments seeded 1 .. N; env_steps_per_s is the AGGREGATE over the lanes."""
+    from deeprl_amd.seed_batch import DQNFeatureSeeds
+    batch = DQNFeatureSeeds(lambda seed: dqn_feature_config(task_seed=seed), range(1, n + 1))
+    return batch, dict(env_per_step=4 * n, updates_per_step=n, warm=300, lanes=n)
+
+
+def dqn_feature_config(task_seed=1, **switches):
     c = d.Config()
     # (switches may name the entry's own replay options too: n_step, replay_cls -- the dqn_feature_per / _nstep cases)
     c.merge(dict(dict(game="classic-CartPole-v0", log_level=0, tag="bench", n_step=1, replay_cls=d.UniformReplay, async_replay=False),
                  **switches))
-    c.task_fn = lambda: d.Task(c.game, seed=1)
+    c.task_fn = lambda: d.Task(c.game, seed=task_seed)
     c.eval_env = d.Task(c.game, seed=2)
     c.optimizer_fn = lambda p: torch.optim.RMSprop(p, 0.001)
     c.network_fn = lambda: d.VanillaNet(c.action_dim, d.FCBody(c.state_dim))
@@ -237,8 +254,9 @@ def dqn_feature(**switches):
     c.random_action_prob = d.LinearSchedule(1.0, 0.1, 1e4)
     c.target_network_update_freq, c.exploration_steps, c.double_q = 200, 1000, False
     c.sgd_update_frequency, c.gradient_clip, c.async_actor = 4, 5, False
-    # (warm: past exploration_steps -- 250 agent steps -- and the graph captures, so that the timed window is all updates)
-    return d.DQNAgent(c), dict(env_per_step=4, updates_per_step=1, warm=300)
+    # (warm, in dqn_feature(): past exploration_steps -- 250 agent steps -- and the graph captures, so that the timed window is all
+    # updates)
+    return c
 
 
 def dist_feature(head, **switches):
@@ -423,6 +441,10 @@ CASES = {
 }
 
 
+# dqn_feature's seeds as lanes of one launch: run only when named in --cases (the default set is CASES)
+SEED_CASES = {"dqn_feature_seeds%d" % n: n for n in (1, 4, 16, 64)}
+
+
 # the continuous entries evaluate on the pendulum, on their device path, the zoo's 20 episodes (of 200 steps) a time
 DPG_EVAL = {"ddpg_continuous_eval": "ddpg_pendulum", "td3_continuous_eval": "td3_pendulum"}
 
@@ -555,19 +577,32 @@ def run_cases(a, tag):
             if name in EVAL_CASES:
                 EVAL_CASES[name](name, tag)
                 continue
-            agent, meta = CASES[name]()
+            agent, meta = dqn_feature_seeds(SEED_CASES[name]) if name in SEED_CASES else CASES[name]()
             warm = 120 if "dqn" in name or "c51" in name or "rainbow" in name else 4      # DQN family: past exploration_steps; on-policy: past graph capture
             warm = meta.get("warm", warm)                                                 # (replay actor-critics: past warm_up)
             for _ in range(warm):
                 agent.step()
             torch.cuda.synchronize()
+            if "lanes" in meta:                 # the draws and the staging of a step, host time: prepare_us_per_lane_step
+                spent, prepare = [0.0], agent.prepare
+
+                def timed_prepare():
+                    t0 = time.perf_counter()
+                    learn = prepare()
+                    spent[0] += time.perf_counter() - t0
+                    return learn
+                agent.prepare = timed_prepare
             n, t0 = 0, time.perf_counter()
             while time.perf_counter() - t0 < a.seconds or n < 2:
                 agent.step()
                 n += 1
             torch.cuda.synchronize()
             dt = time.perf_counter() - t0
-            print(json.dumps({**tag, "case": name, "agent_steps": n, "seconds": round(dt, 2), "agent_steps_per_s": round(n / dt, 2),
+            line_tag = tag
+            if "lanes" in meta:
+                line_tag = dict(tag, lanes=meta["lanes"], prepare_us_per_step=round(spent[0] / n * 1e6, 2),
+                                prepare_us_per_lane_step=round(spent[0] / (n * meta["lanes"]) * 1e6, 2))
+            print(json.dumps({**line_tag, "case": name, "agent_steps": n, "seconds": round(dt, 2), "agent_steps_per_s": round(n / dt, 2),
                               "env_steps_per_s": round(n * meta["env_per_step"] / dt, 1),
                               "updates_per_s": round(n * meta["updates_per_step"] / dt, 1)}), flush=True)
             if hasattr(agent, "close"):
