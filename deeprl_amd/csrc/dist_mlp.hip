@@ -19,6 +19,10 @@
 //   dist_mlp_eval_kernel     the acting kernel's staging and forward over eval_act.h's loop (config.fused_eval): n_episodes greedy
 //                            episodes of the evaluation environment in ONE launch.
 //
+//   dist_mlp_act_lanes_kernel, dist_mlp_update_kernel<.., LANES>   the two launches over n_lanes independent agents (seeds) of one
+//                            shape and one atom count: workgroup (0, lane) reads ITS net and io struct from two tables and runs the
+//                            single launch's text, so a lane carries the single launch's bits (seed_lanes.h; the end of the file).
+//
 // Plain fp32 VALU code, weights in LDS once per launch, every dot product one FMA chain in ascending k, every gradient element
 // owned by ONE thread that adds its rows in ascending order: no atomics, the same bits on every launch.
 #include "common.h"
@@ -26,6 +30,7 @@
 #include "mlp_update_block.h"
 #include "eval_act.h"
 #include "replay_act.h"
+#include "seed_lanes.h"
 #include <math.h>
 
 namespace {
@@ -39,9 +44,9 @@ __host__ __device__ constexpr size_t act_lds_floats(int H, int N) {
          + (size_t)act_scratch_floats(H);
 }
 
+// (the launch's body: dist_mlp_act_kernel runs it on its kernel arguments, dist_mlp_act_lanes_kernel on its lane's row of two tables)
 template <int H, int GATE, int HEAD>
-__global__ void __launch_bounds__(256)
-dist_mlp_act_kernel(dra_dist_mlp_net net, dra_dqn_mlp_act_io io) {
+__device__ __forceinline__ void dist_mlp_act_body(const dra_dist_mlp_net& net, const dra_dqn_mlp_act_io& io) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int tid = threadIdx.x;
   const int K = io.t_len, N = net.n_atoms, M = kA * N;
@@ -103,6 +108,22 @@ dist_mlp_act_kernel(dra_dist_mlp_net net, dra_dqn_mlp_act_io io) {
   }
   __syncthreads();
   actor.finish(io, K, tid);
+}
+
+template <int H, int GATE, int HEAD>
+__global__ void __launch_bounds__(256)
+dist_mlp_act_kernel(dra_dist_mlp_net net, dra_dqn_mlp_act_io io) {
+  dist_mlp_act_body<H, GATE, HEAD>(net, io);
+}
+
+// Lane blockIdx.y of n_lanes independent agents (seed_lanes.h): the workgroup reads ITS net and io struct from the two tables and
+// runs the single launch's body.  Lanes share nothing.
+template <int H, int GATE, int HEAD>
+__global__ void __launch_bounds__(256)
+dist_mlp_act_lanes_kernel(const dra_dist_mlp_net* __restrict__ nets, const dra_dqn_mlp_act_io* __restrict__ ios) {
+  const dra_dist_mlp_net net = nets[blockIdx.y];
+  const dra_dqn_mlp_act_io io = ios[blockIdx.y];
+  dist_mlp_act_body<H, GATE, HEAD>(net, io);
 }
 
 // ---------------------------------------------------------------------------------------------------- evaluation
@@ -191,9 +212,15 @@ __device__ __forceinline__ float huber1(float d) {
 }
 __device__ __forceinline__ float huber1_grad(float d) { return fabsf(d) < 1.f ? d : (d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f)); }
 
-template <int H, int GATE, int HEAD>
+// LANES: the launch of seed_batch.py's n_lanes independent agents -- the arguments are two TABLES and workgroup (0, lane) reads its
+// row of each, then runs the text below as it is (seed_lanes.h).  A flag on this kernel and not a shared __device__ body, as in
+// dqn_mlp.hip: with LANES false the text, the argument list and the figures are the parent's
+// (profiles/dist_lanes_kernel_resources.txt).
+template <int H, int GATE, int HEAD, bool LANES = false>
 __global__ void __launch_bounds__(256)
-dist_mlp_update_kernel(dra_dist_mlp_net net, dra_dist_mlp_update_io io) {
+dist_mlp_update_kernel(lane_arg<LANES, dra_dist_mlp_net> net_arg, lane_arg<LANES, dra_dist_mlp_update_io> io_arg) {
+  const auto& net = lane_struct(net_arg);
+  const auto& io = lane_struct(io_arg);
   extern __shared__ __attribute__((aligned(16))) float lds[];
   constexpr int TPU = 256 / H;       // threads that share one unit's row of dW2
   constexpr int KPT = H / TPU;       // columns of it each carries
@@ -601,11 +628,15 @@ DRA_API int dra_dist_mlp_update_supported(int state_dim, int n_actions, int hidd
   return batch < 1 || batch > kMaxB ? DRA_EINVAL : DRA_OK;
 }
 
+// what dra_dist_mlp_act asks of its two structs (dra_dist_mlp_act_lanes: of every lane's)
+static bool act_args_ok(const dra_dist_mlp_net* net, const dra_dqn_mlp_act_io* io) {
+  if (!net->param) return false;
+  if (dra_dist_mlp_supported(net->state_dim, net->n_actions, net->hidden, io->t_len, net->gate, net->head, net->n_atoms)) return false;
+  return net_ok(net) && replay_act_io_ok(io);
+}
+
 DRA_API int dra_dist_mlp_act(const dra_dist_mlp_net* net, const dra_dqn_mlp_act_io* io, void* stream) {
-  if (!net || !io || !net->param) return DRA_EINVAL;
-  if (dra_dist_mlp_supported(net->state_dim, net->n_actions, net->hidden, io->t_len, net->gate, net->head, net->n_atoms))
-    return DRA_EINVAL;
-  if (!net_ok(net) || !replay_act_io_ok(io)) return DRA_EINVAL;
+  if (!net || !io || !act_args_ok(net, io)) return DRA_EINVAL;
   return dispatch_hidden_gate_head(net->hidden, net->gate, net->head, [&](auto h, auto g, auto hd) {
     constexpr int H = decltype(h)::value, GATE = decltype(g)::value, HEAD = decltype(hd)::value;
     return launch_one_workgroup<&dist_mlp_act_kernel<H, GATE, HEAD>>(act_lds_floats(H, net->n_atoms) * sizeof(float), net, io, stream);
@@ -622,17 +653,60 @@ DRA_API int dra_dist_mlp_eval(const dra_dist_mlp_net* net, const dra_mlp_eval_io
   });
 }
 
-DRA_API int dra_dist_mlp_update(const dra_dist_mlp_net* net, const dra_dist_mlp_update_io* io, void* stream) {
-  if (!net || !io || !net->param || !net->target) return DRA_EINVAL;
+// what dra_dist_mlp_update asks of its two structs (dra_dist_mlp_update_lanes: of every lane's)
+static bool update_args_ok(const dra_dist_mlp_net* net, const dra_dist_mlp_update_io* io) {
+  if (!net->param || !net->target) return false;
   if (dra_dist_mlp_update_supported(net->state_dim, net->n_actions, net->hidden, io->batch, net->gate, net->head, net->n_atoms))
-    return DRA_EINVAL;
-  if (!net_ok(net) || io->capacity < 2 || io->capacity > 0x7fffffff) return DRA_EINVAL;
-  if (!io->ring_frames || !io->ring_actions || !io->ring_rewards || !io->ring_masks || !io->idx || !io->grad || !io->out_loss ||
-      !io->out_loss_vec || !io->out_q_next || !io->out_target || !io->err)
-    return DRA_EINVAL;
+    return false;
+  if (!net_ok(net) || io->capacity < 2 || io->capacity > 0x7fffffff) return false;
+  return io->ring_frames && io->ring_actions && io->ring_rewards && io->ring_masks && io->idx && io->grad && io->out_loss &&
+         io->out_loss_vec && io->out_q_next && io->out_target && io->err;
+}
+
+DRA_API int dra_dist_mlp_update(const dra_dist_mlp_net* net, const dra_dist_mlp_update_io* io, void* stream) {
+  if (!net || !io || !update_args_ok(net, io)) return DRA_EINVAL;
   return dispatch_hidden_gate_head(net->hidden, net->gate, net->head, [&](auto h, auto g, auto hd) {
     constexpr int H = decltype(h)::value, GATE = decltype(g)::value, HEAD = decltype(hd)::value;
     return launch_one_workgroup<&dist_mlp_update_kernel<H, GATE, HEAD>>(update_lds_floats(H, net->n_atoms) * sizeof(float), net, io,
                                                                        stream);
+  });
+}
+
+// ---------------------------------------------------------------------------------------------------- seed lanes
+// n_lanes independent categorical_dqn_feature / quantile_regression_dqn_feature agents of ONE shape as workgroups (0, lane) of the
+// same launches (seed_batch.py; the tables' memory: seed_lanes.h).  The lanes share the kernel instance (hidden, gate, head) and
+// the launch's dynamic LDS size, which follows from lane 0's n_atoms: n_atoms is part of the shape.  v_min / v_max are per-lane data.
+// The update's workgroup holds up to 160 KiB of LDS: one workgroup per CU, 64 lanes on 64 of the 256 CUs, nobody waits for anybody.
+static bool same_shape(const dra_dist_mlp_net* a, const dra_dist_mlp_net* b) {
+  return a->state_dim == b->state_dim && a->n_actions == b->n_actions && a->hidden == b->hidden && a->gate == b->gate &&
+         a->head == b->head && a->n_atoms == b->n_atoms;
+}
+
+DRA_API int dra_dist_mlp_lanes_supported(int state_dim, int n_actions, int hidden, int t_len, int batch, int gate, int head, int n_atoms,
+                                         int n_lanes) {
+  if (n_lanes < 1 || n_lanes > kMaxLanes) return DRA_EINVAL;
+  if (dra_dist_mlp_supported(state_dim, n_actions, hidden, t_len, gate, head, n_atoms)) return DRA_EINVAL;
+  return dra_dist_mlp_update_supported(state_dim, n_actions, hidden, batch, gate, head, n_atoms);
+}
+
+DRA_API int dra_dist_mlp_act_lanes(const dra_dist_mlp_net* nets, const dra_dqn_mlp_act_io* ios, int n_lanes, void* stream) {
+  if (!nets || !ios || n_lanes < 1 || n_lanes > kMaxLanes) return DRA_EINVAL;
+  for (int l = 0; l < n_lanes; ++l)
+    if (!act_args_ok(nets + l, ios + l) || !same_shape(nets, nets + l)) return DRA_EINVAL;
+  return dispatch_hidden_gate_head(nets->hidden, nets->gate, nets->head, [&](auto h, auto g, auto hd) {
+    constexpr int H = decltype(h)::value, GATE = decltype(g)::value, HEAD = decltype(hd)::value;
+    return launch_lanes<&dist_mlp_act_lanes_kernel<H, GATE, HEAD>>(act_lds_floats(H, nets->n_atoms) * sizeof(float), nets, ios, n_lanes,
+                                                                  stream);
+  });
+}
+
+DRA_API int dra_dist_mlp_update_lanes(const dra_dist_mlp_net* nets, const dra_dist_mlp_update_io* ios, int n_lanes, void* stream) {
+  if (!nets || !ios || n_lanes < 1 || n_lanes > kMaxLanes) return DRA_EINVAL;
+  for (int l = 0; l < n_lanes; ++l)
+    if (!update_args_ok(nets + l, ios + l) || !same_shape(nets, nets + l)) return DRA_EINVAL;
+  return dispatch_hidden_gate_head(nets->hidden, nets->gate, nets->head, [&](auto h, auto g, auto hd) {
+    constexpr int H = decltype(h)::value, GATE = decltype(g)::value, HEAD = decltype(hd)::value;
+    return launch_lanes<&dist_mlp_update_kernel<H, GATE, HEAD, true>>(update_lds_floats(H, nets->n_atoms) * sizeof(float), nets, ios,
+                                                                     n_lanes, stream);
   });
 }

@@ -35,6 +35,7 @@
 #include "mlp_update_block.h"
 #include "eval_act.h"
 #include "replay_act.h"
+#include "seed_lanes.h"
 #include <math.h>
 
 namespace {
@@ -166,11 +167,7 @@ __host__ __device__ constexpr size_t replay_update_lds_floats(int H) { return up
 // row of each (uniform addresses: scalar loads, as the single launch reads its kernel arguments), then runs the text below as it
 // is.  A flag on this kernel and not a shared __device__ body: hoisted, dqn_mlp_update_kernel<16, tanh> went 70 -> 78 VGPRs (71 ->
 // 80 over the window's io) -- mlp_rollout.h's banner; with LANES false the figures are the parent's
-// (profiles/dqn_lanes_kernel_resources.txt).
-template <bool LANES, typename T> using lane_arg = std::conditional_t<LANES, const T*, T>;
-template <typename T> __device__ __forceinline__ const T& lane_struct(const T& v) { return v; }
-template <typename T> __device__ __forceinline__ T lane_struct(const T* table) { return table[blockIdx.y]; }
-
+// (profiles/dqn_lanes_kernel_resources.txt).  lane_arg / lane_struct: seed_lanes.h.
 template <int H, int GATE, typename IO, bool LANES = false>
 __global__ void __launch_bounds__(256)
 dqn_mlp_update_kernel(lane_arg<LANES, dra_q_mlp_net> net_arg, lane_arg<LANES, IO> io_arg) {
@@ -523,19 +520,8 @@ DRA_API int dra_dqn_replay_mlp_update(const dra_q_mlp_net* net, const dra_dqn_re
 // n_lanes independent dqn_feature agents of ONE shape as workgroups (0, lane) of the same launches (seed_batch.py).  The tables are
 // read by the host (every lane is checked as the single entry checks its arguments, ahead of the launch) AND by the kernels, from
 // the same addresses: pinned host memory that the device maps (hipHostMalloc, torch's pin_memory()), where HIP keeps a single
-// launch's kernel arguments as well.
+// launch's kernel arguments as well.  kMaxLanes and launch_lanes: seed_lanes.h, shared with dist_mlp.hip.
 namespace {
-
-constexpr int kMaxLanes = 64;
-
-template <auto KERNEL, typename Net, typename Io>
-int launch_lanes(size_t bytes, const Net* nets, const Io* ios, int n_lanes, void* stream) {
-  static DraLdsAttr lds_attr;
-  if (int rc = dra_grant_lds(lds_attr, reinterpret_cast<const void*>(KERNEL), bytes)) return rc;
-  hipLaunchKernelGGL(KERNEL, dim3(1, (unsigned)n_lanes), dim3(256), bytes, dra_stream(stream), nets, ios);
-  DRA_LAUNCH_CHECK();
-  return DRA_OK;
-}
 
 bool same_shape(const dra_q_mlp_net* a, const dra_q_mlp_net* b) {
   return a->state_dim == b->state_dim && a->n_actions == b->n_actions && a->hidden == b->hidden && a->gate == b->gate;

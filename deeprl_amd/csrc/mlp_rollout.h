@@ -28,7 +28,10 @@
 //     begin() behind the staging's barrier there: 9 -> 23 (H 64 tanh qr).  The members' order, the order inside begin() and the
 //     softmax in place or shared moved nothing.
 //   dqn_mlp_act_kernel's whole body (dqn_mlp_act_body) under the single kernel and the seed lanes' dqn_mlp_act_lanes_kernel: all six
-//     single instances keep the parent's figures (profiles/dqn_lanes_kernel_resources.txt).
+//     single instances keep the parent's figures (profiles/dqn_lanes_kernel_resources.txt);
+//   dist_mlp_act_kernel's whole body (dist_mlp_act_body) under the single kernel and dist_mlp_act_lanes_kernel, and
+//     dist_mlp_update_kernel's LANES flag (dqn_mlp_update_kernel's form, tried first): all 36 instances of dist_mlp.hip keep the
+//     parent's figures (profiles/dist_lanes_kernel_resources.txt).  The lane plumbing of both files is seed_lanes.h.
 // NOT shared, each written in place in the four update kernels:
 //   dqn_mlp_update_kernel's whole body under a lane kernel of its own: hoisted, <16, tanh> went 70 -> 78 VGPRs (71 -> 80 over the
 //     window's io), the other ten equal.  The lane form is a template flag on the kernel itself (LANES; false: the parent's text,

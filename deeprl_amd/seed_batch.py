@@ -1,4 +1,6 @@
-"""Many seeds of dqn_feature as lanes of the same device launches (csrc/dqn_mlp.hip and csrc/optim.hip: seed lanes).
+"""Many seeds of a cart-pole replay entry as lanes of the same device launches (csrc/seed_lanes.h, csrc/dqn_mlp.hip,
+csrc/dist_mlp.hip and csrc/optim.hip: seed lanes): dqn_feature (DQNFeatureSeeds), categorical_dqn_feature
+(CategoricalDQNFeatureSeeds) and quantile_regression_dqn_feature (QuantileRegressionDQNFeatureSeeds).
 
 `DQNFeatureSeeds(make_config, seeds)` builds, per seed, an ordinary DQNAgent on the config.fused_dqn_feature path exactly as a user
 would -- random_seed(seed), torch.manual_seed(seed), make_config(seed) -- so lane k's network, target, optimiser state,
@@ -12,15 +14,22 @@ graphs.Regions as dqn_mlp.Step has them (acting alone; acting + update + step); 
 launch between replays; the episode rings of all lanes are one tensor and drain with one copy.  Nothing here has a CPU or
 eager-PyTorch form.
 
-What the lanes cannot be is named in a ValueError: an agent that stayed on the host path (dqn_mlp.why_not's reason: n_step > 1, a
-PrioritizedReplay, another network, ...), the module-path update, fused_eval, an optimiser other than RMSprop, lanes that differ
-in anything the launches share (first_mismatch), more than MAX_LANES seeds."""
+All of that but the head is FeatureSeeds, the base class: construction per seed, the RandomState hand-over, first_mismatch, the
+staged block, rings and error words, prepare, step, the regions, the optimiser and copy tables, drain, check and close.  A
+subclass names the agent class, the switch it sets, the module of its Step (dqn_mlp / dist_mlp: the Step type, why_not, the net,
+act-io and update-io structs), how the update io's outputs are filled, the three library entries and what its lane_signature
+holds beyond the common fields.  The two distributional classes run CategoricalDQNAgent / QuantileRegressionDQNAgent over
+dist_mlp.Step on dra_dist_mlp_act_lanes / dra_dist_mlp_update_lanes (DistFeatureSeeds).
+
+What the lanes cannot be is named in a ValueError: an agent that stayed on the host path (the module's why_not's reason: n_step >
+1, a PrioritizedReplay, another network, ...), the module-path update, fused_eval, an optimiser other than RMSprop, lanes that
+differ in anything the launches share (first_mismatch), more than MAX_LANES seeds."""
 import ctypes
 
 import numpy as np
 import torch
 
-from . import dqn_mlp
+from . import dist_mlp, dqn_mlp
 from ._lib import lib, stream_ptr
 from .graphs import Region
 from .support import Config, StagedUpload, plan_actor_epsilon_greedy, random_seed
@@ -63,16 +72,17 @@ def _schedule_signature(s):
     return (type(s).__name__,) + tuple(sorted((k, v) for k, v in vars(s).items() if not callable(v)))
 
 
-def lane_signature(agent):
-    """What the lanes' launches and the host's common decisions share, in the order first_mismatch names it."""
+def lane_signature(agent, shape=None, **extra):
+    """What the lanes' launches and the host's common decisions share, in the order first_mismatch names it.  `shape`: the
+    network's shape where it is not dqn_mlp.shape's; `extra`: a head's own fields, named behind the common ones."""
     cfg, rp, opt = agent.config, agent._inner_replay(), agent.optimizer
     g = opt.param_groups[0]
-    return dict(shape=tuple(dqn_mlp.shape(agent.network)), sgd_update_frequency=int(cfg.sgd_update_frequency),
+    return dict(shape=tuple(dqn_mlp.shape(agent.network) if shape is None else shape), sgd_update_frequency=int(cfg.sgd_update_frequency),
                 batch=int(rp.batch_size), memory_size=int(rp.memory_size), schedule=_schedule_signature(cfg.random_action_prob),
                 exploration_steps=cfg.exploration_steps, target_network_update_freq=cfg.target_network_update_freq,
                 gradient_clip=cfg.gradient_clip, discount=float(cfg.discount),
                 optimizer=(type(opt).__name__, g['lr'], g.get('alpha'), g.get('eps'), bool(g.get('centered', False))),
-                double_q=bool(cfg.double_q), graph_update=getattr(cfg, 'graph_update', True) is not False)
+                double_q=bool(cfg.double_q), graph_update=getattr(cfg, 'graph_update', True) is not False, **extra)
 
 
 def first_mismatch(signatures):
@@ -84,14 +94,15 @@ def first_mismatch(signatures):
     return None
 
 
-def lane_why_not(agent):
-    """None when `agent`, built with config.fused_dqn_feature on, can be a lane; else the first reason."""
-    cfg = agent.config
+def lane_why_not(agent, module=dqn_mlp):
+    """None when `agent`, built with the switch of `module`'s kind on (dqn_mlp: config.fused_dqn_feature; dist_mlp:
+    config.fused_dist_feature), can be a lane; else the first reason."""
+    cfg, kind = agent.config, module.Kind
     step = getattr(agent, '_feature', None)
-    if type(step) is not dqn_mlp.Step:
-        return dqn_mlp.why_not(agent) or "the agent runs on %s, not on the fused_dqn_feature path" % type(step).__name__
-    if not dqn_mlp.Kind.fused_update(cfg, step.shape):
-        return "config.fused_dqn_update is off: the module-path update has no lane form"
+    if type(step) is not module.Step:
+        return module.why_not(agent) or "the agent runs on %s, not on the %s path" % (type(step).__name__, kind.SWITCH)
+    if not kind.fused_update(cfg, step.shape):
+        return "config.%s is off: the module-path update has no lane form" % kind.UPDATE_SWITCH
     if getattr(cfg, dqn_mlp.EVAL_SWITCH, False) is True:
         return "config.fused_eval is on: the evaluation launch has no lane form"
     if agent._fused.kind != 'rmsprop':
@@ -99,34 +110,58 @@ def lane_why_not(agent):
     return None
 
 
-class DQNFeatureSeeds:
-    """See the module's docstring.  `make_config(seed)` -> a Config for DQNAgent (dqn_feature's); config.fused_dqn_feature is set
-    here.  Surface: step(), total_steps (of every lane: they advance together), episodes(k), drain_episodes(), lane(k) -- the
-    underlying agent, whose network, _target_flat, replay ring and save() see the lane's live buffers --, rng_tail(k) -- the
-    lane's RandomState --, close()."""
-    WARMUP = dqn_mlp.Step.WARMUP
+class FeatureSeeds:
+    """What the seed lanes of every head share: see the module's docstring.  `make_config(seed)` -> a Config for the subclass's
+    agent class; its switch is set here.  Surface: step(), total_steps (of every lane: they advance together), episodes(k),
+    drain_episodes(), lane(k) -- the underlying agent, whose network, _target_flat, replay ring and save() see the lane's live
+    buffers --, rng_tail(k) -- the lane's RandomState --, close().
 
+    A subclass supplies ENTRY (the name in region labels and errors), MODULE (dqn_mlp or dist_mlp: Step, why_not, Kind, Net, ActIO,
+    UpdateIO), the three library entries ACT_LANES / UPDATE_LANES / LANES_SUPPORTED, agent_class(), switch_on(config),
+    signature(agent) and update_outputs(io, step)."""
+    WARMUP = dqn_mlp.Step.WARMUP
+    ENTRY = MODULE = ACT_LANES = UPDATE_LANES = LANES_SUPPORTED = None
+
+    # -- what a subclass supplies ------------------------------------------------------------------------------------------
+    def agent_class(self):
+        raise NotImplementedError
+
+    def switch_on(self, cfg):
+        """Sets the switches of the device path on a lane's Config, ahead of the agent's construction."""
+        setattr(cfg, self.MODULE.Kind.SWITCH, True)
+
+    def why_not(self, agent):
+        return lane_why_not(agent, self.MODULE)
+
+    def signature(self, agent):
+        return lane_signature(agent)
+
+    def update_outputs(self, io, st):
+        """The update io's output pointers from lane Step `st`, as the Step's own update() sets them."""
+        raise NotImplementedError
+
+    # -- construction ------------------------------------------------------------------------------------------------------
     def __init__(self, make_config, seeds):
-        from .agents import DQNAgent
         seeds = [int(s) for s in seeds]
         if not 1 <= len(seeds) <= MAX_LANES:
-            raise ValueError("DQNFeatureSeeds runs 1 to %d seeds as lanes, not %d" % (MAX_LANES, len(seeds)))
+            raise ValueError("%s runs 1 to %d seeds as lanes, not %d" % (type(self).__name__, MAX_LANES, len(seeds)))
+        agent_cls = self.agent_class()
         self.seeds, self.agents, self.rngs = seeds, [], []
         try:
             for seed in seeds:
                 random_seed(seed)
                 torch.manual_seed(seed)
                 cfg = make_config(seed)
-                cfg.fused_dqn_feature = True
-                agent = DQNAgent(cfg)
+                self.switch_on(cfg)
+                agent = agent_cls(cfg)
                 self.agents.append(agent)
-                why = lane_why_not(agent)
+                why = self.why_not(agent)
                 if why is not None:
                     raise ValueError("seed %d cannot run as a lane: %s" % (seed, why))
                 rs = np.random.RandomState()
                 rs.set_state(np.random.get_state())      # where the single run's draws would start
                 self.rngs.append(rs)
-            why = first_mismatch([lane_signature(a) for a in self.agents])
+            why = first_mismatch([self.signature(a) for a in self.agents])
             if why is not None:
                 raise ValueError("the lanes do not share one configuration: %s" % why)
             self._wire()
@@ -135,14 +170,14 @@ class DQNFeatureSeeds:
                 a.close()
             raise
 
-    # -- construction: the lanes' buffers that become one, the tables ------------------------------------------------------
+    # -- the lanes' buffers that become one, the tables ----------------------------------------------------------------------
     def _wire(self):
-        dev, n = Config.DEVICE, len(self.agents)
+        dev, n, m = Config.DEVICE, len(self.agents), self.MODULE
         steps = self.steps_ = [a._feature for a in self.agents]
         s0, cfg = steps[0], self.agents[0].config
         self.k, self.batch, self.cfg = s0.k, s0.batch, cfg
-        if lib.dra_dqn_mlp_lanes_supported.raw(*s0.shape[:3], self.k, self.batch, s0.shape[3], n):
-            raise ValueError("dra_dqn_mlp_*_lanes are not built for %d lanes of shape %r" % (n, (s0.shape, self.k, self.batch)))
+        if getattr(lib, self.LANES_SUPPORTED).raw(*s0.shape[:3], self.k, self.batch, *s0.shape[3:m.Kind.N_SUPPORTED], n):
+            raise ValueError("%s are not built for %d lanes of shape %r" % (self.ACT_LANES.replace("_act_", "_*_"), n, (s0.shape, self.k, self.batch)))
         # ONE staged block of [n] per-lane blocks; every lane's Step sees its block through the views it had of its own
         lay = self.layout = lane_layout(self.k, self.batch)
         self._up = StagedUpload(n * lay['stride'], torch.uint8, dev)
@@ -165,13 +200,13 @@ class DQNFeatureSeeds:
             v.ep_ring = v._ring_buf[:cap3 - 1].view(v.ring_cap, 3)
             v.ep_count = v._ring_buf[cap3 - 1:].view(torch.int64)
             v.drain = lambda k=k: self._lane_rows(k)
-        self.nets, self.act_ios = LaneTable(dqn_mlp.Net, n), LaneTable(dqn_mlp.ActIO, n)
-        self.update_ios, self.opt_lanes, self.copy_lanes = LaneTable(dqn_mlp.UpdateIO, n), LaneTable(OptimLane, n), LaneTable(CopyLane, n)
+        self.nets, self.act_ios = LaneTable(m.Net, n), LaneTable(m.ActIO, n)
+        self.update_ios, self.opt_lanes, self.copy_lanes = LaneTable(m.UpdateIO, n), LaneTable(OptimLane, n), LaneTable(CopyLane, n)
         for k, (a, st) in enumerate(zip(self.agents, steps)):
             self.nets.rows[k] = st.net_struct()
             self.act_ios.rows[k] = st.act_io()
-            io = dqn_mlp.UpdateIO()
-            io.out_q_target, io.out_td, io.out_loss = st.q_target.data_ptr(), st.td.data_ptr(), st.loss.data_ptr()
+            io = m.UpdateIO()
+            self.update_outputs(io, st)
             io.ring_frames, io.ring_actions, io.ring_rewards, io.ring_masks = st.ring.pointers()
             io.idx, io.grad, io.err, io.capacity = st.idx.data_ptr(), a._fused.flat.grad.data_ptr(), st.err.data_ptr(), st.capacity
             io.discount, io.batch, io.double_q = float(a.config.discount), self.batch, int(bool(a.config.double_q))
@@ -183,19 +218,19 @@ class DQNFeatureSeeds:
             c = CopyLane()
             c.dst, c.src, c.n = a._target_flat.flat.data_ptr(), f.flat.flat.data_ptr(), f.flat.numel
             self.copy_lanes.rows[k] = c
-        self.regions = dict(act=Region("the dqn_feature lanes' acting launch", cfg, self.WARMUP),
-                            learn=Region("the dqn_feature lanes' agent step", cfg, self.WARMUP))
+        self.regions = dict(act=Region("the %s lanes' acting launch" % self.ENTRY, cfg, self.WARMUP),
+                            learn=Region("the %s lanes' agent step" % self.ENTRY, cfg, self.WARMUP))
         self.launches = self.agent_steps = 0
 
     # -- the launches --------------------------------------------------------------------------------------------------------
     def _act(self):
-        lib.dra_dqn_mlp_act_lanes(self.nets.ptr, self.act_ios.ptr, len(self.agents), stream_ptr())
+        getattr(lib, self.ACT_LANES)(self.nets.ptr, self.act_ios.ptr, len(self.agents), stream_ptr())
         self.launches += 1
 
     def _learn(self):
         n, h = len(self.agents), self.agents[0]._fused.hyper
         self._act()
-        lib.dra_dqn_mlp_update_lanes(self.nets.ptr, self.update_ios.ptr, n, stream_ptr())
+        getattr(lib, self.UPDATE_LANES)(self.nets.ptr, self.update_ios.ptr, n, stream_ptr())
         lib.dra_clip_rmsprop_step_lanes(self.opt_lanes.ptr, n, float(self.cfg.gradient_clip or 0.0), float(h['lr']), float(h['alpha']),
                                         float(h['eps']), int(bool(h['centered'])), stream_ptr())
 
@@ -279,8 +314,8 @@ class DQNFeatureSeeds:
         """dqn_mlp.Step.check of every lane with one copy."""
         bad = self.err.cpu().numpy()
         if bad.any():
-            raise dqn_mlp.DraError("dqn_feature lanes %r: staged ring slots / indices were outside the ring and have been clamped (%r)"
-                                   % ([self.seeds[i] for i in np.nonzero(bad)[0]], bad[bad != 0].tolist()))
+            raise dqn_mlp.DraError("%s lanes %r: staged ring slots / indices were outside the ring and have been clamped (%r)"
+                                   % (self.ENTRY, [self.seeds[i] for i in np.nonzero(bad)[0]], bad[bad != 0].tolist()))
 
     def drain_episodes(self):
         """One device-to-host copy for all lanes -> per lane the (step, return) pairs of the episodes that ended since the last
@@ -310,3 +345,70 @@ class DQNFeatureSeeds:
             for a in self.agents:
                 a.close()
             self.agents = []
+
+
+class DQNFeatureSeeds(FeatureSeeds):
+    """Seeds of dqn_feature: DQNAgent over dqn_mlp.Step with config.fused_dqn_feature set here, on dra_dqn_mlp_act_lanes and
+    dra_dqn_mlp_update_lanes.  `make_config(seed)` -> a Config for DQNAgent (dqn_feature's).  The surface is FeatureSeeds'."""
+    ENTRY, MODULE = 'dqn_feature', dqn_mlp
+    ACT_LANES, UPDATE_LANES, LANES_SUPPORTED = 'dra_dqn_mlp_act_lanes', 'dra_dqn_mlp_update_lanes', 'dra_dqn_mlp_lanes_supported'
+
+    def agent_class(self):
+        from .agents import DQNAgent
+        return DQNAgent
+
+    def update_outputs(self, io, st):
+        io.out_q_target, io.out_td, io.out_loss = st.q_target.data_ptr(), st.td.data_ptr(), st.loss.data_ptr()
+
+
+def dist_lane_signature(agent):
+    """lane_signature with what the distributional launches share on top: the head kind, the atoms per action (the launches' LDS
+    size follows from lane 0's) and the categorical support (per-lane data to the kernels, but one configuration is what a sweep
+    over seeds means)."""
+    shp = dist_mlp.shape(agent.network)
+    return lane_signature(agent, shape=shp[:4], head=shp[4], n_atoms=shp[5], support=dist_mlp.support(agent.config, shp[4]))
+
+
+class DistFeatureSeeds(FeatureSeeds):
+    """Seeds of categorical_dqn_feature / quantile_regression_dqn_feature (the two subclasses below name the agent class):
+    CategoricalDQNAgent / QuantileRegressionDQNAgent over dist_mlp.Step on dra_dist_mlp_act_lanes and dra_dist_mlp_update_lanes.
+    config.fused_dist_feature is set here, and config.fused_dist_update is set to True where it is unset: the module-path update
+    has no lane form, so the lanes always run the update kernel.  For quantiles that is the single run's default; for the
+    categorical head the unset default of a SINGLE run is the module update (dist_mlp.Kind.fused_update), so a
+    categorical lane is -- to the bit -- the single run with config.fused_dist_update = True, and equals the default single run only
+    within that form's float32 error.  An explicit config.fused_dist_update = False is refused, as fused_eval, an optimiser other
+    than RMSprop and lanes that differ in head, atoms per action or categorical support are."""
+    MODULE = dist_mlp
+    ACT_LANES, UPDATE_LANES, LANES_SUPPORTED = 'dra_dist_mlp_act_lanes', 'dra_dist_mlp_update_lanes', 'dra_dist_mlp_lanes_supported'
+    AGENT = None
+
+    def agent_class(self):
+        from . import agents
+        return getattr(agents, self.AGENT)
+
+    def switch_on(self, cfg):
+        kind = dist_mlp.Kind
+        setattr(cfg, kind.SWITCH, True)
+        if getattr(cfg, kind.UPDATE_SWITCH, None) is None:
+            setattr(cfg, kind.UPDATE_SWITCH, True)
+
+    def signature(self, agent):
+        return dist_lane_signature(agent)
+
+    def update_outputs(self, io, st):
+        io.out_loss, io.out_loss_vec = st.loss.data_ptr(), st.loss_vec.data_ptr()
+        io.out_q_next, io.out_target = st.q_next.data_ptr(), st.target.data_ptr()
+
+
+class CategoricalDQNFeatureSeeds(DistFeatureSeeds):
+    """DistFeatureSeeds over CategoricalDQNAgent (categorical_dqn_feature)."""
+    ENTRY, AGENT = 'categorical_dqn_feature', 'CategoricalDQNAgent'
+
+
+class QuantileRegressionDQNFeatureSeeds(DistFeatureSeeds):
+    """DistFeatureSeeds over QuantileRegressionDQNAgent (quantile_regression_dqn_feature)."""
+    ENTRY, AGENT = 'quantile_regression_dqn_feature', 'QuantileRegressionDQNAgent'
+
+
+# zoo.run_seeds: the entries with a lane form
+SEED_CLASSES = {c.ENTRY: c for c in (DQNFeatureSeeds, CategoricalDQNFeatureSeeds, QuantileRegressionDQNFeatureSeeds)}

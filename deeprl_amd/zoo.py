@@ -293,22 +293,27 @@ def run(name, **kwargs):
 
 def run_seeds(name, seeds, **kwargs):
     """`name` once per seed, the seeds as lanes of the same device launches (deeprl_amd/seed_batch.py): per seed, random_seed(seed),
-    torch.manual_seed(seed) and config(name, fused_dqn_feature=True, **kwargs) over Task(game, seed=seed), stepped until
+    torch.manual_seed(seed) and config(name, <the entry's switch>=True, **kwargs) over Task(game, seed=seed), stepped until
     config.max_steps environment steps of EVERY lane -> per seed the list of (step, episodic_return) pairs of its training
     episodes, each what the single run of that seed gives.  There is no evaluation on this path: eval_interval is forced to 0.
-    Only dqn_feature has a lane form, with n_step 1 and a UniformReplay: anything else raises a ValueError that names the
-    reason."""
-    from deeprl_amd.seed_batch import DQNFeatureSeeds
-    if name != "dqn_feature":
-        raise ValueError("run_seeds: only dqn_feature runs its seeds as lanes, %s has no lane form" % name)
+    Three entries have a lane form (seed_batch.SEED_CLASSES): dqn_feature (fused_dqn_feature; n_step 1 and a UniformReplay),
+    categorical_dqn_feature and quantile_regression_dqn_feature (fused_dist_feature, and fused_dist_update=True unless kwargs set
+    it: the lanes always run the update kernel, so a categorical lane is the single run with fused_dist_update=True, not the
+    single run's unset default, which is the module update).  Anything else raises a ValueError that names the reason."""
+    from deeprl_amd.seed_batch import SEED_CLASSES
+    if name not in SEED_CLASSES:
+        raise ValueError("run_seeds: besides categorical_dqn_feature and quantile_regression_dqn_feature only dqn_feature runs its "
+                         "seeds as lanes, %s has no lane form" % name)
+    cls = SEED_CLASSES[name]
+    switch = {cls.MODULE.Kind.SWITCH: True}
 
     def make_config(seed):
-        c = config(name, fused_dqn_feature=True, **dict(kwargs))
+        c = config(name, **dict(switch, **kwargs))
         c.task_fn = lambda: Task(c.game, seed=seed)
         c.eval_interval = 0
         return c
 
-    batch = DQNFeatureSeeds(make_config, seeds)
+    batch = cls(make_config, seeds)
     try:
         out = [[] for _ in batch.seeds]
         max_steps = batch.lane(0).config.max_steps

@@ -1437,6 +1437,15 @@ int dra_dist_mlp_supported(int state_dim, int n_actions, int hidden, int t_len, 
 int dra_dist_mlp_update_supported(int state_dim, int n_actions, int hidden, int batch, int gate, int head, int n_atoms);   /* 0 = yes */
 int dra_dist_mlp_act(const dra_dist_mlp_net* net, const dra_dqn_mlp_act_io* io, void* stream);
 int dra_dist_mlp_update(const dra_dist_mlp_net* net, const dra_dist_mlp_update_io* io, void* stream);
+/* The two launches over n_lanes independent agents of ONE network shape (seed lanes, above: the tables' memory, 1 <= n_lanes <= 64):
+ * workgroup (0, lane) runs dra_dist_mlp_act / dra_dist_mlp_update on nets[lane] and ios[lane], to the bit.  v_min / v_max are each
+ * lane's own.  DRA_EINVAL, and nothing is launched, for a null table, an n_lanes outside the range, a lane the single entry
+ * refuses, or a lane whose state_dim / n_actions / hidden / gate / head / n_atoms are not lane 0's (the launch's LDS size follows
+ * from lane 0's n_atoms). */
+int dra_dist_mlp_lanes_supported(int state_dim, int n_actions, int hidden, int t_len, int batch, int gate, int head, int n_atoms,
+                                 int n_lanes);   /* 0 = yes */
+int dra_dist_mlp_act_lanes(const dra_dist_mlp_net* nets, const dra_dqn_mlp_act_io* ios, int n_lanes, void* stream);
+int dra_dist_mlp_update_lanes(const dra_dist_mlp_net* nets, const dra_dist_mlp_update_io* ios, int n_lanes, void* stream);
 
 /* ---- rainbow_mlp: rainbow_feature (examples.py:231-280: CategoricalDQNAgent, RainbowNet over FCBody(noisy_linear=True), n-step
  * PrioritizedReplay, double_q) over ONE device-resident cart-pole environment and the HBM replay ring: dist_mlp's two launches

@@ -51,6 +51,9 @@ Seed lanes (deeprl_amd/seed_batch.py), named explicitly with --cases too (SEED_C
   dqn_feature_seeds1 / 4 / 16 / 64  the dqn_feature case's configuration once per seed, the seeds as lanes of the same launches;
             env_steps_per_s is the aggregate over the lanes, prepare_us_per_lane_step the host's draws and staging per lane and agent
             step (time.perf_counter around DQNFeatureSeeds.prepare)
+  categorical_dqn_feature_seeds1 / 4 / 16, quantile_regression_dqn_feature_seeds1 / 4 / 16  the same over the two distributional cases
+            (the lanes always run the update kernel: their single baselines are categorical_dqn_feature -- and its faster single form,
+            categorical_dqn_feature_module_update -- and quantile_regression_dqn_feature)
 """
 import argparse
 import json
@@ -260,9 +263,25 @@ def dqn_feature_config(task_seed=1, **switches):
 
 
 def dist_feature(head, **switches):
+    cls = d.CategoricalDQNAgent if head == "categorical" else d.QuantileRegressionDQNAgent
+    # (warm: past exploration_steps -- 25 agent steps -- and the graph captures, so that the timed window is all updates)
+    return cls(dist_feature_config(head, **switches)), dict(env_per_step=4, updates_per_step=1, warm=120)
+
+
+def dist_feature_seeds(head, n):
+    """categorical_dqn_feature_seedsN / quantile_regression_dqn_feature_seedsN: N seeds of the dist_feature case as lanes of the same
+    launches (deeprl_amd/seed_batch.py: the batch sets fused_dist_feature and fused_dist_update), the environments seeded 1 .. N;
+    env_steps_per_s is the AGGREGATE over the lanes."""
+    from deeprl_amd import seed_batch
+    cls = seed_batch.CategoricalDQNFeatureSeeds if head == "categorical" else seed_batch.QuantileRegressionDQNFeatureSeeds
+    batch = cls(lambda seed: dist_feature_config(head, task_seed=seed), range(1, n + 1))
+    return batch, dict(env_per_step=4 * n, updates_per_step=n, warm=120, lanes=n)
+
+
+def dist_feature_config(head, task_seed=1, **switches):
     c = d.Config()
     c.merge(dict(game="classic-CartPole-v0", log_level=0, tag="bench", **switches))
-    c.task_fn = lambda: d.Task(c.game, seed=1)
+    c.task_fn = lambda: d.Task(c.game, seed=task_seed)
     c.eval_env = d.Task(c.game, seed=2)
     c.optimizer_fn = lambda p: torch.optim.RMSprop(p, 0.001)
     if head == "categorical":
@@ -277,9 +296,7 @@ def dist_feature(head, **switches):
     c.random_action_prob = d.LinearSchedule(1.0, 0.1, 1e4)
     c.target_network_update_freq, c.exploration_steps = 200, 100
     c.sgd_update_frequency, c.gradient_clip = 4, 5
-    cls = d.CategoricalDQNAgent if head == "categorical" else d.QuantileRegressionDQNAgent
-    # (warm: past exploration_steps -- 25 agent steps -- and the graph captures, so that the timed window is all updates)
-    return cls(c), dict(env_per_step=4, updates_per_step=1, warm=120)
+    return c
 
 
 def rainbow_feature(**switches):
@@ -441,8 +458,10 @@ CASES = {
 }
 
 
-# dqn_feature's seeds as lanes of one launch: run only when named in --cases (the default set is CASES)
-SEED_CASES = {"dqn_feature_seeds%d" % n: n for n in (1, 4, 16, 64)}
+# an entry's seeds as lanes of one launch: run only when named in --cases (the default set is CASES)
+SEED_CASES = {"dqn_feature_seeds%d" % n: (lambda n=n: dqn_feature_seeds(n)) for n in (1, 4, 16, 64)}
+SEED_CASES.update({"categorical_dqn_feature_seeds%d" % n: (lambda n=n: dist_feature_seeds("categorical", n)) for n in (1, 4, 16)})
+SEED_CASES.update({"quantile_regression_dqn_feature_seeds%d" % n: (lambda n=n: dist_feature_seeds("quantile", n)) for n in (1, 4, 16)})
 
 
 # the continuous entries evaluate on the pendulum, on their device path, the zoo's 20 episodes (of 200 steps) a time
@@ -577,7 +596,7 @@ def run_cases(a, tag):
             if name in EVAL_CASES:
                 EVAL_CASES[name](name, tag)
                 continue
-            agent, meta = dqn_feature_seeds(SEED_CASES[name]) if name in SEED_CASES else CASES[name]()
+            agent, meta = SEED_CASES[name]() if name in SEED_CASES else CASES[name]()
             warm = 120 if "dqn" in name or "c51" in name or "rainbow" in name else 4      # DQN family: past exploration_steps; on-policy: past graph capture
             warm = meta.get("warm", warm)                                                 # (replay actor-critics: past warm_up)
             for _ in range(warm):
