@@ -302,6 +302,14 @@ struct ChainHook {
 };
 
 // ------------------------------------------------------------------------------------------------
+// A given action outside [0, A) behaves as the nearest valid one: the forward takes log_pi_a there, and the backward kernels
+// (categorical_bwd_kernel, policy_heads_bwd_kernel) differentiate THAT value -- one statement for all three.
+__device__ __forceinline__ int64_t categorical_clamp_action(int64_t action, int A) {
+  if (action < 0) return 0;
+  if (action >= A) return A - 1;
+  return action;
+}
+
 // Categorical(logits = x[0..A)) of one sample (network_heads.py:249-254): log-softmax, entropy, and -- when no action is given --
 // the inverse-CDF draw from one uniform (first a with cumsum(p)[a] > u; the last action absorbs rounding).  ONE statement shared
 // by categorical_fwd_kernel (losses.hip) and the fused rollout head (igemm.hip: policy_heads_sample_kernel), so that both give
@@ -322,14 +330,14 @@ __device__ __forceinline__ void categorical_row(const float* x, int A, bool give
     cum += p;
     if (!found && cum > ub) { act = a; found = true; }
   }
-  if (act < 0) act = 0;
-  if (act >= A) act = A - 1;
+  act = categorical_clamp_action(act, A);
   *act_out = act;
   *log_pi_a = x[act] - lse;
   *entropy = ent;
 }
 
-// Backward of the same: dlogits[a] = g_lp (1[a == action] - p[a]) - g_ent p[a] (logp[a] + entropy).  categorical_row_stats gives
+// Backward of the same: dlogits[a] = g_lp (1[a == action] - p[a]) - g_ent p[a] (logp[a] + entropy), action clamped as the
+// forward clamps it (categorical_clamp_action, by the caller).  categorical_row_stats gives
 // the row's log-sum-exp and entropy (the sums in ascending a, as the forward forms them); categorical_dlogit one component.
 // Shared by categorical_bwd_kernel (losses.hip) and the fused head backward (igemm.hip: policy_heads_bwd_kernel).
 __device__ __forceinline__ void categorical_row_stats(const float* x, int A, float* lse_out, float* ent_out) {

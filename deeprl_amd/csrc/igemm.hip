@@ -381,7 +381,7 @@ policy_heads_bwd_kernel(const float* __restrict__ logits, const int64_t* __restr
       const float* xr = logits + (int64_t)b * A;
       float lse, ent;
       categorical_row_stats(xr, A, &lse, &ent);
-      s_g[t] = categorical_dlogit(xr[t], lse, ent, (int64_t)t == action[b], g_lp ? g_lp[b] : 0.f, g_ent ? g_ent[b] : 0.f);
+      s_g[t] = categorical_dlogit(xr[t], lse, ent, (int64_t)t == categorical_clamp_action(action[b], A), g_lp ? g_lp[b] : 0.f, g_ent ? g_ent[b] : 0.f);
     }
     __syncthreads();
     float a0 = 0.f, a1 = 0.f;
@@ -410,7 +410,7 @@ policy_heads_bwd_kernel(const float* __restrict__ logits, const int64_t* __restr
       const float* xr = logits + (int64_t)b * A;
       float lse, ent;
       categorical_row_stats(xr, A, &lse, &ent);
-      g = categorical_dlogit(xr[o], lse, ent, (int64_t)o == action[b], g_lp ? g_lp[b] : 0.f, g_ent ? g_ent[b] : 0.f);
+      g = categorical_dlogit(xr[o], lse, ent, (int64_t)o == categorical_clamp_action(action[b], A), g_lp ? g_lp[b] : 0.f, g_ent ? g_ent[b] : 0.f);
     } else {
       g = g_v ? g_v[b] : 0.f;
     }

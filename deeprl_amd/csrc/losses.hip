@@ -498,7 +498,7 @@ categorical_bwd_kernel(const float* __restrict__ logits, int B, int A, const int
   float lse, ent;
   categorical_row_stats(x, A, &lse, &ent);
   const float gl = g_lp ? g_lp[b] : 0.f, ge = g_ent ? g_ent[b] : 0.f;
-  const int64_t act = action[b];
+  const int64_t act = categorical_clamp_action(action[b], A);
   for (int a = 0; a < A; ++a) dlogits[(int64_t)b * A + a] = categorical_dlogit(x[a], lse, ent, a == act, gl, ge);
 }
 

@@ -173,6 +173,9 @@ int dra_weighted_mean(const float* x, const float* w, int n, float* out, void* s
  * action_in NULL: actions are sampled by inverse CDF from uniform[batch] into action_out.  n_actions <= 64. */
 int dra_categorical_fwd(const float* logits, int batch, int n_actions, const int64_t* action_in, const float* uniform,
                         int64_t* action_out, float* log_pi_a, float* entropy, void* stream);
+/* out_dlogits [batch, n_actions] = d(g_log_pi_a . log_pi_a + g_entropy . entropy) / d logits for the given actions (g_* may be
+ * NULL = zero).  An action outside [0, n_actions) behaves as the nearest valid one, in dra_categorical_fwd and here alike: the
+ * gradient is the derivative of the value the forward returned. */
 int dra_categorical_bwd(const float* logits, int batch, int n_actions, const int64_t* action, const float* g_log_pi_a,
                         const float* g_entropy, float* out_dlogits, void* stream);
 /* rank-invariant Categorical(logits).sample() for the data-parallel on-policy agents: action[i] = argmax_a
@@ -251,7 +254,9 @@ int dra_policy_heads_sample_fold28(const float* slabs, const float* fold_bias, c
                                    float* out_log_pi_a, float* out_entropy, float* out_v, void* stream);
 /* its backward in one launch (dra_categorical_bwd + dra_linear_bwd_pair [+ dra_act_bwd], same sums in the same order): from the
  * gradients of log_pi_a / entropy / v [batch] (any may be NULL = zero) -> dx [batch, in_features] (optional; relu_mask != 0:
- * times [x > 0], x being a fused-ReLU output), dW0 [n_actions, in_features], db0, dW1 [1, in_features], db1; batch <= 8192 */
+ * times [x > 0], x being a fused-ReLU output), dW0 [n_actions, in_features], db0, dW1 [1, in_features], db1; batch <= 8192.
+ * An action outside [0, n_actions) behaves as the nearest valid one, as in dra_policy_heads_given: the gradients are those of
+ * the log_pi_a the forward returned. */
 int dra_policy_heads_bwd(const float* logits, const int64_t* action, const float* g_log_pi_a, const float* g_entropy,
                          const float* g_v, const float* x, const float* w0, const float* w1, float* dx, float* dw0, float* db0,
                          float* dw1, float* db1, int batch, int in_features, int n_actions, int relu_mask, void* stream);
