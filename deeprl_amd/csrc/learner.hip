@@ -22,11 +22,11 @@
 #include "oneshot_lin.h"     // (LinDgradOne / LinWgradOne / HeadWgradRole: DRA_VAR_HEAD_CHAIN launches them next to the head role)
 #include "actor_env.h"
 #include "per_chain2.h"
+#include "cached_graph.h"    // (CachedGraph / timed_replay / HostTimeScope: how every graph here is captured, kept and timed)
 #include <new>
 #include <stddef.h>
 #include <stdlib.h>
 #include <string.h>
-#include <chrono>
 
 enum { K_GATHER, K_CONV1_F, K_CONV2_F, K_CONV3_F, K_FC4_F, K_HEAD, K_HEAD_BW, K_FC4_BW, K_FC4_BX, K_CONV3_BW, K_CONV3_BX,
        K_CONV2_BW, K_CONV2_BX, K_CONV1_BW, K_NORM, K_STEP, K_COUNT };
@@ -83,24 +83,20 @@ struct dra_dqn_learner {
   int stage_k;
   hipEvent_t stage_ev[8];
   bool stage_used[8];
-  hipGraphExec_t g_update;
-  bool g_update_ready;
-  hipGraphExec_t g_update_per;      // the same chain with PER importance weights (beta from sampling_prob[B])
-  bool g_update_per_ready;
+  CachedGraph g_update;
+  CachedGraph g_update_per;         // the same chain with PER importance weights (beta from sampling_prob[B])
   // pipelined async mode (DRA_VAR_PIPE_GATHER): per step parity, body + optimizer in one graph
-  hipGraphExec_t g_pipe[4];         // (indexed by parity in the two-copy pipelines, by step mod 4 in step_pipelined3)
-  bool g_pipe_ready[4];
-  hipGraphExec_t g_pipe_per[4];     // ... with PER importance weights (exponent from sampling_prob[B]): forward + loss ...
-  bool g_pipe_per_ready[4];
-  hipGraphExec_t g_pipe_per_b[4];   // ... and backward + optimizer, with ev_loss recorded in between
+  CachedGraph g_pipe[4];            // (indexed by parity in the two-copy pipelines, by step mod 4 in step_pipelined3)
+  CachedGraph g_pipe_per[4];        // ... with PER importance weights (exponent from sampling_prob[B]): forward + loss ...
+  CachedGraph g_pipe_per_b[4];      // ... and backward + optimizer, with ev_loss recorded in between (empty with the one-graph
+                                    // prioritized update; g_pipe_per[q].ready then speaks for the pair)
   hipEvent_t ev_loss;               // PER pipeline: the update's TD errors / new priorities exist
   hipEvent_t ev_mb_ready[2], ev_mb_free[2];   // gather of buffer b finished / update body done with buffer b
   bool mb_used[2];
   int64_t step_no;                  // async steps with an update issued so far
   // DRA_VAR_GATHER_IN_GRAPH: actor transitions + the gather of the SAME step as one graph per step parity
-  hipGraphExec_t g_ag[2];
-  bool g_ag_ready[2];
-  int g_ag_nenv[2];
+  CachedGraph g_ag[2];
+  int g_ag_nenv[2];                 // (the n_env each was captured for: another one recaptures)
   bool ag_have_prev;                // a gathered minibatch is waiting for its update
   int ag_prev_par;
   // optional timeline of the pipelined async step (measurement aid): per traced step 5 timing events --
@@ -111,7 +107,7 @@ struct dra_dqn_learner {
   int64_t host_calls;
   // actor graphs are keyed by (n_env, parameter block they read): online params in in-order mode, one of the
   // two actor copies in async mode (DRA_VAR_ACTOR_PARAMS)
-  struct { hipGraphExec_t exec; const float* params; int n_env; bool ready; } g_actor[5];
+  struct { CachedGraph g; const float* params; int n_env; } g_actor[5];
   float* pa[4];                     // parameter copies the async actor reads: two in the pipelines whose update waits for
                                     // the previous actor graph every step, four (rotating) in step_pipelined3, which does not
   hipEvent_t pa_reader[4];          // step_pipelined3: recorded after the last actor launch that reads copy i
@@ -123,8 +119,7 @@ struct dra_dqn_learner {
   float* q_stage;                   // pinned, device-mapped, coherent [64 q values | sequence word]: written by head_q_kernel itself
   unsigned* q_seq_dev;              // device: forwards completed (head_q_kernel publishes it behind the q values)
   unsigned q_seq_host;              // host: forwards issued
-  hipGraphExec_t g_q;
-  bool g_q_ready;
+  CachedGraph g_q;
   // actor v3: parameter blocks are read by the graph's first kernel straight from a pinned ring (no copy
   // command in front of the graph); the device counter selects the ring entry, in lockstep with aprm_seq
   uint8_t* aprm_ring;               // pinned, kAprmSlots x kAprmStride bytes
@@ -143,9 +138,8 @@ struct dra_dqn_learner {
   int32_t* pend_mask;
   uint64_t aring_pushed, aring_issued;
   bool aring_primed;
-  hipGraphExec_t g_aring[4];
-  bool g_aring_ready[4];
-  int g_aring_nenv[4];
+  CachedGraph g_aring[4];
+  int g_aring_nenv[4];              // (the n_env each was captured for: another one recaptures)
   hipEvent_t aprm_ev[16];
   bool aprm_used[16];
   hipStream_t side;                 // fork stream for graph branches
@@ -159,8 +153,7 @@ struct dra_dqn_learner {
   // DRA_VAR_RING_DIRECT: minibatch indices in four fixed pinned buffers (captured graphs bake the address; the host may
   // run up to four steps ahead), the graph / event of the same rotation, and the flag for an additional gather (checkers)
   int64_t* idx_pin[4];
-  hipGraphExec_t g_rd[4], g_rd_per[4], g_rd_per_b[4];
-  bool g_rd_ready[4], g_rd_per_ready[4];
+  CachedGraph g_rd[4], g_rd_per[4], g_rd_per_b[4];
   hipEvent_t ev_upd[4];
   bool upd_used[4];
   int rd_slot;                      // >= 0 while run_body is being captured / run for the ring-direct pipeline
@@ -204,8 +197,7 @@ struct dra_dqn_learner {
   // conv3 / conv2 folds riding in the next backward launch, conv1's fold in front of the optimizer launch
   // host-environment async actor (dra_dqn_learner_update_async / _q_host_async): update t mirrors its parameters into copy
   // t mod 2, the batch-1 forwards of agent step t+1 read the copy update t-1 wrote, on the actor stream
-  hipGraphExec_t g_qa[2];
-  bool g_qa_ready[2];
+  CachedGraph g_qa[2];
   hipEvent_t ev_hq[2];
   int64_t hq_updates;               // async updates issued
   bool hq_seeded;                   // copy (hq_updates - 1) mod 2 holds valid parameters
@@ -599,26 +591,26 @@ DRA_API int dra_dqn_learner_create(dra_dqn_learner** out, dra_ring* ring, const 
 DRA_API int dra_dqn_learner_destroy(dra_dqn_learner* l) {
   if (!l) return DRA_OK;
   (void)hipDeviceSynchronize();
-  if (l->g_update_ready) (void)hipGraphExecDestroy(l->g_update);
-  if (l->g_update_per_ready) (void)hipGraphExecDestroy(l->g_update_per);
+  l->g_update.reset();
+  l->g_update_per.reset();
+  l->g_q.reset();
+  for (auto& g : l->g_ag) g.reset();
+  for (auto& g : l->g_qa) g.reset();
+  for (auto& ga : l->g_actor) ga.g.reset();
+  for (int k = 0; k < 4; ++k) {
+    l->g_pipe[k].reset(); l->g_pipe_per[k].reset(); l->g_pipe_per_b[k].reset();
+    l->g_rd[k].reset(); l->g_rd_per[k].reset(); l->g_rd_per_b[k].reset();
+    l->g_aring[k].reset();
+  }
   if (l->tr_ev) {
     for (int i = 0; i < l->tr_cap * 5; ++i) (void)hipEventDestroy(l->tr_ev[i]);
     delete[] l->tr_ev;
   }
   for (int g = 0; g < 2; ++g) {
-    if (l->g_ag_ready[g]) (void)hipGraphExecDestroy(l->g_ag[g]);
-    for (int h = g; h < 4; h += 2) {
-      if (l->g_pipe_ready[h]) (void)hipGraphExecDestroy(l->g_pipe[h]);
-      if (l->g_pipe_per_ready[h]) {
-        (void)hipGraphExecDestroy(l->g_pipe_per[h]);
-        if (l->g_pipe_per_b[h]) (void)hipGraphExecDestroy(l->g_pipe_per_b[h]);
-      }
-    }
     (void)hipEventDestroy(l->ev_mb_ready[g]); (void)hipEventDestroy(l->ev_mb_free[g]);
     void* mb[] = {l->state_[g], l->next_state_[g], l->action_[g], l->reward_[g], l->mask_[g]};
     for (void* b : mb) if (b) (void)hipFree(b);
   }
-  for (auto& ga : l->g_actor) if (ga.ready) (void)hipGraphExecDestroy(ga.exec);
   for (int k = 0; k < 4; ++k) if (l->pa[k]) (void)hipFree(l->pa[k]);
   if (l->ah4) (void)hipFree(l->ah4);
   if (l->defer_dev) (void)hipFree(l->defer_dev);
@@ -641,7 +633,6 @@ DRA_API int dra_dqn_learner_destroy(dra_dqn_learner* l) {
     (void)hipFree(l->aring_dev); (void)hipHostFree(l->aring_stage); (void)hipFree(l->aring_seq);
     (void)hipFree(l->pend_frame); (void)hipFree(l->pend_reward); (void)hipFree(l->pend_mask);
   }
-  for (int g = 0; g < 4; ++g) if (l->g_aring_ready[g]) (void)hipGraphExecDestroy(l->g_aring[g]);
   if (l->aprm_ring) {
     (void)hipHostFree(l->aprm_ring); (void)hipFree(l->aprm_seq_dev); (void)hipFree(l->fc4_ticket);
     for (int k = 0; k < kAprmSlots; ++k) (void)hipEventDestroy(l->aprm_ev[k]);
@@ -663,11 +654,6 @@ DRA_API int dra_dqn_learner_destroy(dra_dqn_learner* l) {
   (void)hipHostFree(l->idx_stage);
   for (int k = 0; k < 4; ++k) {
     if (l->idx_pin[k]) (void)hipHostFree(l->idx_pin[k]);
-    if (l->g_rd_ready[k]) (void)hipGraphExecDestroy(l->g_rd[k]);
-    if (l->g_rd_per_ready[k]) {
-      (void)hipGraphExecDestroy(l->g_rd_per[k]);
-      if (l->g_rd_per_b[k]) (void)hipGraphExecDestroy(l->g_rd_per_b[k]);   // (null with the one-graph prioritized update)
-    }
     (void)hipEventDestroy(l->ev_upd[k]);
   }
   for (int k = 0; k < 4; ++k) if (l->idx_tag_pin[k]) (void)hipHostFree(l->idx_tag_pin[k]);
@@ -683,9 +669,7 @@ DRA_API int dra_dqn_learner_destroy(dra_dqn_learner* l) {
   if (l->qs_stage) (void)hipHostFree(l->qs_stage);
   if (l->q_stage) (void)hipHostFree(l->q_stage);
   if (l->q_seq_dev) (void)hipFree(l->q_seq_dev);
-  if (l->g_q_ready) (void)hipGraphExecDestroy(l->g_q);
   for (int k = 0; k < 2; ++k) {
-    if (l->g_qa_ready[k]) (void)hipGraphExecDestroy(l->g_qa[k]);
     if (l->ev_hq[k]) (void)hipEventDestroy(l->ev_hq[k]);
   }
   for (int k = 0; k <= K_COUNT; ++k) (void)hipEventDestroy(l->ev[k]);
@@ -1229,6 +1213,66 @@ static int launch_gather(dra_dqn_learner* l, hipStream_t st, const int64_t* idx 
                          l->reward_[l->gb], l->mask_[l->gb], (void*)st);
 }
 
+// The learner-wide values run_body / launch_gather read while a body is issued or captured.  Set for the scope, back to idle on
+// every way out of it (an early return between a hand-written set and reset would poison every later launch).  per2_ride /
+// per2_split have no parameter: per2_body assigns them between its two halves, inside its scope.
+struct BodyFlags {
+  dra_dqn_learner* const l;
+  BodyFlags(dra_dqn_learner* l_, int gb, int rd_slot = -1, int rider_q = -1, bool fs_capturing = false, bool per2_active = false,
+            int only_kernel = -1, int only_chain = 0) : l(l_) {
+    l->gb = gb; l->rd_slot = rd_slot; l->rider_q = rider_q; l->fs_capturing = fs_capturing; l->per2_active = per2_active;
+    l->only_kernel = only_kernel; l->only_chain = only_chain;
+  }
+  BodyFlags(const BodyFlags&) = delete;
+  BodyFlags& operator=(const BodyFlags&) = delete;
+  ~BodyFlags() {
+    l->gb = 0; l->rd_slot = -1; l->rider_q = -1; l->fs_capturing = false;
+    l->per2_active = l->per2_ride = l->per2_split = false;
+    l->only_kernel = -1; l->only_chain = 0;
+  }
+};
+
+// the gather of `idx` into minibatch buffer `gb`
+static int gather_into(dra_dqn_learner* l, hipStream_t st, int gb, const int64_t* idx) {
+  BodyFlags f(l, gb);
+  return launch_gather(l, st, idx);
+}
+
+// The minibatch indices of staging slot k for a gather on `st`: the pinned slot itself (DRA_VAR_PINNED_IDX), or null = the
+// learner's idx buffer, with their copy into it enqueued.
+static int staged_indices(dra_dqn_learner* l, hipStream_t st, int k, const int64_t** idx) {
+  *idx = (l->variant & DRA_VAR_PINNED_IDX) ? l->idx_stage + (size_t)k * 1024 : nullptr;
+  if (!*idx)
+    DRA_HIP(hipMemcpyAsync(l->idx, l->idx_stage + (size_t)k * 1024, (size_t)l->c.batch * sizeof(int64_t), hipMemcpyHostToDevice, st));
+  return DRA_OK;
+}
+
+static int gather_staged(dra_dqn_learner* l, hipStream_t st, int k, int gb) {
+  const int64_t* idx;
+  if (int rc = staged_indices(l, st, k, &idx)) return rc;
+  return gather_into(l, st, gb, idx);
+}
+
+// (Re)seeds actor parameter copy `slot` from the online parameters on `sa`; ev_join[0] says the copy has read them.  What `sa`
+// waits for first differs per pipeline and stays with the caller.
+static int seed_actor_copy(dra_dqn_learner* l, hipStream_t sa, int slot) {
+  l->pa_cur = slot;
+  DRA_HIP(hipMemcpyAsync(l->pa[slot], l->p, (size_t)l->c.n_params * sizeof(float), hipMemcpyDeviceToDevice, sa));
+  DRA_HIP(hipEventRecord(l->ev_join[0], sa));
+  l->pa_valid = true;
+  return DRA_OK;
+}
+
+// dra_conv_fwd_koc for one net at batch 1 (the actors' env steps, the host-environment forwards): layer 1..3 of parameter
+// block P on input x (u8: the uint8 frame stack, scaled by u8_coef) into y.
+static int conv_fwd_b1(const dra_dqn_learner* l, int layer, const void* x, bool u8, const float* P, float* y, void* s) {
+  const void* xs[1] = {x};
+  const float* w[1] = {P + l->c.offset[P_W1 + 2 * (layer - 1)]};
+  const float* b[1] = {P + l->c.offset[P_B1 + 2 * (layer - 1)]};
+  float* ys[1] = {y};
+  return dra_conv_fwd_koc(layer, 1, xs, w, b, ys, 1, u8 ? 1 : 0, u8 ? l->c.u8_coef : 1.0, DRA_ACT_RELU, s);
+}
+
 // the three conv layers' slab segments of the flat gradient (one-pass weight gradients)
 static void conv_fold_segs(const dra_dqn_learner* l, dra_fold_seg segs[3]) {
   const int wi[3] = {P_W1, P_W2, P_W3};
@@ -1760,37 +1804,17 @@ static int run_body(dra_dqn_learner* l, hipStream_t st, int per, float beta, int
 // PER variant of body_graph: the importance exponent comes from device memory (sampling_prob[B], uploaded with the
 // probabilities), so the captured chain has no per-update argument.
 static int body_graph_per(dra_dqn_learner* l, hipStream_t st) {
-  if (!l->g_update_per_ready) {
-    hipGraph_t graph;
-    DRA_HIP(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
-    int rc = run_body(l, st, 1, -1.f, 0);
-    hipError_t e = hipStreamEndCapture(st, &graph);
-    if (rc != DRA_OK) return rc;
-    if (e != hipSuccess) return (int)e;
-    DRA_HIP(hipGraphInstantiate(&l->g_update_per, graph, nullptr, nullptr, 0));
-    (void)hipGraphDestroy(graph);
-    l->g_update_per_ready = true;
-  }
-  DRA_HIP(hipGraphLaunch(l->g_update_per, st));
-  return DRA_OK;
+  if (!l->g_update_per.ready)
+    if (int rc = l->g_update_per.capture(st, [&] { return run_body(l, st, 1, -1.f, 0); })) return rc;
+  return l->g_update_per.launch(st);
 }
 
 static int body_graph(dra_dqn_learner* l, hipStream_t st) {
-  if (!l->g_update_ready) {
-    hipGraph_t graph;
-    DRA_HIP(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
-    // single-queue chain: forked branches end up on other HW queues and every cross-queue join was
-    // measured at 10-13 us of idle gap (profiles/r01_timeline_async_forked.txt); same-queue gaps are 0
-    int rc = run_body(l, st, 0, 0.f, 0);
-    hipError_t e = hipStreamEndCapture(st, &graph);
-    if (rc != DRA_OK) return rc;
-    if (e != hipSuccess) return (int)e;
-    DRA_HIP(hipGraphInstantiate(&l->g_update, graph, nullptr, nullptr, 0));
-    (void)hipGraphDestroy(graph);
-    l->g_update_ready = true;
-  }
-  DRA_HIP(hipGraphLaunch(l->g_update, st));
-  return DRA_OK;
+  // single-queue chain: forked branches end up on other HW queues and every cross-queue join was
+  // measured at 10-13 us of idle gap (profiles/r01_timeline_async_forked.txt); same-queue gaps are 0
+  if (!l->g_update.ready)
+    if (int rc = l->g_update.capture(st, [&] { return run_body(l, st, 0, 0.f, 0); })) return rc;
+  return l->g_update.launch(st);
 }
 
 // Pipelined async mode: update body + optimizer of one step parity as ONE graph (no launch gap in front of
@@ -1800,42 +1824,26 @@ static int body_graph(dra_dqn_learner* l, hipStream_t st) {
 // priority write-back and the next prioritized draw (tree stream + one host round trip) then run under the backward pass.
 // rd: the ring-direct body (idx_pin[q]); otherwise the gathered minibatch of parity q & 1.
 static int capture_part(dra_dqn_learner* l, hipStream_t st, int q, bool rd, int per, int part, bool with_optimizer,
-                        hipGraphExec_t* exec) {
-  hipGraph_t graph;
-  l->gb = q & 1;
-  l->rd_slot = rd ? q : -1;
-  hipError_t b = hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal);
-  if (b != hipSuccess) { l->gb = 0; l->rd_slot = -1; return (int)b; }
+                        CachedGraph* g) {
   // DRA_VAR_DEFER_FC4: this graph's forwards carry the riders that finish update q - 1's optimizer step (its copy: slot q + 3),
   // and its own optimizer launch leaves fc4's segment to the next graph
   const bool defer = rd && l->defer && !per && part == 0 && with_optimizer;
-  l->rider_q = defer ? ((q + 3) & 3) : -1;
   // DRA_VAR_FLAG_SYNC: the plain ring-direct graph's first launch counts itself in fs_count (update_graph counts the replays)
-  l->fs_capturing = l->fs && rd && !per && part == 0 && with_optimizer;
-  int rc = run_body(l, st, per, per ? -1.f : 0.f, 0, part);     // PER: the exponent is read from sampling_prob[B]
-  if (l->fs_capturing) { l->fs_graph[q & 3] = rc == DRA_OK; l->fs_capturing = false; }
-  l->rider_q = -1;
-  if (rc == DRA_OK && with_optimizer) rc = launch_optimizer(l, st, l->pa[q], defer ? q : -1);
-  hipError_t e = hipStreamEndCapture(st, &graph);
-  l->gb = 0;
-  l->rd_slot = -1;
-  if (rc != DRA_OK) return rc;
-  if (e != hipSuccess) return (int)e;
-  DRA_HIP(hipGraphInstantiate(exec, graph, nullptr, nullptr, 0));
-  (void)hipGraphDestroy(graph);
-  return DRA_OK;
+  const bool announce = l->fs && rd && !per && part == 0 && with_optimizer;
+  return g->capture(st, [&] {
+    BodyFlags f(l, q & 1, rd ? q : -1, defer ? ((q + 3) & 3) : -1, announce);
+    int rc = run_body(l, st, per, per ? -1.f : 0.f, 0, part);     // PER: the exponent is read from sampling_prob[B]
+    if (announce) l->fs_graph[q & 3] = rc == DRA_OK;
+    if (rc == DRA_OK && with_optimizer) rc = launch_optimizer(l, st, l->pa[q], defer ? q : -1);
+    return rc;
+  });
 }
 
 // The prioritized update with the draw on the device (dra_sumtree_per_chain2) as ONE graph: [forward + loss], the draw
 // (priorities -> tree, adds, next draw), [backward + norm + optimizer].  Nothing in the backward pass touches what the draw
 // reads or writes (prio / tree / sampling_prob / the NEXT slot's indices), which is what lets it ride inside backward launches.
-static int capture_per2(dra_dqn_learner* l, hipStream_t st, int q, bool rd, hipGraphExec_t* exec) {
-  hipGraph_t graph;
-  l->gb = q & 1;
-  l->rd_slot = rd ? q : -1;
-  hipError_t b = hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal);
-  if (b != hipSuccess) { l->gb = 0; l->rd_slot = -1; return (int)b; }
-  l->per2_active = true;
+static int per2_body(dra_dqn_learner* l, hipStream_t st, int q, bool rd) {
+  BodyFlags f(l, q & 1, rd ? q : -1, -1, false, /*per2_active=*/true);
   int rc = run_body(l, st, 1, -1.f, 0, 1);
   // The draw rides as roles of two backward launches -- priorities / commits / adds in conv3's, descent / filter / hand-over in
   // conv1's weight gradient (late-fold backward; without it: whole in conv3's) -- for minibatches up to 256 (a role has the
@@ -1843,7 +1851,6 @@ static int capture_per2(dra_dqn_learner* l, hipStream_t st, int q, bool rd, hipG
   // backward pass.  (Measured and removed in round 4: the kernel as a parallel BRANCH of the graph -- the forked graph no
   // longer overlapped with the actor stream's, 4.5 k vs 6.0 k updates/s -- and whole-in-conv3's as a choice: 27 instead of
   // 12 us for that launch; DESIGN.md section 4, profiles/r03h_*, r03i_*.)
-  hipStream_t sd = st;
   const int both = DRA_VAR_ONESHOT_WGRAD | DRA_VAR_ONESHOT_DGRAD;
   l->per2_ride = l->c.batch <= 256 && (l->variant & both) == both;
   l->per2_split = l->per2_ride && l->late;
@@ -1855,36 +1862,29 @@ static int capture_per2(dra_dqn_learner* l, hipStream_t st, int q, bool rd, hipG
   else if (rc == DRA_OK)
     rc = dra_sumtree_per_chain2(l->per_tree, l->per2_io[q & 3], l->delta, l->c.replay_eps, l->c.replay_alpha, l->prio, l->per_stat,
                                 l->per2_dev, l->per2_words, l->per2_idx + (size_t)((q + 1) & 3) * 1024, l->samp_prob, l->weights,
-                                l->c.batch, (void*)sd);
+                                l->c.batch, (void*)st);
   if (rc == DRA_OK) rc = run_body(l, st, 1, -1.f, 0, 2);
-  l->per2_active = false;
-  l->per2_ride = l->per2_split = false;
   if (rc == DRA_OK) rc = launch_optimizer(l, st, l->pa[q]);
-  hipError_t e = hipStreamEndCapture(st, &graph);
-  l->gb = 0;
-  l->rd_slot = -1;
-  if (rc != DRA_OK) return rc;
-  if (e != hipSuccess) return (int)e;
-  DRA_HIP(hipGraphInstantiate(exec, graph, nullptr, nullptr, 0));
-  (void)hipGraphDestroy(graph);
-  return DRA_OK;
+  return rc;
+}
+
+static int capture_per2(dra_dqn_learner* l, hipStream_t st, int q, bool rd, CachedGraph* g) {
+  return g->capture(st, [&] { return per2_body(l, st, q, rd); });
 }
 
 static int update_graph(dra_dqn_learner* l, hipStream_t st, int q, bool rd, int per) {
-  hipGraphExec_t* exec = rd ? (per ? &l->g_rd_per[q] : &l->g_rd[q]) : (per ? &l->g_pipe_per[q] : &l->g_pipe[q]);
-  hipGraphExec_t* exec_b = rd ? &l->g_rd_per_b[q] : &l->g_pipe_per_b[q];
-  bool* ready = rd ? (per ? &l->g_rd_per_ready[q] : &l->g_rd_ready[q]) : (per ? &l->g_pipe_per_ready[q] : &l->g_pipe_ready[q]);
-  if (!*ready) {
+  CachedGraph* g = rd ? (per ? &l->g_rd_per[q] : &l->g_rd[q]) : (per ? &l->g_pipe_per[q] : &l->g_pipe[q]);
+  CachedGraph* g_b = rd ? &l->g_rd_per_b[q] : &l->g_pipe_per_b[q];
+  if (!g->ready) {
     int rc;
     if (per && l->per2_dev && l->per_tree) {
-      if ((rc = capture_per2(l, st, q, rd, exec))) return rc;
+      if ((rc = capture_per2(l, st, q, rd, g))) return rc;
     } else if (per) {
-      if ((rc = capture_part(l, st, q, rd, 1, 1, false, exec))) return rc;
-      if ((rc = capture_part(l, st, q, rd, 1, 2, true, exec_b))) return rc;
-    } else if ((rc = capture_part(l, st, q, rd, 0, 0, true, exec))) {
+      if ((rc = capture_part(l, st, q, rd, 1, 1, false, g))) return rc;
+      if ((rc = capture_part(l, st, q, rd, 1, 2, true, g_b))) { g->reset(); return rc; }   // (g->ready speaks for the pair)
+    } else if ((rc = capture_part(l, st, q, rd, 0, 0, true, g))) {
       return rc;
     }
-    *ready = true;
   }
   // DRA_VAR_DEFER_FC4: a pending fc4 segment is completed by THIS graph's riders only if it is the previous rotation slot's and
   // this is a riding graph; anything else steps it first
@@ -1893,12 +1893,12 @@ static int update_graph(dra_dqn_learner* l, hipStream_t st, int q, bool rd, int 
     int rcf = flush_fc4(l, st);
     if (rcf) return rcf;
   }
-  DRA_HIP(hipGraphLaunch(*exec, st));
+  if (int rcl = g->launch(st)) return rcl;
   if (rd && !per && l->fs_graph[q & 3]) l->fs_issued++;     // (its first launch bumps fs_count when it starts)
   if (riding) { l->defer_host = true; l->defer_q = q; }
   if (per && !(l->per2_dev && l->per_tree)) {
     DRA_HIP(hipEventRecord(l->ev_loss, st));
-    DRA_HIP(hipGraphLaunch(*exec_b, st));
+    if (int rcl = g_b->launch(st)) return rcl;
   }
   return DRA_OK;
 }
@@ -1920,7 +1920,7 @@ DRA_API int dra_dqn_learner_set_per_chain2(dra_dqn_learner* l, dra_sumtree* tree
   if (!(l->variant & DRA_VAR_RING_DIRECT) || !(l->variant & DRA_VAR_GATHER_ON_UPDATE)) return DRA_EINVAL;
   if (l->c.batch > DRA_PER_CHAIN_MAX) return DRA_EINVAL;
   for (int k = 0; k < 4; ++k)
-    if (l->g_rd_per_ready[k] || l->g_pipe_per_ready[k]) return DRA_EINVAL;     // the graphs bake the choice
+    if (l->g_rd_per[k].ready || l->g_pipe_per[k].ready) return DRA_EINVAL;     // the graphs bake the choice
   if (!l->per2_dev) {
     int64_t sb = 0;
     (void)dra_sumtree_per_chain2_state_bytes(&sb);
@@ -1961,16 +1961,13 @@ DRA_API int dra_dqn_learner_per_chain2_wait(dra_dqn_learner* l, int slot, uint64
   if (!l || !l->per2_dev || slot < 0 || slot > 3) return DRA_EINVAL;
   const volatile uint64_t* p = &l->per2_io[slot]->out_seq;
   if (__atomic_load_n(p, __ATOMIC_ACQUIRE) >= seq) return DRA_OK;
-  const auto t0 = std::chrono::steady_clock::now();
+  HostTimeScope waited(l->host_wait_s);
   for (;;) {
     for (int i = 0; i < 256; ++i) {
-      if (__atomic_load_n(p, __ATOMIC_ACQUIRE) >= seq) {
-        l->host_wait_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-        return DRA_OK;
-      }
+      if (__atomic_load_n(p, __ATOMIC_ACQUIRE) >= seq) return DRA_OK;
       __builtin_ia32_pause();
     }
-    if (std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count() > (double)timeout_us) return DRA_ETIMEDOUT;
+    if (waited.seconds() * 1e6 > (double)timeout_us) return DRA_ETIMEDOUT;
   }
 }
 DRA_API int dra_dqn_learner_next_slot(dra_dqn_learner* l, int* slot) {
@@ -2075,39 +2072,27 @@ DRA_API int dra_dqn_learner_kernel_replay(dra_dqn_learner* l, int kernel, int re
   DRA_HIP(hipStreamSynchronize(st));
   float us[2] = {0.f, 0.f};
   for (int pass = 0; pass < 2; ++pass) {
-    hipGraph_t graph;
-    hipGraphExec_t exec;
-    const bool rd = l->variant & DRA_VAR_RING_DIRECT;
-    l->gb = 0;
-    l->rd_slot = rd ? 0 : -1;
-    l->only_kernel = kernel;
-    hipError_t b = hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal);
-    int rc = b == hipSuccess ? DRA_OK : (int)b;
-    for (int r = 0; r < reps && rc == DRA_OK && b == hipSuccess; ++r) {
-      if (pass == 0) rc = run_body(l, st, 0, 0.f, 0);
-      else hipLaunchKernelGGL(empty_probe_kernel, dim3(224), dim3(256), 0, st, (const int*)nullptr);
-    }
-    l->only_kernel = -1;
-    l->rd_slot = -1;
-    hipError_t e = b == hipSuccess ? hipStreamEndCapture(st, &graph) : b;
-    if (rc != DRA_OK) return rc;
-    if (e != hipSuccess) return (int)e;
-    DRA_HIP(hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
-    (void)hipGraphDestroy(graph);
-    DRA_HIP(hipGraphLaunch(exec, st));                   // warm: code objects / TLB / clocks
-    DRA_HIP(hipStreamSynchronize(st));
+    CachedGraph g = {};
+    int rc = g.capture(st, [&] {
+      BodyFlags f(l, 0, (l->variant & DRA_VAR_RING_DIRECT) ? 0 : -1, -1, false, false, /*only_kernel=*/kernel);
+      int rcb = DRA_OK;
+      for (int r = 0; r < reps && rcb == DRA_OK; ++r) {
+        if (pass == 0) rcb = run_body(l, st, 0, 0.f, 0);
+        else hipLaunchKernelGGL(empty_probe_kernel, dim3(224), dim3(256), 0, st, (const int*)nullptr);
+      }
+      return rcb;
+    });
+    if (rc == DRA_OK) rc = g.launch(st);                 // warm: code objects / TLB / clocks
+    if (rc == DRA_OK) rc = (int)hipStreamSynchronize(st);
     float best = 0.f;
-    for (int t = 0; t < 3; ++t) {                        // the fastest of three replays (a host hiccup only ever adds time)
-      DRA_HIP(hipEventRecord(l->ev[0], st));
-      DRA_HIP(hipGraphLaunch(exec, st));
-      DRA_HIP(hipEventRecord(l->ev[1], st));
-      DRA_HIP(hipEventSynchronize(l->ev[1]));
+    for (int t = 0; t < 3 && rc == DRA_OK; ++t) {        // the fastest of three replays (a host hiccup only ever adds time)
       float ms = 0.f;
-      DRA_HIP(hipEventElapsedTime(&ms, l->ev[0], l->ev[1]));
+      rc = timed_replay(g, st, l->ev[0], l->ev[1], &ms);
       if (t == 0 || ms < best) best = ms;
     }
+    g.reset();
+    if (rc != DRA_OK) return rc;
     us[pass] = best * 1e3f / (float)reps;
-    (void)hipGraphExecDestroy(exec);
   }
   out_us[0] = us[0];
   out_us[1] = us[1];
@@ -2132,45 +2117,34 @@ DRA_API int dra_dqn_learner_chain_replay(dra_dqn_learner* l, int which, int reps
   unsigned* epoch = l->fchain_dev + kFwdChainCounters;
   float us[2] = {0.f, 0.f};
   for (int pass = 0; pass < 2; ++pass) {
-    hipGraph_t graph;
-    hipGraphExec_t exec;
-    l->gb = 0;
-    l->rd_slot = 0;
-    l->only_chain = which + 1;
-    hipError_t b = hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal);
-    int rc = b == hipSuccess ? DRA_OK : (int)b;
-    for (int r = 0; r < reps && rc == DRA_OK && b == hipSuccess; ++r) {
-      // (the forward chain waits for (epoch + 1) x arrivals: the bump follows it; the backward chain for epoch x arrivals, its
-      // own update's head included: the bump precedes it)
-      if (which == 1) hipLaunchKernelGGL(chain_epoch_bump_kernel, dim3(1), dim3(1), 0, st, epoch);
-      if (pass == 0) rc = run_body(l, st, 0, 0.f, 0);
-      else hipLaunchKernelGGL(empty_probe_kernel, dim3(224), dim3(256), 0, st, (const int*)nullptr);
-      if (which == 0) hipLaunchKernelGGL(chain_epoch_bump_kernel, dim3(1), dim3(1), 0, st, epoch);
-    }
-    l->only_chain = 0;
-    l->rd_slot = -1;
-    hipError_t e = b == hipSuccess ? hipStreamEndCapture(st, &graph) : b;
-    if (rc != DRA_OK) return rc;
-    if (e != hipSuccess) return (int)e;
-    DRA_HIP(hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
-    (void)hipGraphDestroy(graph);
+    CachedGraph g = {};
+    int rc = g.capture(st, [&] {
+      BodyFlags f(l, 0, 0, -1, false, false, -1, /*only_chain=*/which + 1);
+      int rcb = DRA_OK;
+      for (int r = 0; r < reps && rcb == DRA_OK; ++r) {
+        // (the forward chain waits for (epoch + 1) x arrivals: the bump follows it; the backward chain for epoch x arrivals, its
+        // own update's head included: the bump precedes it)
+        if (which == 1) hipLaunchKernelGGL(chain_epoch_bump_kernel, dim3(1), dim3(1), 0, st, epoch);
+        if (pass == 0) rcb = run_body(l, st, 0, 0.f, 0);
+        else hipLaunchKernelGGL(empty_probe_kernel, dim3(224), dim3(256), 0, st, (const int*)nullptr);
+        if (which == 0) hipLaunchKernelGGL(chain_epoch_bump_kernel, dim3(1), dim3(1), 0, st, epoch);
+      }
+      return rcb;
+    });
     float best = 0.f;
-    for (int t = 0; t < 4; ++t) {                        // one warm replay, then the fastest of three
-      DRA_HIP(hipEventRecord(l->ev[0], st));
-      DRA_HIP(hipGraphLaunch(exec, st));
-      DRA_HIP(hipEventRecord(l->ev[1], st));
-      DRA_HIP(hipEventSynchronize(l->ev[1]));
+    for (int t = 0; t < 4 && rc == DRA_OK; ++t) {        // one warm replay, then the fastest of three
       float ms = 0.f;
-      DRA_HIP(hipEventElapsedTime(&ms, l->ev[0], l->ev[1]));
+      rc = timed_replay(g, st, l->ev[0], l->ev[1], &ms);
       if (t == 1 || (t > 1 && ms < best)) best = ms;
     }
     // the replays advanced the epoch word for ONE chain's counters (the empty pass for none): both chains are brought level
     // again -- every arrival counter holds epoch x (arrivals per epoch) between updates, so all zero is a level state
-    DRA_HIP(hipMemsetAsync(l->fchain_dev, 0, (size_t)(kFwdChainCounters + 1) * sizeof(unsigned), st));
-    DRA_HIP(hipMemsetAsync(l->bchain_dev, 0, (size_t)dra_bwd_chain_counters() * sizeof(unsigned), st));
-    DRA_HIP(hipStreamSynchronize(st));
+    if (rc == DRA_OK) rc = (int)hipMemsetAsync(l->fchain_dev, 0, (size_t)(kFwdChainCounters + 1) * sizeof(unsigned), st);
+    if (rc == DRA_OK) rc = (int)hipMemsetAsync(l->bchain_dev, 0, (size_t)dra_bwd_chain_counters() * sizeof(unsigned), st);
+    if (rc == DRA_OK) rc = (int)hipStreamSynchronize(st);
+    g.reset();
+    if (rc != DRA_OK) return rc;
     us[pass] = best * 1e3f / (float)reps;
-    (void)hipGraphExecDestroy(exec);
   }
   out_us[0] = us[0];
   out_us[1] = us[1];
@@ -2557,12 +2531,8 @@ static int run_actor_steps_v3(dra_dqn_learner* l, int n_env, const float* P, hip
     if ((rc = dra_conv1_fwd_koc_ring(frames, &l->prm_dev->slot[e], &l->prm_dev->stack_age[e], c.ring_capacity, P + o[P_W1], P + o[P_B1], l->ay1,
                                      c.u8_coef, DRA_ACT_RELU, s)))
       return rc;
-    const void* x2[1] = {l->ay1}; const float* w2[1] = {P + o[P_W2]}; const float* b2[1] = {P + o[P_B2]};
-    float* y2[1] = {l->ay2};
-    if ((rc = dra_conv_fwd_koc(2, 1, x2, w2, b2, y2, 1, 0, 1.0, DRA_ACT_RELU, s))) return rc;
-    const void* x3[1] = {l->ay2}; const float* w3[1] = {P + o[P_W3]}; const float* b3[1] = {P + o[P_B3]};
-    float* y3[1] = {l->ay3};
-    if ((rc = dra_conv_fwd_koc(3, 1, x3, w3, b3, y3, 1, 0, 1.0, DRA_ACT_RELU, s))) return rc;
+    if ((rc = conv_fwd_b1(l, 2, l->ay1, false, P, l->ay2, s))) return rc;
+    if ((rc = conv_fwd_b1(l, 3, l->ay2, false, P, l->ay3, s))) return rc;
     if (l->variant & DRA_VAR_ACTOR_FUSED_HEAD) {
       hipLaunchKernelGGL(actor_fc4_head_env_kernel, dim3(128), dim3(256), 0, st, (const dra_dqn_step_params*)l->prm_dev, e,
                          (const float*)l->ay3, P + o[P_W4], P + o[P_B4], l->ah4, 3136, l->fc4_ticket, P + o[P_WH],
@@ -2672,40 +2642,26 @@ DRA_API int dra_dqn_learner_q_host(dra_dqn_learner* l, const uint8_t* state_host
   hipStream_t st = dra_stream(stream);
   const dra_dqn_config& c = l->c;
   memcpy(l->qs_stage, state_host, (size_t)4 * 7056);         // (mapped, coherent: conv1 reads it in place)
-  if (!l->g_q_ready) {
+  if (!l->g_q.ready) {
     const int64_t* o = c.offset;
     const float* P = l->p;
     void* s = (void*)st;
-    hipGraph_t graph;
-    DRA_HIP(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
-    int rc = DRA_OK;
-    {
-      const void* x1[1] = {l->qs_stage};
-      const float* w1[1] = {P + o[P_W1]}; const float* b1[1] = {P + o[P_B1]};
-      float* y1[1] = {l->ay1};
-      rc = dra_conv_fwd_koc(1, 1, x1, w1, b1, y1, 1, 1, c.u8_coef, DRA_ACT_RELU, s);
-      const void* x2[1] = {l->ay1}; const float* w2[1] = {P + o[P_W2]}; const float* b2[1] = {P + o[P_B2]};
-      float* y2[1] = {l->ay2};
-      if (!rc) rc = dra_conv_fwd_koc(2, 1, x2, w2, b2, y2, 1, 0, 1.0, DRA_ACT_RELU, s);
-      const void* x3[1] = {l->ay2}; const float* w3[1] = {P + o[P_W3]}; const float* b3[1] = {P + o[P_B3]};
-      float* y3[1] = {l->ay3};
-      if (!rc) rc = dra_conv_fwd_koc(3, 1, x3, w3, b3, y3, 1, 0, 1.0, DRA_ACT_RELU, s);
-      if (!rc) {
+    int rc = l->g_q.capture(st, [&] {
+      int rcb = conv_fwd_b1(l, 1, l->qs_stage, true, P, l->ay1, s);
+      if (!rcb) rcb = conv_fwd_b1(l, 2, l->ay1, false, P, l->ay2, s);
+      if (!rcb) rcb = conv_fwd_b1(l, 3, l->ay2, false, P, l->ay3, s);
+      if (!rcb) {
         hipLaunchKernelGGL(actor_fc4_kernel, dim3(128), dim3(256), 0, st, (const float*)l->ay3, P + o[P_W4], P + o[P_B4],
                            l->ah4, 3136);
         hipLaunchKernelGGL(head_q_kernel, dim3(1), dim3(c.head_kind != DRA_HEAD_VANILLA ? 1024 : 256), 0, st, (const float*)l->ah4,
                            P + o[P_WH], P + o[P_BH], c.n_actions, l->aq, head_spec(l), (unsigned*)nullptr, 0,
                            l->q_stage, l->q_seq_dev);
       }
-    }
-    hipError_t e = hipStreamEndCapture(st, &graph);
-    if (rc != DRA_OK) return rc;
-    if (e != hipSuccess) return (int)e;
-    DRA_HIP(hipGraphInstantiate(&l->g_q, graph, nullptr, nullptr, 0));
-    (void)hipGraphDestroy(graph);
-    l->g_q_ready = true;
+      return rcb;
+    });
+    if (rc) return rc;
   }
-  DRA_HIP(hipGraphLaunch(l->g_q, st));
+  if (int rc = l->g_q.launch(st)) return rc;
   return q_mail_wait(l, ++l->q_seq_host, q_host);
 }
 
@@ -2759,36 +2715,26 @@ DRA_API int dra_dqn_learner_q_host_async(dra_dqn_learner* l, const uint8_t* stat
     }
   }
   memcpy(l->qs_stage, state_host, (size_t)4 * 7056);         // (mapped, coherent: conv1 reads it in place)
-  if (!l->g_qa_ready[k]) {
+  if (!l->g_qa[k].ready) {
     const int64_t* o = c.offset;
     const float* P = l->pa[k];
     void* s = (void*)st;
-    hipGraph_t graph;
-    DRA_HIP(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
-    int rc = DRA_OK;
-    {
-      const void* x1[1] = {l->qs_stage};
-      const float* w1[1] = {P + o[P_W1]}; const float* b1[1] = {P + o[P_B1]};
-      float* y1[1] = {l->ay1};
-      rc = dra_conv_fwd_koc(1, 1, x1, w1, b1, y1, 1, 1, c.u8_coef, DRA_ACT_RELU, s);
+    int rc = l->g_qa[k].capture(st, [&] {
+      int rcb = conv_fwd_b1(l, 1, l->qs_stage, true, P, l->ay1, s);
       // conv2 with its reduction split over two workgroups per tile, conv3 + fc4 as one launch (the device actor's kernels)
-      if (!rc) rc = dra_conv_b1_split(2, l->ay1, nullptr, P + o[P_W2], P + o[P_B2], l->ay2p, s);
-      if (!rc) rc = dra_actor_c3fc4(l->ay2p, P + o[P_W3], P + o[P_B3], P + o[P_W4], P + o[P_B4], l->ay3p, l->ah4,
+      if (!rcb) rcb = dra_conv_b1_split(2, l->ay1, nullptr, P + o[P_W2], P + o[P_B2], l->ay2p, s);
+      if (!rcb) rcb = dra_actor_c3fc4(l->ay2p, P + o[P_W3], P + o[P_B3], P + o[P_W4], P + o[P_B4], l->ay3p, l->ah4,
                                     l->aflags + 4 * (kMaxEnvSteps - 1), l->timeout_flag, s);
-      if (!rc) {
+      if (!rcb) {
         hipLaunchKernelGGL(head_q_kernel, dim3(1), dim3(c.head_kind != DRA_HEAD_VANILLA ? 1024 : 256), 0, st, (const float*)l->ah4,
                            P + o[P_WH], P + o[P_BH], c.n_actions, l->aq, head_spec(l), l->aflags + 4 * (kMaxEnvSteps - 1), 4,
                            l->q_stage, l->q_seq_dev);
       }
-    }
-    hipError_t e = hipStreamEndCapture(st, &graph);
-    if (rc != DRA_OK) return rc;
-    if (e != hipSuccess) return (int)e;
-    DRA_HIP(hipGraphInstantiate(&l->g_qa[k], graph, nullptr, nullptr, 0));
-    (void)hipGraphDestroy(graph);
-    l->g_qa_ready[k] = true;
+      return rcb;
+    });
+    if (rc) return rc;
   }
-  DRA_HIP(hipGraphLaunch(l->g_qa[k], st));
+  if (int rc = l->g_qa[k].launch(st)) return rc;
   return q_mail_wait(l, ++l->q_seq_host, q_host);
 }
 
@@ -2972,12 +2918,8 @@ static int run_actor_steps_ring_fused(dra_dqn_learner* l, int n_env, const float
       }
       continue;
     }
-    const void* x2[1] = {l->ay1}; const float* w2[1] = {P + o[P_W2]}; const float* b2[1] = {P + o[P_B2]};
-    float* y2[1] = {l->ay2};
-    if ((rc = dra_conv_fwd_koc(2, 1, x2, w2, b2, y2, 1, 0, 1.0, DRA_ACT_RELU, s))) return rc;
-    const void* x3[1] = {l->ay2}; const float* w3[1] = {P + o[P_W3]}; const float* b3[1] = {P + o[P_B3]};
-    float* y3[1] = {l->ay3};
-    if ((rc = dra_conv_fwd_koc(3, 1, x3, w3, b3, y3, 1, 0, 1.0, DRA_ACT_RELU, s))) return rc;
+    if ((rc = conv_fwd_b1(l, 2, l->ay1, false, P, l->ay2, s))) return rc;
+    if ((rc = conv_fwd_b1(l, 3, l->ay2, false, P, l->ay3, s))) return rc;
     hipLaunchKernelGGL(actor_fc4_kernel, dim3(128), dim3(256), 0, st, (const float*)l->ay3, P + o[P_W4], P + o[P_B4],
                        l->ah4, 3136);
     DRA_LAUNCH_CHECK();
@@ -3012,12 +2954,8 @@ static int run_actor_steps_ring(dra_dqn_learner* l, int n_env, const float* P, h
                                          e == 0 ? l->pend_frame : nullptr, P + o[P_W1], P + o[P_B1], l->ay1, c.u8_coef,
                                          DRA_ACT_RELU, s)))
       return rc;
-    const void* x2[1] = {l->ay1}; const float* w2[1] = {P + o[P_W2]}; const float* b2[1] = {P + o[P_B2]};
-    float* y2[1] = {l->ay2};
-    if ((rc = dra_conv_fwd_koc(2, 1, x2, w2, b2, y2, 1, 0, 1.0, DRA_ACT_RELU, s))) return rc;
-    const void* x3[1] = {l->ay2}; const float* w3[1] = {P + o[P_W3]}; const float* b3[1] = {P + o[P_B3]};
-    float* y3[1] = {l->ay3};
-    if ((rc = dra_conv_fwd_koc(3, 1, x3, w3, b3, y3, 1, 0, 1.0, DRA_ACT_RELU, s))) return rc;
+    if ((rc = conv_fwd_b1(l, 2, l->ay1, false, P, l->ay2, s))) return rc;
+    if ((rc = conv_fwd_b1(l, 3, l->ay2, false, P, l->ay3, s))) return rc;
     hipLaunchKernelGGL(actor_fc4_kernel, dim3(128), dim3(256), 0, st, (const float*)l->ay3, P + o[P_W4], P + o[P_B4],
                        l->ah4, 3136);
     HeadSpec hs = head_spec(l);
@@ -3093,26 +3031,18 @@ static int issue_actor_ring(dra_dqn_learner* l, int n_env, const float* P, int p
   if (!use_graph) {
     rc = run_actor_steps_ring(l, n_env, P, st);
   } else {
-    if (l->g_aring_ready[par] && l->g_aring_nenv[par] != n_env) {
-      (void)hipGraphExecDestroy(l->g_aring[par]);
-      l->g_aring_ready[par] = false;
-    }
-    if (!l->g_aring_ready[par]) {
-      hipGraph_t graph;
-      DRA_HIP(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
-      l->fs_persist_taken = false;
-      rc = run_actor_steps_ring(l, n_env, P, st);
-      l->fs_agraph[par] = l->fs_persist_taken && rc == DRA_OK;
-      hipError_t e = hipStreamEndCapture(st, &graph);
+    CachedGraph& g = l->g_aring[par];
+    if (!g.ready || l->g_aring_nenv[par] != n_env) {
+      rc = g.capture(st, [&] {
+        l->fs_persist_taken = false;
+        const int rcb = run_actor_steps_ring(l, n_env, P, st);
+        l->fs_agraph[par] = l->fs_persist_taken && rcb == DRA_OK;
+        return rcb;
+      });
       if (rc != DRA_OK) return rc;
-      if (e != hipSuccess) return (int)e;
-      DRA_HIP(hipGraphInstantiate(&l->g_aring[par], graph, nullptr, nullptr, 0));
-      (void)hipGraphDestroy(graph);
-      l->g_aring_ready[par] = true;
       l->g_aring_nenv[par] = n_env;
     }
-    DRA_HIP(hipGraphLaunch(l->g_aring[par], st));
-    rc = DRA_OK;
+    rc = g.launch(st);
   }
   if (rc == DRA_OK) l->aring_issued++;
   return rc;
@@ -3132,12 +3062,8 @@ static int run_actor_steps_v2(dra_dqn_learner* l, int n_env, const float* P, hip
     if ((rc = dra_conv1_fwd_koc_ring(frames, &l->prm_dev->slot[e], &l->prm_dev->stack_age[e], c.ring_capacity, P + o[P_W1], P + o[P_B1], l->ay1,
                                      c.u8_coef, DRA_ACT_RELU, s)))
       return rc;
-    const void* x2[1] = {l->ay1}; const float* w2[1] = {P + o[P_W2]}; const float* b2[1] = {P + o[P_B2]};
-    float* y2[1] = {l->ay2};
-    if ((rc = dra_conv_fwd_koc(2, 1, x2, w2, b2, y2, 1, 0, 1.0, DRA_ACT_RELU, s))) return rc;
-    const void* x3[1] = {l->ay2}; const float* w3[1] = {P + o[P_W3]}; const float* b3[1] = {P + o[P_B3]};
-    float* y3[1] = {l->ay3};
-    if ((rc = dra_conv_fwd_koc(3, 1, x3, w3, b3, y3, 1, 0, 1.0, DRA_ACT_RELU, s))) return rc;
+    if ((rc = conv_fwd_b1(l, 2, l->ay1, false, P, l->ay2, s))) return rc;
+    if ((rc = conv_fwd_b1(l, 3, l->ay2, false, P, l->ay3, s))) return rc;
     hipLaunchKernelGGL(actor_fc4_kernel, dim3(128), dim3(256), 0, st, (const float*)l->ay3, P + o[P_W4], P + o[P_B4],
                        l->ah4, 3136);
     DRA_LAUNCH_CHECK();
@@ -3164,15 +3090,9 @@ static int run_actor_steps(dra_dqn_learner* l, int n_env, const float* P, hipStr
                        (uint8_t*)frames, (double*)rewards, (int32_t*)masks, c.ring_capacity, (uint64_t)c.env_seed,
                        (int)c.env_done_period, l->act_state);
     DRA_LAUNCH_CHECK();
-    const void* x1[1] = {l->act_state}; const float* w1[1] = {P + o[P_W1]}; const float* b1[1] = {P + o[P_B1]};
-    float* y1[1] = {l->ay1};
-    if ((rc = dra_conv_fwd_koc(1, 1, x1, w1, b1, y1, 1, 1, c.u8_coef, DRA_ACT_RELU, s))) return rc;
-    const void* x2[1] = {l->ay1}; const float* w2[1] = {P + o[P_W2]}; const float* b2[1] = {P + o[P_B2]};
-    float* y2[1] = {l->ay2};
-    if ((rc = dra_conv_fwd_koc(2, 1, x2, w2, b2, y2, 1, 0, 1.0, DRA_ACT_RELU, s))) return rc;
-    const void* x3[1] = {l->ay2}; const float* w3[1] = {P + o[P_W3]}; const float* b3[1] = {P + o[P_B3]};
-    float* y3[1] = {l->ay3};
-    if ((rc = dra_conv_fwd_koc(3, 1, x3, w3, b3, y3, 1, 0, 1.0, DRA_ACT_RELU, s))) return rc;
+    if ((rc = conv_fwd_b1(l, 1, l->act_state, true, P, l->ay1, s))) return rc;
+    if ((rc = conv_fwd_b1(l, 2, l->ay1, false, P, l->ay2, s))) return rc;
+    if ((rc = conv_fwd_b1(l, 3, l->ay2, false, P, l->ay3, s))) return rc;
     const float* x4[1] = {l->ay3}; const float* w4[1] = {P + o[P_W4]};
     if ((rc = dra_linear_fwd_slabs(1, x4, w4, 1, 3136, 512, kFc4Split, l->afc4_slabs, s))) return rc;
     hipLaunchKernelGGL(actor_head_kernel, dim3(1), dim3(512), 0, st, (const dra_dqn_step_params*)l->prm_dev, e,
@@ -3186,29 +3106,18 @@ static int run_actor_steps(dra_dqn_learner* l, int n_env, const float* P, hipStr
 static int actor_graph(dra_dqn_learner* l, int n_env, const float* P, hipStream_t st) {
   int slot = -1;
   constexpr int NS = 5;
-  for (int k = 0; k < NS; ++k) if (l->g_actor[k].ready && l->g_actor[k].params == P && l->g_actor[k].n_env == n_env) slot = k;
+  for (int k = 0; k < NS; ++k) if (l->g_actor[k].g.ready && l->g_actor[k].params == P && l->g_actor[k].n_env == n_env) slot = k;
   if (slot < 0) {
-    for (int k = 0; k < NS && slot < 0; ++k) if (!l->g_actor[k].ready) slot = k;
-    if (slot < 0) {  // evict an entry of the same parameter block (n_env changed), else entry 0
+    for (int k = 0; k < NS && slot < 0; ++k) if (!l->g_actor[k].g.ready) slot = k;
+    if (slot < 0) {  // evict an entry of the same parameter block (n_env changed), else entry 0 (the capture destroys it)
       slot = 0;
       for (int k = 0; k < NS; ++k) if (l->g_actor[k].params == P) slot = k;
-      (void)hipGraphExecDestroy(l->g_actor[slot].exec);
-      l->g_actor[slot].ready = false;
     }
-    hipGraph_t graph;
-    DRA_HIP(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
-    int rc = run_actor_steps(l, n_env, P, st);
-    hipError_t e = hipStreamEndCapture(st, &graph);
-    if (rc != DRA_OK) return rc;
-    if (e != hipSuccess) return (int)e;
-    DRA_HIP(hipGraphInstantiate(&l->g_actor[slot].exec, graph, nullptr, nullptr, 0));
-    (void)hipGraphDestroy(graph);
-    l->g_actor[slot].ready = true;
+    if (int rc = l->g_actor[slot].g.capture(st, [&] { return run_actor_steps(l, n_env, P, st); })) return rc;
     l->g_actor[slot].params = P;
     l->g_actor[slot].n_env = n_env;
   }
-  DRA_HIP(hipGraphLaunch(l->g_actor[slot].exec, st));
-  return DRA_OK;
+  return l->g_actor[slot].g.launch(st);
 }
 
 static int actor_graph(dra_dqn_learner* l, int n_env, const float* P, hipStream_t st);
@@ -3256,19 +3165,14 @@ DRA_API int dra_dqn_learner_trace_read(dra_dqn_learner* l, float* out_ms, int ma
 // buffer free again, optimizer of step t-1 done) refer to work issued a whole step earlier.
 static int step_pipelined(dra_dqn_learner* l, const dra_dqn_step_params* prm, int do_update, hipStream_t su,
                           hipStream_t sa, int k) {
-  const int B = l->c.batch;
   const int par = (int)(l->step_no & 1);
   int rc;
   if (do_update) {
     if (l->mb_used[par]) DRA_HIP(hipStreamWaitEvent(sa, l->ev_mb_free[par], 0));
-    const int64_t* pinned = (l->variant & DRA_VAR_PINNED_IDX) ? l->idx_stage + (size_t)k * 1024 : nullptr;
-    if (!pinned)
-      DRA_HIP(hipMemcpyAsync(l->idx, l->idx_stage + (size_t)k * 1024, (size_t)B * sizeof(int64_t), hipMemcpyHostToDevice, sa));
+    const int64_t* idx;
+    if ((rc = staged_indices(l, sa, k, &idx))) return rc;
     TRACE(0, sa);
-    l->gb = par;
-    rc = launch_gather(l, sa, pinned);
-    l->gb = 0;
-    if (rc) return rc;
+    if ((rc = gather_into(l, sa, par, idx))) return rc;
     DRA_HIP(hipEventRecord(l->ev_mb_ready[par], sa));
     TRACE(1, sa);
   }
@@ -3277,10 +3181,7 @@ static int step_pipelined(dra_dqn_learner* l, const dra_dqn_step_params* prm, in
     if (l->pa_valid && l->pa_cur != (par ^ 1)) l->pa_valid = false;   // copies out of phase with the step parity
     if (l->last_done) DRA_HIP(hipStreamWaitEvent(sa, l->last_done, 0));   // the optimizer that produced the copy read below
     if (!l->pa_valid) {
-      l->pa_cur = par ^ 1;
-      DRA_HIP(hipMemcpyAsync(l->pa[l->pa_cur], l->p, (size_t)l->c.n_params * sizeof(float), hipMemcpyDeviceToDevice, sa));
-      DRA_HIP(hipEventRecord(l->ev_join[0], sa));
-      l->pa_valid = true;
+      if ((rc = seed_actor_copy(l, sa, par ^ 1))) return rc;
       seeded = true;
     }
     if (l->variant & DRA_VAR_ACTOR_RING) rc = issue_actor_ring(l, prm->n_env, l->pa[l->pa_cur], l->pa_cur, sa, true);
@@ -3406,17 +3307,13 @@ static int step_pipelined3(dra_dqn_learner* l, const dra_dqn_step_params* prm, i
   }
   if (seed && phase != 2) {   // (re)seed the actor copy from the online parameters BEFORE this step's optimizer overwrites them
     if (opt_prev) DRA_HIP(hipStreamWaitEvent(sa, opt_prev, 0));
-    l->pa_cur = qr;
-    DRA_HIP(hipMemcpyAsync(l->pa[l->pa_cur], l->p, (size_t)l->c.n_params * sizeof(float), hipMemcpyDeviceToDevice, sa));
-    DRA_HIP(hipEventRecord(l->ev_join[0], sa));
-    l->pa_valid = true;
+    if ((rc = seed_actor_copy(l, sa, qr))) return rc;
   }
   if (phase == 1) l->split_seed = seed;
   if (do_update && phase != 2) {
     if (l->pa_reader[q]) {           // the optimizer of this update overwrites copy q: its last reader must be done
-      const auto t0 = std::chrono::steady_clock::now();
+      HostTimeScope waited(l->host_wait_s);
       DRA_HIP(hipEventSynchronize(l->pa_reader[q]));
-      l->host_wait_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
       l->pa_reader[q] = nullptr;
     }
     if (needs_actor) DRA_HIP(hipStreamWaitEvent(su, needs_actor, 0));   // the sampled transitions are in the ring
@@ -3425,9 +3322,8 @@ static int step_pipelined3(dra_dqn_learner* l, const dra_dqn_step_params* prm, i
       // no gather: the update's own kernels read the ring through idx_pin[q] (four rotating pinned buffers: a captured graph
       // bakes the address; buffer q is free again once update t-4 is done)
       if (l->upd_used[q]) {
-        const auto t0 = std::chrono::steady_clock::now();
+        HostTimeScope waited(l->host_wait_s);
         DRA_HIP(hipEventSynchronize(l->ev_upd[q]));
-        l->host_wait_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
       }
       if (phase == 0) memcpy(l->idx_pin[q], prm->idx, (size_t)B * sizeof(int64_t));
       if (phase == 0 && (l->variant & DRA_VAR_IDX_PREFETCH)) {
@@ -3445,10 +3341,7 @@ static int step_pipelined3(dra_dqn_learner* l, const dra_dqn_step_params* prm, i
       l->rd_issued++;
       TRACE(0, su);
       if (l->keep_minibatch) {
-        l->gb = par;
-        rc = launch_gather(l, su, phase == 1 ? l->per2_idx + (size_t)q * 1024 : l->idx_pin[q]);
-        l->gb = 0;
-        if (rc) return rc;
+        if ((rc = gather_into(l, su, par, phase == 1 ? l->per2_idx + (size_t)q * 1024 : l->idx_pin[q]))) return rc;
       } else {
         l->last_gb = par;
       }
@@ -3460,14 +3353,10 @@ static int step_pipelined3(dra_dqn_learner* l, const dra_dqn_step_params* prm, i
       l->last_done = l->ev_upd[q];
       l->upd_used[q] = true;
     } else {
-      const int64_t* pinned = (l->variant & DRA_VAR_PINNED_IDX) ? l->idx_stage + (size_t)k * 1024 : nullptr;
-      if (!pinned)
-        DRA_HIP(hipMemcpyAsync(l->idx, l->idx_stage + (size_t)k * 1024, (size_t)B * sizeof(int64_t), hipMemcpyHostToDevice, su));
+      const int64_t* idx;
+      if ((rc = staged_indices(l, su, k, &idx))) return rc;
       TRACE(0, su);
-      l->gb = par;
-      rc = launch_gather(l, su, pinned);
-      l->gb = 0;
-      if (rc) return rc;
+      if ((rc = gather_into(l, su, par, idx))) return rc;
       TRACE(1, su);
       TRACE(3, su);
       if ((rc = pipe_graph(l, su, q, l->step_per))) return rc;
@@ -3526,30 +3415,16 @@ static int issue_actor(dra_dqn_learner* l, const dra_dqn_step_params* prm, int k
 // optimizer k-2; optimizer k-1 after actor(k-1)), hence bit-identical results; one launch boundary and one event
 // less per step on the actor chain.  A call with n_env == 0 flushes: it only issues the pending update.
 static int ag_graph(dra_dqn_learner* l, int n_env, int par, hipStream_t st) {
-  if (l->g_ag_ready[par] && l->g_ag_nenv[par] != n_env) {
-    (void)hipGraphExecDestroy(l->g_ag[par]);
-    l->g_ag_ready[par] = false;
-  }
-  if (!l->g_ag_ready[par]) {
-    hipGraph_t graph;
-    hipError_t b = hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal);
-    if (b != hipSuccess) return (int)b;
-    int rc = run_actor_steps(l, n_env, l->pa[par], st);
-    if (rc == DRA_OK) {
-      l->gb = par;
-      rc = launch_gather(l, st, l->prm_dev->idx);
-      l->gb = 0;
-    }
-    hipError_t e = hipStreamEndCapture(st, &graph);
+  CachedGraph& g = l->g_ag[par];
+  if (!g.ready || l->g_ag_nenv[par] != n_env) {
+    const int rc = g.capture(st, [&] {
+      const int rcb = run_actor_steps(l, n_env, l->pa[par], st);
+      return rcb != DRA_OK ? rcb : gather_into(l, st, par, l->prm_dev->idx);
+    });
     if (rc != DRA_OK) return rc;
-    if (e != hipSuccess) return (int)e;
-    DRA_HIP(hipGraphInstantiate(&l->g_ag[par], graph, nullptr, nullptr, 0));
-    (void)hipGraphDestroy(graph);
-    l->g_ag_ready[par] = true;
     l->g_ag_nenv[par] = n_env;
   }
-  DRA_HIP(hipGraphLaunch(l->g_ag[par], st));
-  return DRA_OK;
+  return g.launch(st);
 }
 
 static int step_pipelined2(dra_dqn_learner* l, const dra_dqn_step_params* prm, int do_update, hipStream_t su,
@@ -3566,10 +3441,7 @@ static int step_pipelined2(dra_dqn_learner* l, const dra_dqn_step_params* prm, i
     if (l->pa_valid && l->pa_cur != par) l->pa_valid = false;
     if (l->last_done) DRA_HIP(hipStreamWaitEvent(sa, l->last_done, 0));   // optimizer k-2 produced the copy this graph reads
     if (!l->pa_valid) {
-      l->pa_cur = par;
-      DRA_HIP(hipMemcpyAsync(l->pa[par], l->p, (size_t)l->c.n_params * sizeof(float), hipMemcpyDeviceToDevice, sa));
-      DRA_HIP(hipEventRecord(l->ev_join[0], sa));
-      l->pa_valid = true;
+      if ((rc = seed_actor_copy(l, sa, par))) return rc;
       seeded = true;
     }
     if ((rc = ag_graph(l, prm->n_env, par, sa))) return rc;
@@ -3656,17 +3528,14 @@ static inline bool fs_reached(uint64_t done32, uint64_t target) { return (uint32
 
 static int fs_wait_actor(dra_dqn_learner* l, uint64_t target) {
   if (fs_reached(fs_actor_done(l), target)) return DRA_OK;
-  const auto t0 = std::chrono::steady_clock::now();
+  HostTimeScope waited(l->host_wait_s);
   for (;;) {
     for (int i = 0; i < 64; ++i) {
-      if (fs_reached(fs_actor_done(l), target)) {
-        l->host_wait_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-        return DRA_OK;
-      }
+      if (fs_reached(fs_actor_done(l), target)) return DRA_OK;
       __builtin_ia32_pause();
     }
     if (*l->timeout_flag) return DRA_ETIMEDOUT;
-    if (std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() > 20.0) return DRA_ETIMEDOUT;
+    if (waited.seconds() > 20.0) return DRA_ETIMEDOUT;
   }
 }
 
@@ -3675,8 +3544,8 @@ static bool fs_eligible(const dra_dqn_learner* l, const dra_dqn_step_params* prm
   if (!l->fs || !stream_actor || !do_update || prm->n_env < 1 || l->step_per || l->keep_minibatch || l->tr_ev) return false;
   const int q = (int)(l->step_no & 3), qr = (q + 3) & 3;
   if (!l->pa_valid || l->pa_cur != qr) return false;                       // (a seed copy: event path)
-  if (!l->g_rd_ready[q] || !l->fs_graph[q]) return false;                  // (the first four updates capture on the event path)
-  if (!l->g_aring_ready[qr] || !l->fs_agraph[qr] || l->g_aring_nenv[qr] != prm->n_env) return false;
+  if (!l->g_rd[q].ready || !l->fs_graph[q]) return false;                  // (the first four updates capture on the event path)
+  if (!l->g_aring[qr].ready || !l->fs_agraph[qr] || l->g_aring_nenv[qr] != prm->n_env) return false;
   if (!l->aring_primed || l->aring_issued >= l->aring_pushed) return false;
   if (l->defer ? (l->defer_host && l->defer_q != qr) : l->defer_host) return false;   // (a pending fc4 segment this graph's riders do not finish)
   return true;
@@ -3733,9 +3602,10 @@ static int step_lane(dra_dqn_learner* l, const dra_dqn_step_params* prm, hipStre
     const auto& r = l->fs_arec[i];
     if (fs_reached(fs_actor_done(l), r.done_at)) continue;
     if (gather_reads_slots(l, prm->idx, r.slots, r.n)) {
-      const auto t0 = std::chrono::steady_clock::now();
-      DRA_HIP(hipStreamSynchronize(sa));
-      l->host_wait_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+      {
+        HostTimeScope waited(l->host_wait_s);
+        DRA_HIP(hipStreamSynchronize(sa));
+      }
       l->fs_stat[3]++;
       break;
     }
@@ -3880,12 +3750,11 @@ static int stage_acquire(dra_dqn_learner* l, int* k_out) {
   const int k = l->stage_k;
   l->stage_k = (k + 1) % 8;
   if (l->stage_used[k]) {
-    const auto t0 = std::chrono::steady_clock::now();
+    HostTimeScope waited(l->host_wait_s);
     DRA_HIP(hipEventSynchronize(l->stage_ev[k]));
     // GATHER_ON_UPDATE: the gather of that call read its indices from slot k on the UPDATE stream; the actor graph of the
     // call after it waited for that update, so its event (7 calls old) implies the gather is done
     if ((l->variant & DRA_VAR_GATHER_ON_UPDATE) && l->stage_used[(k + 1) % 8]) DRA_HIP(hipEventSynchronize(l->stage_ev[(k + 1) % 8]));
-    l->host_wait_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
   }
   l->stage_used[k] = true;
   *k_out = k;
@@ -3926,11 +3795,9 @@ DRA_API int dra_dqn_learner_step(dra_dqn_learner* l, const dra_dqn_step_params* 
                                  void* stream_actor) {
   if (!l || !prm || prm->n_env < 0 || prm->n_env > kMaxEnvSteps) return DRA_EINVAL;
   if (*l->timeout_flag) return DRA_ETIMEDOUT;   // a bounded device-side wait gave up: results are invalid
-  const auto t0 = std::chrono::steady_clock::now();
-  const int rc = learner_step_impl(l, prm, do_update, stream_update, stream_actor);
-  l->host_call_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+  HostTimeScope in_call(l->host_call_s);
   l->host_calls++;
-  return rc;
+  return learner_step_impl(l, prm, do_update, stream_update, stream_actor);
 }
 
 // dra_dqn_learner_step in two calls (device-drawn prioritized minibatch; include/deeprl_amd.h)
@@ -3947,21 +3814,20 @@ DRA_API int dra_dqn_learner_step_update(dra_dqn_learner* l, const dra_dqn_step_p
   int rc = step_split_check(l, prm, stream_update, stream_actor);
   if (rc) return rc;
   if (l->split_open) return DRA_EINVAL;
-  const auto t0 = std::chrono::steady_clock::now();
+  HostTimeScope in_call(l->host_call_s);
   l->profiling = false;
   rc = step_pipelined3(l, prm, 1, dra_stream(stream_update), dra_stream(stream_actor), -1, 1);
   if (rc == DRA_OK) {
     l->split_open = true;
     (void)hipStreamQuery(dra_stream(stream_update));     // on its way to the device before the host turns to the chain block
   }
-  l->host_call_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
   return rc;
 }
 DRA_API int dra_dqn_learner_step_actor(dra_dqn_learner* l, const dra_dqn_step_params* prm, void* stream_update, void* stream_actor) {
   int rc = step_split_check(l, prm, stream_update, stream_actor);
   if (rc) return rc;
   if (!l->split_open) return DRA_EINVAL;
-  const auto t0 = std::chrono::steady_clock::now();
+  HostTimeScope in_call(l->host_call_s);     // (a refused staging slot below is charged too)
   int k;
   if ((rc = stage_acquire(l, &k))) return rc;
   memcpy(&l->prm_stage[k], prm, kPrmHeadBytes);
@@ -3971,7 +3837,6 @@ DRA_API int dra_dqn_learner_step_actor(dra_dqn_learner* l, const dra_dqn_step_pa
     l->split_open = false;
     (void)hipStreamQuery(dra_stream(stream_actor));
   }
-  l->host_call_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
   l->host_calls++;
   return rc;
 }
@@ -4055,10 +3920,7 @@ static int learner_step_impl(dra_dqn_learner* l, const dra_dqn_step_params* prm,
     }
     if (do_update) l->pa_valid = false;
     if (do_update) {
-      const int64_t* pinned = (l->variant & DRA_VAR_PINNED_IDX) ? l->idx_stage + (size_t)k * 1024 : nullptr;
-      if (!pinned)
-        DRA_HIP(hipMemcpyAsync(l->idx, l->idx_stage + (size_t)k * 1024, (size_t)B * sizeof(int64_t), hipMemcpyHostToDevice, su));
-      if ((rc = launch_gather(l, su, pinned))) return rc;
+      if ((rc = gather_staged(l, su, k, 0))) return rc;
       // PER: beta >= 0 is a kernel argument that changes every update (eager chain); beta < 0 = read it from
       // sampling_prob[B] on the device (captured graph)
       if ((rc = l->step_per ? (l->step_beta < 0.f ? body_graph_per(l, su) : run_body(l, su, 1, l->step_beta, 0)) : body_graph(l, su)))
@@ -4081,10 +3943,7 @@ static int learner_step_impl(dra_dqn_learner* l, const dra_dqn_step_params* prm,
   }
   if (do_update) {
     if (l->actor_pending) DRA_HIP(hipStreamWaitEvent(su, l->ev_actor_done, 0));  // transitions of this step are in the ring
-    const int64_t* pinned = (l->variant & DRA_VAR_PINNED_IDX) ? l->idx_stage + (size_t)k * 1024 : nullptr;
-    if (!pinned)
-      DRA_HIP(hipMemcpyAsync(l->idx, l->idx_stage + (size_t)k * 1024, (size_t)B * sizeof(int64_t), hipMemcpyHostToDevice, su));
-    if ((rc = launch_gather(l, su, pinned))) return rc;
+    if ((rc = gather_staged(l, su, k, 0))) return rc;
     DRA_HIP(hipEventRecord(l->ev_gather_done, su));
   }
   const bool dbuf = l->variant & DRA_VAR_ACTOR_PARAMS;
@@ -4095,9 +3954,7 @@ static int learner_step_impl(dra_dqn_learner* l, const dra_dqn_step_params* prm,
     if (dbuf) {
       if (!l->pa_valid) {  // (re)seed the actor copy: first async step, or the parameters changed behind it
         if (l->last_done) DRA_HIP(hipStreamWaitEvent(sa, l->last_done, 0));   // after the last optimiser step ...
-        DRA_HIP(hipMemcpyAsync(l->pa[l->pa_cur], l->p, (size_t)l->c.n_params * sizeof(float), hipMemcpyDeviceToDevice, sa));
-        DRA_HIP(hipEventRecord(l->ev_join[0], sa));            // ... and before this step's (see below)
-        l->pa_valid = true;
+        if ((rc = seed_actor_copy(l, sa, l->pa_cur))) return rc;   // ... and before this step's (ev_join[0]: see below)
         seeded = true;
       }
       pact = l->pa[l->pa_cur];

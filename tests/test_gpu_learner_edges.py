@@ -13,7 +13,8 @@ library's conditions.  Here every case
                      gradient norm, parameters; after the first update both optimizer-state tensors of every parameter tensor (=
                      every gradient element, signed); at variant 0 the flat gradient too
   actor              set_env_steps + act (variant 0; the default's ring actor owns its environment: the pipelined cases check it):
-                     action values against float64, the stored action against the decision rule on the kernel's own values
+                     action values against float64, the stored action against the decision rule on the kernel's own values;
+                     n_env = 1 .. 8 twice through the five-entry graph cache against the eager launches, bit for bit
   pipelined          DQNLearnerBench(async_actor=True) at the library default, 8 agent steps on a 512-slot ring: per step as above
                      along oracle/async_schedule_oracle.py's schedule, stored actions, ring frames bit for bit; for batches 17 .. 32
                      the same seeds without synchronisation, with the chains cleared and with the opt-in chains set end on
@@ -166,6 +167,60 @@ def _check_actor(d, c, learner, ring, net):
         stored = int(d.ops._wrap_device_pointer(ring.pointers()[1], cap, torch.int64)[newest].item())
         assert stored == decided, "%s: stored action %d, the rule on the kernel's own values gives %d" % (c["name"], stored, decided)
     assert not learner.path_flags()["timed_out"]
+
+
+def test_actor_graph_cache_cycles_more_keys_than_slots(dra):
+    """The first-generation actor's graph cache keeps five (parameter block, n_env) entries; kMaxEnvSteps is 8.  Two learners on
+    the same seeded parameters and ring contents run act() with n_env = 1 .. 8, twice -- one through the cached graphs (the
+    second round meets evicted entries and recaptures them), one eagerly.  After every call the frames and actions of the slots
+    written and actor_q are the same bits on both (the same kernels on the same data), and the frames are the documented counter
+    hash."""
+    d = dra
+    from deeprl_amd.learner import DQNLearner
+    from oracle.synth_oracle import synth_transitions
+    cap, a, seed, period = 64, 4, 11, 5
+    p_np = fake_envs.numpy_params(fake_envs.nature_vanilla_shapes(a), 17)
+    sides = []
+    try:
+        for graph in (True, False):
+            ring = d.ops.Ring(cap, 7056, 8, 4, 1, E.GAMMA)
+            sides.append([ring, None, graph])
+            ring.fill_synthetic(0, cap, 0, seed, n_actions=a, done_period=period)
+            torch.cuda.synchronize()
+            net, tgt = d.VanillaNet(a, d.NatureConvBody()), d.VanillaNet(a, d.NatureConvBody())
+            for m in (net, tgt):
+                m.load_state_dict({k: torch.from_numpy(v) for k, v in p_np.items()})
+            sides[-1][1] = DQNLearner(net, tgt, ring, 1, a, E.GAMMA, 5.0, 0.00025, 0.95, 0.01, centered=True, env_seed=seed,
+                                      env_done_period=period, variant=0, cu_partition=False)
+        schedule = list(range(1, 9)) * 2
+        want_frames, _, _, _ = synth_transitions(cap, sum(schedule), 7056, seed=seed, n_actions=a, done_period=period)
+        rng = np.random.RandomState(5)
+        pos, done = 0, 0
+        for call, n in enumerate(schedule):
+            slots = [(pos + e) % cap for e in range(n)]
+            rnd = [int(rng.randint(a)) for _ in range(n)]
+            dice = [float(rng.rand()) for _ in range(n)]
+            got = []
+            for ring, learner, graph in sides:
+                learner.set_env_steps(slots, [cap + done + e for e in range(n)], rnd, dice, [0.5] * n)
+                learner.act(use_graph=graph)
+                learner.synchronize()
+                frames = d.ops._wrap_device_pointer(ring.pointers()[0], cap * 7056, torch.uint8).cpu().numpy().reshape(cap, 7056)
+                actions = d.ops._wrap_device_pointer(ring.pointers()[1], cap, torch.int64).cpu().numpy()
+                got.append((frames[slots].copy(), actions[slots].copy(), learner.actor_q.cpu().numpy().copy()))
+            where = "call %d (n_env %d)" % (call, n)
+            assert np.array_equal(got[0][0], got[1][0]), "%s: ring frames differ between graph and eager" % where
+            assert np.array_equal(got[0][1], got[1][1]), "%s: stored actions differ between graph and eager" % where
+            assert np.array_equal(got[0][2].view(np.uint32), got[1][2].view(np.uint32)), "%s: actor_q differs" % where
+            assert np.array_equal(got[0][0], want_frames[done:done + n]), "%s: the frames are not the counter hash" % where
+            pos, done = (pos + n) % cap, done + n
+        for _, learner, _ in sides:
+            assert not learner.path_flags()["timed_out"]
+    finally:
+        for ring, learner, _ in sides:
+            if learner is not None:
+                learner.close()
+            ring.close()
 
 
 # ---- the pipelined path ----------------------------------------------------------------------------------------------------
