@@ -218,6 +218,10 @@ int dra_conv_fwd_chain(const void* frames, const int64_t* idx, int64_t* idx_copy
                        unsigned* done_counters, const unsigned* epoch, int* timeout_flag, const DraFc4Rider* rider,
                        unsigned* rider_count, int* rider_pending, int* rider_valid, void* stream);
 
+// the level state of those counters after `epoch` chains (every counter = epoch x its arrivals per chain, modulo 2^32) into a host
+// image of kFwdChainCounters words (null: none); arrivals[0..2) = arrivals per chain on a {conv1 -> conv2, conv2 -> conv3} counter
+void dra_conv_fwd_chain_level(unsigned epoch, unsigned* image, unsigned* arrivals);
+
 // fused.hip (library-internal), DRA_VAR_BWD_CHAIN: conv3's, conv2's and conv1's backward launches (one-pass roles, late fold) of a
 // minibatch of at most 32 as ONE launch in dependency order; counters = dra_bwd_chain_counters() zeroed unsigned, never reset
 int dra_bwd_chain_counters(void);
@@ -238,3 +242,8 @@ int dra_conv_bwd_chain(const float* dy3, const float* y2, const float* wt3, floa
                        const dra_fold_seg* fold3, const dra_fold_seg* fold2, float* grad, double* partials3, int* n_partials3,
                        double* partials2, int* n_partials2, double* reset_slots, int n_reset, unsigned* counters,
                        const unsigned* epoch, int* timeout_flag, const DraBwdChainFc* fc, void* stream);
+// the level state of `counters` after `epoch` chains of a minibatch of `batch` (fc_in_features > 0: with the DRA_VAR_BWD_CHAIN_FC
+// roles) into a host image of dra_bwd_chain_counters() words (null: none); arrivals[0..5) = arrivals per chain on a counter of
+// {conv3 input gradient (per sample), conv2 input gradient (per sample), conv3 weight gradient, conv2 weight gradient, fc4 input
+// gradient (0 without the FC roles)}
+int dra_bwd_chain_level(int batch, int fc_in_features, unsigned epoch, unsigned* image, unsigned* arrivals);

@@ -246,6 +246,15 @@ struct MegaSync {
 };
 constexpr unsigned long long kMegaWaitTicks = 5000000ull;   // 50 ms of s_memrealtime (100 MHz)
 
+// Has an arrival counter reached `target`?  The counters that are never reset and their targets (epoch x arrivals per epoch) both
+// wrap modulo 2^32, so the comparison is by modular distance: a plain `count < target` lets every consumer through in the update
+// whose target wraps to a small number (or to 0: a power-of-two arrival count) while the counter is still just below 2^32.  Valid
+// while the outstanding distance stays under 2^31 -- it is at most one epoch's arrivals, a few hundred.  The ONE statement of the
+// device-side waits (mega_wait); tests/test_chain_counter_wrap_host.py runs it on the host around every wrap.
+__host__ __device__ __forceinline__ bool chain_reached(unsigned count, unsigned target) {
+  return (unsigned)(count - target) < 0x80000000u;
+}
+
 __device__ __forceinline__ void mega_publish(const MegaSync& ms) {
   if (!ms.done) return;
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -257,7 +266,7 @@ __device__ __forceinline__ void mega_wait(const MegaSync& ms) {
   if (threadIdx.x == 0) {
     const unsigned long long t0 = wall_clock64();
     const unsigned target = ms.epoch ? (*ms.epoch + ms.epoch_bias) * ms.wait_target : ms.wait_target;
-    while (__hip_atomic_load(ms.wait, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < target) {
+    while (!chain_reached(__hip_atomic_load(ms.wait, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), target)) {
       if (ms.slow) __builtin_amdgcn_s_sleep(16);
       else __builtin_amdgcn_s_sleep(1);
       if (wall_clock64() - t0 > kMegaWaitTicks) {

@@ -1480,8 +1480,29 @@ static int launch_conv1_u8_tp(const ConvV2Args& a, int nz, hipStream_t st) {
 // workgroups dispatched before it), every (net, sample) has an arrival counter per layer: a producer stores agent-scope,
 // completes its stores and counts itself; a consumer requests its weights FIRST, then polls its sample's counter (bounded), then
 // reads the planes with agent-scope loads.  The counters are never reset: a wait is for (epoch + 1) x (workgroups per sample)
-// arrivals, `epoch` = chains completed, bumped by the update's head kernel (learner.hip).  Same arithmetic in the same order as
+// arrivals, `epoch` = chains completed, bumped by the update's head kernel (learner.hip); counter and product wrap modulo 2^32
+// and are compared by modular distance (common.h chain_reached).  Same arithmetic in the same order as
 // the three launches: bit-identical activations (tests/test_gpu_agents.py::test_forward_chain_is_bit_identical).
+// arrivals per chain on one (net, sample) counter = the producing layer's workgroups per sample: the kernel's waits, the grid and
+// the level state (dra_conv_fwd_chain_level) all take them from here
+constexpr unsigned kFwdChainArrivals1 = V2Tile<VG1, 1>::TPG * (VG1::OC / 32);   // conv1 -> conv2
+constexpr unsigned kFwdChainArrivals2 = V2Tile<VG2, 1>::TPG * (VG2::OC / 32);   // conv2 -> conv3
+constexpr unsigned kFwdChainWgs3 = V2Tile<VG3, 1>::TPG * (VG3::OC / 32);        // (conv3's workgroups per sample: nobody waits for them)
+constexpr int kFwdChainDone2 = DRA_MAX_Z * 32 * kChainPad;                      // conv2's counters follow conv1's
+static_assert(2 * kFwdChainDone2 == kFwdChainCounters, "two counter classes");
+
+// Library-internal (actor_env.h): the counters as they stand between two updates after `epoch` chains -- every counter holds
+// epoch x (its arrivals per chain), modulo 2^32 -- written into a HOST image of kFwdChainCounters words; arrivals[0..2) = the
+// arrivals per chain of {conv1 -> conv2, conv2 -> conv3}.  For dra_dqn_learner_chain_set_epoch.
+void dra_conv_fwd_chain_level(unsigned epoch, unsigned* image, unsigned* arrivals) {
+  arrivals[0] = kFwdChainArrivals1;
+  arrivals[1] = kFwdChainArrivals2;
+  if (!image) return;
+  for (int i = 0; i < kFwdChainDone2; ++i) {
+    image[i] = epoch * kFwdChainArrivals1;
+    image[kFwdChainDone2 + i] = epoch * kFwdChainArrivals2;
+  }
+}
 struct FwdChainArgs {
   ConvV2Args c1, c2, c3;
   unsigned* done1;           // [nz * batch] x kChainPad: arrivals of conv1's workgroups per (net, sample), one 128-byte line each
@@ -1534,7 +1555,7 @@ __global__ void __launch_bounds__(256, 4) conv_fwd_chain_kernel(const FwdChainAr
   const int f2 = a.n1 + (a.n1 >= a.rider_after ? a.n_riders : 0), f3 = a.n1 + a.n2 + (a.n1 + a.n2 >= a.rider_after ? a.n_riders : 0);
   const int f1 = 0 >= a.rider_after ? a.n_riders : 0;
   if (b < a.n1) {
-    constexpr int TPG = V2Tile<VG1, 1>::TPG, per = TPG * (VG1::OC / 32);
+    constexpr int TPG = V2Tile<VG1, 1>::TPG, per = (int)kFwdChainArrivals1;
     const int v = a.c1.xcd_order ? xcd_order(b, f1, a.n1 / per, per) : b;
     const int g = v / per, w = v - g * per;
     const int bz = g / batch, bi = g - bz * batch;
@@ -1545,24 +1566,24 @@ __global__ void __launch_bounds__(256, 4) conv_fwd_chain_kernel(const FwdChainAr
   }
   b -= a.n1;
   if (b < a.n2) {
-    constexpr int TPG = V2Tile<VG2, 1>::TPG, ny = VG2::OC / 32, per = TPG * ny;
+    constexpr int TPG = V2Tile<VG2, 1>::TPG, ny = VG2::OC / 32, per = (int)kFwdChainArrivals2;
     const int v = a.c2.xcd_order ? xcd_order(b, f2, a.n2 / per, per) : b;
     const int g = v / per, w = v - g * per;
     const int bz = g / batch, bi = g - bz * batch, grp = w / ny, by = w - grp * ny;
     MegaSync ms;
-    ms.wait = a.done1 + g * kChainPad; ms.wait_target = V2Tile<VG1, 1>::TPG * (VG1::OC / 32); ms.epoch = a.epoch; ms.timeout_flag = a.timeout_flag;
+    ms.wait = a.done1 + g * kChainPad; ms.wait_target = kFwdChainArrivals1; ms.epoch = a.epoch; ms.timeout_flag = a.timeout_flag;
     ms.done = a.done2 + g * kChainPad;
     conv_fwd_v2_body<VG2, false, 1, 4, false, true, true>(a.c2, none, bi * TPG + grp, by, bz, false, ms);
     return;
   }
   b -= a.n2;
   {
-    constexpr int TPG = V2Tile<VG3, 1>::TPG, ny = VG3::OC / 32, per = TPG * ny;
+    constexpr int TPG = V2Tile<VG3, 1>::TPG, ny = VG3::OC / 32, per = (int)kFwdChainWgs3;
     const int v = a.c3.xcd_order ? xcd_order(b, f3, a.n3 / per, per) : b;
     const int g = v / per, w = v - g * per;
     const int bz = g / batch, bi = g - bz * batch, grp = w / ny, by = w - grp * ny;
     MegaSync ms;
-    ms.wait = a.done2 + g * kChainPad; ms.wait_target = V2Tile<VG2, 1>::TPG * (VG2::OC / 32); ms.epoch = a.epoch; ms.timeout_flag = a.timeout_flag;
+    ms.wait = a.done2 + g * kChainPad; ms.wait_target = kFwdChainArrivals2; ms.epoch = a.epoch; ms.timeout_flag = a.timeout_flag;
     conv_fwd_v2_body<VG3, false, 1, 4, false, false, true>(a.c3, none, bi * TPG + grp, by, bz, false, ms);
   }
 }
@@ -1608,10 +1629,10 @@ int dra_conv_fwd_chain(const void* frames, const int64_t* idx, int64_t* idx_copy
     c->xcd_order = dra_xcd_order_enabled();
   }
   a.c1.coef = u8_coef;
-  a.done1 = done_counters; a.done2 = done_counters + DRA_MAX_Z * 32 * kChainPad; a.epoch = epoch; a.timeout_flag = timeout_flag;
-  a.n1 = nz * batch * V2Tile<VG1, 1>::TPG * (VG1::OC / 32);
-  a.n2 = nz * batch * V2Tile<VG2, 1>::TPG * (VG2::OC / 32);
-  a.n3 = nz * batch * V2Tile<VG3, 1>::TPG * (VG3::OC / 32);
+  a.done1 = done_counters; a.done2 = done_counters + kFwdChainDone2; a.epoch = epoch; a.timeout_flag = timeout_flag;
+  a.n1 = nz * batch * (int)kFwdChainArrivals1;
+  a.n2 = nz * batch * (int)kFwdChainArrivals2;
+  a.n3 = nz * batch * (int)kFwdChainWgs3;
   a.n_riders = 0; a.rider_after = 0;
   if (rider) {
     if (!rider_count || !rider_pending || !rider_valid) return DRA_EINVAL;

@@ -442,6 +442,33 @@ bwd_chain_kernel(const FCD fd, const FCW fw, const HeadWgradRole fh, const BD3 d
 
 constexpr int kBwdChainCounters = (2 * 32 + 3) * kChainLine;
 int dra_bwd_chain_counters(void) { return kBwdChainCounters; }
+// the counter lines: conv3's input-gradient workgroups per sample, conv2's, conv3's weight-gradient workgroups (all samples),
+// conv2's, fc4's input-gradient workgroups (DRA_VAR_BWD_CHAIN_FC)
+constexpr int kBwdChainA = 0, kBwdChainB = 32 * kChainLine, kBwdChainW3 = 64 * kChainLine, kBwdChainW2 = 65 * kChainLine,
+              kBwdChainF = 66 * kChainLine;
+// arrivals per chain on one counter of each class = the producing role's workgroups (per sample / in all): the waits of
+// dra_conv_bwd_chain and the level state (dra_bwd_chain_level) both take them from here
+struct BwdChainArrivals { unsigned d3, d2, w3, w2, fd; };
+static int fc_dgrad_tiles(int in_features) { return (in_features + 31) / 32; }
+static BwdChainArrivals bwd_chain_arrivals(int batch, int fc_in_features) {
+  WG3l w3; w3.B = batch;
+  WG2l w2; w2.B = batch;
+  BwdChainArrivals n;
+  n.d3 = BD3::WGS_PER_SAMPLE; n.d2 = BD2::WGS_PER_SAMPLE; n.w3 = (unsigned)w3.blocks(); n.w2 = (unsigned)w2.blocks();
+  n.fd = fc_in_features > 0 ? (unsigned)(fc_dgrad_tiles(fc_in_features) * ((batch + 31) / 32)) : 0u;
+  return n;
+}
+int dra_bwd_chain_level(int batch, int fc_in_features, unsigned epoch, unsigned* image, unsigned* arrivals) {
+  if (batch < 1 || batch > 32 || !arrivals) return DRA_EINVAL;
+  const BwdChainArrivals n = bwd_chain_arrivals(batch, fc_in_features);
+  arrivals[0] = n.d3; arrivals[1] = n.d2; arrivals[2] = n.w3; arrivals[3] = n.w2; arrivals[4] = n.fd;
+  if (!image) return DRA_OK;
+  for (int i = 0; i < 32 * kChainLine; ++i) { image[kBwdChainA + i] = epoch * n.d3; image[kBwdChainB + i] = epoch * n.d2; }
+  for (int i = 0; i < kChainLine; ++i) {
+    image[kBwdChainW3 + i] = epoch * n.w3; image[kBwdChainW2 + i] = epoch * n.w2; image[kBwdChainF + i] = epoch * n.fd;
+  }
+  return DRA_OK;
+}
 
 // Library-internal (actor_env.h).  counters: kBwdChainCounters zeroed unsigned (never reset); *epoch = updates whose head kernel
 // has run (so: chains launched, this one included).  The fold arguments are those of dra_conv_bwd_fused_fold (layer 2: conv3's
@@ -472,11 +499,11 @@ int dra_conv_bwd_chain(const float* dy3, const float* y2, const float* wt3, floa
   n.fd = n.fw = n.fh = 0;
   n.d3 = d3.blocks(); n.w3 = w3.blocks(); n.d2 = d2.blocks(); n.w2 = w2.blocks(); n.w1 = w1.blocks(); n.f3 = f3.blocks(); n.f2 = f2.blocks();
   *n_partials3 = n.f3; *n_partials2 = n.f2;
-  unsigned* cA = counters;                       // conv3's input-gradient workgroups, per sample
-  unsigned* cB = counters + 32 * kChainLine;     // conv2's
-  unsigned* cW3 = counters + 64 * kChainLine;    // conv3's weight-gradient workgroups, all samples
-  unsigned* cW2 = counters + 65 * kChainLine;
-  unsigned* cF = counters + 66 * kChainLine;     // fc4's input-gradient workgroups (DRA_VAR_BWD_CHAIN_FC)
+  unsigned *cA = counters + kBwdChainA, *cB = counters + kBwdChainB, *cW3 = counters + kBwdChainW3, *cW2 = counters + kBwdChainW2,
+           *cF = counters + kBwdChainF;
+  const BwdChainArrivals na = bwd_chain_arrivals(batch, fc ? fc->in_features : 0);
+  // (what the consumers wait for is what the producers' grids deliver)
+  if (n.w3 != (int)na.w3 || n.w2 != (int)na.w2 || n.d3 != (int)na.d3 * batch || n.d2 != (int)na.d2 * batch) return DRA_EINVAL;
   ChainHook base;
   base.epoch = epoch; base.epoch_bias = 0; base.timeout_flag = timeout_flag;
   FCD fd = {};
@@ -489,13 +516,13 @@ int dra_conv_bwd_chain(const float* dy3, const float* y2, const float* wt3, floa
       return DRA_EINVAL;
     // (the roles of dra_fc_bwd_fused_sq, argument for argument; the input gradient IS dy3)
     fd.dy = fc->dh4; fd.w = fc->w4; fd.xact = fc->x3; fd.dx = const_cast<float*>(dy3); fd.B = batch; fd.I = fc->in_features; fd.act = act;
-    fd.tiles_n = (fc->in_features + 31) / 32;
+    fd.tiles_n = fc_dgrad_tiles(fc->in_features);
     fd.hook = base; fd.hook.done = cF;
     fw.dy = fc->dh4; fw.x = fc->x3; fw.dw = fc->dw4; fw.db = fc->db4; fw.partials = fc->sq_partials; fw.B = batch; fw.O = 512;
     fw.I = fc->in_features; fw.tiles_o = 512 / 32; fw.groups_i = (fd.tiles_n + kFcWgradNI - 1) / kFcWgradNI;
     fh.dq = fc->dq; fh.h4 = fc->h4; fh.dwh = fc->dwh; fh.dbh = fc->dbh; fh.B = batch; fh.A = fc->n_actions;
     if (fc->head_action && fc->head_group > 1 && fc->n_actions % fc->head_group == 0) { fh.action = fc->head_action; fh.group = fc->head_group; }
-    n.fd = fd.tiles_n * ((batch + 31) / 32); n.fw = fw.blocks(); n.fh = 2 * fc->n_actions;
+    n.fd = (int)na.fd; n.fw = fw.blocks(); n.fh = 2 * fc->n_actions;
     fh.partials = fc->sq_partials + n.fw;
     *fc->n_sq_partials = n.fw + 2 * fc->n_actions;
   }
@@ -503,15 +530,15 @@ int dra_conv_bwd_chain(const float* dy3, const float* y2, const float* wt3, floa
   w3.hook = base; w3.hook.done = cW3;
   if (fc) {
     // (480 workgroups on ONE counter: polled slowly, like the folds' -- tight polls on the line starve the producers' adds)
-    d3.hook.wait = cF; d3.hook.wait_stride = 0; d3.hook.wait_target = (unsigned)n.fd; d3.hook.slow = 1;
-    w3.hook.wait = cF; w3.hook.wait_stride = 0; w3.hook.wait_target = (unsigned)n.fd; w3.hook.slow = 1;
+    d3.hook.wait = cF; d3.hook.wait_stride = 0; d3.hook.wait_target = na.fd; d3.hook.slow = 1;
+    w3.hook.wait = cF; w3.hook.wait_stride = 0; w3.hook.wait_target = na.fd; w3.hook.slow = 1;
   }
-  d2.hook = base; d2.hook.wait = cA; d2.hook.wait_stride = kChainLine; d2.hook.wait_target = BD3::WGS_PER_SAMPLE;
+  d2.hook = base; d2.hook.wait = cA; d2.hook.wait_stride = kChainLine; d2.hook.wait_target = na.d3;
   d2.hook.done = cB; d2.hook.done_stride = kChainLine;
-  w2.hook = base; w2.hook.wait = cA; w2.hook.wait_stride = kChainLine; w2.hook.wait_target = BD3::WGS_PER_SAMPLE; w2.hook.done = cW2;
-  w1.hook = base; w1.hook.wait = cB; w1.hook.wait_stride = kChainLine; w1.hook.wait_target = BD2::WGS_PER_SAMPLE;
-  f3.hook = base; f3.hook.wait = cW3; f3.hook.wait_target = (unsigned)n.w3; f3.hook.slow = 1;
-  f2.hook = base; f2.hook.wait = cW2; f2.hook.wait_target = (unsigned)n.w2; f2.hook.slow = 1;
+  w2.hook = base; w2.hook.wait = cA; w2.hook.wait_stride = kChainLine; w2.hook.wait_target = na.d3; w2.hook.done = cW2;
+  w1.hook = base; w1.hook.wait = cB; w1.hook.wait_stride = kChainLine; w1.hook.wait_target = na.d2;
+  f3.hook = base; f3.hook.wait = cW3; f3.hook.wait_target = na.w3; f3.hook.slow = 1;
+  f2.hook = base; f2.hook.wait = cW2; f2.hook.wait_target = na.w2; f2.hook.slow = 1;
   constexpr int fa = BD3::LDS_FLOATS > WG3l::LDS_FLOATS ? BD3::LDS_FLOATS : WG3l::LDS_FLOATS;
   constexpr int fb = BD2::LDS_FLOATS > WG2l::LDS_FLOATS ? BD2::LDS_FLOATS : WG2l::LDS_FLOATS;
   constexpr int fcl = WG1u::LDS_FLOATS > FoldRole::LDS_FLOATS ? WG1u::LDS_FLOATS : FoldRole::LDS_FLOATS;

@@ -27,6 +27,7 @@
 #include <stddef.h>
 #include <stdlib.h>
 #include <string.h>
+#include <vector>
 
 enum { K_GATHER, K_CONV1_F, K_CONV2_F, K_CONV3_F, K_FC4_F, K_HEAD, K_HEAD_BW, K_FC4_BW, K_FC4_BX, K_CONV3_BW, K_CONV3_BX,
        K_CONV2_BW, K_CONV2_BX, K_CONV1_BW, K_NORM, K_STEP, K_COUNT };
@@ -2149,6 +2150,48 @@ DRA_API int dra_dqn_learner_chain_replay(dra_dqn_learner* l, int which, int reps
   out_us[0] = us[0];
   out_us[1] = us[1];
   return *l->timeout_flag ? DRA_ETIMEDOUT : DRA_OK;   // (a chain workgroup's bounded wait gave up: the reading is void)
+}
+
+// Test aid: puts the chained launches' never-reset arrival counters where they stand after `epoch` updates (< 2^32), so that a test
+// reaches the updates in which the 32-bit counters and their targets wrap (tests/test_gpu_chain_counter_wrap.py) without running
+// millions of updates.  Leaves the lane, flushes a pending fc4 segment and synchronises, as dra_dqn_learner_chain_replay does;
+// then writes the epoch word of the update's chains (and of the target-ahead chains, where the learner has them) and every
+// arrival counter's level state (unsigned)(epoch x its arrivals per epoch) -- the state the counters have between two updates
+// (see chain_replay above).  The arrival counts come from the launch set-up's own expressions (conv_v2.hip
+// dra_conv_fwd_chain_level, fused.hip dra_bwd_chain_level).  arrivals[0..8) = arrivals per epoch on one counter of each class,
+// 0 = this learner's launches do not use the class: [0] forward conv1 -> conv2, [1] forward conv2 -> conv3 (per net and sample),
+// [2] backward conv3 / [3] conv2 input gradient (per sample), [4] conv3 / [5] conv2 weight gradient (all samples), [6] fc4 input
+// gradient (DRA_VAR_BWD_CHAIN_FC); [7] = 1 when the target-ahead chains were set as well.  Changes no numerics; not on a timed
+// path.  DRA_EINVAL on a learner without chained launches.
+DRA_API int dra_dqn_learner_chain_set_epoch(dra_dqn_learner* l, uint64_t epoch, int64_t* arrivals, int n_arrivals, void* stream) {
+  if (!l || !arrivals || n_arrivals < 8 || epoch > 0xffffffffull) return DRA_EINVAL;
+  if (!l->fchain && !l->bchain) return DRA_EINVAL;
+  if (int rcl = fs_leave_any(l)) return rcl;
+  hipStream_t st = dra_stream(stream);
+  if (int rcf = flush_fc4(l, st)) return rcf;
+  DRA_HIP(hipStreamSynchronize(st));
+  if (l->ah_stream) DRA_HIP(hipStreamSynchronize(l->ah_stream));
+  const unsigned e = (unsigned)epoch;
+  for (int i = 0; i < 8; ++i) arrivals[i] = 0;
+  unsigned fa[2] = {0, 0}, ba[5] = {0, 0, 0, 0, 0};
+  std::vector<unsigned> img((size_t)kFwdChainCounters + 1);
+  dra_conv_fwd_chain_level(e, img.data(), fa);
+  img[kFwdChainCounters] = e;                      // the epoch word (both chains of the update read it)
+  DRA_HIP(hipMemcpy(l->fchain_dev, img.data(), img.size() * sizeof(unsigned), hipMemcpyHostToDevice));
+  if (l->fchain) { arrivals[0] = fa[0]; arrivals[1] = fa[1]; }
+  for (int k = 0; k < 2; ++k)
+    if (l->ah_chain[k]) {
+      DRA_HIP(hipMemcpy(l->ah_chain[k], img.data(), img.size() * sizeof(unsigned), hipMemcpyHostToDevice));
+      arrivals[7] = 1;
+    }
+  if (l->bchain) {
+    const bool fc = (l->variant & DRA_VAR_BWD_CHAIN_FC) != 0;
+    std::vector<unsigned> bimg((size_t)dra_bwd_chain_counters());
+    if (int rcb = dra_bwd_chain_level(l->c.batch, fc ? 3136 : 0, e, bimg.data(), ba)) return rcb;
+    DRA_HIP(hipMemcpy(l->bchain_dev, bimg.data(), bimg.size() * sizeof(unsigned), hipMemcpyHostToDevice));
+    for (int i = 0; i < 5; ++i) arrivals[2 + i] = ba[i];
+  }
+  return DRA_OK;
 }
 
 // The minibatch the most recently issued update consumed (device pointers into the learner's own buffers: uint8

@@ -408,6 +408,19 @@ class DQNLearner:
         lib.dra_dqn_learner_chain_replay(self.h, {"fwd": 0, "bwd": 1}[which], int(reps), out, self._sp())
         return float(out[0]), float(out[1])
 
+    CHAIN_COUNTER_CLASSES = ("fwd_conv1_to_conv2", "fwd_conv2_to_conv3", "bwd_conv3_dgrad", "bwd_conv2_dgrad", "bwd_conv3_wgrad",
+                             "bwd_conv2_wgrad", "bwd_fc4_dgrad")
+
+    def chain_set_epoch(self, epoch):
+        """Test aid (dra_dqn_learner_chain_set_epoch): the chained launches' never-reset 32-bit arrival counters and their epoch
+        word as they stand after `epoch` updates.  Returns {counter class: arrivals per epoch} of the classes this learner's
+        launches use, plus "target_ahead": whether the target-ahead chains were set as well.  Synchronises."""
+        out = (ctypes.c_int64 * 8)()
+        lib.dra_dqn_learner_chain_set_epoch(self.h, int(epoch), out, 8, self._sp())
+        res = {k: int(out[i]) for i, k in enumerate(self.CHAIN_COUNTER_CLASSES) if out[i]}
+        res["target_ahead"] = bool(out[7])
+        return res
+
     def synchronize(self):
         # (DRA_VAR_DEFER_FC4: a pending fc4 segment of the last optimizer step is completed first -- after this call the
         # parameters, the optimizer state and the actor copies are what optimizer.step() of DQN_agent.py:133 left)

@@ -731,6 +731,15 @@ int dra_dqn_learner_kernel_replay(dra_dqn_learner* learner, int kernel, int reps
  * difference is the chained kernel's own duration (rocprofv3's figure for it, less the deferred fc4 optimizer segment's riders:
  * a replay never steps parameters, a pending segment is flushed first).  Runs on the workspaces of the last update.  Synchronises. */
 int dra_dqn_learner_chain_replay(dra_dqn_learner* learner, int which, int reps, float* out_us, void* stream);
+/* test aid: the chained launches hand data between workgroups through 32-bit arrival counters that are never reset (a wait is for
+ * epoch x arrivals-per-epoch arrivals, compared modulo 2^32).  Puts this learner's chains where they stand after `epoch` (< 2^32)
+ * updates: synchronises (pending fc4 segment flushed, event-free lane left), sets the epoch word of the update's chains and of
+ * the target-ahead chains, and every arrival counter to (unsigned)(epoch x its arrivals per epoch).  arrivals[0..8) (n_arrivals >=
+ * 8) = arrivals per epoch on one counter of each class, 0 where this learner's launches do not use the class: [0] forward conv1 ->
+ * conv2, [1] forward conv2 -> conv3, [2] backward conv3 / [3] conv2 input gradient (per sample), [4] conv3 / [5] conv2 weight
+ * gradient, [6] fc4 input gradient (DRA_VAR_BWD_CHAIN_FC), [7] 1 = target-ahead chains set too.  Changes no numerics.  DRA_EINVAL
+ * on a learner without chained launches (tests/test_gpu_chain_counter_wrap.py). */
+int dra_dqn_learner_chain_set_epoch(dra_dqn_learner* learner, uint64_t epoch, int64_t* arrivals, int n_arrivals, void* stream);
 /* the minibatch the most recently issued update consumed (device pointers into the learner's buffers: u8 states /
  * next states [B][4][84][84], int64 actions [B], f32 rewards / masks [B]); for checkers, after a synchronise */
 int dra_dqn_learner_last_minibatch(dra_dqn_learner* learner, void** state, void** next_state, void** action, void** reward,
