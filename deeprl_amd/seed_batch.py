@@ -23,7 +23,18 @@ dist_mlp.Step on dra_dist_mlp_act_lanes / dra_dist_mlp_update_lanes (DistFeature
 
 What the lanes cannot be is named in a ValueError: an agent that stayed on the host path (the module's why_not's reason: n_step >
 1, a PrioritizedReplay, another network, ...), the module-path update, fused_eval, an optimiser other than RMSprop, lanes that
-differ in anything the launches share (first_mismatch), more than MAX_LANES seeds."""
+differ in anything the launches share (first_mismatch), more than MAX_LANES seeds.
+
+`device_draws=True` (off by default; every head has it, it lives in FeatureSeeds) takes the lanes' draws on the device WITHOUT
+changing the stream: each lane's RandomState.get_state() (key, pos; a cached Gaussian is refused) is uploaded once, and
+dra_np_mt_draw_lanes (csrc/np_mt.hip), first launch of both regions, draws lane k's step from lane k's state in numpy's own
+arithmetic -- randint's masked rejection, rand's two words, the twist when pos reaches 624 -- and fills the very blocks the act and
+update lane kernels read (lane_layout stays the one source of the offsets).  prepare() then evaluates the schedule once, sends one
+small common block (first slot, the ring's pos / size after the step's appends, the k epsilons: dra_np_mt_common) and keeps the
+per-lane counters; it makes no numpy draw and stages nothing per lane, and last_draws is None -- fetch_draws(k) copies the last
+step's values back from the lane's block.  rng_tail(k) and close() copy the lane's state back into rngs[k] first, so the generator
+handed out stands where the single run's np.random stands.  A ring state without a valid index is refused with a ValueError
+before the step; shapes dra_np_mt_lanes_supported rejects are refused at construction."""
 import ctypes
 
 import numpy as np
@@ -46,6 +57,52 @@ class OptimLane(ctypes.Structure):
 class CopyLane(ctypes.Structure):
     """Mirror of dra_copy_lane."""
     _fields_ = [("dst", ctypes.c_void_p), ("src", ctypes.c_void_p), ("n", ctypes.c_int64)]
+
+
+class NpMtCommon(ctypes.Structure):
+    """Mirror of dra_np_mt_common: what a step of the device draws shares among the lanes."""
+    _fields_ = [("slot0", ctypes.c_int64), ("ring_pos", ctypes.c_int64), ("ring_size", ctypes.c_int64), ("eps", ctypes.c_double * 8)]
+
+
+class NpMtState(ctypes.Structure):
+    """Mirror of dra_np_mt_state: a lane's RandomState.get_state() as the draw kernel keeps it."""
+    _fields_ = [("key", ctypes.c_uint32 * 624), ("pos", ctypes.c_int32), ("reserved", ctypes.c_int32 * 3)]
+
+
+NP_MT_STATE_WORDS = ctypes.sizeof(NpMtState) // 4      # DRA_NP_MT_STATE_WORDS
+NP_MT_ERR_BUDGET = 1 << 30                             # DRA_NP_MT_ERR_BUDGET
+
+
+def np_mt_words(rs):
+    """The get_state() of RandomState `rs` as the uint32 [NP_MT_STATE_WORDS] words of a dra_np_mt_state.  A state that holds a
+    cached Gaussian is refused: the device draws have no Gaussian, and dropping the cached value would change the stream."""
+    kind, key, pos, has_gauss, _ = rs.get_state()
+    if kind != 'MT19937' or has_gauss != 0:
+        raise ValueError("device_draws: the lane's np.random state %s, which the draw kernel cannot carry"
+                         % ("is a %s's" % kind if kind != 'MT19937' else "holds a cached Gaussian (has_gauss != 0)"))
+    words = np.zeros(NP_MT_STATE_WORDS, dtype=np.uint32)
+    words[:624], words[624] = key, pos
+    return words
+
+
+def np_mt_restore(rs, words):
+    """set_state of `rs` from the words of a dra_np_mt_state."""
+    rs.set_state(('MT19937', np.array(words[:624], dtype=np.uint32), int(words[624]), 0, 0.0))
+    return rs
+
+
+def ring_after(pos, size, memory_size, k):
+    """(pos, size) of a UniformReplay after advance(k)."""
+    for _ in range(k):
+        if pos >= size:
+            size += 1
+        pos = (pos + 1) % memory_size
+    return pos, size
+
+
+def valid_index_count(pos, size):
+    """How many slots UniformReplay.valid_index accepts at history_length = n_step = 1."""
+    return max(pos - 1, 0) + max(size - 1 - pos, 0)
 
 
 class LaneTable:
@@ -112,9 +169,9 @@ def lane_why_not(agent, module=dqn_mlp):
 
 class FeatureSeeds:
     """What the seed lanes of every head share: see the module's docstring.  `make_config(seed)` -> a Config for the subclass's
-    agent class; its switch is set here.  Surface: step(), total_steps (of every lane: they advance together), episodes(k),
+    agent class; its switch is set here; `device_draws`: the module's docstring.  Surface: step(), total_steps (of every lane: they advance together), episodes(k),
     drain_episodes(), lane(k) -- the underlying agent, whose network, _target_flat, replay ring and save() see the lane's live
-    buffers --, rng_tail(k) -- the lane's RandomState --, close().
+    buffers --, rng_tail(k) -- the lane's RandomState --, fetch_draws(k), close().
 
     A subclass supplies ENTRY (the name in region labels and errors), MODULE (dqn_mlp or dist_mlp: Step, why_not, Kind, Net, ActIO,
     UpdateIO), the three library entries ACT_LANES / UPDATE_LANES / LANES_SUPPORTED, agent_class(), switch_on(config),
@@ -141,8 +198,9 @@ class FeatureSeeds:
         raise NotImplementedError
 
     # -- construction ------------------------------------------------------------------------------------------------------
-    def __init__(self, make_config, seeds):
+    def __init__(self, make_config, seeds, device_draws=False):
         seeds = [int(s) for s in seeds]
+        self.device_draws = bool(device_draws)
         if not 1 <= len(seeds) <= MAX_LANES:
             raise ValueError("%s runs 1 to %d seeds as lanes, not %d" % (type(self).__name__, MAX_LANES, len(seeds)))
         agent_cls = self.agent_class()
@@ -180,7 +238,22 @@ class FeatureSeeds:
             raise ValueError("%s are not built for %d lanes of shape %r" % (self.ACT_LANES.replace("_act_", "_*_"), n, (s0.shape, self.k, self.batch)))
         # ONE staged block of [n] per-lane blocks; every lane's Step sees its block through the views it had of its own
         lay = self.layout = lane_layout(self.k, self.batch)
-        self._up = StagedUpload(n * lay['stride'], torch.uint8, dev)
+        if self.device_draws:
+            # the draw kernel fills the lanes' blocks: a plain device tensor, the lanes' generators beside it, and the little the
+            # lanes share in a step as the one staged upload
+            if lib.dra_np_mt_lanes_supported.raw(n, self.k, self.batch, s0.shape[1], s0.capacity):
+                raise ValueError("device_draws: dra_np_mt_draw_lanes is not built for %d lanes of k %d, batch %d, %d actions and a ring "
+                                 "of %d slots" % (n, self.k, self.batch, s0.shape[1], s0.capacity))
+            self._up = None
+            self._blocks = torch.zeros(n * lay['stride'], dtype=torch.uint8, device=dev)
+            self._uploaded = np.stack([np_mt_words(rs) for rs in self.rngs])
+            self._mt = torch.from_numpy(self._uploaded.view(np.int32)).to(dev)
+            self._mt_stale = [False] * n      # whether rngs[k] lags behind the device's state of lane k
+            self._learned = False             # whether the last prepared step updates
+            self._common = StagedUpload(ctypes.sizeof(NpMtCommon), torch.uint8, dev)
+        else:
+            self._up = StagedUpload(n * lay['stride'], torch.uint8, dev)
+        blocks = self._blocks if self.device_draws else self._up.dev
         # the episode rings [n][3 cap + 1] and the error words [n] as one tensor each, and the rings' pinned twin
         cap3 = 3 * s0.vec.ring_cap + 1
         self._rings = torch.zeros((n, cap3), dtype=torch.float64, device=dev)
@@ -188,7 +261,7 @@ class FeatureSeeds:
         self.err = torch.zeros(n, dtype=torch.int32, device=dev)
         self._draining = False
         for k, st in enumerate(steps):
-            d = self._up.dev[k * lay['stride']:(k + 1) * lay['stride']]
+            d = blocks[k * lay['stride']:(k + 1) * lay['stride']]
             st.slot0 = d[:8].view(torch.int64)
             st.idx = d[lay['idx']:lay['rand']].view(torch.int64)
             st.random_action = d[lay['rand']:lay['flag']].view(torch.int64)
@@ -223,13 +296,24 @@ class FeatureSeeds:
         self.launches = self.agent_steps = 0
 
     # -- the launches --------------------------------------------------------------------------------------------------------
-    def _act(self):
+    def _draw(self, learn):
+        """device_draws: the lanes' blocks filled by dra_np_mt_draw_lanes from the lanes' generators, ahead of the launches that
+        read them."""
+        lay = self.layout
+        lib.dra_np_mt_draw_lanes(self._mt.data_ptr(), self._blocks.data_ptr(), self._common.dev.data_ptr(), self.err.data_ptr(),
+                                 len(self.agents), self.k, self.batch, self.steps_[0].shape[1], int(learn), lay['idx'], lay['rand'],
+                                 lay['flag'], lay['stride'], stream_ptr())
+        self.launches += 1
+
+    def _act(self, learn=False):
+        if self.device_draws:
+            self._draw(learn)
         getattr(lib, self.ACT_LANES)(self.nets.ptr, self.act_ios.ptr, len(self.agents), stream_ptr())
         self.launches += 1
 
     def _learn(self):
         n, h = len(self.agents), self.agents[0]._fused.hyper
-        self._act()
+        self._act(learn=True)
         getattr(lib, self.UPDATE_LANES)(self.nets.ptr, self.update_ios.ptr, n, stream_ptr())
         lib.dra_clip_rmsprop_step_lanes(self.opt_lanes.ptr, n, float(self.cfg.gradient_clip or 0.0), float(h['lr']), float(h['alpha']),
                                         float(h['eps']), int(bool(h['centered'])), stream_ptr())
@@ -250,6 +334,8 @@ class FeatureSeeds:
         # the others replay its values and end where it ends
         eps = [cfg.random_action_prob() for t in range(k) if not actor_steps + t < cfg.exploration_steps]
         learn = a0.total_steps + k > cfg.exploration_steps
+        if self.device_draws:
+            return self._prepare_counters(eps, learn)
         raw = self._up.stage().numpy()
         for n, (agent, st, rs) in enumerate(zip(self.agents, self.steps_, self.rngs)):
             replay = iter(eps)
@@ -271,6 +357,35 @@ class FeatureSeeds:
             blk[lay['flag']:lay['flag'] + k] = explore
             st.last_draws = (explore, rand, slot0, idx)
         self._up.send()
+        return learn
+
+    def _prepare_counters(self, eps, learn):
+        """prepare() with device_draws: the common block (first slot, the ring's pos / size after the k appends, the k epsilons)
+        staged and sent, then per lane the host bookkeeping alone -- no numpy draw, no per-lane staging."""
+        k, cfg = self.k, self.cfg
+        a0 = self.agents[0]
+        rp0 = a0._inner_replay()
+        slot0 = int(rp0.pos)
+        pos, size = ring_after(slot0, rp0.size(), rp0.memory_size, k)
+        if learn and valid_index_count(pos, size) == 0:
+            raise ValueError("device_draws: a replay ring of size %d at pos %d holds no valid index, the minibatch's rejection loop "
+                             "could not end" % (size, pos))
+        c = NpMtCommon.from_buffer(self._common.stage().numpy())
+        c.slot0, c.ring_pos, c.ring_size = slot0, pos, size
+        behind = k - len(eps)      # transitions below exploration_steps: epsilon is 1 and the schedule is not called
+        for t in range(k):
+            c.eps[t] = 1.0 if t < behind else eps[t - behind]
+        self._common.send()
+        for n, (agent, st) in enumerate(zip(self.agents, self.steps_)):
+            if n:
+                vars(agent.config.random_action_prob).update(vars(cfg.random_action_prob))
+            agent.actor._total_steps += k
+            agent._inner_replay().advance(k)
+            st.episodes.begin(k)
+            agent.total_steps += k
+            st.last_draws = None
+            self._mt_stale[n] = True
+        self._learned = learn
         return learn
 
     def step(self):
@@ -313,6 +428,9 @@ class FeatureSeeds:
     def check(self):
         """dqn_mlp.Step.check of every lane with one copy."""
         bad = self.err.cpu().numpy()
+        if (bad & NP_MT_ERR_BUDGET).any():
+            raise dqn_mlp.DraError("%s lanes %r: the draw kernel gave up on a draw after its budget of words (err %r)"
+                                   % (self.ENTRY, [self.seeds[i] for i in np.nonzero(bad & NP_MT_ERR_BUDGET)[0]], bad[bad != 0].tolist()))
         if bad.any():
             raise dqn_mlp.DraError("%s lanes %r: staged ring slots / indices were outside the ring and have been clamped (%r)"
                                    % (self.ENTRY, [self.seeds[i] for i in np.nonzero(bad)[0]], bad[bad != 0].tolist()))
@@ -336,12 +454,42 @@ class FeatureSeeds:
     def lane(self, k):
         return self.agents[k]
 
+    def _lane_block(self, k):
+        lay = self.layout
+        torch.cuda.current_stream().synchronize()
+        return self._blocks[k * lay['stride']:(k + 1) * lay['stride']].cpu().numpy()
+
+    def fetch_draws(self, k, learned=None):
+        """device_draws: (explore, random_action, first slot, indices) of lane k's last step, copied from the lane's device block
+        -- last_draws' counterpart, for tests and debugging.  The indices are None when the step did not update (`learned`: whether
+        it did, where the caller knows better than the last prepare())."""
+        if not self.device_draws:
+            return self.steps_[k].last_draws
+        lay, blk = self.layout, self._lane_block(k)
+        learned = self._learned if learned is None else learned
+        idx = blk[lay['idx']:lay['rand']].view(np.int64).copy() if learned else None
+        return (blk[lay['flag']:lay['flag'] + self.k].astype(np.bool_), blk[lay['rand']:lay['flag']].view(np.int64).copy(),
+                int(blk[:8].view(np.int64)[0]), idx)
+
+    def mt_words(self, k):
+        """device_draws: the dra_np_mt_state words of lane k as they stand on the device (one copy behind a stream sync)."""
+        torch.cuda.current_stream().synchronize()
+        return self._mt[k].cpu().numpy().view(np.uint32)
+
     def rng_tail(self, k):
+        """Lane k's RandomState, standing where the single run's np.random stands.  With device_draws the lane's state is copied
+        back from the device first (one copy behind a stream sync); the device keeps its own copy and goes on from it, so draws
+        made from the returned generator do not move the lane."""
+        if self.device_draws and self._mt_stale[k]:
+            np_mt_restore(self.rngs[k], self.mt_words(k))
+            self._mt_stale[k] = False
         return self.rngs[k]
 
     def close(self):
         if self.agents:
             self.drain_episodes()
+            for k in range(len(self.agents) if self.device_draws else 0):
+                self.rng_tail(k)
             for a in self.agents:
                 a.close()
             self.agents = []

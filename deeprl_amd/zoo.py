@@ -291,7 +291,7 @@ def run(name, **kwargs):
     return ag
 
 
-def run_seeds(name, seeds, **kwargs):
+def run_seeds(name, seeds, device_draws=False, **kwargs):
     """`name` once per seed, the seeds as lanes of the same device launches (deeprl_amd/seed_batch.py): per seed, random_seed(seed),
     torch.manual_seed(seed) and config(name, <the entry's switch>=True, **kwargs) over Task(game, seed=seed), stepped until
     config.max_steps environment steps of EVERY lane -> per seed the list of (step, episodic_return) pairs of its training
@@ -299,7 +299,9 @@ def run_seeds(name, seeds, **kwargs):
     Three entries have a lane form (seed_batch.SEED_CLASSES): dqn_feature (fused_dqn_feature; n_step 1 and a UniformReplay),
     categorical_dqn_feature and quantile_regression_dqn_feature (fused_dist_feature, and fused_dist_update=True unless kwargs set
     it: the lanes always run the update kernel, so a categorical lane is the single run with fused_dist_update=True, not the
-    single run's unset default, which is the module update).  Anything else raises a ValueError that names the reason."""
+    single run's unset default, which is the module update).  Anything else raises a ValueError that names the reason.
+    `device_draws=True` (off by default) draws every lane's np.random stream on the device, word for word (seed_batch.py's
+    docstring; csrc/np_mt.hip): the same (step, return) lists, without the per-lane host draws."""
     from deeprl_amd.seed_batch import SEED_CLASSES
     if name not in SEED_CLASSES:
         raise ValueError("run_seeds: besides categorical_dqn_feature and quantile_regression_dqn_feature only dqn_feature runs its "
@@ -313,7 +315,7 @@ def run_seeds(name, seeds, **kwargs):
         c.eval_interval = 0
         return c
 
-    batch = cls(make_config, seeds)
+    batch = cls(make_config, seeds, device_draws=device_draws)
     try:
         out = [[] for _ in batch.seeds]
         max_steps = batch.lane(0).config.max_steps

@@ -1461,6 +1461,42 @@ int dra_dist_mlp_lanes_supported(int state_dim, int n_actions, int hidden, int t
 int dra_dist_mlp_act_lanes(const dra_dist_mlp_net* nets, const dra_dqn_mlp_act_io* ios, int n_lanes, void* stream);
 int dra_dist_mlp_update_lanes(const dra_dist_mlp_net* nets, const dra_dist_mlp_update_io* ios, int n_lanes, void* stream);
 
+/* ---- np_mt: the seed lanes' draws taken on the device from numpy's own stream (seed_batch.py, device_draws=True; csrc/np_mt.h has
+ * the protocol).  A lane owns a legacy np.random.RandomState: dra_np_mt_state is its get_state() -- key[624], then pos (624 = the
+ * key is regenerated before the next word) --, DRA_NP_MT_STATE_WORDS uint32 per lane, 16-byte aligned.  One step of a lane is, in
+ * the order of support.plan_actor_epsilon_greedy then replay.draw_uniform_indices: per transition randint(n_actions, size=1) and
+ * rand(1) < eps[j] in float64; then, if learn, the rejection loop of randint(0, ring_size) until `batch` indices are valid at
+ * history_length = n_step = 1.  The values go into the lane's block where the act / update lane kernels read them: int64 first
+ * slot at 0, int64 idx[batch] at idx_off, int64 random actions[k] at rand_off, uint8 flags[k] at flag_off (seed_batch.lane_layout;
+ * idx is left alone when learn is 0); the state ends where numpy's ends.  What the lanes share in a step comes from
+ * dra_np_mt_common, read when the launch RUNS (a captured launch sees what was uploaded last).
+ * No lane spins: a step makes no further attempt once it has taken more than 4096 words; the draws it gave up on are 0 and
+ * DRA_NP_MT_ERR_BUDGET is or-ed into the lane's err word (the act / update kernels count into the same word).
+ * dra_np_mt_draw_lanes: workgroup (0, lane) of 64 threads per lane; states [n_lanes][DRA_NP_MT_STATE_WORDS], out_blocks n_lanes
+ * blocks block_stride bytes apart, err [n_lanes], all device memory.  1 <= n_lanes <= 64, 1 <= k <= 8, 1 <= batch <= 256,
+ * 1 <= n_actions, ring capacity 2 .. 2^32 - 1 (dra_np_mt_lanes_supported: 0 = yes).
+ * dra_np_mt_draw_host: the same step of ONE lane, serially, over host memory -- no device is touched.  It states the protocol for
+ * the CPU tests and is the kernel's debugging twin, not a path of the product.  DRA_EINVAL also for a ring state with no valid
+ * index (learn != 0) and for a pos outside 0 .. 624. */
+#define DRA_NP_MT_STATE_WORDS 628
+#define DRA_NP_MT_ERR_BUDGET 1073741824
+typedef struct dra_np_mt_state {
+  uint32_t key[624];
+  int32_t pos;
+  int32_t reserved[3];
+} dra_np_mt_state;
+typedef struct dra_np_mt_common {
+  int64_t slot0;       /* the ring slot of the step's first transition */
+  int64_t ring_pos;    /* the ring's pos and size AFTER the step's k appends */
+  int64_t ring_size;
+  double eps[8];       /* [k]: epsilon of transition j (1.0 below exploration_steps) */
+} dra_np_mt_common;
+int dra_np_mt_lanes_supported(int n_lanes, int k, int batch, int n_actions, int64_t capacity);   /* 0 = yes */
+int dra_np_mt_draw_lanes(void* states, void* out_blocks, const dra_np_mt_common* common, int* err, int n_lanes, int k, int batch,
+                         int n_actions, int learn, int idx_off, int rand_off, int flag_off, int block_stride, void* stream);
+int dra_np_mt_draw_host(void* state, void* out_block, const dra_np_mt_common* common, int* err, int k, int batch, int n_actions,
+                        int learn, int idx_off, int rand_off, int flag_off);
+
 /* ---- rainbow_mlp: rainbow_feature (examples.py:231-280: CategoricalDQNAgent, RainbowNet over FCBody(noisy_linear=True), n-step
  * PrioritizedReplay, double_q) over ONE device-resident cart-pole environment and the HBM replay ring: dist_mlp's two launches
  * over four NoisyLinear layers and the dueling head.  A layer's effective parameters are formed in the kernels from its RAW noise

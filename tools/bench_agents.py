@@ -54,6 +54,8 @@ Seed lanes (deeprl_amd/seed_batch.py), named explicitly with --cases too (SEED_C
   categorical_dqn_feature_seeds1 / 4 / 16, quantile_regression_dqn_feature_seeds1 / 4 / 16  the same over the two distributional cases
             (the lanes always run the update kernel: their single baselines are categorical_dqn_feature -- and its faster single form,
             categorical_dqn_feature_module_update -- and quantile_regression_dqn_feature)
+  <a seeds case>_device_draws (SEED_DRAW_CASES: dqn_feature 1 / 4 / 16 / 64, the distributional two 4 / 16)  the same lanes with
+            device_draws=True: prepare_us_per_lane_step is then the common block and the counters alone
 """
 import argparse
 import json
@@ -233,11 +235,12 @@ def dqn_feature(**switches):
     return d.DQNAgent(dqn_feature_config(**switches)), dict(env_per_step=4, updates_per_step=1, warm=300)
 
 
-def dqn_feature_seeds(n):
+def dqn_feature_seeds(n, device_draws=False):
     """dqn_feature_seedsN: N seeds of the dqn_feature case as lanes of the same launches (deeprl_amd/seed_batch.py), the
-    environments seeded 1 .. N; env_steps_per_s is the AGGREGATE over the lanes."""
+    environments seeded 1 .. N; env_steps_per_s is the AGGREGATE over the lanes.  device_draws: the lanes' np.random draws taken
+    by dra_np_mt_draw_lanes (the _device_draws cases)."""
     from deeprl_amd.seed_batch import DQNFeatureSeeds
-    batch = DQNFeatureSeeds(lambda seed: dqn_feature_config(task_seed=seed), range(1, n + 1))
+    batch = DQNFeatureSeeds(lambda seed: dqn_feature_config(task_seed=seed), range(1, n + 1), device_draws=device_draws)
     return batch, dict(env_per_step=4 * n, updates_per_step=n, warm=300, lanes=n)
 
 
@@ -268,13 +271,13 @@ def dist_feature(head, **switches):
     return cls(dist_feature_config(head, **switches)), dict(env_per_step=4, updates_per_step=1, warm=120)
 
 
-def dist_feature_seeds(head, n):
+def dist_feature_seeds(head, n, device_draws=False):
     """categorical_dqn_feature_seedsN / quantile_regression_dqn_feature_seedsN: N seeds of the dist_feature case as lanes of the same
     launches (deeprl_amd/seed_batch.py: the batch sets fused_dist_feature and fused_dist_update), the environments seeded 1 .. N;
     env_steps_per_s is the AGGREGATE over the lanes."""
     from deeprl_amd import seed_batch
     cls = seed_batch.CategoricalDQNFeatureSeeds if head == "categorical" else seed_batch.QuantileRegressionDQNFeatureSeeds
-    batch = cls(lambda seed: dist_feature_config(head, task_seed=seed), range(1, n + 1))
+    batch = cls(lambda seed: dist_feature_config(head, task_seed=seed), range(1, n + 1), device_draws=device_draws)
     return batch, dict(env_per_step=4 * n, updates_per_step=n, warm=120, lanes=n)
 
 
@@ -463,6 +466,13 @@ SEED_CASES = {"dqn_feature_seeds%d" % n: (lambda n=n: dqn_feature_seeds(n)) for 
 SEED_CASES.update({"categorical_dqn_feature_seeds%d" % n: (lambda n=n: dist_feature_seeds("categorical", n)) for n in (1, 4, 16)})
 SEED_CASES.update({"quantile_regression_dqn_feature_seeds%d" % n: (lambda n=n: dist_feature_seeds("quantile", n)) for n in (1, 4, 16)})
 
+# the same with the lanes' draws taken on the device (seed_batch.py, device_draws=True): a dict of their own, named in --cases
+SEED_DRAW_CASES = {"dqn_feature_seeds%d_device_draws" % n: (lambda n=n: dqn_feature_seeds(n, True)) for n in (1, 4, 16, 64)}
+SEED_DRAW_CASES.update({"categorical_dqn_feature_seeds%d_device_draws" % n: (lambda n=n: dist_feature_seeds("categorical", n, True))
+                        for n in (4, 16)})
+SEED_DRAW_CASES.update({"quantile_regression_dqn_feature_seeds%d_device_draws" % n: (lambda n=n: dist_feature_seeds("quantile", n, True))
+                        for n in (4, 16)})
+
 
 # the continuous entries evaluate on the pendulum, on their device path, the zoo's 20 episodes (of 200 steps) a time
 DPG_EVAL = {"ddpg_continuous_eval": "ddpg_pendulum", "td3_continuous_eval": "td3_pendulum"}
@@ -596,7 +606,7 @@ def run_cases(a, tag):
             if name in EVAL_CASES:
                 EVAL_CASES[name](name, tag)
                 continue
-            agent, meta = SEED_CASES[name]() if name in SEED_CASES else CASES[name]()
+            agent, meta = {**CASES, **SEED_CASES, **SEED_DRAW_CASES}[name]()
             warm = 120 if "dqn" in name or "c51" in name or "rainbow" in name else 4      # DQN family: past exploration_steps; on-policy: past graph capture
             warm = meta.get("warm", warm)                                                 # (replay actor-critics: past warm_up)
             for _ in range(warm):
