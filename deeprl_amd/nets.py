@@ -65,7 +65,8 @@ def direct_param_grads(enable=True, defer_folds_to=None, covers=()):
     layer whose gradient segment lives in that optimizer's flat buffer leaves its per-(sample, chunk) slabs unfolded and
     registers them (FusedOptimizer.defer_fold); the optimizer folds every registered layer inside the launch that forms the
     gradient norm -- one launch instead of one per layer plus the norm's (profiles/r05r_kernel_stats_*: fold_norm_kernel x 3 +
-    grad_sqnorm_kernel per update)."""
+    grad_sqnorm_kernel per update).  The fold overwrites its segment, so a conv layer reached a SECOND time folds the slabs its
+    first reach registered there and then (FusedOptimizer.flush_fold), before autograd accumulates the further contribution."""
     prev, prev_defer = _DIRECT[0], _DEFER[0]
     _DIRECT[0] = bool(enable)
     _DEFER[0] = defer_folds_to if enable else None
@@ -99,23 +100,27 @@ def _claim_direct(params):
 # ReLU masks applied by the PRODUCER of a gradient.  A fused-ReLU layer's backward starts with dpre = dy * (y > 0) -- a launch of
 # its own in front of every conv layer's backward.  The layer ABOVE knows the same mask (its input x IS that y) and its
 # input-gradient kernel has an epilogue for it (xact): it hands down dx * (x > 0) and leaves the tensor's address here; the layer
-# below skips its own mask when the gradient it receives is that very tensor (anything autograd copied or accumulated in between
-# has another address and is masked as before).  (y > 0) in {0, 1}: the values are the same either way.
-_MASKED = [0, 0, None]       # (address, element count, weak reference) of the gradient the layer above has already masked
+# below skips its own mask when the gradient it receives is that very tensor, UNWRITTEN since (anything autograd copied in between
+# has another address; a second consumer's gradient that autograd ADDED INTO the marked tensor in place leaves the address and
+# bumps the tensor's version counter: masked + unmasked is masked as before).  (y > 0) in {0, 1}: the values are the same either way.
+_MASKED = [0, 0, None, 0]    # (address, element count, weak reference, version counter) of the gradient the layer above has already masked
 
 
 def _mark_masked(dx):
     import weakref
-    _MASKED[0], _MASKED[1], _MASKED[2] = dx.data_ptr(), dx.numel(), weakref.ref(dx)
+    _MASKED[0], _MASKED[1], _MASKED[2], _MASKED[3] = dx.data_ptr(), dx.numel(), weakref.ref(dx), dx._version
 
 
 def _already_masked(dy):
     """The mark names a tensor OBJECT that is still alive (a freed tensor's address may be handed to an unrelated gradient by
     the caching allocator: a stale mark must not match it) with the address / size this gradient has (autograd may hand the
-    consumer a view or the same storage through another Python object)."""
+    consumer a view or the same storage through another Python object) and the version counter it had when it was marked (views
+    share the counter of their base; autograd's input buffer accumulates a further gradient into the first one IN PLACE when it
+    may: same object, same address, one version later -- no longer the masked gradient alone)."""
     ref = _MASKED[2]
     alive = ref is not None and ref() is not None
-    hit = alive and _MASKED[0] != 0 and dy.data_ptr() == _MASKED[0] and dy.numel() == _MASKED[1]
+    hit = (alive and _MASKED[0] != 0 and dy.data_ptr() == _MASKED[0] and dy.numel() == _MASKED[1]
+           and getattr(dy, "_version", _MASKED[3]) == _MASKED[3] and ref()._version == _MASKED[3])
     _MASKED[0] = _MASKED[1] = 0          # consumed (or not ours): a mark never outlives the next layer's backward
     _MASKED[2] = None
     return hit
@@ -504,7 +509,13 @@ class _ConvKocFn(torch.autograd.Function):
             _mark_masked(dx)
         # direct_param_grads(): FlatParams lays [weight (KOC) | bias] out back to back, which is a slab's own layout -- the fold
         # writes the layer's gradient segment of the optimizer's flat buffer itself
-        gw, gb = (_grad_slot(ctx.params[0]), _grad_slot(ctx.params[1])) if _claim_direct(ctx.params) else (None, None)
+        claimed = _claim_direct(ctx.params)
+        if not claimed and _DIRECT[0] and _DEFER[0] is not None:
+            # a shared layer reached again: the first reach may have left its slabs with the optimizer, whose fold OVERWRITES the
+            # segment inside step() -- after autograd has added this reach's gradient to it.  Fold them now: the direct write
+            # comes first, the accumulation lands on top of it (direct_param_grads' promise)
+            _DEFER[0].flush_fold(_grad_slot(ctx.params[0]))
+        gw, gb = (_grad_slot(ctx.params[0]), _grad_slot(ctx.params[1])) if claimed else (None, None)
         direct = (gw is not None and gb is not None and stride == n_w + oc and gw.permute(1, 2, 3, 0).is_contiguous()
                   and gb.is_contiguous() and gb.data_ptr() == gw.data_ptr() + 4 * n_w and gw.data_ptr() % 16 == 0)
         _SHARED[0] = _SHARED[0] or not direct

@@ -110,6 +110,22 @@ class FusedOptimizer:
         self._pending_folds.append((int(off), int(floats), slabs, int(floats), int(n_slabs)))
         return True
 
+    def flush_fold(self, grad_view):
+        """Folds NOW the registered slabs of the layer whose gradient segment starts at grad_view, if any (a shared layer's
+        backward reached it a second time: the fold is an overwrite and must precede autograd's accumulation of the further
+        contributions).  The other layers stay registered."""
+        if grad_view is None or not self._pending_folds:
+            return
+        off = (grad_view.data_ptr() - self.flat.grad.data_ptr()) // 4
+        mine = [s for s in self._pending_folds if s[0] == off]
+        if not mine:
+            return
+        self._pending_folds = [s for s in self._pending_folds if s[0] != off]
+        if self._partials_segs is None:
+            self._partials_segs = torch.zeros(ops.norm_partials_max(), dtype=torch.float64, device=self.flat.flat.device)
+        for off, cnt, slabs, stride, ns in mine:
+            ops.grad_sqnorm_segs(self.flat.grad[off:off + cnt], [(0, cnt, slabs, stride, ns)], self._partials_segs)
+
     def _fold_pending(self, want_norm):
         """Folds the registered layers.  -> (partials, count) covering the WHOLE gradient when one launch could do everything
         (segments contiguous from offset 0: the NatureConvBody layers of a FlatParams buffer), else None (folded, no norm)."""
