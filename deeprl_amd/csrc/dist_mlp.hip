@@ -19,7 +19,7 @@
 //   dist_mlp_eval_kernel     the acting kernel's staging and forward over eval_act.h's loop (config.fused_eval): n_episodes greedy
 //                            episodes of the evaluation environment in ONE launch.
 //
-//   dist_mlp_act_lanes_kernel, dist_mlp_update_kernel<.., LANES>   the two launches over n_lanes independent agents (seeds) of one
+//   dist_mlp_act_lanes_kernel, dist_mlp_update_kernel<.., LANES>, dist_mlp_eval_kernel<.., LANES>   the launches over n_lanes independent agents (seeds) of one
 //                            shape and one atom count: workgroup (0, lane) reads ITS net and io struct from two tables and runs the
 //                            single launch's text, so a lane carries the single launch's bits (seed_lanes.h; the end of the file).
 //
@@ -128,9 +128,15 @@ dist_mlp_act_lanes_kernel(const dra_dist_mlp_net* __restrict__ nets, const dra_d
 
 // ---------------------------------------------------------------------------------------------------- evaluation
 // dist_mlp_act_kernel's staging and forward over eval_act.h's loop: greedy, no ring row, until n_episodes episodes have ended.
-template <int H, int GATE, int HEAD>
+//
+// LANES: the evaluation of seed_batch.py's n_lanes independent agents in ONE launch -- two TABLES, workgroup (0, lane) reads its row
+// of each and runs the text below as it is, with its own loop bound and its own done_word (dqn_mlp.hip's evaluation kernel; the
+// figures: profiles/eval_lanes_kernel_resources.txt).  With LANES false the text and the argument list are the parent's.
+template <int H, int GATE, int HEAD, bool LANES = false>
 __global__ void __launch_bounds__(256)
-dist_mlp_eval_kernel(dra_dist_mlp_net net, dra_mlp_eval_io io) {
+dist_mlp_eval_kernel(lane_arg<LANES, dra_dist_mlp_net> net_arg, lane_arg<LANES, dra_mlp_eval_io> io_arg) {
+  const auto& net = lane_struct(net_arg);
+  const auto& io = lane_struct(io_arg);
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int tid = threadIdx.x;
   const int K = io.n_episodes * (int)io.horizon, N = net.n_atoms, M = kA * N;      // (K <= 65536: dra_mlp_eval_supported)
@@ -643,10 +649,15 @@ DRA_API int dra_dist_mlp_act(const dra_dist_mlp_net* net, const dra_dqn_mlp_act_
   });
 }
 
+// what dra_dist_mlp_eval asks of its two structs (dra_dist_mlp_eval_lanes: of every lane's)
+static bool eval_args_ok(const dra_dist_mlp_net* net, const dra_mlp_eval_io* io) {
+  if (!net->param) return false;
+  if (dra_dist_mlp_supported(net->state_dim, net->n_actions, net->hidden, 1, net->gate, net->head, net->n_atoms)) return false;
+  return net_ok(net) && mlp_eval_io_ok(io);
+}
+
 DRA_API int dra_dist_mlp_eval(const dra_dist_mlp_net* net, const dra_mlp_eval_io* io, void* stream) {
-  if (!net || !io || !net->param) return DRA_EINVAL;
-  if (dra_dist_mlp_supported(net->state_dim, net->n_actions, net->hidden, 1, net->gate, net->head, net->n_atoms)) return DRA_EINVAL;
-  if (!net_ok(net) || !mlp_eval_io_ok(io)) return DRA_EINVAL;
+  if (!net || !io || !eval_args_ok(net, io)) return DRA_EINVAL;
   return dispatch_hidden_gate_head(net->hidden, net->gate, net->head, [&](auto h, auto g, auto hd) {
     constexpr int H = decltype(h)::value, GATE = decltype(g)::value, HEAD = decltype(hd)::value;
     return launch_one_workgroup<&dist_mlp_eval_kernel<H, GATE, HEAD>>(act_lds_floats(H, net->n_atoms) * sizeof(float), net, io, stream);
@@ -708,5 +719,18 @@ DRA_API int dra_dist_mlp_update_lanes(const dra_dist_mlp_net* nets, const dra_di
     constexpr int H = decltype(h)::value, GATE = decltype(g)::value, HEAD = decltype(hd)::value;
     return launch_lanes<&dist_mlp_update_kernel<H, GATE, HEAD, true>>(update_lds_floats(H, nets->n_atoms) * sizeof(float), nets, ios,
                                                                      n_lanes, stream);
+  });
+}
+
+// n_lanes evaluations in one launch (dra_mlp_eval_lanes_supported: dqn_mlp.hip): lane l runs ios[l].n_episodes episodes of at most
+// ios[l].horizon steps (both per lane) on nets[l] and leaves on its own
+DRA_API int dra_dist_mlp_eval_lanes(const dra_dist_mlp_net* nets, const dra_mlp_eval_io* ios, int n_lanes, void* stream) {
+  if (!nets || !ios || n_lanes < 1 || n_lanes > kMaxLanes) return DRA_EINVAL;
+  for (int l = 0; l < n_lanes; ++l)
+    if (!eval_args_ok(nets + l, ios + l) || !same_shape(nets, nets + l)) return DRA_EINVAL;
+  return dispatch_hidden_gate_head(nets->hidden, nets->gate, nets->head, [&](auto h, auto g, auto hd) {
+    constexpr int H = decltype(h)::value, GATE = decltype(g)::value, HEAD = decltype(hd)::value;
+    return launch_lanes<&dist_mlp_eval_kernel<H, GATE, HEAD, true>>(act_lds_floats(H, nets->n_atoms) * sizeof(float), nets, ios, n_lanes,
+                                                                   stream);
   });
 }

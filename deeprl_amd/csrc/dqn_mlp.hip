@@ -20,7 +20,7 @@
 //                           kernel's staging and forward over eval_act.h's loop -- greedy, no ring row -- until n_episodes episodes
 //                           of the evaluation environment have ended.
 //
-//   dqn_mlp_act_lanes_kernel, dqn_mlp_update_kernel<.., LANES>   the two launches over n_lanes independent agents (seeds) of one shape:
+//   dqn_mlp_act_lanes_kernel, dqn_mlp_update_kernel<.., LANES>, dqn_mlp_eval_kernel<.., LANES>   the launches over n_lanes independent agents (seeds) of one shape:
 //                           workgroup (0, lane) reads ITS net and io struct from two tables and runs the single launch's text, so a
 //                           lane carries the single launch's bits.  Lanes share nothing and wait for nobody (the end of the file).
 //
@@ -104,9 +104,18 @@ dqn_mlp_act_lanes_kernel(const dra_q_mlp_net* __restrict__ nets, const dra_dqn_m
 
 // ---------------------------------------------------------------------------------------------------- evaluation
 // dqn_mlp_act_kernel's staging and forward over eval_act.h's loop: greedy, no ring row, until n_episodes episodes have ended.
-template <int H, int GATE>
+//
+// LANES: the evaluation of seed_batch.py's n_lanes independent agents in ONE launch -- the arguments are two TABLES and workgroup
+// (0, lane) reads its row of each, then runs the text below as it is: its own K = n_episodes * horizon, its own done_word in its
+// own LDS, so a lane leaves when ITS episodes have ended and waits for nobody.  A flag on this kernel (lane_arg / lane_struct:
+// seed_lanes.h), as on the update kernel: with LANES false the text, the argument list and the figures are the parent's.  A shared
+// __device__ body under two kernels gives the same figures here, single and lane (profiles/eval_lanes_kernel_resources.txt): the
+// flag keeps one kernel text.
+template <int H, int GATE, bool LANES = false>
 __global__ void __launch_bounds__(256)
-dqn_mlp_eval_kernel(dra_q_mlp_net net, dra_mlp_eval_io io) {
+dqn_mlp_eval_kernel(lane_arg<LANES, dra_q_mlp_net> net_arg, lane_arg<LANES, dra_mlp_eval_io> io_arg) {
+  const auto& net = lane_struct(net_arg);
+  const auto& io = lane_struct(io_arg);
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int tid = threadIdx.x;
   const int K = io.n_episodes * (int)io.horizon;      // (<= 65536: dra_mlp_eval_supported)
@@ -470,10 +479,15 @@ DRA_API int dra_dqn_mlp_act(const dra_q_mlp_net* net, const dra_dqn_mlp_act_io* 
 
 DRA_API int dra_mlp_eval_supported(int n_episodes, int64_t horizon) { return mlp_eval_supported(n_episodes, horizon); }
 
+// what dra_dqn_mlp_eval asks of its two structs (dra_dqn_mlp_eval_lanes: of every lane's)
+static bool eval_args_ok(const dra_q_mlp_net* net, const dra_mlp_eval_io* io) {
+  if (!net->param) return false;
+  if (cartpole_mlp_supported(net->state_dim, net->n_actions, net->hidden, 1, net->gate)) return false;
+  return offsets_ok(net) && mlp_eval_io_ok(io);
+}
+
 DRA_API int dra_dqn_mlp_eval(const dra_q_mlp_net* net, const dra_mlp_eval_io* io, void* stream) {
-  if (!net || !io || !net->param) return DRA_EINVAL;
-  if (cartpole_mlp_supported(net->state_dim, net->n_actions, net->hidden, 1, net->gate)) return DRA_EINVAL;
-  if (!offsets_ok(net) || !mlp_eval_io_ok(io)) return DRA_EINVAL;
+  if (!net || !io || !eval_args_ok(net, io)) return DRA_EINVAL;
   return dispatch_hidden_gate(net->hidden, net->gate, [&](auto h, auto g) {
     constexpr int H = decltype(h)::value, GATE = decltype(g)::value;
     return launch_one_workgroup<&dqn_mlp_eval_kernel<H, GATE>>(act_lds_floats(H) * sizeof(float), net, io, stream);
@@ -552,5 +566,22 @@ DRA_API int dra_dqn_mlp_update_lanes(const dra_q_mlp_net* nets, const dra_dqn_ml
   return dispatch_hidden_gate(nets->hidden, nets->gate, [&](auto h, auto g) {
     constexpr int H = decltype(h)::value, GATE = decltype(g)::value;
     return launch_lanes<&dqn_mlp_update_kernel<H, GATE, dra_dqn_mlp_update_io, true>>(update_lds_floats(H) * sizeof(float), nets, ios, n_lanes, stream);
+  });
+}
+
+DRA_API int dra_mlp_eval_lanes_supported(int n_episodes, int64_t horizon, int n_lanes) {
+  if (n_lanes < 1 || n_lanes > kMaxLanes) return DRA_EINVAL;
+  return mlp_eval_supported(n_episodes, horizon);
+}
+
+// n_lanes evaluations in one launch: lane l runs ios[l].n_episodes episodes of at most ios[l].horizon steps (both per lane) on
+// nets[l] and leaves on its own
+DRA_API int dra_dqn_mlp_eval_lanes(const dra_q_mlp_net* nets, const dra_mlp_eval_io* ios, int n_lanes, void* stream) {
+  if (!nets || !ios || n_lanes < 1 || n_lanes > kMaxLanes) return DRA_EINVAL;
+  for (int l = 0; l < n_lanes; ++l)
+    if (!eval_args_ok(nets + l, ios + l) || !same_shape(nets, nets + l)) return DRA_EINVAL;
+  return dispatch_hidden_gate(nets->hidden, nets->gate, [&](auto h, auto g) {
+    constexpr int H = decltype(h)::value, GATE = decltype(g)::value;
+    return launch_lanes<&dqn_mlp_eval_kernel<H, GATE, true>>(act_lds_floats(H) * sizeof(float), nets, ios, n_lanes, stream);
   });
 }

@@ -7,7 +7,8 @@
 //
 // Two forms of a lane kernel (mlp_rollout.h's banner: the figures decide which): a kernel of its own over a __forceinline__ body
 // that the single kernel runs too (the acting kernels), or a template flag on the single kernel -- lane_arg<LANES, T> as the
-// parameter's type, lane_struct() as its first statement; with LANES false both are the struct itself (the update kernels).
+// parameter's type, lane_struct() as its first statement; with LANES false both are the struct itself (the update and the evaluation
+// kernels).
 //
 // What a lane form pays beside its registers: a pointer read out of a table is a GENERIC pointer to the compiler (inside a kernel
 // argument it is known to be global), so the accesses through it are flat_load / flat_store, which count against the LDS counter

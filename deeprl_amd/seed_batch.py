@@ -22,8 +22,21 @@ holds beyond the common fields.  The two distributional classes run CategoricalD
 dist_mlp.Step on dra_dist_mlp_act_lanes / dra_dist_mlp_update_lanes (DistFeatureSeeds).
 
 What the lanes cannot be is named in a ValueError: an agent that stayed on the host path (the module's why_not's reason: n_step >
-1, a PrioritizedReplay, another network, ...), the module-path update, fused_eval, an optimiser other than RMSprop, lanes that
-differ in anything the launches share (first_mismatch), more than MAX_LANES seeds.
+1, a PrioritizedReplay, another network, ...), the module-path update, fused_eval on a lane's own config (below), an optimiser
+other than RMSprop, lanes that differ in anything the launches share (first_mismatch), more than MAX_LANES seeds.
+
+Evaluation is a property of the BATCH, not of one lane: `eval_lanes=True` (off by default; every head has it) moves each lane's
+config.eval_env onto the device through the lane Step's own eval_vec(config.eval_episodes) -- a lane whose evaluation environment
+cannot move is refused with a ValueError, lanes have no host evaluation to fall back to -- and `evaluate(n)` runs n greedy episodes
+of every lane as ONE launch of dra_dqn_mlp_eval_lanes / dra_dist_mlp_eval_lanes (workgroup (0, lane) is the single evaluation
+launch on the lane's row of the acting lanes' net table and of an io table; lanes end at different steps and wait for nobody) and
+ONE copy back of one block [n_lanes][n + 1 + (n + 1) // 2], whatever the lane count, eagerly between the graph replays.
+`eval_episodes()` is BaseAgent.eval_episodes of every lane: drain_episodes(), evaluate(config.eval_episodes) and each lane agent's
+own _report_eval.  config.eval_episodes and the evaluation horizon join the lanes' signature.  Evaluation draws nothing from
+np.random, so it composes with device_draws unchanged.  A lane config that sets config.fused_eval itself stays refused: that switch
+asks for the single launch per agent.  On an eval_lanes batch `lane(k).eval_episodes()` and `lane(k).eval_episode()` raise a
+RuntimeError that points to the batch's eval_episodes(): the lane's evaluation environment has retired from the host, and the
+host loop must not step it.  (On a batch without eval_lanes they are the agent's own host evaluation, as before.)
 
 `device_draws=True` (off by default; every head has it, it lives in FeatureSeeds) takes the lanes' draws on the device WITHOUT
 changing the stream: each lane's RandomState.get_state() (key, pos; a cached Gaussian is refused) is uploaded once, and
@@ -151,9 +164,20 @@ def first_mismatch(signatures):
     return None
 
 
+def eval_signature(agent):
+    """What an eval_lanes batch asks its lanes to share on top of lane_signature: config.eval_episodes and the evaluation
+    environment's horizon (read from the host environment, ahead of its move onto the device).  The kernels take both per lane;
+    one configuration is what a sweep over seeds means, and first_mismatch names the lane that differs."""
+    from .device_env import _RolloutVec
+    cfg = agent.config
+    return dict(eval_episodes=int(cfg.eval_episodes), eval_horizon=int(_RolloutVec._host_envs(cfg.eval_env, cfg)[0].horizon))
+
+
 def lane_why_not(agent, module=dqn_mlp):
     """None when `agent`, built with the switch of `module`'s kind on (dqn_mlp: config.fused_dqn_feature; dist_mlp:
-    config.fused_dist_feature), can be a lane; else the first reason."""
+    config.fused_dist_feature), can be a lane; else the first reason.  config.fused_eval on a LANE's config is refused: it asks
+    for the single evaluation launch, per agent.  Evaluation of lanes is a property of the batch -- FeatureSeeds(...,
+    eval_lanes=True) evaluates every lane in one launch -- not of one lane's config."""
     cfg, kind = agent.config, module.Kind
     step = getattr(agent, '_feature', None)
     if type(step) is not module.Step:
@@ -169,15 +193,16 @@ def lane_why_not(agent, module=dqn_mlp):
 
 class FeatureSeeds:
     """What the seed lanes of every head share: see the module's docstring.  `make_config(seed)` -> a Config for the subclass's
-    agent class; its switch is set here; `device_draws`: the module's docstring.  Surface: step(), total_steps (of every lane: they advance together), episodes(k),
-    drain_episodes(), lane(k) -- the underlying agent, whose network, _target_flat, replay ring and save() see the lane's live
+    agent class; its switch is set here; `device_draws`, `eval_lanes`: the module's docstring.  Surface: step(), evaluate(n),
+    eval_episodes(), eval_returns, eval_lengths, eval_steps, eval_launches, eval_copies (eval_lanes), total_steps (of every lane:
+    they advance together), episodes(k), drain_episodes(), lane(k) -- the underlying agent, whose network, _target_flat, replay ring and save() see the lane's live
     buffers --, rng_tail(k) -- the lane's RandomState --, fetch_draws(k), close().
 
     A subclass supplies ENTRY (the name in region labels and errors), MODULE (dqn_mlp or dist_mlp: Step, why_not, Kind, Net, ActIO,
-    UpdateIO), the three library entries ACT_LANES / UPDATE_LANES / LANES_SUPPORTED, agent_class(), switch_on(config),
+    UpdateIO), the library entries ACT_LANES / UPDATE_LANES / LANES_SUPPORTED / EVAL_LANES, agent_class(), switch_on(config),
     signature(agent) and update_outputs(io, step)."""
     WARMUP = dqn_mlp.Step.WARMUP
-    ENTRY = MODULE = ACT_LANES = UPDATE_LANES = LANES_SUPPORTED = None
+    ENTRY = MODULE = ACT_LANES = UPDATE_LANES = LANES_SUPPORTED = EVAL_LANES = None
 
     # -- what a subclass supplies ------------------------------------------------------------------------------------------
     def agent_class(self):
@@ -198,9 +223,9 @@ class FeatureSeeds:
         raise NotImplementedError
 
     # -- construction ------------------------------------------------------------------------------------------------------
-    def __init__(self, make_config, seeds, device_draws=False):
+    def __init__(self, make_config, seeds, device_draws=False, eval_lanes=False):
         seeds = [int(s) for s in seeds]
-        self.device_draws = bool(device_draws)
+        self.device_draws, self.eval_lanes = bool(device_draws), bool(eval_lanes)
         if not 1 <= len(seeds) <= MAX_LANES:
             raise ValueError("%s runs 1 to %d seeds as lanes, not %d" % (type(self).__name__, MAX_LANES, len(seeds)))
         agent_cls = self.agent_class()
@@ -216,13 +241,18 @@ class FeatureSeeds:
                 why = self.why_not(agent)
                 if why is not None:
                     raise ValueError("seed %d cannot run as a lane: %s" % (seed, why))
+                why = agent._feature._eval_why_not(int(cfg.eval_episodes)) if self.eval_lanes else None
+                if why is not None:      # (lanes have no host evaluation to fall back to)
+                    raise ValueError("seed %d cannot run as a lane: fused evaluation: %s" % (seed, why))
                 rs = np.random.RandomState()
                 rs.set_state(np.random.get_state())      # where the single run's draws would start
                 self.rngs.append(rs)
-            why = first_mismatch([self.signature(a) for a in self.agents])
+            why = first_mismatch([dict(self.signature(a), **(eval_signature(a) if self.eval_lanes else {})) for a in self.agents])
             if why is not None:
                 raise ValueError("the lanes do not share one configuration: %s" % why)
             self._wire()
+            if self.eval_lanes:
+                self._wire_eval()
         except Exception:
             for a in self.agents:
                 a.close()
@@ -294,6 +324,77 @@ class FeatureSeeds:
         self.regions = dict(act=Region("the %s lanes' acting launch" % self.ENTRY, cfg, self.WARMUP),
                             learn=Region("the %s lanes' agent step" % self.ENTRY, cfg, self.WARMUP))
         self.launches = self.agent_steps = 0
+
+    # -- evaluation of every lane in one launch (eval_lanes) -------------------------------------------------------------------
+    def _wire_eval(self):
+        """Every lane's config.eval_env onto the device through the lane Step's own eval_vec (checked eligible in __init__), the
+        io table, and a lane agent whose own eval_episodes() says where evaluation lives instead of stepping a retired host
+        environment."""
+        n_ep = int(self.cfg.eval_episodes)
+        self.eval_vecs = [st.eval_vec(n_ep) for st in self.steps_]
+        self.eval_ios = LaneTable(dqn_mlp.EvalIO, len(self.agents))
+        self._eval_blocks = {}
+        self.eval_launches = self.eval_copies = 0
+        self.eval_returns = self.eval_lengths = self.eval_steps = None      # the last evaluation's
+        for k, a in enumerate(self.agents):
+            # (the evaluation reads the ONLINE parameters through the acting lanes' net table, self.nets: Kind.eval_net changes nothing
+            # in net_struct()'s struct for the kinds that have lanes)
+            a.eval_episodes = a.eval_episode = self._not_per_lane
+
+    def _not_per_lane(self, *args, **kwargs):
+        raise RuntimeError("%s: this agent is a lane of an eval_lanes batch, whose evaluation environment lives on the device and is "
+                           "stepped by the batch's launch: call the batch's eval_episodes() (or evaluate(n)), not the lane's"
+                           % self.ENTRY)
+
+    def _eval_block(self, n):
+        """Per episode count ONE device block [n_lanes][n + 1 + (n + 1) // 2] fp64 -- each row dqn_mlp.Step._eval_buffers' layout:
+        fp64 returns [n] | int64 steps | int32 lengths [n] -- and its pinned twin: what an evaluation leaves comes back in one copy."""
+        if n not in self._eval_blocks:
+            shape = (len(self.agents), n + 1 + (n + 1) // 2)
+            self._eval_blocks[n] = (torch.zeros(shape, dtype=torch.float64, device=Config.DEVICE),
+                                    torch.zeros(shape, dtype=torch.float64).pin_memory())
+        return self._eval_blocks[n]
+
+    def evaluate(self, n=None):
+        """`n` (default: config.eval_episodes) greedy episodes of EVERY lane's evaluation environment under the lane's online
+        network, as ONE launch on the current stream (eagerly, outside both captured regions, behind whatever the steps queued)
+        and ONE copy back, whatever the lane count -> the episodic returns, fp64 [n_lanes][n], each row what the single run's
+        Step.evaluate(n) gives (kept in eval_returns).  eval_lengths [n_lanes][n] and eval_steps [n_lanes] hold the episodes' lengths
+        and their sums.
+        Nothing is drawn from np.random and no generator state is touched (the cart-pole's reset is a hash of seed and counter),
+        with device_draws or without."""
+        if not self.eval_lanes:
+            raise dqn_mlp.DraError("%s lanes: evaluate() needs a batch built with eval_lanes=True" % self.ENTRY)
+        n = int(self.cfg.eval_episodes if n is None else n)
+        lanes, horizon = len(self.agents), self.eval_vecs[0].horizon
+        if lib.dra_mlp_eval_lanes_supported.raw(n, horizon, lanes):
+            raise dqn_mlp.DraError("%s is not built for %d lanes of %d episodes of at most %d steps" % (self.EVAL_LANES, lanes, n, horizon))
+        dev, host = self._eval_block(n)
+        for k, vec in enumerate(self.eval_vecs):
+            io, row = dqn_mlp.EvalIO(), dev[k]
+            io.env_state, io.env_counter, io.env_seed = vec.env_state.data_ptr(), vec.env_counter.data_ptr(), vec.env_seed.data_ptr()
+            io.ep_steps, io.ep_return = vec.ep_steps.data_ptr(), vec.ep_return.data_ptr()
+            io.out_return, io.out_steps, io.out_length = row.data_ptr(), row[n:].data_ptr(), row[n + 1:].data_ptr()
+            io.horizon, io.n_episodes = vec.horizon, n
+            self.eval_ios.rows[k] = io
+        getattr(lib, self.EVAL_LANES)(self.nets.ptr, self.eval_ios.ptr, lanes, stream_ptr())
+        self.eval_launches += 1
+        host.copy_(dev, non_blocking=True)
+        torch.cuda.current_stream().synchronize()
+        self.eval_copies += 1
+        raw = host.numpy()
+        self.eval_steps = raw[:, n].copy().view(np.int64)
+        self.eval_lengths = np.ascontiguousarray(raw[:, n + 1:]).view(np.int32)[:, :n].copy()
+        self.eval_returns = raw[:, :n].copy()
+        return self.eval_returns
+
+    def eval_episodes(self):
+        """BaseAgent.eval_episodes of every lane: the pending training episodes first (drain_episodes, as the single run's
+        eval_episodes does), then evaluate(config.eval_episodes) and per lane the agent's own _report_eval, so each lane's logger
+        receives the 'episodic_return_test' line and scalar the single run writes -> the list of their dicts."""
+        self.drain_episodes()
+        returns = self.evaluate(self.cfg.eval_episodes)
+        return [a._report_eval(returns[k]) for k, a in enumerate(self.agents)]
 
     # -- the launches --------------------------------------------------------------------------------------------------------
     def _draw(self, learn):
@@ -500,6 +601,7 @@ class DQNFeatureSeeds(FeatureSeeds):
     dra_dqn_mlp_update_lanes.  `make_config(seed)` -> a Config for DQNAgent (dqn_feature's).  The surface is FeatureSeeds'."""
     ENTRY, MODULE = 'dqn_feature', dqn_mlp
     ACT_LANES, UPDATE_LANES, LANES_SUPPORTED = 'dra_dqn_mlp_act_lanes', 'dra_dqn_mlp_update_lanes', 'dra_dqn_mlp_lanes_supported'
+    EVAL_LANES = 'dra_dqn_mlp_eval_lanes'
 
     def agent_class(self):
         from .agents import DQNAgent
@@ -528,6 +630,7 @@ class DistFeatureSeeds(FeatureSeeds):
     than RMSprop and lanes that differ in head, atoms per action or categorical support are."""
     MODULE = dist_mlp
     ACT_LANES, UPDATE_LANES, LANES_SUPPORTED = 'dra_dist_mlp_act_lanes', 'dra_dist_mlp_update_lanes', 'dra_dist_mlp_lanes_supported'
+    EVAL_LANES = 'dra_dist_mlp_eval_lanes'
     AGENT = None
 
     def agent_class(self):

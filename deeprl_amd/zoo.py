@@ -291,17 +291,38 @@ def run(name, **kwargs):
     return ag
 
 
-def run_seeds(name, seeds, device_draws=False, **kwargs):
+def eval_points(max_steps, eval_interval, steps_per_agent_step):
+    """The total_steps at which a run of `max_steps` environment steps evaluates, in support.run_steps' order -- evaluate when due,
+    then stop at max_steps, then step -- with the interval tested on total_steps exactly: an agent whose step() advances
+    total_steps by `steps_per_agent_step` only triggers on the multiples of eval_interval that it lands on.  There is one at step
+    0, and one at the step the run stops at when that is a multiple; eval_interval 0 never evaluates.  Pure: run_seeds' cadence,
+    pinned without a device."""
+    points, total = [], 0
+    while True:
+        if eval_interval and total % eval_interval == 0:
+            points.append(total)
+        if total >= max_steps:
+            return points
+        total += steps_per_agent_step
+
+
+def run_seeds(name, seeds, device_draws=False, evaluate=False, **kwargs):
     """`name` once per seed, the seeds as lanes of the same device launches (deeprl_amd/seed_batch.py): per seed, random_seed(seed),
     torch.manual_seed(seed) and config(name, <the entry's switch>=True, **kwargs) over Task(game, seed=seed), stepped until
     config.max_steps environment steps of EVERY lane -> per seed the list of (step, episodic_return) pairs of its training
-    episodes, each what the single run of that seed gives.  There is no evaluation on this path: eval_interval is forced to 0.
+    episodes, each what the single run of that seed gives.  With `evaluate` off (the default) there is no evaluation on this path:
+    eval_interval is forced to 0.
     Three entries have a lane form (seed_batch.SEED_CLASSES): dqn_feature (fused_dqn_feature; n_step 1 and a UniformReplay),
     categorical_dqn_feature and quantile_regression_dqn_feature (fused_dist_feature, and fused_dist_update=True unless kwargs set
     it: the lanes always run the update kernel, so a categorical lane is the single run with fused_dist_update=True, not the
     single run's unset default, which is the module update).  Anything else raises a ValueError that names the reason.
     `device_draws=True` (off by default) draws every lane's np.random stream on the device, word for word (seed_batch.py's
-    docstring; csrc/np_mt.hip): the same (step, return) lists, without the per-lane host draws."""
+    docstring; csrc/np_mt.hip): the same (step, return) lists, without the per-lane host draws.
+    `evaluate=True` keeps the entry's eval_interval and eval_episodes (kwargs and overrides still apply), builds the batch with
+    eval_lanes=True and runs support.run_steps' order -- evaluate when due (total_steps % eval_interval == 0 exactly: eval_points),
+    then stop at max_steps, then step --, every evaluation ONE launch for all lanes (batch.eval_episodes(): each lane's logger gets
+    its 'episodic_return_test' line) -> (episodes, evaluations): `episodes` as above, evaluations[k] the list of (total_steps,
+    returns fp64 [eval_episodes]) of seed k, each what the single run of that seed with fused_eval=True evaluates."""
     from deeprl_amd.seed_batch import SEED_CLASSES
     if name not in SEED_CLASSES:
         raise ValueError("run_seeds: besides categorical_dqn_feature and quantile_regression_dqn_feature only dqn_feature runs its "
@@ -312,23 +333,31 @@ def run_seeds(name, seeds, device_draws=False, **kwargs):
     def make_config(seed):
         c = config(name, **dict(switch, **kwargs))
         c.task_fn = lambda: Task(c.game, seed=seed)
-        c.eval_interval = 0
+        if not evaluate:
+            c.eval_interval = 0
         return c
 
-    batch = cls(make_config, seeds, device_draws=device_draws)
+    batch = cls(make_config, seeds, device_draws=device_draws, eval_lanes=bool(evaluate))
     try:
-        out = [[] for _ in batch.seeds]
-        max_steps = batch.lane(0).config.max_steps
+        out, evals = [[] for _ in batch.seeds], [[] for _ in batch.seeds]
+        cfg = batch.lane(0).config
+        max_steps = cfg.max_steps
         if not max_steps:
             raise ValueError("run_seeds steps until config.max_steps, which is not set")
-        while batch.total_steps < max_steps:
+        while True:
+            if evaluate and cfg.eval_interval and batch.total_steps % cfg.eval_interval == 0:
+                batch.eval_episodes()
+                for k, got in enumerate(evals):
+                    got.append((batch.total_steps, batch.eval_returns[k].copy()))
+            if batch.total_steps >= max_steps:
+                break
             batch.step()
             if batch.agent_steps % 1024 == 0:
                 for k, got in enumerate(out):
                     got += batch.episodes(k)
         for k, got in enumerate(out):
             got += batch.episodes(k)
-        return out
+        return (out, evals) if evaluate else out
     finally:
         batch.close()
 

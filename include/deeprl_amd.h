@@ -1593,6 +1593,15 @@ int dra_dqn_mlp_eval(const dra_q_mlp_net* net, const dra_mlp_eval_io* io, void* 
 int dra_dist_mlp_eval(const dra_dist_mlp_net* net, const dra_mlp_eval_io* io, void* stream);
 int dra_rainbow_mlp_eval(const dra_rainbow_mlp_net* net, const dra_mlp_eval_io* io, void* stream);
 
+/* The evaluation of n_lanes independent agents of ONE network shape in ONE launch (seed lanes, above: the tables' memory,
+ * 1 <= n_lanes <= 64): workgroup (0, lane) runs dra_dqn_mlp_eval / dra_dist_mlp_eval on nets[lane] and ios[lane], to the bit.
+ * n_episodes and horizon are the lane's own and may differ between lanes; a lane leaves when ITS episodes have ended and waits for
+ * no other.  DRA_EINVAL, and nothing is launched or written, for a null table, an n_lanes outside the range, a lane the single
+ * entry refuses, or a lane whose network shape is not lane 0's.  dra_rainbow_mlp_eval has no lane form. */
+int dra_mlp_eval_lanes_supported(int n_episodes, int64_t horizon, int n_lanes);                   /* 0 = yes */
+int dra_dqn_mlp_eval_lanes(const dra_q_mlp_net* nets, const dra_mlp_eval_io* ios, int n_lanes, void* stream);
+int dra_dist_mlp_eval_lanes(const dra_dist_mlp_net* nets, const dra_mlp_eval_io* ios, int n_lanes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

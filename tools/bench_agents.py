@@ -56,6 +56,12 @@ Seed lanes (deeprl_amd/seed_batch.py), named explicitly with --cases too (SEED_C
             categorical_dqn_feature_module_update -- and quantile_regression_dqn_feature)
   <a seeds case>_device_draws (SEED_DRAW_CASES: dqn_feature 1 / 4 / 16 / 64, the distributional two 4 / 16)  the same lanes with
             device_draws=True: prepare_us_per_lane_step is then the common block and the counters alone
+  <a seeds case>_eval (SEED_EVAL_CASES: dqn_feature 1 / 4 / 16 / 64, the distributional two 1 / 4 / 16)  the lanes built with
+            eval_lanes=True and trained for 5 000 agent steps (20 000 environment steps per lane); then eval_episodes = 10 of every
+            lane as ONE launch and one copy (batch.evaluate) against the alternative that needs no lane kernel, a loop over the lanes
+            of the single launch (each lane Step's own evaluate: one launch and one synchronising copy per lane).  Three alternating
+            repeats from the same start of the evaluation environments each, the returns required equal to the bit; microseconds
+            per evaluation (all lanes), min-max over the repeats
 """
 import argparse
 import json
@@ -235,12 +241,13 @@ def dqn_feature(**switches):
     return d.DQNAgent(dqn_feature_config(**switches)), dict(env_per_step=4, updates_per_step=1, warm=300)
 
 
-def dqn_feature_seeds(n, device_draws=False):
+def dqn_feature_seeds(n, device_draws=False, eval_lanes=False):
     """dqn_feature_seedsN: N seeds of the dqn_feature case as lanes of the same launches (deeprl_amd/seed_batch.py), the
     environments seeded 1 .. N; env_steps_per_s is the AGGREGATE over the lanes.  device_draws: the lanes' np.random draws taken
     by dra_np_mt_draw_lanes (the _device_draws cases)."""
     from deeprl_amd.seed_batch import DQNFeatureSeeds
-    batch = DQNFeatureSeeds(lambda seed: dqn_feature_config(task_seed=seed), range(1, n + 1), device_draws=device_draws)
+    batch = DQNFeatureSeeds(lambda seed: dqn_feature_config(task_seed=seed), range(1, n + 1), device_draws=device_draws,
+                            eval_lanes=eval_lanes)
     return batch, dict(env_per_step=4 * n, updates_per_step=n, warm=300, lanes=n)
 
 
@@ -271,13 +278,13 @@ def dist_feature(head, **switches):
     return cls(dist_feature_config(head, **switches)), dict(env_per_step=4, updates_per_step=1, warm=120)
 
 
-def dist_feature_seeds(head, n, device_draws=False):
+def dist_feature_seeds(head, n, device_draws=False, eval_lanes=False):
     """categorical_dqn_feature_seedsN / quantile_regression_dqn_feature_seedsN: N seeds of the dist_feature case as lanes of the same
     launches (deeprl_amd/seed_batch.py: the batch sets fused_dist_feature and fused_dist_update), the environments seeded 1 .. N;
     env_steps_per_s is the AGGREGATE over the lanes."""
     from deeprl_amd import seed_batch
     cls = seed_batch.CategoricalDQNFeatureSeeds if head == "categorical" else seed_batch.QuantileRegressionDQNFeatureSeeds
-    batch = cls(lambda seed: dist_feature_config(head, task_seed=seed), range(1, n + 1), device_draws=device_draws)
+    batch = cls(lambda seed: dist_feature_config(head, task_seed=seed), range(1, n + 1), device_draws=device_draws, eval_lanes=eval_lanes)
     return batch, dict(env_per_step=4 * n, updates_per_step=n, warm=120, lanes=n)
 
 
@@ -579,11 +586,64 @@ def run_steps_eval_case(name, tag, runs=3, max_steps=25000):
     print(json.dumps(out), flush=True)
 
 
+def run_eval_lanes_case(name, tag, calls=3, warm=5000):
+    """<a seeds case>_eval: see the module's docstring.  Both sides step the SAME device environments, so each repeat's two sides
+    start from one snapshot of them (restored outside the timed windows); the next repeat goes on from where the loop side ended."""
+    batch, meta = SEED_EVAL_CASES[name]()
+    for _ in range(warm):
+        batch.step()
+    batch.drain_episodes()
+    n_ep, lanes = int(batch.cfg.eval_episodes), meta["lanes"]
+    batch.evaluate(n_ep)                             # (not timed: the first launch of either kernel, the blocks' allocation)
+    for st in batch.steps_:
+        st.evaluate(n_ep)
+    got = dict(lanes_launch=[], lane_loop=[])
+    steps, longest = [], []
+    for _ in range(calls):
+        start = [vec.state_dict() for vec in batch.eval_vecs]
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        together = batch.evaluate(n_ep)
+        torch.cuda.synchronize()
+        got["lanes_launch"].append((time.perf_counter() - t0) * 1e6)
+        lengths, per_lane = batch.eval_lengths.copy(), batch.eval_steps.copy()
+        for vec, state in zip(batch.eval_vecs, start):
+            vec.load_state_dict(state)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        one_by_one = [st.evaluate(n_ep) for st in batch.steps_]
+        torch.cuda.synchronize()
+        got["lane_loop"].append((time.perf_counter() - t0) * 1e6)
+        if not (np.array_equal(together.view(np.uint64), np.asarray(one_by_one).view(np.uint64))
+                and all(np.array_equal(lengths[k], st.eval_lengths) for k, st in enumerate(batch.steps_))):
+            raise AssertionError("%s: the lane launch and the loop over the single launches returned different episodes" % name)
+        steps.append(int(per_lane.sum()))
+        longest.append(int(per_lane.max()))
+    assert batch.eval_launches == calls + 1 == batch.eval_copies
+    out = {**tag, "case": name, "lanes": lanes, "episodes": n_ep, "calls": calls, "trained_agent_steps": warm, "eval_steps_all_lanes": steps,
+           "eval_steps_longest_lane": longest, "mean_return": [round(float(together.mean()), 2)]}
+    for side, us in got.items():
+        out[side + "_us_per_evaluation"] = [round(min(us), 1), round(max(us), 1)]
+    out["lanes_launch_us_per_longest_lane_step"] = [round(min(u / n for u, n in zip(got["lanes_launch"], longest)), 2),
+                                                    round(max(u / n for u, n in zip(got["lanes_launch"], longest)), 2)]
+    out["loop_over_lanes_launch"] = [round(min(got["lane_loop"]) / max(got["lanes_launch"]), 2),
+                                     round(max(got["lane_loop"]) / min(got["lanes_launch"]), 2)]
+    print(json.dumps(out), flush=True)
+    batch.close()
+
+
+# the lanes' evaluation in one launch against a loop over the lanes of the single launch: named in --cases
+SEED_EVAL_CASES = {"dqn_feature_seeds%d_eval" % n: (lambda n=n: dqn_feature_seeds(n, eval_lanes=True)) for n in (1, 4, 16, 64)}
+SEED_EVAL_CASES.update({"categorical_dqn_feature_seeds%d_eval" % n: (lambda n=n: dist_feature_seeds("categorical", n, eval_lanes=True))
+                        for n in (1, 4, 16)})
+SEED_EVAL_CASES.update({"quantile_regression_dqn_feature_seeds%d_eval" % n: (lambda n=n: dist_feature_seeds("quantile", n, eval_lanes=True))
+                        for n in (1, 4, 16)})
+
 EVAL_CASES = {"dqn_feature_eval": run_eval_case, "categorical_dqn_feature_eval": run_eval_case,
               "quantile_regression_dqn_feature_eval": run_eval_case, "rainbow_feature_eval": run_eval_case,
               "dqn_feature_run_steps_eval": run_steps_eval_case,
               "ddpg_continuous_eval": run_eval_case, "td3_continuous_eval": run_eval_case,
-              "ddpg_pendulum_run_steps_eval": run_steps_eval_case}
+              "ddpg_pendulum_run_steps_eval": run_steps_eval_case, **{name: run_eval_lanes_case for name in SEED_EVAL_CASES}}
 
 
 def main():
