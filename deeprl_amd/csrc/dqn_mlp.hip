@@ -23,6 +23,8 @@
 //   dqn_mlp_act_lanes_kernel, dqn_mlp_update_kernel<.., LANES>, dqn_mlp_eval_kernel<.., LANES>   the launches over n_lanes independent agents (seeds) of one shape:
 //                           workgroup (0, lane) reads ITS net and io struct from two tables and runs the single launch's text, so a
 //                           lane carries the single launch's bits.  Lanes share nothing and wait for nobody (the end of the file).
+//                           The update's lane form exists over both io structs (dra_dqn_mlp_update_lanes; over the window:
+//                           dra_dqn_replay_mlp_update_lanes, one n_step for all lanes).
 //
 // Both are q_mlp.hip's kernels with the replay between them: latency-bound chains over a few rows, plain fp32 VALU code, weights in
 // LDS once per launch, activations TRANSPOSED and read 16 bytes at a time, every dot product one FMA chain in ascending k.  The
@@ -516,14 +518,19 @@ DRA_API int dra_dqn_replay_mlp_update_supported(int state_dim, int n_actions, in
   return n_step < 1 || n_step > kMaxNStep ? DRA_EINVAL : DRA_OK;
 }
 
-DRA_API int dra_dqn_replay_mlp_update(const dra_q_mlp_net* net, const dra_dqn_replay_mlp_update_io* io, void* stream) {
-  if (!net || !io || !net->param || !net->target) return DRA_EINVAL;
-  if (dra_dqn_replay_mlp_update_supported(net->state_dim, net->n_actions, net->hidden, io->batch, net->gate, io->n_step)) return DRA_EINVAL;
-  if (!offsets_ok(net) || io->capacity < 1 + io->n_step || io->capacity > 0x7fffffff) return DRA_EINVAL;
+// what dra_dqn_replay_mlp_update asks of its two structs (dra_dqn_replay_mlp_update_lanes: of every lane's)
+static bool replay_update_args_ok(const dra_q_mlp_net* net, const dra_dqn_replay_mlp_update_io* io) {
+  if (!net->param || !net->target) return false;
+  if (dra_dqn_replay_mlp_update_supported(net->state_dim, net->n_actions, net->hidden, io->batch, net->gate, io->n_step)) return false;
+  if (!offsets_ok(net) || io->capacity < 1 + io->n_step || io->capacity > 0x7fffffff) return false;
   if (!io->ring_frames || !io->ring_actions || !io->ring_rewards || !io->ring_masks || !io->idx || !io->grad || !io->out_q_target ||
       !io->out_td || !io->out_loss || !io->err)
-    return DRA_EINVAL;
-  if (io->prob && (!io->beta || !io->out_prio || !io->out_weights)) return DRA_EINVAL;
+    return false;
+  return !io->prob || (io->beta && io->out_prio && io->out_weights);
+}
+
+DRA_API int dra_dqn_replay_mlp_update(const dra_q_mlp_net* net, const dra_dqn_replay_mlp_update_io* io, void* stream) {
+  if (!net || !io || !replay_update_args_ok(net, io)) return DRA_EINVAL;
   return dispatch_hidden_gate(net->hidden, net->gate, [&](auto h, auto g) {
     constexpr int H = decltype(h)::value, GATE = decltype(g)::value;
     return launch_one_workgroup<&dqn_mlp_update_kernel<H, GATE, dra_dqn_replay_mlp_update_io>>(replay_update_lds_floats(H) * sizeof(float), net, io, stream);
@@ -566,6 +573,25 @@ DRA_API int dra_dqn_mlp_update_lanes(const dra_q_mlp_net* nets, const dra_dqn_ml
   return dispatch_hidden_gate(nets->hidden, nets->gate, [&](auto h, auto g) {
     constexpr int H = decltype(h)::value, GATE = decltype(g)::value;
     return launch_lanes<&dqn_mlp_update_kernel<H, GATE, dra_dqn_mlp_update_io, true>>(update_lds_floats(H) * sizeof(float), nets, ios, n_lanes, stream);
+  });
+}
+
+DRA_API int dra_dqn_replay_mlp_lanes_supported(int state_dim, int n_actions, int hidden, int t_len, int batch, int gate, int n_step,
+                                               int n_lanes) {
+  if (n_lanes < 1 || n_lanes > kMaxLanes) return DRA_EINVAL;
+  if (dra_dqn_mlp_supported(state_dim, n_actions, hidden, t_len, gate)) return DRA_EINVAL;
+  return dra_dqn_replay_mlp_update_supported(state_dim, n_actions, hidden, batch, gate, n_step);
+}
+
+// the window's update of every lane: one window (n_step) for all of them, as one shape; prob may be set per lane (the kernel's text
+// is the single launch's either way)
+DRA_API int dra_dqn_replay_mlp_update_lanes(const dra_q_mlp_net* nets, const dra_dqn_replay_mlp_update_io* ios, int n_lanes, void* stream) {
+  if (!nets || !ios || n_lanes < 1 || n_lanes > kMaxLanes) return DRA_EINVAL;
+  for (int l = 0; l < n_lanes; ++l)
+    if (!replay_update_args_ok(nets + l, ios + l) || !same_shape(nets, nets + l) || ios[l].n_step != ios->n_step) return DRA_EINVAL;
+  return dispatch_hidden_gate(nets->hidden, nets->gate, [&](auto h, auto g) {
+    constexpr int H = decltype(h)::value, GATE = decltype(g)::value;
+    return launch_lanes<&dqn_mlp_update_kernel<H, GATE, dra_dqn_replay_mlp_update_io, true>>(replay_update_lds_floats(H) * sizeof(float), nets, ios, n_lanes, stream);
   });
 }
 

@@ -1,7 +1,8 @@
 // numpy's legacy RandomState stream (MT19937) as the seed lanes draw from it, word for word: what np_mt.hip's kernel and its host
 // twin share.  A lane's step, in the order of support.plan_actor_epsilon_greedy then replay.draw_uniform_indices:
 //   per transition  randint(n_actions, size=1), then rand(1) < epsilon in float64;
-//   if it learns    attempts of randint(0, size), each kept iff the ring holds its transition and the next, until `batch` are kept.
+//   if it learns    attempts of randint(0, size), each kept iff the ring holds its transition and the n_step behind it (np_mt_valid;
+//                   n_step = 1: the transition and the next), until `batch` are kept.
 // word:     y = key[pos++], tempered; pos == 624 regenerates the key first (the twist), never ahead of time.
 // randint:  rng = n - 1; rng == 0 is 0 and takes NO word; else mask = the smallest 2^j - 1 >= rng and every attempt takes one word,
 //           v = word & mask, accepted iff v <= rng.
@@ -48,14 +49,21 @@ NP_MT_HD double np_mt_double(uint32_t w0, uint32_t w1) {
   return ((double)(w0 >> 5) * 67108864.0 + (double)(w1 >> 6)) / 9007199254740992.0;
 }
 
-// UniformReplay.valid_index at history_length = n_step = 1 (what the lanes run)
-NP_MT_HD bool np_mt_valid(uint32_t i, int64_t ring_pos, int64_t ring_size) {
+constexpr int kNpMtMaxNStep = 8;            // the update kernels' longest window (dqn_mlp.hip's kMaxNStep)
+
+// UniformReplay.valid_index at history_length = 1 over an n-step window: the ring holds the transition and the n_step behind it,
+// none of them across the write position
+NP_MT_HD bool np_mt_valid(uint32_t i, int64_t ring_pos, int64_t ring_size, int64_t n_step) {
   const int64_t v = (int64_t)i;
-  return v + 1 < ring_pos || (v >= ring_pos && v + 1 < ring_size);
+  return v + n_step < ring_pos || (v >= ring_pos && v + n_step < ring_size);
 }
 
 // how many slots np_mt_valid accepts: 0 = the rejection loop could never end
-NP_MT_HD int64_t np_mt_valid_count(int64_t ring_pos, int64_t ring_size) {
-  const int64_t lo = ring_pos - 1 > 0 ? ring_pos - 1 : 0, hi = ring_size - 1 - ring_pos > 0 ? ring_size - 1 - ring_pos : 0;
+NP_MT_HD int64_t np_mt_valid_count(int64_t ring_pos, int64_t ring_size, int64_t n_step) {
+  const int64_t lo = ring_pos - n_step > 0 ? ring_pos - n_step : 0, hi = ring_size - n_step - ring_pos > 0 ? ring_size - n_step - ring_pos : 0;
   return lo + hi;
 }
+
+// n_step = 1: what the lanes of the 1-step entries run
+NP_MT_HD bool np_mt_valid(uint32_t i, int64_t ring_pos, int64_t ring_size) { return np_mt_valid(i, ring_pos, ring_size, 1); }
+NP_MT_HD int64_t np_mt_valid_count(int64_t ring_pos, int64_t ring_size) { return np_mt_valid_count(ring_pos, ring_size, 1); }

@@ -1,6 +1,6 @@
 """Many seeds of a cart-pole replay entry as lanes of the same device launches (csrc/seed_lanes.h, csrc/dqn_mlp.hip,
-csrc/dist_mlp.hip and csrc/optim.hip: seed lanes): dqn_feature (DQNFeatureSeeds), categorical_dqn_feature
-(CategoricalDQNFeatureSeeds) and quantile_regression_dqn_feature (QuantileRegressionDQNFeatureSeeds).
+csrc/dist_mlp.hip and csrc/optim.hip: seed lanes): dqn_feature (DQNFeatureSeeds; with an n-step window: DQNReplayFeatureSeeds),
+categorical_dqn_feature (CategoricalDQNFeatureSeeds) and quantile_regression_dqn_feature (QuantileRegressionDQNFeatureSeeds).
 
 `DQNFeatureSeeds(make_config, seeds)` builds, per seed, an ordinary DQNAgent on the config.fused_dqn_feature path exactly as a user
 would -- random_seed(seed), torch.manual_seed(seed), make_config(seed) -- so lane k's network, target, optimiser state,
@@ -20,6 +20,15 @@ subclass names the agent class, the switch it sets, the module of its Step (dqn_
 act-io and update-io structs), how the update io's outputs are filled, the three library entries and what its lane_signature
 holds beyond the common fields.  The two distributional classes run CategoricalDQNAgent / QuantileRegressionDQNAgent over
 dist_mlp.Step on dra_dist_mlp_act_lanes / dra_dist_mlp_update_lanes (DistFeatureSeeds).
+
+dqn_feature with an n-step window (n_step 1..8 over a UniformReplay) is DQNReplayFeatureSeeds, opt-in under the single path's own
+switch as there: DQNFeatureSeeds keeps refusing n_step > 1, and zoo.run_seeds picks the new class (REPLAY_SEED_CLASSES) only with
+fused_dqn_replay_feature=True among its keyword arguments.  Its lanes are DQNAgents over dqn_replay_mlp.Step
+(config.fused_dqn_replay_feature, set here); acting and evaluation are dqn_mlp's lane launches as they are, the update is
+dra_dqn_replay_mlp_update_lanes over the lane Steps' own replay_io(); the lanes share n_step and the replay's discount.  The host
+draws honour the window already (UniformReplay.draw_indices); the device draws go through dra_np_mt_draw_window_lanes with the
+batch's n_step.  A PrioritizedReplay stays refused by name: the prioritised draw (python's `random` per lane, the tree's launches)
+and the priorities' commit (per-lane pending sets) have no lane form.
 
 What the lanes cannot be is named in a ValueError: an agent that stayed on the host path (the module's why_not's reason: n_step >
 1, a PrioritizedReplay, another network, ...), the module-path update, fused_eval on a lane's own config (below), an optimiser
@@ -46,14 +55,15 @@ update lane kernels read (lane_layout stays the one source of the offsets).  pre
 small common block (first slot, the ring's pos / size after the step's appends, the k epsilons: dra_np_mt_common) and keeps the
 per-lane counters; it makes no numpy draw and stages nothing per lane, and last_draws is None -- fetch_draws(k) copies the last
 step's values back from the lane's block.  rng_tail(k) and close() copy the lane's state back into rngs[k] first, so the generator
-handed out stands where the single run's np.random stands.  A ring state without a valid index is refused with a ValueError
-before the step; shapes dra_np_mt_lanes_supported rejects are refused at construction."""
+handed out stands where the single run's np.random stands.  A ring state without a valid index (over the batch's n-step
+window) is refused with a ValueError before the step; shapes dra_np_mt_lanes_supported (a window class:
+dra_np_mt_window_lanes_supported) rejects are refused at construction."""
 import ctypes
 
 import numpy as np
 import torch
 
-from . import dist_mlp, dqn_mlp
+from . import dist_mlp, dqn_mlp, dqn_replay_mlp
 from ._lib import lib, stream_ptr
 from .graphs import Region
 from .support import Config, StagedUpload, plan_actor_epsilon_greedy, random_seed
@@ -113,9 +123,9 @@ def ring_after(pos, size, memory_size, k):
     return pos, size
 
 
-def valid_index_count(pos, size):
-    """How many slots UniformReplay.valid_index accepts at history_length = n_step = 1."""
-    return max(pos - 1, 0) + max(size - 1 - pos, 0)
+def valid_index_count(pos, size, n_step=1):
+    """How many slots UniformReplay.valid_index accepts at history_length = 1 over a window of `n_step`."""
+    return max(pos - n_step, 0) + max(size - n_step - pos, 0)
 
 
 class LaneTable:
@@ -175,7 +185,7 @@ def eval_signature(agent):
 
 def lane_why_not(agent, module=dqn_mlp):
     """None when `agent`, built with the switch of `module`'s kind on (dqn_mlp: config.fused_dqn_feature; dist_mlp:
-    config.fused_dist_feature), can be a lane; else the first reason.  config.fused_eval on a LANE's config is refused: it asks
+    config.fused_dist_feature; ReplayModule: config.fused_dqn_replay_feature), can be a lane; else the first reason.  config.fused_eval on a LANE's config is refused: it asks
     for the single evaluation launch, per agent.  Evaluation of lanes is a property of the batch -- FeatureSeeds(...,
     eval_lanes=True) evaluates every lane in one launch -- not of one lane's config."""
     cfg, kind = agent.config, module.Kind
@@ -198,11 +208,14 @@ class FeatureSeeds:
     they advance together), episodes(k), drain_episodes(), lane(k) -- the underlying agent, whose network, _target_flat, replay ring and save() see the lane's live
     buffers --, rng_tail(k) -- the lane's RandomState --, fetch_draws(k), close().
 
-    A subclass supplies ENTRY (the name in region labels and errors), MODULE (dqn_mlp or dist_mlp: Step, why_not, Kind, Net, ActIO,
-    UpdateIO), the library entries ACT_LANES / UPDATE_LANES / LANES_SUPPORTED / EVAL_LANES, agent_class(), switch_on(config),
-    signature(agent) and update_outputs(io, step)."""
+    A subclass supplies ENTRY (the name in region labels and errors), MODULE (dqn_mlp or dist_mlp, or a namespace of the same
+    names: Step, why_not, Kind, Net, ActIO, UpdateIO), the library entries ACT_LANES / UPDATE_LANES / LANES_SUPPORTED / EVAL_LANES,
+    agent_class(), switch_on(config), signature(agent), update_outputs(io, step) and, where LANES_SUPPORTED takes more than the
+    shape, lanes_supported_args(shape, n).  WINDOW: the lanes' replay has an n-step window, and the device draws go through the
+    np_mt window entries with it (else: the 1-step entries, which are the window entries at n_step 1)."""
     WARMUP = dqn_mlp.Step.WARMUP
     ENTRY = MODULE = ACT_LANES = UPDATE_LANES = LANES_SUPPORTED = EVAL_LANES = None
+    WINDOW = False
 
     # -- what a subclass supplies ------------------------------------------------------------------------------------------
     def agent_class(self):
@@ -221,6 +234,10 @@ class FeatureSeeds:
     def update_outputs(self, io, st):
         """The update io's output pointers from lane Step `st`, as the Step's own update() sets them."""
         raise NotImplementedError
+
+    def lanes_supported_args(self, shape, n):
+        """LANES_SUPPORTED's arguments for `n` lanes of network shape `shape`."""
+        return (*shape[:3], self.k, self.batch, *shape[3:self.MODULE.Kind.N_SUPPORTED], n)
 
     # -- construction ------------------------------------------------------------------------------------------------------
     def __init__(self, make_config, seeds, device_draws=False, eval_lanes=False):
@@ -264,16 +281,21 @@ class FeatureSeeds:
         steps = self.steps_ = [a._feature for a in self.agents]
         s0, cfg = steps[0], self.agents[0].config
         self.k, self.batch, self.cfg = s0.k, s0.batch, cfg
-        if getattr(lib, self.LANES_SUPPORTED).raw(*s0.shape[:3], self.k, self.batch, *s0.shape[3:m.Kind.N_SUPPORTED], n):
+        self.n_step = int(self.agents[0]._inner_replay().n_step)      # (the lanes share it: the signature, or the 1-step kinds' why_not)
+        if getattr(lib, self.LANES_SUPPORTED).raw(*self.lanes_supported_args(s0.shape, n)):
             raise ValueError("%s are not built for %d lanes of shape %r" % (self.ACT_LANES.replace("_act_", "_*_"), n, (s0.shape, self.k, self.batch)))
         # ONE staged block of [n] per-lane blocks; every lane's Step sees its block through the views it had of its own
         lay = self.layout = lane_layout(self.k, self.batch)
         if self.device_draws:
             # the draw kernel fills the lanes' blocks: a plain device tensor, the lanes' generators beside it, and the little the
             # lanes share in a step as the one staged upload
-            if lib.dra_np_mt_lanes_supported.raw(n, self.k, self.batch, s0.shape[1], s0.capacity):
+            dims = (n, self.k, self.batch, s0.shape[1], s0.capacity)
+            if self.WINDOW and lib.dra_np_mt_window_lanes_supported.raw(*dims, self.n_step):
+                raise ValueError("device_draws: dra_np_mt_draw_window_lanes is not built for %d lanes of k %d, batch %d, %d actions and a "
+                                 "ring of %d slots over an n-step window of %d" % (dims + (self.n_step,)))
+            if not self.WINDOW and lib.dra_np_mt_lanes_supported.raw(*dims):
                 raise ValueError("device_draws: dra_np_mt_draw_lanes is not built for %d lanes of k %d, batch %d, %d actions and a ring "
-                                 "of %d slots" % (n, self.k, self.batch, s0.shape[1], s0.capacity))
+                                 "of %d slots" % dims)
             self._up = None
             self._blocks = torch.zeros(n * lay['stride'], dtype=torch.uint8, device=dev)
             self._uploaded = np.stack([np_mt_words(rs) for rs in self.rngs])
@@ -312,7 +334,9 @@ class FeatureSeeds:
             self.update_outputs(io, st)
             io.ring_frames, io.ring_actions, io.ring_rewards, io.ring_masks = st.ring.pointers()
             io.idx, io.grad, io.err, io.capacity = st.idx.data_ptr(), a._fused.flat.grad.data_ptr(), st.err.data_ptr(), st.capacity
-            io.discount, io.batch, io.double_q = float(a.config.discount), self.batch, int(bool(a.config.double_q))
+            # (the bootstrap factor as Step.launch_update states it; x ** 1 is x)
+            io.discount = float(a.config.discount) ** int(a.config.n_step)
+            io.batch, io.double_q = self.batch, int(bool(a.config.double_q))
             self.update_ios.rows[k] = io
             f, o = a._fused, OptimLane()
             o.param, o.grad, o.square_avg, o.grad_avg = f.flat.flat.data_ptr(), f.flat.grad.data_ptr(), f.state1.data_ptr(), f.state2.data_ptr()
@@ -398,12 +422,15 @@ class FeatureSeeds:
 
     # -- the launches --------------------------------------------------------------------------------------------------------
     def _draw(self, learn):
-        """device_draws: the lanes' blocks filled by dra_np_mt_draw_lanes from the lanes' generators, ahead of the launches that
-        read them."""
+        """device_draws: the lanes' blocks filled by dra_np_mt_draw_lanes (WINDOW: dra_np_mt_draw_window_lanes with the batch's
+        n_step) from the lanes' generators, ahead of the launches that read them."""
         lay = self.layout
-        lib.dra_np_mt_draw_lanes(self._mt.data_ptr(), self._blocks.data_ptr(), self._common.dev.data_ptr(), self.err.data_ptr(),
-                                 len(self.agents), self.k, self.batch, self.steps_[0].shape[1], int(learn), lay['idx'], lay['rand'],
-                                 lay['flag'], lay['stride'], stream_ptr())
+        args = (self._mt.data_ptr(), self._blocks.data_ptr(), self._common.dev.data_ptr(), self.err.data_ptr(), len(self.agents), self.k,
+                self.batch, self.steps_[0].shape[1], int(learn), lay['idx'], lay['rand'], lay['flag'], lay['stride'])
+        if self.WINDOW:
+            lib.dra_np_mt_draw_window_lanes(*args, self.n_step, stream_ptr())
+        else:
+            lib.dra_np_mt_draw_lanes(*args, stream_ptr())
         self.launches += 1
 
     def _act(self, learn=False):
@@ -468,9 +495,9 @@ class FeatureSeeds:
         rp0 = a0._inner_replay()
         slot0 = int(rp0.pos)
         pos, size = ring_after(slot0, rp0.size(), rp0.memory_size, k)
-        if learn and valid_index_count(pos, size) == 0:
-            raise ValueError("device_draws: a replay ring of size %d at pos %d holds no valid index, the minibatch's rejection loop "
-                             "could not end" % (size, pos))
+        if learn and valid_index_count(pos, size, self.n_step) == 0:
+            raise ValueError("device_draws: a replay ring of size %d at pos %d holds no valid index%s, the minibatch's rejection loop "
+                             "could not end" % (size, pos, " over an n-step window of %d" % self.n_step if self.WINDOW else ""))
         c = NpMtCommon.from_buffer(self._common.stage().numpy())
         c.slot0, c.ring_pos, c.ring_size = slot0, pos, size
         behind = k - len(eps)      # transitions below exploration_steps: epsilon is 1 and the schedule is not called
@@ -611,6 +638,54 @@ class DQNFeatureSeeds(FeatureSeeds):
         io.out_q_target, io.out_td, io.out_loss = st.q_target.data_ptr(), st.td.data_ptr(), st.loss.data_ptr()
 
 
+class ReplayModule:
+    """What FeatureSeeds reads from MODULE for dqn_feature under config.fused_dqn_replay_feature: the Step, its kind, why_not and
+    the update io are dqn_replay_mlp's; the net and the acting io are dqn_mlp's as they are (the window changes nothing in acting)."""
+    Net, ActIO = dqn_mlp.Net, dqn_mlp.ActIO
+    UpdateIO, Step, Kind = dqn_replay_mlp.UpdateIO, dqn_replay_mlp.Step, dqn_replay_mlp.WindowKind
+    why_not = staticmethod(dqn_replay_mlp.why_not)
+
+
+def replay_lane_signature(agent):
+    """lane_signature with what the window's launches share on top: n_step (one launch, one window; the draws' validity test) and
+    the replay's discount (the fold's factor)."""
+    rp = agent._inner_replay()
+    return lane_signature(agent, n_step=int(rp.n_step), replay_discount=float(rp.discount))
+
+
+class DQNReplayFeatureSeeds(FeatureSeeds):
+    """Seeds of dqn_feature with an n-step window (n_step 1..8 over a UniformReplay): DQNAgent over dqn_replay_mlp.Step with
+    config.fused_dqn_replay_feature set here, on dra_dqn_mlp_act_lanes, dra_dqn_replay_mlp_update_lanes and (eval_lanes)
+    dra_dqn_mlp_eval_lanes; with device_draws the minibatch's indices are drawn valid over the window
+    (dra_np_mt_draw_window_lanes).  The lanes share n_step and the replay's discount on top of DQNFeatureSeeds' signature.  A
+    PrioritizedReplay stays refused: the prioritised draw (python's `random` per lane, the tree's launches) and the priorities'
+    commit (per-lane pending sets) have no lane form, although the update launch itself takes priorities per lane.
+    `make_config(seed)` -> a Config for DQNAgent (dqn_feature's).  The surface is FeatureSeeds'."""
+    ENTRY, MODULE, WINDOW = 'dqn_feature', ReplayModule, True
+    ACT_LANES, UPDATE_LANES = 'dra_dqn_mlp_act_lanes', 'dra_dqn_replay_mlp_update_lanes'
+    LANES_SUPPORTED, EVAL_LANES = 'dra_dqn_replay_mlp_lanes_supported', 'dra_dqn_mlp_eval_lanes'
+
+    def agent_class(self):
+        from .agents import DQNAgent
+        return DQNAgent
+
+    def why_not(self, agent):
+        if isinstance(getattr(agent, '_feature', None), dqn_replay_mlp.PerStep):
+            return ("the replay is a PrioritizedReplay: the prioritised draw and the priorities' commit have no lane form")
+        return lane_why_not(agent, self.MODULE)
+
+    def signature(self, agent):
+        return replay_lane_signature(agent)
+
+    def lanes_supported_args(self, shape, n):
+        return (*shape[:3], self.k, self.batch, shape[3], self.n_step, n)
+
+    def update_outputs(self, io, st):
+        """The whole io as the lane Step's own replay_io() states it -- the outputs, the window and the fold's discount have one
+        source --; _wire fills the ring, the indices and the scalars over it, as Step.launch_update does."""
+        ctypes.memmove(ctypes.byref(io), ctypes.byref(st.replay_io()), ctypes.sizeof(io))
+
+
 def dist_lane_signature(agent):
     """lane_signature with what the distributional launches share on top: the head kind, the atoms per action (the launches' LDS
     size follows from lane 0's) and the categorical support (per-lane data to the kernels, but one configuration is what a sweep
@@ -663,3 +738,5 @@ class QuantileRegressionDQNFeatureSeeds(DistFeatureSeeds):
 
 # zoo.run_seeds: the entries with a lane form
 SEED_CLASSES = {c.ENTRY: c for c in (DQNFeatureSeeds, CategoricalDQNFeatureSeeds, QuantileRegressionDQNFeatureSeeds)}
+# ... and the ones picked instead where a keyword of run_seeds sets the class's own switch (fused_dqn_replay_feature=True)
+REPLAY_SEED_CLASSES = {c.ENTRY: c for c in (DQNReplayFeatureSeeds,)}

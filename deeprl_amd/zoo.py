@@ -316,6 +316,10 @@ def run_seeds(name, seeds, device_draws=False, evaluate=False, **kwargs):
     categorical_dqn_feature and quantile_regression_dqn_feature (fused_dist_feature, and fused_dist_update=True unless kwargs set
     it: the lanes always run the update kernel, so a categorical lane is the single run with fused_dist_update=True, not the
     single run's unset default, which is the module update).  Anything else raises a ValueError that names the reason.
+    `fused_dqn_replay_feature=True` among the kwargs picks the class from seed_batch.REPLAY_SEED_CLASSES instead: dqn_feature with
+    an n-step window, `n_step=N` (1..8) over a UniformReplay, each lane the single run of its seed with the same two keywords (both
+    travel to config() as they do for a single agent).  A PrioritizedReplay stays refused there too, by name.  Without that keyword
+    nothing changes: n_step > 1 is refused as before.
     `device_draws=True` (off by default) draws every lane's np.random stream on the device, word for word (seed_batch.py's
     docstring; csrc/np_mt.hip): the same (step, return) lists, without the per-lane host draws.
     `evaluate=True` keeps the entry's eval_interval and eval_episodes (kwargs and overrides still apply), builds the batch with
@@ -323,11 +327,15 @@ def run_seeds(name, seeds, device_draws=False, evaluate=False, **kwargs):
     then stop at max_steps, then step --, every evaluation ONE launch for all lanes (batch.eval_episodes(): each lane's logger gets
     its 'episodic_return_test' line) -> (episodes, evaluations): `episodes` as above, evaluations[k] the list of (total_steps,
     returns fp64 [eval_episodes]) of seed k, each what the single run of that seed with fused_eval=True evaluates."""
-    from deeprl_amd.seed_batch import SEED_CLASSES
+    from deeprl_amd.seed_batch import REPLAY_SEED_CLASSES, SEED_CLASSES
     if name not in SEED_CLASSES:
         raise ValueError("run_seeds: besides categorical_dqn_feature and quantile_regression_dqn_feature only dqn_feature runs its "
                          "seeds as lanes, %s has no lane form" % name)
     cls = SEED_CLASSES[name]
+    if kwargs.get("fused_dqn_replay_feature") is True:
+        if name not in REPLAY_SEED_CLASSES:
+            raise ValueError("run_seeds: fused_dqn_replay_feature is dqn_feature's switch, %s has no lane form under it" % name)
+        cls = REPLAY_SEED_CLASSES[name]
     switch = {cls.MODULE.Kind.SWITCH: True}
 
     def make_config(seed):

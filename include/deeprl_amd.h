@@ -1400,6 +1400,17 @@ typedef struct dra_dqn_replay_mlp_update_io {
 } dra_dqn_replay_mlp_update_io;
 int dra_dqn_replay_mlp_update_supported(int state_dim, int n_actions, int hidden, int batch, int gate, int n_step);   /* 0 = yes */
 int dra_dqn_replay_mlp_update(const dra_q_mlp_net* net, const dra_dqn_replay_mlp_update_io* io, void* stream);
+/* The window's update over n_lanes independent agents of ONE network shape and ONE window (seed lanes, above: the tables' memory,
+ * 1 <= n_lanes <= 64; seed_batch.DQNReplayFeatureSeeds): workgroup (0, lane) runs dra_dqn_replay_mlp_update on nets[lane] and
+ * ios[lane], to the bit.  prob is each lane's own: lanes with and without priorities may share a launch.  The acting and
+ * evaluation launches of such lanes are dra_dqn_mlp_act_lanes and dra_dqn_mlp_eval_lanes as they are (acting writes 1-step rows).
+ * DRA_EINVAL, and nothing is launched, for a null table, an n_lanes outside the range, a lane the single entry refuses, a lane
+ * whose state_dim / n_actions / hidden / gate are not lane 0's, or a lane whose n_step is not lane 0's.
+ * dra_dqn_replay_mlp_lanes_supported: dra_dqn_mlp_supported (t_len), dra_dqn_replay_mlp_update_supported (batch, n_step) and the
+ * lane count. */
+int dra_dqn_replay_mlp_lanes_supported(int state_dim, int n_actions, int hidden, int t_len, int batch, int gate, int n_step,
+                                       int n_lanes);   /* 0 = yes */
+int dra_dqn_replay_mlp_update_lanes(const dra_q_mlp_net* nets, const dra_dqn_replay_mlp_update_io* ios, int n_lanes, void* stream);
 
 /* ---- dist_mlp: categorical_dqn_feature (examples.py:164-193, CategoricalDQN_agent.py) and quantile_regression_dqn_feature
  * (examples.py:101-127, QuantileRegressionDQN_agent.py) over ONE device-resident cart-pole environment and the HBM replay ring:
@@ -1477,7 +1488,14 @@ int dra_dist_mlp_update_lanes(const dra_dist_mlp_net* nets, const dra_dist_mlp_u
  * 1 <= n_actions, ring capacity 2 .. 2^32 - 1 (dra_np_mt_lanes_supported: 0 = yes).
  * dra_np_mt_draw_host: the same step of ONE lane, serially, over host memory -- no device is touched.  It states the protocol for
  * the CPU tests and is the kernel's debugging twin, not a path of the product.  DRA_EINVAL also for a ring state with no valid
- * index (learn != 0) and for a pos outside 0 .. 624. */
+ * index (learn != 0) and for a pos outside 0 .. 624.
+ * The *_window_* entries are the same step over an n-step window (the lanes of dqn_feature with n_step > 1,
+ * seed_batch.DQNReplayFeatureSeeds): an index v is valid iff v + n_step < ring_pos or (v >= ring_pos and v + n_step < ring_size),
+ * UniformReplay.valid_index at history_length = 1; max(ring_pos - n_step, 0) + max(ring_size - n_step - ring_pos, 0) slots are.
+ * 1 <= n_step <= 8, ring capacity n_step + 1 .. 2^32 - 1 (dra_np_mt_window_lanes_supported: 0 = yes); everything else as above.  The
+ * entries without a window ARE these with n_step 1 (the same launch, the same bits).  A ring state with no window-valid index is
+ * the host's to refuse before the step (dra_np_mt_draw_window_host: DRA_EINVAL); a launch over one ends within its budget, sets
+ * DRA_NP_MT_ERR_BUDGET and writes index 0. */
 #define DRA_NP_MT_STATE_WORDS 628
 #define DRA_NP_MT_ERR_BUDGET 1073741824
 typedef struct dra_np_mt_state {
@@ -1496,6 +1514,12 @@ int dra_np_mt_draw_lanes(void* states, void* out_blocks, const dra_np_mt_common*
                          int n_actions, int learn, int idx_off, int rand_off, int flag_off, int block_stride, void* stream);
 int dra_np_mt_draw_host(void* state, void* out_block, const dra_np_mt_common* common, int* err, int k, int batch, int n_actions,
                         int learn, int idx_off, int rand_off, int flag_off);
+int dra_np_mt_window_lanes_supported(int n_lanes, int k, int batch, int n_actions, int64_t capacity, int n_step);   /* 0 = yes */
+int dra_np_mt_draw_window_lanes(void* states, void* out_blocks, const dra_np_mt_common* common, int* err, int n_lanes, int k,
+                                int batch, int n_actions, int learn, int idx_off, int rand_off, int flag_off, int block_stride,
+                                int n_step, void* stream);
+int dra_np_mt_draw_window_host(void* state, void* out_block, const dra_np_mt_common* common, int* err, int k, int batch,
+                               int n_actions, int learn, int idx_off, int rand_off, int flag_off, int n_step);
 
 /* ---- rainbow_mlp: rainbow_feature (examples.py:231-280: CategoricalDQNAgent, RainbowNet over FCBody(noisy_linear=True), n-step
  * PrioritizedReplay, double_q) over ONE device-resident cart-pole environment and the HBM replay ring: dist_mlp's two launches

@@ -56,6 +56,9 @@ Seed lanes (deeprl_amd/seed_batch.py), named explicitly with --cases too (SEED_C
             categorical_dqn_feature_module_update -- and quantile_regression_dqn_feature)
   <a seeds case>_device_draws (SEED_DRAW_CASES: dqn_feature 1 / 4 / 16 / 64, the distributional two 4 / 16)  the same lanes with
             device_draws=True: prepare_us_per_lane_step is then the common block and the counters alone
+  dqn_feature_nstep_seeds1 / 4 / 16 / 64, and each with _device_draws  the dqn_feature_nstep case's configuration (n_step 3 over a
+            UniformReplay, config.fused_dqn_replay_feature) once per seed as lanes (seed_batch.DQNReplayFeatureSeeds); the single
+            baseline is dqn_feature_nstep
   <a seeds case>_eval (SEED_EVAL_CASES: dqn_feature 1 / 4 / 16 / 64, the distributional two 1 / 4 / 16)  the lanes built with
             eval_lanes=True and trained for 5 000 agent steps (20 000 environment steps per lane); then eval_episodes = 10 of every
             lane as ONE launch and one copy (batch.evaluate) against the alternative that needs no lane kernel, a loop over the lanes
@@ -248,6 +251,15 @@ def dqn_feature_seeds(n, device_draws=False, eval_lanes=False):
     from deeprl_amd.seed_batch import DQNFeatureSeeds
     batch = DQNFeatureSeeds(lambda seed: dqn_feature_config(task_seed=seed), range(1, n + 1), device_draws=device_draws,
                             eval_lanes=eval_lanes)
+    return batch, dict(env_per_step=4 * n, updates_per_step=n, warm=300, lanes=n)
+
+
+def dqn_feature_nstep_seeds(n, device_draws=False):
+    """dqn_feature_nstep_seedsN: N seeds of the dqn_feature_nstep case (n_step 3) as lanes of the same launches
+    (seed_batch.DQNReplayFeatureSeeds: the batch sets fused_dqn_replay_feature), as dqn_feature_seeds."""
+    from deeprl_amd.seed_batch import DQNReplayFeatureSeeds
+    batch = DQNReplayFeatureSeeds(lambda seed: dqn_feature_config(task_seed=seed, n_step=3, fused_dqn_replay_update=True), range(1, n + 1),
+                                  device_draws=device_draws)
     return batch, dict(env_per_step=4 * n, updates_per_step=n, warm=300, lanes=n)
 
 
@@ -472,6 +484,7 @@ CASES = {
 SEED_CASES = {"dqn_feature_seeds%d" % n: (lambda n=n: dqn_feature_seeds(n)) for n in (1, 4, 16, 64)}
 SEED_CASES.update({"categorical_dqn_feature_seeds%d" % n: (lambda n=n: dist_feature_seeds("categorical", n)) for n in (1, 4, 16)})
 SEED_CASES.update({"quantile_regression_dqn_feature_seeds%d" % n: (lambda n=n: dist_feature_seeds("quantile", n)) for n in (1, 4, 16)})
+SEED_CASES.update({"dqn_feature_nstep_seeds%d" % n: (lambda n=n: dqn_feature_nstep_seeds(n)) for n in (1, 4, 16, 64)})
 
 # the same with the lanes' draws taken on the device (seed_batch.py, device_draws=True): a dict of their own, named in --cases
 SEED_DRAW_CASES = {"dqn_feature_seeds%d_device_draws" % n: (lambda n=n: dqn_feature_seeds(n, True)) for n in (1, 4, 16, 64)}
@@ -479,6 +492,7 @@ SEED_DRAW_CASES.update({"categorical_dqn_feature_seeds%d_device_draws" % n: (lam
                         for n in (4, 16)})
 SEED_DRAW_CASES.update({"quantile_regression_dqn_feature_seeds%d_device_draws" % n: (lambda n=n: dist_feature_seeds("quantile", n, True))
                         for n in (4, 16)})
+SEED_DRAW_CASES.update({"dqn_feature_nstep_seeds%d_device_draws" % n: (lambda n=n: dqn_feature_nstep_seeds(n, True)) for n in (1, 4, 16, 64)})
 
 
 # the continuous entries evaluate on the pendulum, on their device path, the zoo's 20 episodes (of 200 steps) a time
